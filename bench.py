@@ -162,6 +162,26 @@ def cpu_baseline(part, u, C, budget_s=10.0):
                 omp_num_threads_env=os.environ.get("OMP_NUM_THREADS"))
 
 
+DUMP_BYTES = 60 << 20   # --dump-outputs: sampled rows of all files together (headroom for headers: <= 64 MB)
+
+
+def write_outputs(dirname, arrays, budget=DUMP_BYTES, suffix=""):
+    """``arrays``: name -> host array (rows = cells).  Each is written as ``dirname/<name><suffix>.npy`` (float32 stays
+    float32, anything else becomes float64).  If they do not fit in ``budget`` bytes together, every array keeps the same
+    fraction of its rows, chosen by a fixed seed from the row count alone: arrays of equal length keep the same rows, and
+    two runs with the same arguments write the same files."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float32 if np.asarray(v).dtype == np.float32 else np.float64)
+              for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > budget and a.ndim > 0 and a.shape[0] > 1:
+            keep = max(1, a.shape[0] * budget // total)
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+            a = a[rows]
+        np.save(os.path.join(dirname, name + suffix + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -214,6 +234,10 @@ def main():
                     help="the timed block of --steps sweeps is repeated this many times; the median is reported")
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="check the launch path only: ranks meet (gloo), rank 0 prints one JSON line; no GPU is touched")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (N > 1: "
+                         "<name>_rank<r>.npy, the rank's own cells); at most 64 MB in all, a fixed seeded sample of "
+                         "the rows of larger outputs")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -647,6 +671,11 @@ def main():
     side = torch.cuda.Stream()
     if batch:
         batch = min(batch, args.steps)
+        if march:
+            # the march ping-pongs between um[0] and um[1] and a graph bakes in the pointers of its capture: an even number
+            # of steps captured from um[0] ends in um[0] again, so replays chain on; eager steps continue from there
+            batch -= batch % 2
+    if batch:
         with torch.cuda.stream(side):
             for _ in range(4):
                 step()
@@ -709,12 +738,22 @@ def main():
     # feed their own image-point interpolation, and over hundreds of steps the temperature of a few ghost cells drifts
     # linearly (-1.7 K per step at 7.9 M cells) until the sound speed is NaN.  Every timed block starts from the initial
     # state (restored outside the timed region), as a solver's step would start from a state its update produced.
-    state4 = None
+    # The steps that carry their state from one step to the next -- the march's u, the V-cycles' Q on one GPU -- restart
+    # from it too: every block is `steps` consecutive steps from the same inputs, whatever the number of blocks, so what
+    # the last block computes (--dump-outputs) depends on the arguments alone.
+    state0 = []
     if config4:
-        state4 = (P4, P4.clone()) if world > 1 else (P, P.clone())
+        state0 = [(P4, P4.clone())] if world > 1 else [(P, P.clone())]
+    elif march:
+        state0 = [(um[0], u)]
+    elif config5 and world == 1:
+        state0 = [(Q5, Q5_0)]
     while len(dts) < n_rep or len(dts) < n_goal:
-        if state4 is not None:
-            state4[0].copy_(state4[1])
+        if state0:
+            for dst, src in state0:
+                dst.copy_(src)
+            if march:
+                mstate["k"] = 0
             torch.cuda.synchronize()
         barrier()
         g0, g1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -732,6 +771,20 @@ def main():
                 dist.all_reduce(tt, op=dist.ReduceOp.MAX)
                 tot = float(tt.item())
             n_goal = n_rep if tot >= 0.2 else min(max(n_rep, 400), int(n_rep * 0.2 / max(tot, 1e-9)) + 1)
+    if args.dump_outputs:
+        # what a caller of the timed step holds after its last step (before the passes below overwrite the buffers)
+        if march:
+            outs = {"u": um[mstate["k"] & 1], "dt": dt_m}
+        elif config5:
+            outs = {"Q": Q5[:dpart.nc]}
+        elif config4:
+            outs = {"P": (P4 if world > 1 else P)[:dpart.nc], "residual": Rres}
+        else:
+            outs = {"residual": Rres if euler else ud}
+        own = torch.as_tensor(part.image_in_domain, dtype=torch.int64, device=u.device) if world > 1 else None
+        outs = {k: (v if own is None or v.numel() == 1 else v[own]).cpu().numpy() for k, v in outs.items()}
+        write_outputs(args.dump_outputs, outs, budget=DUMP_BYTES // world,
+                      suffix=f"_rank{rank}" if world > 1 else "")
     if world > 1:
         red_dev = u.device if args.backend == "nccl" else "cpu"
         tmax = torch.tensor(dts, dtype=torch.float64, device=red_dev)
