@@ -127,6 +127,8 @@ _SIGS = {
     "ibh_fas_update": [c_i64, C.c_float, c_vp, c_vp, c_vp, c_vp],
     "ibh_axpy": [c_i64, C.c_float, c_vp, c_vp],
     "ibh_sumsq": [c_i64, c_vp, c_vp],
+    "ibh_time_average_push": [c_i64, c_int, c_vp, c_i64, c_vp, c_vp, c_int, c_vp, c_i64, c_i64, C.c_double, C.c_double,
+                              c_int],
     "ibh_turb_wall_function_rey": [c_i64, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp],
     "ibh_turb_wall_function": [c_i64, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "ibh_turb_shear_rate": [c_int, c_i64, c_vp, c_vp],

@@ -1,15 +1,22 @@
 """``CFD`` pointwise physics on device arrays (mirror of /root/reference/src/cfd.jl for the functions residual
 closures call): ``Fluid``, ``speed_of_sound``, ``dynamic_viscosity``, ``heat_conductivity``,
 ``primitive2state``, ``state2primitive``, ``inviscid_fluxes`` (HLL and sensor/Rusanov methods),
-``viscous_fluxes``.  Same names and argument order; ``dim`` is the 1-based Cartesian direction (the
-matrix-normal form of the reference is a curvilinear extension outside this hot path).
-Arithmetic runs in libibhip kernels (csrc/ibh_cfd.hip); device arrays only.
+``viscous_fluxes``, ``pressure_coefficient`` and ``TimeAverage``.  Same names and argument order; ``dim`` is the
+1-based Cartesian direction (the matrix-normal form of the reference is a curvilinear extension outside this hot path).
+Arithmetic runs in libibhip kernels (csrc/ibh_cfd.hip, csrc/ibh_stats.hip); device arrays only.
+
+The free-stream utilities ``ISA_atmosphere``, ``streamwise_direction``, ``Reynolds_number`` and ``adjust_Reynolds``
+(cfd.jl:302-436, 619-654) are host scalars: numpy, no device.
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
+import numbers
+import warnings
 
 import numpy as np
+import torch
 
 from . import _lib
 from . import backend as B
@@ -228,3 +235,238 @@ class FlowBC:
                C.c_float(self.T_inf), self.u_inf.ctypes.data_as(B.c_vp), int(self.normal_flow), B._ptr(imd), B._ptr(dn),
                C.c_float(tc), B._ptr(tv), B._ptr(out), n)
         return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# pressure coefficient and running statistics (device arrays)
+# ---------------------------------------------------------------------------------------------------------------------
+def pressure_coefficient(fluid, p, p_inf, M_inf):
+    """``CFD.pressure_coefficient`` (cfd.jl:411-424): ``2 * (p / p∞ - 1) / (M∞^2 * γ)`` as one broadcast launch
+    (``ibh_ew_eval``), in the reference's order with ``M∞^2 * γ`` folded on the host in Float32 (``M*M``, then ``*γ``).
+    The result is Float32 with ``p∞`` and ``M∞`` rounded to Float32; the reference returns Float64 for Float64 scalars.
+    Takes and returns a device tensor or a ``HipArray``."""
+    from .hiparray import HipArray
+    hit = isinstance(p, HipArray)
+    pa = p if hit else HipArray(B._field(p)[0])
+    M = np.float32(M_inf)
+    s = np.float32(M * M) * np.float32(fluid.gamma)
+    cp = 2.0 * (pa / np.float32(p_inf) - 1.0) / s
+    return cp if hit else cp.t
+
+
+def _kind(x):
+    """Julia type class of a host scalar: 'i' (Integer), 'f32' (Float32 and narrower), 'f64' (Float64, Python float)."""
+    if isinstance(x, (bool, numbers.Integral, np.integer)):
+        return "i"
+    if isinstance(x, np.floating) and x.dtype.itemsize <= 4:
+        return "f32"
+    if isinstance(x, (float, np.floating)):
+        return "f64"
+    raise TypeError(f"expected a real scalar, got {type(x).__name__}")
+
+
+class _TA:
+    """dt forms and flags of ibh_time_average_push (include/ibhip.h)."""
+    DT_HOST, DT_DEVICE, DT_PER_VAR, DT_ELEMENT = 0, 1, 2, 3
+    F64, FIRST = 1, 2
+
+
+class TimeAverage:
+    """``CFD.TimeAverage`` (cfd.jl:738-802): exponential moving average ``mu`` and its standard deviation ``sigma`` of a
+    device field for the time scale ``tau``.  ``push(Q, dt)`` is one launch (``ibh_time_average_push``) that updates
+    ``mu`` and ``sigma`` in place, so a held reference to ``mu`` sees every later push.
+
+    ``dt``: a host scalar (Python / numpy), or a Float32 device tensor that is one element (e.g. the march's device dt:
+    no host sync), 1-D of length ``nv`` with a 2-D ``Q`` (per variable: the reference's reshape along the last axis), or
+    of ``Q``'s shape (elementwise).  Anything else raises before a launch.  Precision follows Julia's promotion: ``eta =
+    dt / tau`` and every product with it are Float64 if ``tau`` or a host ``dt`` is Float64 (a Python float counts),
+    otherwise Float32; ``sigma^2`` and ``(mu - Q)^2`` stay Float32.  ``dt > tau`` gives NaN in sigma where the
+    reference's ``sqrt`` would throw."""
+
+    def __init__(self, tau):
+        _kind(tau)
+        self.tau = tau
+        self.mu = None
+        self.sigma = None
+
+    def _dt_form(self, dt, n, nv, ndim):
+        """(form, device tensor or None, numel, ld) of ``dt`` for a Q of shape (n,) / (n, nv); raises for other shapes."""
+        if not hasattr(dt, "data_ptr"):
+            _kind(dt)
+            return _TA.DT_HOST, None, 0, 0
+        if not isinstance(dt, torch.Tensor) or not dt.is_cuda or dt.dtype != torch.float32:
+            raise TypeError("TimeAverage.push: an array dt must be a Float32 device tensor")
+        shape = tuple(dt.shape)
+        qshape = (n,) if ndim == 1 else (n, nv)
+        if dt.numel() == 1 and dt.ndim <= ndim:
+            return _TA.DT_DEVICE, dt.reshape(1), 1, 1
+        if ndim == 2 and shape == (nv,):
+            return _TA.DT_PER_VAR, dt.contiguous(), nv, nv
+        if shape == qshape:
+            d, _, ld = B._field(dt)
+            return _TA.DT_ELEMENT, d, (nv - 1) * ld + n, ld
+        raise ValueError(f"TimeAverage.push: dt of shape {shape} does not broadcast with Q of shape {qshape} "
+                         "(DimensionMismatch): dt is a scalar, one element, per variable (nv,) or Q's shape")
+
+    def push(self, Q, dt=np.float32(1)):
+        """``push!(avg, Q, dt)``: the first call registers ``mu = copy(Q)``, ``sigma = mu .* 0``; returns ``mu``."""
+        from .hiparray import HipArray
+        hit = isinstance(Q, HipArray)
+        q, nv, ldq = B._field(Q.t if hit else Q)
+        n = q.shape[0]
+        if self.mu is None:
+            mu, sg = B._like(q, n), B._like(q, n)
+            B._stream()
+            B.call("ibh_time_average_push", n, nv, B._ptr(q), ldq, B._ptr(mu), B._ptr(sg), _TA.DT_HOST, B._ptr(None),
+                   0, 0, C.c_double(0.0), C.c_double(1.0), _TA.FIRST)
+            self.mu, self.sigma = (HipArray(mu), HipArray(sg)) if hit else (mu, sg)
+            return self.mu
+        mu, sg = self.mu, self.sigma
+        if isinstance(mu, HipArray):
+            mu._flush_readers()   # pending broadcasts that read mu / sigma see the old values, as in Julia
+            sg._flush_readers()
+            mu, sg = mu.t, sg.t
+        if tuple(mu.shape) != tuple(q.shape):
+            raise ValueError(f"TimeAverage.push: Q of shape {tuple(q.shape)} after {tuple(mu.shape)} (DimensionMismatch)")
+        form, d, numel, ldd = self._dt_form(dt, n, nv, q.ndim)
+        kt = _kind(self.tau)
+        kd = "f32" if d is not None else _kind(dt)
+        f64 = "f64" in (kt, kd) or (kt == "i" and kd == "i")    # Int / Int is Float64 in Julia
+        real = np.float64 if f64 else np.float32
+        tau = real(self.tau)
+        eta = real(dt) / tau if d is None else real(0)
+        B._stream()
+        B.call("ibh_time_average_push", n, nv, B._ptr(q), ldq, B._ptr(mu), B._ptr(sg), form, B._ptr(d), numel, ldd,
+               C.c_double(float(eta)), C.c_double(float(tau)), _TA.F64 if f64 else 0)
+        return self.mu
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# free-stream utilities (host scalars, numpy).  Julia's promotion is kept: the reference's constants are Float32, a
+# Python float is a Float64 and a Python int an Int (numpy's weak Python scalars would turn them into Float32).
+# ---------------------------------------------------------------------------------------------------------------------
+_f32 = np.float32
+
+
+def _jl(x):
+    if isinstance(x, (bool, numbers.Integral, np.integer)):
+        return int(x)
+    if isinstance(x, float) and not isinstance(x, np.floating):
+        return np.float64(x)
+    return x
+
+
+_ISA_LAYERS = [  # base altitude [m], base temperature [K], lapse rate [K/km], base pressure [Pa]
+    (_f32(0.0), _f32(288.15), _f32(-6.5), _f32(101325.0)),     # Troposphere
+    (_f32(11000.0), _f32(216.65), _f32(0.0), _f32(22632.0)),   # Tropopause
+    (_f32(20000.0), _f32(216.65), _f32(1.0), _f32(5474.9)),    # Stratosphere 1
+    (_f32(32000.0), _f32(228.65), _f32(2.8), _f32(868.02)),    # Stratosphere 2
+    (_f32(47000.0), _f32(270.65), _f32(0.0), _f32(110.91)),    # Stratopause
+    (_f32(51000.0), _f32(270.65), _f32(-2.8), _f32(66.939)),   # Mesosphere 1
+    (_f32(71000.0), _f32(214.65), _f32(-2.0), _f32(3.9564)),   # Mesosphere 2
+]
+
+
+def _ISA_atmosphere(altitude_m, dT=0.0):
+    """cfd.jl:304-368: (p, T) of the standard atmosphere.  As in the reference: the loop over ``1:length(layers)-1`` never
+    selects the 71 km layer, and isothermal layers use ``T_base + ΔT``."""
+    altitude_m, dT = _jl(altitude_m), _jl(dT)
+    R, g0 = _f32(287.05287), _f32(9.80665)
+    if altitude_m < 0:
+        raise ValueError("Altitude cannot be negative")
+    elif altitude_m > 86000:
+        warnings.warn("Altitude above 86 km - model accuracy decreases")
+    layer_idx = 0
+    for i in range(len(_ISA_LAYERS) - 1):
+        if altitude_m >= _ISA_LAYERS[i][0]:
+            layer_idx = i
+    h_base, T_base, lapse_rate, P_base = _ISA_LAYERS[layer_idx]
+    lapse_rate_per_m = lapse_rate / _f32(1000.0)
+    delta_h = altitude_m - h_base
+    T = T_base + lapse_rate_per_m * delta_h + dT
+    if abs(lapse_rate_per_m) < _f32(1e-10):
+        P = P_base * np.exp(-g0 * delta_h / (R * (T_base + dT)))
+    else:
+        exponent = -g0 / (R * lapse_rate_per_m)
+        T_base_offset = T_base + dT
+        T_offset = T_base_offset + lapse_rate_per_m * delta_h
+        P = P_base * (T_offset / T_base_offset) ** exponent
+    return P, T
+
+
+def _host_speed_of_sound(fluid, T):
+    """cfd.jl:62-64 on a host scalar, with the Float32 fluid constants."""
+    return np.sqrt(_f32(fluid.gamma) * _f32(fluid.R) * np.clip(T, _f32(10.0), np.float32(np.inf)))
+
+
+def ISA_atmosphere(altitude_m, dT=_f32(0.0), Mach=_f32(0.0), V=None, u_hat=(_f32(1.0),)):
+    """``CFD.ISA_atmosphere(altitude_m; ΔT, Mach, V, û)`` (cfd.jl:370-397): ``(Fluid(), [p, T, u * û])``.  ``V`` overrides
+    the Mach number; ``û`` is normalised with ``eps`` added to its norm.  The speed of sound uses ``Fluid()``'s R = 283,
+    the pressure the ISA's R = 287.05287, as in the reference.  Negative altitudes raise; above 86 km it warns."""
+    p, T = _ISA_atmosphere(altitude_m, dT)
+    fluid = Fluid()
+    u = _jl(V)
+    if u is None:
+        a = _host_speed_of_sound(fluid, T)
+        u = _jl(Mach) * a
+    uh = np.asarray([_jl(x) for x in u_hat])
+    if uh.dtype.kind != "f":
+        uh = uh.astype(np.float64)
+    uh = uh / (np.finfo(uh.dtype).eps + np.sqrt(np.sum(uh * uh)))
+    vel = u * uh
+    dtype = np.result_type(p, T, vel)
+    return fluid, np.concatenate([np.asarray([p, T], dtype=dtype), vel.astype(dtype)])
+
+
+def _sind(x):
+    """Julia's ``sind``: exact at multiples of 90 degrees."""
+    r = math.fmod(float(x), 360.0)
+    if r % 90.0 == 0.0:
+        return (0.0, 1.0, 0.0, -1.0)[int(r // 90.0) % 4]
+    return math.sin(math.radians(r))
+
+
+def _cosd(x):
+    r = math.fmod(float(x), 360.0)
+    if r % 90.0 == 0.0:
+        return (1.0, 0.0, -1.0, 0.0)[int(r // 90.0) % 4]
+    return math.cos(math.radians(r))
+
+
+def streamwise_direction(alpha, beta=None):
+    """``CFD.streamwise_direction(α[, β])`` (cfd.jl:401-409, 426-436), angles in degrees: ``[cosd α, sind α]`` in 2-D,
+    ``[cosd α cosd β, -cosd α sind β, sind α]`` in 3-D."""
+    args = (alpha,) if beta is None else (alpha, beta)
+    dtype = np.float32 if all(_kind(x) == "f32" for x in args) else np.float64
+    if beta is None:
+        return np.array([_cosd(alpha), _sind(alpha)], dtype=dtype)
+    if dtype == np.float32:   # each factor is a Float32 in Julia, and so is the product
+        ca, cb, sb = _f32(_cosd(alpha)), _f32(_cosd(beta)), _f32(_sind(beta))
+        return np.array([ca * cb, -ca * sb, _f32(_sind(alpha))], dtype=dtype)
+    return np.array([_cosd(alpha) * _cosd(beta), -_cosd(alpha) * _sind(beta), _sind(alpha)], dtype=dtype)
+
+
+def _host_dynamic_viscosity(fluid, T):
+    """cfd.jl:71-77 (Sutherland, with the reference's exponent 2/3) on a host scalar, Float32 fluid constants."""
+    T = np.clip(T, _f32(10.0), np.float32(np.inf))
+    Tref, S = _f32(fluid.Tref), _f32(fluid.S)
+    return _f32(fluid.mu_ref) * ((T / Tref) ** (_f32(2.0) / 3)) * (Tref + S) / (T + S)
+
+
+def Reynolds_number(fluid, P_inf, Lref):
+    """``CFD.Reynolds_number(fluid, P∞, Lref)`` (cfd.jl:626-638): ``|u∞| Lref ρ / μ(T∞)`` with ``P∞ = [p, T, u...]``."""
+    P = np.asarray(P_inf)
+    V = np.sqrt(np.sum(P[2:] * P[2:]))
+    T = P[1]
+    p = P[0]
+    rho = p / (_f32(fluid.R) * T)
+    mu = _host_dynamic_viscosity(fluid, T)
+    return V * _jl(Lref) * rho / mu
+
+
+def adjust_Reynolds(fluid, P_inf, Lref, Re):
+    """``CFD.adjust_Reynolds(fluid, P∞, Lref, Re)`` (cfd.jl:640-654): a new ``Fluid`` whose reference viscosity gives the
+    Reynolds number ``Re``."""
+    Re_old = Reynolds_number(fluid, P_inf, Lref)
+    mu_ref = _f32(fluid.mu_ref) * Re_old / _jl(Re)
+    return Fluid(fluid.R, fluid.gamma, fluid.k, float(mu_ref), fluid.Tref, fluid.S)

@@ -392,6 +392,26 @@ int ibh_axpy_clamped_sumsq(int64_t n, float omega, const float* r, float* q, dou
  * sum(rr^2)] -- `r .+= source`, the update and the norm on one read of r; source, q and out_sumsq may each be NULL. */
 int ibh_fas_update(int64_t n, float omega, const float* r, const float* source, float* q, double* out_sumsq);
 
+/* push!(::CFD.TimeAverage, Q, dt) (cfd.jl:775-800), mu and sigma updated in place in one launch:
+ *   eta = dt / tau;  sigma = sqrt(sigma^2 * (1 - eta) + (mu - Q)^2 * eta);  mu = mu * (1 - eta) + Q * eta
+ * sigma from the old mu.  Q is (n, nv) with leading dimension ldq; mu and sigma are compact (n * nv), 16-byte aligned.
+ * Precision P of eta (flags & IBH_TA_F64: Float64, else Float32) follows Julia's promotion: sigma^2, mu - Q and
+ * (mu - Q)^2 stay Float32, everything with eta is in P, rounded to Float32 on store.  dt_form:
+ *   IBH_TA_DT_HOST     eta (already dt / tau in P, computed by the caller) by value; dt unused
+ *   IBH_TA_DT_DEVICE   dt: one device element (dt_numel == 1), read on the device -- no host sync
+ *   IBH_TA_DT_PER_VAR  dt: nv device elements, one per variable (the reference's reshape along Q's last axis)
+ *   IBH_TA_DT_ELEMENT  dt: device array of Q's shape with leading dimension ldd (dt_numel >= (nv-1)*ldd + n)
+ * tau (in P) divides the device dt forms.  flags & IBH_TA_FIRST: the first registry, mu = Q and sigma = mu .* 0 (-0.0
+ * where Q < 0, NaN where Q is not finite); dt, eta and tau are then ignored. */
+#define IBH_TA_DT_HOST 0
+#define IBH_TA_DT_DEVICE 1
+#define IBH_TA_DT_PER_VAR 2
+#define IBH_TA_DT_ELEMENT 3
+#define IBH_TA_F64 1
+#define IBH_TA_FIRST 2
+int ibh_time_average_push(int64_t n, int nv, const float* Q, int64_t ldq, float* mu, float* sigma, int dt_form,
+                          const float* dt, int64_t dt_numel, int64_t ldd, double eta, double tau, int flags);
+
 /* FlowBC call (cfd.jl:243-300): boundary state [p T u v (w)] from the image-point primitives P and the unit normals.
  * u_inf: nd components, or ONE component (the normal velocity) when normal_flow != 0.  image_distances / dudn: both
  * null or both given (wall-function slip scaling :287-292); transpiration: scalar, or per-row array when

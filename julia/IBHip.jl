@@ -840,6 +840,59 @@ function Turbulence.WALE_νSGS(Δ::HipArray{Float32, 1}, velocity_gradient::Abst
 end
 
 # ---------------------------------------------------------------------------------------------------
+# CFD.TimeAverage (cfd.jl:738-802): `push!` as ONE launch that updates μ and σ in place (ibh_time_average_push), and
+# CFD.pressure_coefficient (cfd.jl:411-424), whose generic method would reach `literal_pow`, which the broadcast
+# interpreter above does not take.
+# ---------------------------------------------------------------------------------------------------
+const TA_DT_HOST, TA_DT_DEVICE, TA_DT_PER_VAR, TA_DT_ELEMENT = Cint.(0:3)
+const TA_F64, TA_FIRST = Cint(1), Cint(2)
+function _ta_push(avg::CFD.TimeAverage, Q::HipArray{Float32}, form::Cint, dt::Ptr{Cvoid}, numel::Int, ldd::Int,
+                  η::Float64, τ::Float64, flags::Cint)
+    check(ccall((:ibh_time_average_push, lib), Cint,
+        (Int64, Cint, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Int64, Cdouble, Cdouble, Cint),
+        size(Q, 1), nv(Q), Q.ptr, ld(Q), avg.μ.ptr, avg.σ.ptr, form, dt, numel, ldd, η, τ, flags))
+end
+"`push!(avg, Q, dt)` (cfd.jl:775-800): η = dt / τ in Julia's promotion of `typeof(avg.τ)` and `typeof(dt)` (Float64 or
+Float32; σ^2 and (μ - Q)^2 stay Float32).  `dt` a host scalar, or a device array of one element (no host sync), of
+`size(Q, 2)` elements (per variable: the reference's reshape) or of `size(Q)`."
+function Base.push!(avg::CFD.TimeAverage, Q::HipArray{Float32}, dt::Union{Real, HipArray{Float32}} = 1.0f0)
+    if isnothing(avg.μ)                                       # first registry: μ = copy(Q); σ = μ .* 0
+        avg.μ, avg.σ = _vec_like(Q), _vec_like(Q)
+        _ta_push(avg, Q, TA_DT_HOST, C_NULL, 0, 0, 0.0, 1.0, TA_FIRST)
+        return avg.μ
+    end
+    size(avg.μ) == size(Q) || throw(DimensionMismatch("push!: Q of size $(size(Q)) after $(size(avg.μ))"))
+    if dt isa Real
+        η = dt / avg.τ
+        f64 = η isa Float64
+        _ta_push(avg, Q, TA_DT_HOST, C_NULL, 0, 0, Float64(f64 ? η : Float32(η)),
+                 Float64(f64 ? Float64(avg.τ) : Float32(avg.τ)), f64 ? TA_F64 : Cint(0))
+    else
+        f64 = (1.0f0 / avg.τ) isa Float64
+        form, numel, ldd = if length(dt) == 1 && ndims(dt) <= ndims(Q)
+            TA_DT_DEVICE, 1, 1
+        elseif ndims(Q) == 2 && ndims(dt) == 1 && length(dt) == size(Q, 2)
+            TA_DT_PER_VAR, length(dt), length(dt)
+        elseif size(dt) == size(Q)
+            TA_DT_ELEMENT, length(dt), Int(ld(dt))
+        else
+            throw(DimensionMismatch("push!: dt of size $(size(dt)) does not broadcast with Q of size $(size(Q))"))
+        end
+        _ta_push(avg, Q, form, dt.ptr, numel, ldd, 0.0, Float64(f64 ? Float64(avg.τ) : Float32(avg.τ)),
+                 f64 ? TA_F64 : Cint(0))
+    end
+    avg.μ
+end
+"`pressure_coefficient(fluid, p, p∞, M∞)`: `2 * (p / p∞ - 1) / (M∞^2 * γ)` with `M∞^2 * γ` folded in Float32; the result
+is Float32 (the reference's is Float64 for Float64 scalars)."
+function CFD.pressure_coefficient(fluid::CFD.Fluid, p::HipArray{Float32}, p∞::Real, M∞::Real)
+    M = Float32(M∞)
+    s = (M * M) * Float32(fluid.γ)
+    pinf = Float32(p∞)
+    @. 2 * (p / pinf - 1.0f0) / s
+end
+
+# ---------------------------------------------------------------------------------------------------
 # Solver.FAS! (src/solver.jl:39-91) on device arrays: the reference's loop with its array passes as library calls --
 # `r .+= source; Q .+= clamp(ω, 0, 1) .* r; norm(r)` is ONE launch (ibh_fas_update), the prolongation step another
 # (accumulate_diff_add!).  Same keyword arguments, same quirks (recursion guard `length(coarseners) > 1`), same return value.
