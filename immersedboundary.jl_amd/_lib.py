@@ -129,6 +129,12 @@ _SIGS = {
     "ibh_sumsq": [c_i64, c_vp, c_vp],
     "ibh_time_average_push": [c_i64, c_int, c_vp, c_i64, c_vp, c_vp, c_int, c_vp, c_i64, c_i64, C.c_double, C.c_double,
                               c_int],
+    "ibh_domain_plan_create": [C.POINTER(c_vp), c_int, C.POINTER(c_vp), c_vp, C.POINTER(c_vp), C.POINTER(c_vp), c_vp,
+                               c_i64, c_int],
+    "ibh_domain_plan_destroy": [c_vp],
+    "ibh_domain_plan_info": [c_vp, C.POINTER(c_i64), c_int],
+    "ibh_domain_gather": [c_vp, c_int, C.POINTER(c_vp), c_vp, c_vp, C.POINTER(c_vp)],
+    "ibh_domain_scatter": [c_vp, c_int, C.POINTER(c_vp), c_vp, c_vp, C.POINTER(c_vp)],
     "ibh_turb_wall_function_rey": [c_i64, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp],
     "ibh_turb_wall_function": [c_i64, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "ibh_turb_shear_rate": [c_int, c_i64, c_vp, c_vp],

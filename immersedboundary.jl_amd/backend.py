@@ -5,7 +5,8 @@ Mirrors, for the hot path only,
     (/root/reference/src/arraybends.jl:14-77, src/ImmersedBoundary.jl:788-790, :846-855);
   * the grid operators on a Partition (src/ImmersedBoundary.jl:873-1157) -- same names,
     argument order and return shapes (fresh arrays), ``dim`` 1-based;
-  * ``(dom::Domain)(f, args...)`` (:820-864) and ``impose_bc!`` (:1197-1247).
+  * ``(dom::Domain)(f, args...)`` (:820-864) -- through the host with converters, or on device-resident arrays
+    (``ibh_domain_gather`` / ``ibh_domain_scatter``) -- and ``impose_bc!`` (:1197-1247).
 
 Device memory, streams and (elsewhere) torch.distributed come from PyTorch -- plumbing only;
 all arithmetic is in the HIP kernels of libibhip.so, reached through the C ABI with raw device
@@ -747,12 +748,18 @@ def residual_euler_hll(part, P, fluid_R=283.0, fluid_gamma=1.4, out=None, flags=
 # partition runtime and ghost-cell BC
 # ---------------------------------------------------------------------------
 def domain_call(dom, f, args, conv_to_backend, conv_from_backend, kwargs):
-    """``(dom::Domain)(f, args...)`` (ImmersedBoundary.jl:820-864) with the GPU backend."""
+    """``(dom::Domain)(f, args...)`` (ImmersedBoundary.jl:820-864) with the GPU backend.
+
+    With both converters: per partition, the host gathers ``a[part.domain]``, converts it, runs ``f`` and writes the
+    image rows back (the reference's loop, sequential).  Without converters and with every argument a device array
+    (CUDA/HIP ``torch.Tensor`` or ``HipArray``, at least one): ``_domain_call_device``.  Anything else raises."""
     if (conv_to_backend is None) != (conv_from_backend is None):
         raise AssertionError("Backend converters must be provided at the same time")
     if conv_to_backend is None:
-        raise TypeError("Domain call needs conv_to_backend=ibamd.hip, conv_from_backend=ibamd.to_host: "
-                        "the per-partition compute runs on the GPU only (no CPU path)")
+        if args and all(_on_device(a) for a in args):
+            return _domain_call_device(dom, f, args, kwargs)
+        raise TypeError("Domain call needs conv_to_backend=ibamd.hip, conv_from_backend=ibamd.to_host, or device arrays "
+                        "only (no host array among them): the per-partition compute runs on the GPU only (no CPU path)")
     results = []
     for i in dom.partitions:
         part = dom.partitions[i]
@@ -764,6 +771,117 @@ def domain_call(dom, f, args, conv_to_backend, conv_from_backend, kwargs):
         for a, da in zip(args, dargs):
             a[part.image] = da[part.image_in_domain]
         results.append(r)
+    return results
+
+
+def _on_device(a):
+    from .hiparray import HipArray
+    return isinstance(a, HipArray) or (isinstance(a, torch.Tensor) and a.is_cuda)
+
+
+class DomainPlan:
+    """Device tables of the domain call of one Domain (``ibh_domain_plan_create``; ``domain_plan_tables`` is the same
+    construction in numpy) plus the partitions' ``to_backend`` handles, in call order.  Cached on the Domain."""
+
+    def __init__(self, dom):
+        from .domain import domain_plan_tables
+        T = domain_plan_tables(dom)   # validates: indices in range, images disjoint
+        _dev()
+        self.ids = T["ids"]
+        self.n = [int(x) for x in T["n"]]
+        self.ws_off = [int(x) for x in T["ws_off"]]
+        self.parts = [to_backend(dom.partitions[i], hip) for i in self.ids]
+        np_ = len(self.ids)
+        keep = []
+
+        def ptrs(arrs):
+            arrs = [np.ascontiguousarray(a, dtype=np.int32) for a in arrs]
+            keep.append(arrs)
+            return (c_vp * max(np_, 1))(*[a.ctypes.data for a in arrs])
+        parts = [dom.partitions[i] for i in self.ids]
+        nd = np.array([p.domain.size for p in parts], dtype=np.int32)
+        ni = np.array([p.image.size for p in parts], dtype=np.int32)
+        h = c_vp()
+        call("ibh_domain_plan_create", C.byref(h), np_, ptrs([p.domain for p in parts]), _hptr(nd),
+             ptrs([p.image for p in parts]), ptrs([p.image_in_domain for p in parts]), _hptr(ni), len(dom), 0)
+        self.handle = h
+        off = (C.c_int64 * (np_ + 1))()
+        call("ibh_domain_plan_info", h, off, np_ + 1)
+        if list(off) != self.ws_off:
+            raise _lib.IbhError(f"domain plan: workspace offsets of the library {list(off)} != {self.ws_off}")
+
+    def _run(self, name, a, nvs, lds, b):
+        k = len(a)
+        call(name, self.handle, k, (c_vp * k)(*a), _hptr(np.asarray(nvs, dtype=np.int32)),
+             _hptr(np.asarray(lds, dtype=np.int64)), (c_vp * k)(*b))
+
+    def __del__(self):
+        try:
+            if getattr(self, "handle", None):
+                _lib.load().ibh_domain_plan_destroy(self.handle)
+                self.handle = None
+        except Exception:  # noqa: BLE001
+            pass
+
+
+def domain_plan(dom):
+    """The Domain's ``DomainPlan`` (built on first use)."""
+    plan = getattr(dom, "_device_plan", None)
+    if plan is None:
+        plan = dom._device_plan = DomainPlan(dom)
+    return plan
+
+
+def _domain_call_device(dom, f, args, kwargs):
+    """``(dom::Domain)(f, args...)`` on device-resident global arrays: nothing goes through the host.
+
+    1. one ``ibh_domain_gather`` launch copies ``a[part.domain]`` of every argument and every partition into stacked
+       workspaces (torch's allocator: no host sync, capturable in a graph);
+    2. ``f(device_partition, local_args...; kwargs...)`` runs per partition, in ``dom.partitions`` order; each local
+       argument is a view ``(n_p,)`` / ``(n_p, nv)``, column-major with ``ld = n_p`` (the layout ``hip()`` gives), of
+       the kind given (torch tensor or ``HipArray``);
+    3. one ``ibh_domain_scatter`` launch writes ``a[part.image] = local[part.image_in_domain]`` for every argument.
+
+    These are snapshot semantics: every partition reads the arguments as they were before the call -- the deterministic
+    form of the reference's threaded ``tmap``.  For every closure whose result does not depend on the order of the
+    partitions (one that reads its inputs and writes outputs, e.g. test/advection.jl:67-83) it equals the sequential
+    host path bit for bit.  Returns the per-partition results in partition order."""
+    from .hiparray import HipArray
+    n = len(dom)
+    for a in args:   # validate everything before anything is launched
+        if isinstance(a, HipArray):
+            if a.n != n:
+                raise ValueError(f"domain call argument has {a.n} rows, the domain {n} cells")
+        else:
+            _field_inplace(a, n, "domain call argument")
+            if a.ndim == 2 and a.shape[1] == 0:
+                raise ValueError("domain call argument has no columns")
+    for a in args:
+        if isinstance(a, HipArray):
+            a._flush_readers()   # pending broadcasts that read it see the old values
+    tens = [a.t if isinstance(a, HipArray) else a for a in args]   # (materialises pending expressions)
+    fields = [_field_inplace(t, n, "domain call argument") for t in tens]
+    plan = domain_plan(dom)
+    dev = tens[0].device
+    wss = [torch.empty(nv * plan.ws_off[-1], dtype=torch.float32, device=dev) for (_, nv, _) in fields]
+    nvs = [nv for (_, nv, _) in fields]
+    lds = [ld for (_, _, ld) in fields]
+    _stream()
+    plan._run("ibh_domain_gather", [t.data_ptr() for t in tens], nvs, lds, [w.data_ptr() for w in wss])
+    results = []
+    for k, dpart in enumerate(plan.parts):
+        n_p = plan.n[k]
+        local = []
+        for t, ws, nv, wrap in zip(tens, wss, nvs, (isinstance(a, HipArray) for a in args)):
+            o = nv * plan.ws_off[k]
+            v = ws[o:o + n_p] if t.ndim == 1 else torch.as_strided(ws, (n_p, nv), (1, n_p), o)
+            local.append(HipArray(v) if wrap else v)
+        results.append(f(dpart, *local, **kwargs))
+    for a in args:
+        if isinstance(a, HipArray):
+            a._flush_readers()   # the arguments are written in place: pending broadcasts that read them go first
+    _stream()
+    plan._run("ibh_domain_scatter", [w.data_ptr() for w in wss], nvs, lds, [t.data_ptr() for t in tens])
     return results
 
 

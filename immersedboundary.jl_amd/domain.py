@@ -671,12 +671,59 @@ class Domain:
     def __call__(self, f, *args, conv_to_backend=None, conv_from_backend=None, n_threads=0, **kwargs):
         """``(dom::Domain)(f, args...; conv_to_backend, conv_from_backend)`` (:820-864).
 
-        The per-partition compute runs on the GPU only: both converters are required
-        (use ``ibamd.hip`` / ``ibamd.to_host``); see backend.py for the resident form that
-        avoids the per-call gather/upload altogether.
+        The per-partition compute runs on the GPU only.  Host arrays need both converters (use ``ibamd.hip`` /
+        ``ibamd.to_host``).  Without converters every argument must be a device array (a CUDA/HIP ``torch.Tensor``
+        or an ``ibamd.HipArray``): the call then stays on the device (``backend.domain_call``), with snapshot
+        semantics -- all partitions gather before any closure runs, the write-back follows the last closure.
         """
         from . import backend
         return backend.domain_call(self, f, args, conv_to_backend, conv_from_backend, kwargs)
+
+
+DOMAIN_PLAN_BLOCK = 256   # rows per workgroup of the device gather / scatter (csrc/ibh_domain.hip)
+
+
+def domain_plan_tables(dom):
+    """Host-side tables of the device domain call (``ibh_domain_plan_create``, csrc/ibh_domain.hip), in numpy.
+
+    Partitions in ``dom.partitions`` order (the call order); all indices 0-based.  Returns a dict:
+      ``ids``: partition ids; ``n``: rows of each partition (``len(part.domain)``);
+      ``rows`` / ``row_off``: the concatenated ``part.domain`` and its ``n_parts + 1`` offsets;
+      ``image`` / ``image_in_domain`` / ``img_off``: the concatenated write-back pairs and their offsets;
+      ``ws_off``: ``n_parts + 1`` row offsets of the stacked workspace -- partition p's local array of ``nv``
+      variables starts at element ``nv * ws_off[p]`` (a multiple of 64 floats: 256 bytes), column-major with
+      leading dimension ``n[p]``; a field needs ``nv * ws_off[-1]`` elements;
+      ``wg_gather`` / ``wg_scatter``: ``(n_wg, 2)`` int32, workgroup -> (partition index, first row).
+    Raises ``ValueError`` on an index out of range and on overlapping images (the write-back of all partitions is
+    one launch, so the order of two writes to one row would be undefined).  Images need not cover every cell."""
+    ids = list(dom.partitions)
+    parts = [dom.partitions[i] for i in ids]
+    ncells = len(dom)
+    n = np.array([p.domain.size for p in parts], dtype=np.int64)
+    m = np.array([p.image.size for p in parts], dtype=np.int64)
+    row_off = np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
+    img_off = np.concatenate([[0], np.cumsum(m)]).astype(np.int64)
+    ws_off = np.concatenate([[0], np.cumsum((n + 63) // 64 * 64)]).astype(np.int64)
+    cat = (lambda xs: np.concatenate([np.asarray(x, dtype=np.int64) for x in xs]) if xs else np.zeros(0, np.int64))
+    rows = cat([p.domain for p in parts])
+    image = cat([p.image for p in parts])
+    iid = cat([p.image_in_domain for p in parts])
+    if rows.size and (rows.min() < 0 or rows.max() >= ncells):
+        raise ValueError("domain_plan_tables: a partition's domain index is out of range")
+    if image.size and (image.min() < 0 or image.max() >= ncells):
+        raise ValueError("domain_plan_tables: a partition's image index is out of range")
+    for k in range(len(parts)):
+        loc = iid[img_off[k]:img_off[k + 1]]
+        if loc.size and (loc.min() < 0 or loc.max() >= n[k]):
+            raise ValueError(f"domain_plan_tables: image_in_domain of partition {ids[k]} is out of range")
+    if np.unique(image).size != image.size:
+        raise ValueError("domain_plan_tables: partition images overlap (the write-back order would matter)")
+
+    def wg(counts):
+        t = [(k, r) for k, c in enumerate(counts) for r in range(0, int(c), DOMAIN_PLAN_BLOCK)]
+        return np.array(t, dtype=np.int32).reshape(-1, 2)
+    return dict(ids=ids, n=n, rows=rows.astype(np.int32), row_off=row_off, image=image.astype(np.int32),
+                image_in_domain=iid.astype(np.int32), img_off=img_off, ws_off=ws_off, wg_gather=wg(n), wg_scatter=wg(m))
 
 
 def multigrid(dom, max_levels=0, factor=2):

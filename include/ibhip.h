@@ -412,6 +412,31 @@ int ibh_fas_update(int64_t n, float omega, const float* r, const float* source, 
 int ibh_time_average_push(int64_t n, int nv, const float* Q, int64_t ldq, float* mu, float* sigma, int dt_form,
                           const float* dt, int64_t dt_numel, int64_t ldd, double eta, double tau, int flags);
 
+/* ---- domain call on device-resident global arrays: `(dom::Domain)(f, args...)` (ImmersedBoundary.jl:820-864) ------
+ * A plan holds the gather and scatter tables of all partitions of a Domain.  Per partition p (host arrays in
+ * `index_base`): domain[p] (n_domain[p] global rows, part.domain), image[p] and image_in_domain[p] (n_image[p] entries:
+ * part.image, part.image_in_domain).  Every index must be in range and the images disjoint (the scatter of all
+ * partitions is one launch); images need not cover all n_global rows -- uncovered rows are left as they are.
+ * The local arrays are stacked in ONE workspace per field: partition p's block starts at element nv * ws_off[p], where
+ * ws_off[p] = sum over q < p of (n_domain[q] rounded up to 64) (256-byte boundaries), and is column-major
+ * (n_domain[p], nv) with leading dimension n_domain[p].  A field of nv variables needs nv * ws_off[n_parts] elements.
+ *   ibh_domain_gather   ws[k][block_p + v*n_p + i] = src[k][domain_p[i] + v*ld[k]]                 (:835-840)
+ *   ibh_domain_scatter  dst[k][image_p[j] + v*ld[k]] = ws[k][block_p + v*n_p + image_in_domain_p[j]]  (:857-859)
+ * one launch each for all partitions and up to IBH_DOM_MAXF fields (more fields: one launch per IBH_DOM_MAXF).
+ * nfields, src/ws/dst (device pointers), nv and ld: host arrays of nfields entries.
+ * ibh_domain_plan_info: ws_off[0 .. n_parts] (n = n_parts + 1). */
+#define IBH_DOM_MAXF 8
+typedef struct ibh_domain_plan ibh_domain_plan;
+int ibh_domain_plan_create(ibh_domain_plan** out, int n_parts, const int32_t* const* domain, const int32_t* n_domain,
+                           const int32_t* const* image, const int32_t* const* image_in_domain, const int32_t* n_image,
+                           int64_t n_global, int index_base);
+int ibh_domain_plan_destroy(ibh_domain_plan* plan);
+int ibh_domain_plan_info(const ibh_domain_plan* plan, int64_t* ws_off, int n);
+int ibh_domain_gather(const ibh_domain_plan* plan, int nfields, const float* const* src, const int* nv,
+                      const int64_t* ld, float* const* ws);
+int ibh_domain_scatter(const ibh_domain_plan* plan, int nfields, const float* const* ws, const int* nv,
+                       const int64_t* ld, float* const* dst);
+
 /* FlowBC call (cfd.jl:243-300): boundary state [p T u v (w)] from the image-point primitives P and the unit normals.
  * u_inf: nd components, or ONE component (the normal velocity) when normal_flow != 0.  image_distances / dudn: both
  * null or both given (wall-function slip scaling :287-292); transpiration: scalar, or per-row array when

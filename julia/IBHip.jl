@@ -8,7 +8,7 @@
 #     src/ImmersedBoundary.jl:788) -- specialised here to upload ONCE and cache a native handle;
 #   * Julia multiple dispatch on the operators (src/ImmersedBoundary.jl:873-1157): methods for
 #     `HipPartition` + `HipArray` that `ccall` the library, including `divergent`, the tuple `face_gradient`, the
-#     `Accumulator` call and `impose_bc!` on device-resident arrays;
+#     `Accumulator` call, `impose_bc!` and the domain call `dom(f, args...)` on device-resident arrays;
 #   * `Base.Broadcast` on `HipArray`: every broadcast node (`+ - * / max min abs`, scalars, `.=`, `.-=`, `@.`)
 #     becomes one elementwise kernel (`ibh_ew_*`), so closures like test/advection.jl:67-83 run unchanged --
 #     tests/test_gpu_broadcast.py runs exactly that expression tree through the same C entry points from Python.
@@ -494,6 +494,78 @@ function impose_bc!(f, dom::Domain, bname::String, args::HipArray{Float32}...; k
         end
     end
     nothing
+end
+
+# ---------------------------------------------------------------------------------------------------
+# the domain call on device-resident global arrays (src/ImmersedBoundary.jl:820-864): one gather launch copies
+# `a[part.domain]` of every argument and partition into stacked workspaces, `f` runs per partition on aliases of
+# them, one scatter launch writes `a[part.image] .= local[part.image_in_domain]` -- snapshot semantics, the
+# deterministic form of the reference's `tmap` (include/ibhip.h, ibh_domain_*)
+# ---------------------------------------------------------------------------------------------------
+mutable struct HipDomainPlan
+    handle::Ptr{Cvoid}
+    ids::Vector{Any}         # partition keys, in call order
+    n::Vector{Int}           # rows of each partition (length(part.domain))
+    ws_off::Vector{Int64}    # partition p's block of a field of nv variables starts at element nv * ws_off[p]
+end
+
+function domain_plan(dom::Domain)
+    get!(_cache, (dom, :domain_plan)) do
+        ids = collect(keys(dom.partitions))
+        parts = [dom.partitions[i] for i in ids]
+        doms = [Int32.(p.domain) for p in parts]
+        imgs = [Int32.(p.image) for p in parts]
+        iids = [Int32.(p.image_in_domain) for p in parts]
+        nd = Int32[length(x) for x in doms]
+        ni = Int32[length(x) for x in imgs]
+        h = Ref{Ptr{Cvoid}}(C_NULL)
+        GC.@preserve doms imgs iids begin
+            check(ccall((:ibh_domain_plan_create, lib), Cint,
+                (Ptr{Ptr{Cvoid}}, Cint, Ptr{Ptr{Int32}}, Ptr{Int32}, Ptr{Ptr{Int32}}, Ptr{Ptr{Int32}}, Ptr{Int32}, Int64,
+                 Cint),
+                h, length(ids), Ptr{Int32}[pointer(x) for x in doms], nd, Ptr{Int32}[pointer(x) for x in imgs],
+                Ptr{Int32}[pointer(x) for x in iids], ni, length(dom), 1 #= Julia indices =#))
+        end
+        off = Vector{Int64}(undef, length(ids) + 1)
+        check(ccall((:ibh_domain_plan_info, lib), Cint, (Ptr{Cvoid}, Ptr{Int64}, Cint), h[], off, length(off)))
+        pl = HipDomainPlan(h[], ids, Int.(nd), off)
+        finalizer(x -> ccall((:ibh_domain_plan_destroy, lib), Cint, (Ptr{Cvoid},), x.handle), pl)
+        pl
+    end
+end
+
+# at least one positional HipArray: the zero-argument call stays the reference's method
+function (dom::Domain)(f, a::HipArray{Float32}, args::HipArray{Float32}...;
+                       conv_to_backend = nothing, conv_from_backend = nothing, n_threads::Int = 0, kwargs...)
+    (isnothing(conv_to_backend) && isnothing(conv_from_backend)) ||
+        error("domain call on HipArrays: no converters (the arrays are already on the device)")
+    arrs = (a, args...)
+    n = length(dom)
+    for x in arrs
+        size(x, 1) == n || throw(DimensionMismatch("domain call argument has $(size(x, 1)) rows, the domain $n cells"))
+    end
+    pl = domain_plan(dom)
+    k = length(arrs)
+    nvs = Cint[nv(x) for x in arrs]
+    lds = Int64[ld(x) for x in arrs]
+    ws = [HipArray{Float32, 1}(undef, (Int(nvs[j]) * Int(pl.ws_off[end]),)) for j = 1:k]
+    check(ccall((:ibh_domain_gather, lib), Cint,
+        (Ptr{Cvoid}, Cint, Ptr{Ptr{Cvoid}}, Ptr{Cint}, Ptr{Int64}, Ptr{Ptr{Cvoid}}),
+        pl.handle, k, Ptr{Cvoid}[x.ptr for x in arrs], nvs, lds, Ptr{Cvoid}[w.ptr for w in ws]))
+    conv = converter(dom)
+    results = map(enumerate(pl.ids)) do (p, i)
+        np = pl.n[p]
+        locals = map(1:k) do j   # (n_p, nv...) column-major with ld = n_p: aliases of the workspace
+            N = ndims(arrs[j])
+            HipArray{Float32, N}(ws[j].ptr + Int(nvs[j]) * pl.ws_off[p] * sizeof(Float32),
+                                 (np, size(arrs[j])[2:end]...), ws[j])
+        end
+        f(to_backend(dom.partitions[i], conv), locals...; kwargs...)
+    end
+    check(ccall((:ibh_domain_scatter, lib), Cint,
+        (Ptr{Cvoid}, Cint, Ptr{Ptr{Cvoid}}, Ptr{Cint}, Ptr{Int64}, Ptr{Ptr{Cvoid}}),
+        pl.handle, k, Ptr{Cvoid}[w.ptr for w in ws], nvs, lds, Ptr{Cvoid}[x.ptr for x in arrs]))
+    results
 end
 
 # ---------------------------------------------------------------------------------------------------
