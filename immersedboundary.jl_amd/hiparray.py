@@ -7,6 +7,7 @@ does the same through Python's operator protocol, so that the very same expressi
 entry points.  torch only owns the memory (column-major Float32).
 """
 import ctypes as C
+import struct
 import weakref
 
 import numpy as np
@@ -17,6 +18,13 @@ from ._lib import c_vp, call
 
 ADD, SUB, MUL, DIV, MAX, MIN, SUM = range(7)
 ABS, NEG, SQRT, COPY = 16, 17, 18, 19
+# the rest of Julia's elementwise Float32 math (include/ibhip.h); Bool values are Float32 0 / 1 on the device
+LT, LE, GT, GE, EQ, NE, AND, OR, POW, COPYSIGN, ATAN2, BMUL = range(64, 76)
+EXP, EXP2, LOG, LOG2, LOG10, SIN, COS, TANH, ATAN, SIGN, INV, NOT, POW0, SQR, CUBE, INVSQR = range(80, 96)
+CLAMP, IFELSE = 112, 113
+_PLAIN_BINARY = (ADD, SUB, MUL, DIV, MAX, MIN)
+_PLAIN_UNARY = (ABS, NEG, SQRT, COPY)
+_LITERAL_POW = {0: POW0, 1: COPY, 2: SQR, 3: CUBE, -1: INV, -2: INVSQR}   # Base.literal_pow
 
 
 _backend = None
@@ -30,8 +38,39 @@ def _B():
     return _backend
 
 
-PUSH_ARRAY, PUSH_SCALAR = 32, 33
-_MAX_PROG, _MAX_ARR, _MAX_SCAL, _MAX_DEPTH = 48, 8, 8, 8
+PUSH_ARRAY, PUSH_SCALAR, PUSH_ROW = 32, 33, 34
+_MAX_PROG, _MAX_ARR, _MAX_SCAL, _MAX_DEPTH = 48, 8, 32, 8
+
+
+def _f32bits(x):
+    return struct.pack("<f", x)
+
+
+class _Row:
+    """A host row vector (Julia's ``u∞'``): one Float32 per column of an ``(n, nv)`` operand.  It travels in the
+    program's scalar table (``IBH_EW_PUSH_ROW``), so it needs no upload and is captured by value in a graph."""
+
+    def __init__(self, values):
+        self.values = [float(v) for v in np.asarray(values, dtype=np.float32).ravel()]
+
+
+def _exact_compare(op, s):
+    """``x OP s`` for a Float32 x and a host scalar s compared exactly, as Julia compares Float32 with Float64
+    (``x > 0.1`` is not ``x > 0.1f0``): the same truth table as a comparison with one Float32 threshold."""
+    s = float(s)
+    with np.errstate(over="ignore"):
+        f = np.float32(s)
+    if np.isnan(s) or float(f) == s:
+        return op, float(f)
+    up = f if float(f) > s else np.nextafter(f, np.float32(np.inf))
+    down = f if float(f) < s else np.nextafter(f, np.float32(-np.inf))
+    if op in (GT, GE):                      # x > s  <=>  x > (largest Float32 below s)
+        return GT, float(down)
+    if op in (LT, LE):
+        return LT, float(up)
+    if op == EQ:                            # no Float32 equals s: false everywhere (x < -Inf)
+        return LT, float("-inf")
+    return NE, float("nan")                 # true everywhere (x != NaN)
 
 
 class HipArray:
@@ -47,10 +86,18 @@ class HipArray:
 
     def __init__(self, t):
         B = _B()
+        self._bool = False   # a Bool array (Julia's HipArray{Bool}): Float32 0 / 1 on the device
         if isinstance(t, HipArray):
+            self._bool = t._bool
             t = t.t
-        elif not isinstance(t, torch.Tensor):
-            t = B.hip(np.asarray(t))
+        elif isinstance(t, torch.Tensor):
+            if t.dtype == torch.bool:
+                t, self._bool = t.to(torch.float32), True
+        else:
+            t = np.asarray(t)
+            if t.dtype == np.bool_:
+                t, self._bool = t.astype(np.float32), True
+            t = B.hip(t)
         t, _, ld = B._field(t)
         if t.ndim == 2 and t.shape[1] > 1 and ld != t.shape[0]:
             t = t.T.contiguous().T  # broadcast kernels want the columns back to back
@@ -60,9 +107,10 @@ class HipArray:
         self._deps = weakref.WeakSet()  # pending expressions that read this array (materialised before it is written)
 
     @classmethod
-    def _pending(cls, expr, n, nv, ndim):
+    def _pending(cls, expr, n, nv, ndim, bool_=False):
         self = cls.__new__(cls)
         self._t = None
+        self._bool = bool_
         self._expr = expr
         self._meta = (n, nv, ndim)
         self._deps = weakref.WeakSet()
@@ -122,14 +170,15 @@ class HipArray:
                 if d is None:
                     return None
             else:
-                if x in scal:
-                    k = scal.index(x)
-                else:
-                    if len(scal) == _MAX_SCAL:
+                vals, push = (x.values, PUSH_ROW) if isinstance(x, _Row) else ([x], PUSH_SCALAR)
+                bits, have = [_f32bits(v) for v in vals], [_f32bits(v) for v in scal]   # -0.0 is not 0.0
+                k = next((i for i in range(len(have) - len(bits) + 1) if have[i:i + len(bits)] == bits), None)
+                if k is None:
+                    if len(scal) + len(vals) > _MAX_SCAL:
                         return None
-                    scal.append(x)
-                    k = len(scal) - 1
-                prog.append(PUSH_SCALAR | (k << 8))
+                    k = len(scal)
+                    scal.extend(vals)
+                prog.append(push | (k << 8))
                 d = 1
             depth = max(depth, width + d)
             width += 1
@@ -205,6 +254,7 @@ class HipArray:
 
     def copy(self):
         out = self.similar()
+        out._bool = self._bool
         _B()._stream()
         call("ibh_ew_unary", COPY, self.t.numel(), c_vp(self.t.data_ptr()), c_vp(out.t.data_ptr()))
         return out
@@ -214,6 +264,7 @@ class HipArray:
         if self.ndim != 2:
             raise IndexError("col() of a vector")
         v = HipArray(self.t[:, j - 1])
+        v._bool = self._bool
         v._deps = self._deps   # a write through either name flushes the readers of both
         return v
 
@@ -225,7 +276,18 @@ class HipArray:
         return self
 
     def to_host(self):
-        return _B().to_host(self.t)
+        h = _B().to_host(self.t)
+        return h != 0 if self._bool else h
+
+    @property
+    def dtype(self):
+        return np.bool_ if self._bool else np.float32
+
+    def __bool__(self):
+        if self._bool:
+            raise TypeError("the truth value of a Bool HipArray is ambiguous (use it in ifelse or copy it back with "
+                            "to_host)")
+        return len(self) > 0
 
     def __getitem__(self, i):
         raise TypeError("scalar indexing of a HipArray; copy it back with to_host()")
@@ -237,22 +299,34 @@ class HipArray:
             return x
         if isinstance(x, (int, float, np.floating, np.integer)):
             return float(np.float32(x))
+        if isinstance(x, (list, tuple, np.ndarray)) and np.ndim(x) == 1:
+            return _Row(x)   # a host vector broadcasts along the rows: Julia's `u∞'`
         raise TypeError(f"cannot broadcast a HipArray with {type(x).__name__} (convert with HipArray(...))")
 
-    def _binary(self, op, other, reverse=False, out=None):
-        a, b = (other, self) if reverse else (self, other)
-        a, b = self._operand(a), self._operand(b)
-        fields = [f for f in (a, b) if isinstance(f, HipArray)]
+    @staticmethod
+    def _shape(operands):
+        fields = [f for f in operands if isinstance(f, HipArray)]
+        rows = [len(r.values) for r in operands if isinstance(r, _Row)]
         n = fields[0].n
-        nv = max(f.nv for f in fields)
+        nv = max([f.nv for f in fields] + rows)
         for f in fields:
             if f.n != n or f.nv not in (1, nv):
                 raise ValueError(f"shapes {tuple(x.shape for x in fields)} do not broadcast")
-        ndim = 1 if nv == 1 and all(f.ndim == 1 for f in fields) else 2
+        if any(r != nv for r in rows):
+            raise ValueError(f"a row vector of length {rows} does not broadcast with {nv} columns")
+        ndim = 1 if nv == 1 and not rows and all(f.ndim == 1 for f in fields) else 2
+        return n, nv, ndim
+
+    def _node(self, op, operands, bool_=False, out=None):
+        """The broadcast node ``op(operands...)`` (operands already typed: HipArray, Float32 scalar or row)."""
+        n, nv, ndim = self._shape(operands)
         if out is not None and (out.n != n or out.nv != nv):
             raise ValueError("in-place broadcast changes the shape")
+        if out is not None and out._bool != bool_:
+            raise TypeError("in-place broadcast changes the element type (Bool / Float32)")
+        plain = op in _PLAIN_BINARY + _PLAIN_UNARY and not any(isinstance(x, _Row) for x in operands)
         if HipArray.fuse:
-            node = HipArray._pending((op, a, b), n, nv, ndim)
+            node = HipArray._pending((op, *operands), n, nv, ndim, bool_)
             if out is None:
                 return node
             # `out .= out op other`: the fused expression straight into out's memory
@@ -275,24 +349,56 @@ class HipArray:
         B = _B()
         if out is None:
             out = HipArray(B.colmajor_empty(n) if ndim == 1 else B.colmajor_empty(n, nv))
+            out._bool = bool_
         else:
             out._flush_readers()
-        fa, sa = (a, 0.0) if isinstance(a, HipArray) else (None, a)
-        fb, sb = (b, 0.0) if isinstance(b, HipArray) else (None, b)
-        B._stream()
-        call("ibh_ew_binary", op, n, nv, c_vp(fa.t.data_ptr()) if fa is not None else c_vp(None),
-             fa.nv if fa is not None else 0, C.c_float(sa), c_vp(fb.t.data_ptr()) if fb is not None else c_vp(None),
-             fb.nv if fb is not None else 0, C.c_float(sb), c_vp(out.t.data_ptr()))
+        if plain and len(operands) == 2:
+            a, b = operands
+            fa, sa = (a, 0.0) if isinstance(a, HipArray) else (None, a)
+            fb, sb = (b, 0.0) if isinstance(b, HipArray) else (None, b)
+            B._stream()
+            call("ibh_ew_binary", op, n, nv, c_vp(fa.t.data_ptr()) if fa is not None else c_vp(None),
+                 fa.nv if fa is not None else 0, C.c_float(sa), c_vp(fb.t.data_ptr()) if fb is not None else c_vp(None),
+                 fb.nv if fb is not None else 0, C.c_float(sb), c_vp(out.t.data_ptr()))
+        elif plain:
+            B._stream()
+            call("ibh_ew_unary", op, self.t.numel(), c_vp(self.t.data_ptr()), c_vp(out.t.data_ptr()))
+        else:
+            # any other node: a one-node program (the same device code as inside a fused tree: the same bits)
+            HipArray._pending((op, *operands), n, nv, ndim, bool_)._evaluate_into(out.t)
         return out
 
+    def _binary(self, op, other, reverse=False, out=None):
+        a, b = (other, self) if reverse else (self, other)
+        a, b = self._operand(a), self._operand(b)
+        ba, bb = _isbool(a), _isbool(b)
+        if op in (AND, OR):
+            if not (ba and bb):
+                raise TypeError("& and | take Bool operands")
+            return self._node(op, (a, b), True, out)
+        if op in (LT, LE, GT, GE, EQ, NE):
+            return self._node(op, (a, b), True, out)
+        if ba and bb:
+            raise TypeError("arithmetic between two Bool arrays (Julia gives Int): multiply one by 1f0 first")
+        if op == MUL and (ba or bb):   # Julia's strong zero: ifelse(b, x, copysign(0, x))
+            return self._node(BMUL, (a, b) if ba else (b, a), False, out)
+        if (ba or bb) and op in (POW, COPYSIGN, ATAN2):
+            raise TypeError("math functions take Float32 operands (multiply a Bool by 1f0 first)")
+        return self._node(op, (a, b), False, out)
+
     def _unary(self, op):
-        if HipArray.fuse:
-            n, nv, ndim = self._meta
-            return HipArray._pending((op, self), n, nv, ndim)
-        out = self.similar()
-        _B()._stream()
-        call("ibh_ew_unary", op, self.t.numel(), c_vp(self.t.data_ptr()), c_vp(out.t.data_ptr()))
-        return out
+        if self._bool and op not in (ABS, COPY, NOT):
+            raise TypeError("math functions take Float32 operands (multiply a Bool by 1f0 first)")
+        if op == NOT and not self._bool:
+            raise TypeError("! / ~ takes a Bool array")
+        return self._node(op, (self,), self._bool)
+
+    def _compare(self, op, other):
+        if isinstance(other, (bool, np.bool_)):
+            other = float(other)
+        if isinstance(other, (int, float, np.floating, np.integer)) and not isinstance(other, np.float32):
+            op, other = _exact_compare(op, other)
+        return self._binary(op, other)
 
     def __add__(self, o): return self._binary(ADD, o)
     def __radd__(self, o): return self._binary(ADD, o, reverse=True)
@@ -308,6 +414,28 @@ class HipArray:
     def __itruediv__(self, o): return self._binary(DIV, o, out=self)
     def __neg__(self): return self._unary(NEG)
     def __abs__(self): return self._unary(ABS)
+    # comparisons give Bool arrays; == / != stay Python's identity (the arrays live in WeakSets): use eq / ne
+    def __lt__(self, o): return self._compare(LT, o)
+    def __le__(self, o): return self._compare(LE, o)
+    def __gt__(self, o): return self._compare(GT, o)
+    def __ge__(self, o): return self._compare(GE, o)
+    def __and__(self, o): return self._binary(AND, o)
+    def __rand__(self, o): return self._binary(AND, o, reverse=True)
+    def __or__(self, o): return self._binary(OR, o)
+    def __ror__(self, o): return self._binary(OR, o, reverse=True)
+    def __invert__(self): return self._unary(NOT)   # Julia's `!` on a Bool
+
+    def __pow__(self, p):
+        """``x .^ p``: a Python int exponent is Julia's literal power (``Base.literal_pow``: x^2 = x*x, x^-1 = inv(x),
+        ...); any other exponent is Julia's Float32 ``^``, evaluated in double and rounded once."""
+        if isinstance(p, (int, np.integer)) and not isinstance(p, (bool, np.bool_)):
+            if int(p) in _LITERAL_POW:
+                return self._unary(_LITERAL_POW[int(p)])
+            return self._binary(POW, float(p))
+        return self._binary(POW, p)
+
+    def __rpow__(self, base):
+        return self._binary(POW, base, reverse=True)
 
     def maximum_with(self, o):
         """``max.(a, o)``."""
@@ -333,8 +461,84 @@ class HipArray:
     def minimum(self):
         return self._reduce(MIN)
 
-    def sum(self):
-        return self._reduce(SUM)
+    def sum(self, dims=None):
+        """``sum(a)``, or ``sum(a; dims = 2)``: the columns of each row added in order ((a1 + a2) + a3 ..., Julia's
+        order), one launch; in Julia the result is ``(n, 1)``, here ``(n,)``."""
+        if dims is None:
+            return self._reduce(SUM)
+        if dims != 2:
+            raise ValueError("sum(dims=...) supports dims = 2 (along the rows)")
+        if self._bool:
+            raise TypeError("sum of a Bool array (Julia gives Int): multiply it by 1f0 first")
+        out = HipArray(_B().colmajor_empty(self.n))
+        _B()._stream()
+        call("ibh_ew_reduce_rows", self.n, self.nv, c_vp(self.t.data_ptr()), c_vp(out.t.data_ptr()))
+        return out
+
+
+def _isbool(x):
+    return isinstance(x, HipArray) and x._bool
+
+
+def _fn1(op):
+    def f(x):
+        return HipArray._operand(x)._unary(op) if isinstance(x, HipArray) else _host1[op](x)
+    return f
+
+
+_host1 = {EXP: np.exp, EXP2: np.exp2, LOG: np.log, LOG2: np.log2, LOG10: np.log10, SIN: np.sin, COS: np.cos,
+          TANH: np.tanh, ATAN: np.arctan, SIGN: np.sign, INV: lambda x: 1 / x}
+# Julia's elementwise functions by their Julia names, on HipArrays (host numbers fall through to numpy)
+exp, exp2, log, log2, log10 = _fn1(EXP), _fn1(EXP2), _fn1(LOG), _fn1(LOG2), _fn1(LOG10)
+sin, cos, tanh, sign, inv = _fn1(SIN), _fn1(COS), _fn1(TANH), _fn1(SIGN), _fn1(INV)
+
+
+def _first(*xs):
+    for x in xs:
+        if isinstance(x, HipArray):
+            return x
+    raise TypeError("expected a HipArray operand")
+
+
+def atan(y, x=None):
+    """``atan(y)`` or ``atan(y, x)`` (the quadrant-aware two-argument form)."""
+    if x is None:
+        return _fn1(ATAN)(y)
+    h = _first(y, x)
+    return h._binary(ATAN2, x) if y is h else h._binary(ATAN2, y, reverse=True)
+
+
+def copysign(x, y):
+    h = _first(x, y)
+    return h._binary(COPYSIGN, y) if x is h else h._binary(COPYSIGN, x, reverse=True)
+
+
+def eq(a, b):
+    """``a .== b`` (Bool array): HipArray keeps Python's identity ``==``."""
+    h = _first(a, b)
+    return h._compare(EQ, b if a is h else a)
+
+
+def ne(a, b):
+    """``a .!= b`` (Bool array)."""
+    h = _first(a, b)
+    return h._compare(NE, b if a is h else a)
+
+
+def clamp(x, lo, hi):
+    """``clamp.(x, lo, hi)`` = ``ifelse(x > hi, hi, ifelse(x < lo, lo, x))``: a NaN in x stays NaN."""
+    ops = tuple(HipArray._operand(v) for v in (x, lo, hi))
+    if any(_isbool(v) for v in ops):
+        raise TypeError("clamp takes Float32 operands")
+    return _first(*ops)._node(CLAMP, ops, False)
+
+
+def ifelse(c, a, b):
+    """``ifelse.(c, a, b)``; c must be a Bool array (a comparison)."""
+    if not _isbool(c):
+        raise TypeError("ifelse needs a Bool condition (a comparison), not a Float32 array or a number")
+    ops = (c, HipArray._operand(a), HipArray._operand(b))
+    return c._node(IFELSE, ops, _isbool(ops[1]) and _isbool(ops[2]))
 
 
 def unwrap(x):

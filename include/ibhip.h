@@ -117,6 +117,29 @@ int ibh_ew_reduce(int op, int64_t total, const float* a, float* out_device);
 enum { IBH_EW_PUSH_ARRAY = 32, IBH_EW_PUSH_SCALAR = 33 };
 int ibh_ew_eval(int64_t n, int nv, int nprog, const int32_t* prog, int narr, const float* const* arrays,
                 const int32_t* arr_nv, int nscal, const float* scalars, float* out);
+/* The rest of Julia's elementwise Float32 math, also taken by ibh_ew_eval.  A program that uses any of these opcodes
+ * (or more than 8 scalars) runs on an interpreter instantiation of its own, so the kernels of the opcodes above are
+ * unchanged; its limits are 48 instructions, 8 arrays, 32 scalars and stack depth 8.  Bool values are Float32 0 / 1.
+ *   binary   (a, b -> a OP b):  LT LE GT GE EQ NE (IEEE, Bool result), AND OR (Bool operands), POW (double pow,
+ *            rounded once), COPYSIGN, ATAN2 (atan(a, b) in double), BMUL (a is a Bool: ifelse(a, b, copysign(0, b)))
+ *   unary    EXP EXP2 LOG LOG2 LOG10 SIN COS TANH ATAN (in double, rounded once), SIGN (keeps +-0 and NaN),
+ *            INV (1 / x), NOT (Bool), and Base.literal_pow: POW0 (= 1, also for NaN), SQR (x*x), CUBE ((x*x)*x),
+ *            INVSQR ((1/x) * (1/x))
+ *   ternary  (a, b, c): CLAMP (ifelse(a > c, c, ifelse(a < b, b, a)): NaN stays NaN), IFELSE (a != 0 ? b : c)
+ *   IBH_EW_PUSH_ROW (operand = k): a row vector of nv values scalars[k .. k + nv - 1], value scalars[k + j] in column j
+ *            (Julia's `u_inf'` broadcast down the rows of an (n, nv) field)
+ * Rounded operations: NaN where Julia throws a DomainError (log of a negative number, a negative base under a
+ * non-integer exponent). */
+enum { IBH_EW_PUSH_ROW = 34 };
+enum { IBH_EW_LT = 64, IBH_EW_LE = 65, IBH_EW_GT = 66, IBH_EW_GE = 67, IBH_EW_EQ = 68, IBH_EW_NE = 69, IBH_EW_AND = 70,
+       IBH_EW_OR = 71, IBH_EW_POW = 72, IBH_EW_COPYSIGN = 73, IBH_EW_ATAN2 = 74, IBH_EW_BMUL = 75 };
+enum { IBH_EW_EXP = 80, IBH_EW_EXP2 = 81, IBH_EW_LOG = 82, IBH_EW_LOG2 = 83, IBH_EW_LOG10 = 84, IBH_EW_SIN = 85,
+       IBH_EW_COS = 86, IBH_EW_TANH = 87, IBH_EW_ATAN = 88, IBH_EW_SIGN = 89, IBH_EW_INV = 90, IBH_EW_NOT = 91,
+       IBH_EW_POW0 = 92, IBH_EW_SQR = 93, IBH_EW_CUBE = 94, IBH_EW_INVSQR = 95 };
+enum { IBH_EW_CLAMP = 112, IBH_EW_IFELSE = 113 };
+/* `sum(a; dims = 2)` of a column-major (n, nv) field: out[i] = ((a[i, 1] + a[i, 2]) + a[i, 3]) + ..., the columns in
+ * order as Julia adds them; one launch, no host sync.  `out` (n values) must not overlap `a` unless nv == 1. */
+int ibh_ew_reduce_rows(int64_t n, int nv, const float* a, float* out);
 
 /* Measurement switches of the kernels (A/B runs inside one process, no effect on results beyond rounding):
  *   "quad_variant"  variant of the quad / 3-D sweeps (4: wave time stamps; 512, 518: round-2 3-D kernels; ...)

@@ -9,7 +9,8 @@
 #   * Julia multiple dispatch on the operators (src/ImmersedBoundary.jl:873-1157): methods for
 #     `HipPartition` + `HipArray` that `ccall` the library, including `divergent`, the tuple `face_gradient`, the
 #     `Accumulator` call, `impose_bc!` and the domain call `dom(f, args...)` on device-resident arrays;
-#   * `Base.Broadcast` on `HipArray`: every broadcast node (`+ - * / max min abs`, scalars, `.=`, `.-=`, `@.`)
+#   * `Base.Broadcast` on `HipArray`: every broadcast node (`+ - * / max min abs`, powers, exp/log/trig, clamp, ifelse,
+#     comparisons to `HipArray{Bool}`, scalars, row vectors `u∞'`, `.=`, `.-=`, `@.`)
 #     becomes one elementwise kernel (`ibh_ew_*`), so closures like test/advection.jl:67-83 run unchanged --
 #     tests/test_gpu_broadcast.py runs exactly that expression tree through the same C entry points from Python.
 #
@@ -26,6 +27,7 @@ import ImmersedBoundary: Partition, Boundary, Domain, Accumulator, at_owners, at
 import ImmersedBoundary.CFD: JST_sensor
 import ImmersedBoundary.ArrayBackends: to_backend
 import ImmersedBoundary: CFD, Turbulence, Solver
+import LinearAlgebra
 
 const lib = get(ENV, "IBHIP_LIB", "libibhip")
 
@@ -45,7 +47,7 @@ mutable struct HipArray{T, N} <: AbstractArray{T, N}
     parent::Any   # the array a column view aliases (kept alive), or nothing for an owning array
     function HipArray{T, N}(::UndefInitializer, dims::NTuple{N, Int}) where {T, N}
         p = Ref{Ptr{Cvoid}}(C_NULL)
-        check(ccall((:ibh_malloc, lib), Cint, (Ptr{Ptr{Cvoid}}, Csize_t), p, max(prod(dims), 1) * sizeof(T)))
+        check(ccall((:ibh_malloc, lib), Cint, (Ptr{Ptr{Cvoid}}, Csize_t), p, max(prod(dims), 1) * _esize(T)))
         a = new{T, N}(p[], dims, nothing)
         finalizer(x -> ccall((:ibh_free, lib), Cint, (Ptr{Cvoid},), x.ptr), a)
         a
@@ -54,12 +56,14 @@ mutable struct HipArray{T, N} <: AbstractArray{T, N}
     HipArray{T, N}(ptr::Ptr{Cvoid}, dims::NTuple{N, Int}, parent) where {T, N} = new{T, N}(ptr, dims, parent)
 end
 HipArray{T}(u::UndefInitializer, dims::Int...) where {T} = HipArray{T, length(dims)}(u, dims)
+# HipArray{Bool}: the result of a comparison; stored as Float32 0 / 1, the value the broadcast kernels compute with
+_esize(::Type{T}) where {T} = T === Bool ? sizeof(Float32) : sizeof(T)
 Base.size(a::HipArray) = a.dims
 Base.similar(a::HipArray{T}, ::Type{S}, dims::Dims) where {T, S} = HipArray{S, length(dims)}(undef, dims)
 Base.getindex(::HipArray, i...) = error("scalar indexing of a HipArray; copy it back with Array(a)")
 # columns of a column-major (n, nv) field are contiguous: `@view C[:, dim]` / `C[:, dim]` alias them
 Base.view(a::HipArray{T, 2}, ::Colon, j::Integer) where {T} =
-    HipArray{T, 1}(a.ptr + (j - 1) * size(a, 1) * sizeof(T), (size(a, 1),), a)
+    HipArray{T, 1}(a.ptr + (j - 1) * size(a, 1) * _esize(T), (size(a, 1),), a)
 Base.getindex(a::HipArray{T, 2}, ::Colon, j::Integer) where {T} = copy(view(a, :, j))
 
 "`conv_to_backend`: host array -> device array."
@@ -68,8 +72,20 @@ function hip(a::Array{T, N}) where {T, N}
     check(ccall((:ibh_h2d, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Csize_t), d.ptr, a, sizeof(a)))
     d
 end
+function hip(a::Array{Bool, N}) where {N}
+    d = HipArray{Bool, N}(undef, size(a))
+    h = Float32.(a)
+    check(ccall((:ibh_h2d, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Csize_t), d.ptr, h, sizeof(h)))
+    d
+end
 hip(a::AbstractArray) = hip(Array(a))
 hip(a::HipArray) = a
+
+function Base.Array(d::HipArray{Bool, N}) where {N}
+    a = Array{Float32, N}(undef, d.dims)
+    check(ccall((:ibh_d2h, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Csize_t), a, d.ptr, sizeof(a)))
+    a .!= 0
+end
 
 "`conv_from_backend`: device array -> host array."
 function Base.Array(d::HipArray{T, N}) where {T, N}
@@ -95,19 +111,35 @@ converter(dom::Domain) = HipConv(dom.mesh.block_size)
 # ---------------------------------------------------------------------------------------------------
 const EW_ADD, EW_SUB, EW_MUL, EW_DIV, EW_MAX, EW_MIN, EW_SUM = Cint.(0:6)
 const EW_ABS, EW_NEG, EW_SQRT, EW_COPY = Cint.(16:19)
-const _binop = IdDict{Any, Cint}(+ => EW_ADD, - => EW_SUB, * => EW_MUL, / => EW_DIV, max => EW_MAX, min => EW_MIN)
-const _unop = IdDict{Any, Cint}(abs => EW_ABS, - => EW_NEG, sqrt => EW_SQRT, identity => EW_COPY, + => EW_COPY)
+const EW_LT, EW_LE, EW_GT, EW_GE, EW_EQ, EW_NE, EW_AND, EW_OR, EW_POW, EW_COPYSIGN, EW_ATAN2, EW_BMUL = Cint.(64:75)
+const EW_EXP, EW_EXP2, EW_LOG, EW_LOG2, EW_LOG10, EW_SIN, EW_COS, EW_TANH, EW_ATAN, EW_SIGN, EW_INV, EW_NOT, EW_POW0, EW_SQR, EW_CUBE, EW_INVSQR = Cint.(80:95)
+const EW_CLAMP, EW_IFELSE = Cint(112), Cint(113)
+const _binop = IdDict{Any, Cint}(+ => EW_ADD, - => EW_SUB, * => EW_MUL, / => EW_DIV, max => EW_MAX, min => EW_MIN,
+    (<) => EW_LT, (<=) => EW_LE, (>) => EW_GT, (>=) => EW_GE, (==) => EW_EQ, (!=) => EW_NE, (&) => EW_AND,
+    (|) => EW_OR, (^) => EW_POW, copysign => EW_COPYSIGN, atan => EW_ATAN2)
+const _unop = IdDict{Any, Cint}(abs => EW_ABS, - => EW_NEG, sqrt => EW_SQRT, identity => EW_COPY, + => EW_COPY,
+    exp => EW_EXP, exp2 => EW_EXP2, log => EW_LOG, log2 => EW_LOG2, log10 => EW_LOG10, sin => EW_SIN, cos => EW_COS,
+    tanh => EW_TANH, atan => EW_ATAN, sign => EW_SIGN, inv => EW_INV, (!) => EW_NOT)
+const _ternop = IdDict{Any, Cint}(clamp => EW_CLAMP, ifelse => EW_IFELSE)
+# Base.literal_pow(^, x, Val(p)) -- what `x .^ 2` lowers to -- for the exponents it defines by products
+const _litpow = Dict{Int, Cint}(0 => EW_POW0, 1 => EW_COPY, 2 => EW_SQR, 3 => EW_CUBE, -1 => EW_INV, -2 => EW_INVSQR)
+const _cmps = (EW_LT, EW_LE, EW_GT, EW_GE, EW_EQ, EW_NE)
 
 struct HipStyle <: Base.Broadcast.BroadcastStyle end
 Base.Broadcast.BroadcastStyle(::Type{<:HipArray}) = HipStyle()
 Base.Broadcast.BroadcastStyle(::HipStyle, ::Base.Broadcast.DefaultArrayStyle{0}) = HipStyle()   # scalars
-Base.Broadcast.BroadcastStyle(::HipStyle, ::Base.Broadcast.BroadcastStyle) =
-    error("broadcast between a HipArray and a host array: convert it with IBHip.hip first")
+_hostarray() = error("broadcast between a HipArray and a host array: convert it with IBHip.hip first")
+# host row vectors `u∞'` (1 x nv) broadcast down the rows; so 2-D host operands enter HipStyle, and every one that is not
+# a row vector is rejected by `_push!` / `_operand` / `_eval` below with the message above
+Base.Broadcast.BroadcastStyle(::HipStyle, ::Base.Broadcast.DefaultArrayStyle{2}) = HipStyle()
+const _HostRow = Union{LinearAlgebra.Adjoint{<:Real, <:AbstractVector}, LinearAlgebra.Transpose{<:Real, <:AbstractVector}}
+Base.Broadcast.BroadcastStyle(::HipStyle, ::Base.Broadcast.BroadcastStyle) = _hostarray()
 
 _rows(a::HipArray) = size(a, 1)
 _operand(a::HipArray) = (a.ptr, nv(a), 0f0)
 _operand(x::Number) = (C_NULL, Cint(0), Float32(x))
 _operand(x::Base.RefValue) = _operand(x[])
+_operand(x::AbstractArray) = _hostarray()
 
 "Evaluate one node: operands are HipArrays (same shape, or a column vector over the columns) or scalars."
 function _ew(op, a, b, out::Union{HipArray, Nothing} = nothing)
@@ -136,19 +168,36 @@ end
 # recursive evaluation of a (possibly nested, `@.`-fused) Broadcasted tree; n-ary + * max min fold left like Julia does
 # (`max.(a, b, 1f-7)` of the reference's MUSCL, src/ImmersedBoundary.jl:1113-1157)
 _eval(x) = x
-_eval(bc::Base.Broadcast.Broadcasted) = _node(bc.f, map(_eval, bc.args)...)
-_node(f, a) = a isa HipArray ? _ew(f, a) : f(a)
-_node(f, a, b) = _ew(f, a, b)
+function _eval(bc::Base.Broadcast.Broadcasted)
+    args = map(_eval, bc.args)
+    any(x -> x isa AbstractArray && !(x isa Union{HipArray, _HostRow}), args) && _hostarray()
+    _node(bc.f, args...)
+end
+_node(f, a) = a isa HipArray ? (_oldop(f, a) ? _ew(f, a) : _one(f, a)) : f(_unref(a))
+_node(f, a, b) = any(x -> x isa HipArray, (a, b)) && !_oldop(f, a, b) ? _one(f, a, b) : _ew(f, a, b)
+_node(f, a, b, c) = any(x -> x isa HipArray, (a, b, c)) ? _one(f, a, b, c) : f(_unref(a), _unref(b), _unref(c))
+_node(f::typeof(Base.literal_pow), p, x, v) = x isa HipArray ? _one(f, p, x, v) : f(_unref(p), x, _unref(v))
+_oldop(f, args...) = (length(args) == 1 ? haskey(_unop, f) && _unop[f] <= EW_COPY : haskey(_binop, f) && _binop[f] <= EW_MIN) &&
+    all(x -> _eltype(x) !== Bool && !(x isa _HostRow), args)
+"One node as a one-instruction ibh_ew_eval program: the same device code a fused tree runs, so the same bits."
+function _one(f, args...)
+    r = _fused(Base.Broadcast.Broadcasted{HipStyle}(f, args), nothing)
+    isnothing(r) && error("IBHip broadcast: unsupported operation $f on $(map(typeof, args))")
+    r
+end
 _node(f::Union{typeof(+), typeof(*), typeof(max), typeof(min)}, a, b, c, rest...) = _node(f, _node(f, a, b), c, rest...)
+_node(f::Union{typeof(+), typeof(*), typeof(max), typeof(min)}, a, b, c) = _node(f, _node(f, a, b), c)
 
 # ---- the whole (fused) Broadcasted tree as ONE launch: a postfix program for ibh_ew_eval (at most 48 instructions,
 # 8 arrays, 8 scalars, stack depth 8); n-ary + and * fold left like Julia does.  `nothing` = does not fit / unsupported
 # node: the caller falls back to the node-by-node evaluation above (same bits).
 const EW_PUSH_ARRAY, EW_PUSH_SCALAR = Cint(32), Cint(33)
+const EW_PUSH_ROW = Cint(34)
 mutable struct _Prog
     code::Vector{Int32}
     arrs::Vector{HipArray}
     scal::Vector{Float32}
+    row::Int   # length of a row-vector operand (0: none): the number of columns of the result
 end
 function _push!(P::_Prog, a::HipArray)
     k = findfirst(x -> x.ptr == a.ptr && size(x) == size(a), P.arrs)
@@ -162,46 +211,136 @@ function _push!(P::_Prog, a::HipArray)
 end
 function _push!(P::_Prog, x::Number)
     v = Float32(x)
-    k = findfirst(==(v), P.scal)
+    k = findfirst(y -> reinterpret(UInt32, y) == reinterpret(UInt32, v), P.scal)   # -0f0 is not 0f0
     if isnothing(k)
-        length(P.scal) == 8 && return nothing
+        length(P.scal) == 32 && return nothing
         push!(P.scal, v)
         k = length(P.scal)
     end
     push!(P.code, EW_PUSH_SCALAR | Int32((k - 1) << 8))
     1
 end
+function _push!(P::_Prog, x::_HostRow)   # `u∞'`: nv scalars, the one of column j in column j
+    v = Float32.(vec(collect(x)))
+    length(P.scal) + length(v) > 32 && return nothing
+    push!(P.code, EW_PUSH_ROW | Int32(length(P.scal) << 8))
+    append!(P.scal, v)
+    P.row = length(v)
+    1
+end
 _push!(P::_Prog, x::Base.RefValue) = _push!(P, x[])
+_push!(P::_Prog, x::AbstractArray) = _hostarray()   # (HipArray and row vectors have their own methods)
 _push!(P::_Prog, x) = nothing
+
+# element types as Julia's broadcast sees them: Float32 arithmetic, Bool comparisons
+_eltype(a::HipArray{T}) where {T} = T
+_eltype(x::Number) = typeof(x)
+_eltype(x::Base.RefValue) = _eltype(x[])
+_eltype(x::_HostRow) = eltype(x)
+_eltype(bc::Base.Broadcast.Broadcasted) = Base.Broadcast.combine_eltypes(bc.f, bc.args)
+_eltype(x) = Any
+_unref(x) = x isa Base.RefValue ? x[] : x
+# the value of a subtree without device operands (`s > 0.1`, `M∞^2` for host numbers), computed on the host exactly as
+# Julia does; `nothing` if the subtree reads a device array or a host array
+_hostval(x::Number) = x
+_hostval(x::Base.RefValue) = x[] isa Union{Number, Function, Val} ? x[] : nothing
+function _hostval(bc::Base.Broadcast.Broadcasted)
+    vals = map(_hostval, bc.args)
+    (any(isnothing, vals) || !any(v -> v isa Number, vals)) && return nothing
+    bc.f(vals...)
+end
+_hostval(x) = nothing
+
+"`x OP s` for Float32 x and Float64 s, exactly as Julia compares them: one Float32 threshold with the same truth table."
+function _exact_cmp(code::Cint, s::Float64)
+    f = Float32(s)
+    (isnan(s) || Float64(f) == s) && return code, f
+    up, down = Float64(f) > s ? f : nextfloat(f), Float64(f) < s ? f : prevfloat(f)
+    code in (EW_GT, EW_GE) && return EW_GT, down
+    code in (EW_LT, EW_LE) && return EW_LT, up
+    code == EW_EQ ? (EW_LT, -Inf32) : (EW_NE, NaN32)   # never equal / always different
+end
+const _flip = Dict(EW_LT => EW_GT, EW_LE => EW_GE, EW_GT => EW_LT, EW_GE => EW_LE, EW_EQ => EW_EQ, EW_NE => EW_NE)
+
 function _push!(P::_Prog, bc::Base.Broadcast.Broadcasted)
+    hv = _hostval(bc)
+    isnothing(hv) || return _push!(P, hv)   # no device operand: one scalar (a Bool is 0 / 1)
     f, args = bc.f, bc.args
+    if f === Base.literal_pow && length(args) == 3 && _unref(args[1]) === (^) && _unref(args[3]) isa Val
+        p = typeof(_unref(args[3])).parameters[1]
+        _eltype(args[2]) === Bool && throw(TypeError(:literal_pow, "a Float32 base", Float32, Bool))
+        if haskey(_litpow, p)
+            d = _push!(P, args[2])
+            isnothing(d) && return nothing
+            push!(P.code, _litpow[p])
+            return d
+        end
+        f, args = (^), (args[2], Float32(p))   # any other integer exponent: Float32 ^, in double, rounded once
+    end
     if length(args) == 1
         haskey(_unop, f) || return nothing
+        isb = _eltype(args[1]) === Bool
+        (f === (!)) == isb || f in (abs, identity, +) ||
+            throw(TypeError(Symbol(f), "a Float32 operand (a Bool one only for !)", Float32, _eltype(args[1])))
         d = _push!(P, args[1])
         isnothing(d) && return nothing
         push!(P.code, _unop[f])
         return d
     end
+    if length(args) == 3 && haskey(_ternop, f)
+        f === ifelse && _eltype(args[1]) !== Bool && throw(TypeError(:ifelse, "a Bool condition", Bool, _eltype(args[1])))
+        f === clamp && any(a -> _eltype(a) === Bool, args) && throw(TypeError(:clamp, "Float32 operands", Float32, Bool))
+        depth = 0
+        for (w, a) in enumerate(args)
+            d = _push!(P, a)
+            isnothing(d) && return nothing
+            depth = max(depth, w - 1 + d)
+        end
+        push!(P.code, _ternop[f])
+        return depth
+    end
     (haskey(_binop, f) && (length(args) == 2 || f === (+) || f === (*) || f === max || f === min)) || return nothing
+    code = _binop[f]
+    if length(args) == 2
+        ta, tb = _eltype(args[1]), _eltype(args[2])
+        if code in _cmps   # a Float64 scalar (or host subtree) is compared exactly; at most one side is host-only here
+            a, b = _hostval(args[1]), _hostval(args[2])
+            b isa Float64 && ((code, t) = _exact_cmp(code, b); args = (args[1], t))
+            a isa Float64 && ((code, t) = _exact_cmp(_flip[code], a); args = (args[2], t))
+        elseif code in (EW_AND, EW_OR)
+            (ta === Bool && tb === Bool) || throw(TypeError(Symbol(f), "Bool operands", Bool, ta === Bool ? tb : ta))
+        elseif ta === Bool && tb === Bool
+            throw(TypeError(Symbol(f), "at most one Bool operand (two Bools give Int)", Float32, Bool))
+        elseif code == EW_MUL && (ta === Bool || tb === Bool)   # Bool * Float: the strong zero
+            code, args = EW_BMUL, ta === Bool ? args : (args[2], args[1])
+        elseif code in (EW_POW, EW_COPYSIGN, EW_ATAN2) && (ta === Bool || tb === Bool)
+            throw(TypeError(Symbol(f), "Float32 operands", Float32, Bool))
+        end
+    end
     depth = _push!(P, args[1])
     isnothing(depth) && return nothing
     for a in args[2:end]
         d = _push!(P, a)
         isnothing(d) && return nothing
         depth = max(depth, 1 + d)
-        push!(P.code, _binop[f])
+        push!(P.code, code)
     end
     depth
 end
 "Evaluate `bc` into `dest` (or a new array) with one `ibh_ew_eval`; `nothing` if the tree does not fit one program."
 function _fused(bc::Base.Broadcast.Broadcasted, dest::Union{HipArray, Nothing})
-    P = _Prog(Int32[], HipArray[], Float32[])
+    T = _eltype(bc)
+    T === Bool || T <: AbstractFloat ||
+        throw(TypeError(:broadcast, "a Float32 or Bool result (arithmetic between Bools gives Int)", Float32, T))
+    P = _Prog(Int32[], HipArray[], Float32[], 0)
     depth = _push!(P, bc)
     (isnothing(depth) || depth > 8 || length(P.code) > 48 || isempty(P.arrs)) && return nothing
     big = P.arrs[argmax(map(length, P.arrs))]
-    n, k = _rows(big), nv(big)
+    n, k = _rows(big), max(nv(big), P.row)
     all(a -> _rows(a) == n && (nv(a) == k || nv(a) == 1), P.arrs) || return nothing
-    o = isnothing(dest) ? similar(big) : dest
+    (P.row == 0 || P.row == k) || error("IBHip broadcast: a row vector of length $(P.row) over $k columns")
+    # Float64 scalars are rounded to Float32 (the result stays Float32); comparisons give HipArray{Bool}
+    o = isnothing(dest) ? HipArray{T === Bool ? Bool : Float32, k > 1 ? 2 : ndims(big)}(undef, k > 1 ? (n, k) : size(big)) : dest
     (size(o, 1) == n && nv(o) == k) || return nothing
     ptrs = Ptr{Cvoid}[a.ptr for a in P.arrs]
     nvs = Int32[nv(a) for a in P.arrs]
@@ -218,7 +357,7 @@ end
 function Base.copyto!(dest::HipArray, bc::Base.Broadcast.Broadcasted{HipStyle})
     # `dest .= f.(dest, x)` / `dest .-= x`: one launch straight into dest (elementwise: dest may be an operand)
     isnothing(_fused(bc, dest)) || return dest
-    if length(bc.args) == 2 && haskey(_binop, bc.f)
+    if length(bc.args) == 2 && _oldop(bc.f, bc.args...)
         a, b = map(_eval, bc.args)
         _ew(bc.f, a, b, dest)
     else
@@ -242,6 +381,15 @@ end
 Base.maximum(a::HipArray{Float32}) = _reduce(EW_MAX, a)
 Base.minimum(a::HipArray{Float32}) = _reduce(EW_MIN, a)
 Base.sum(a::HipArray{Float32}) = _reduce(EW_SUM, a)
+"`sum(a; dims = 2)` of an (n, nv) field: the columns added in order, one launch; the result is (n, 1) as in Julia.
+`sum(a)` (no `dims`) stays the whole-array reduction."
+function Base.sum(a::HipArray{Float32, 2}; dims = :)
+    dims === (:) && return _reduce(EW_SUM, a)   # `sum(a)`: the whole array, as before
+    dims == 2 || error("IBHip: sum(a; dims) supports dims = 2")
+    o = HipArray{Float32, 2}(undef, (size(a, 1), 1))
+    check(ccall((:ibh_ew_reduce_rows, lib), Cint, (Int64, Cint, Ptr{Cvoid}, Ptr{Cvoid}), size(a, 1), nv(a), a.ptr, o.ptr))
+    o
+end
 
 # ---------------------------------------------------------------------------------------------------
 # Partition on the device: to_backend(part, hip) uploads once (the reference re-uploads per call, :848)
@@ -913,8 +1061,7 @@ end
 
 # ---------------------------------------------------------------------------------------------------
 # CFD.TimeAverage (cfd.jl:738-802): `push!` as ONE launch that updates μ and σ in place (ibh_time_average_push), and
-# CFD.pressure_coefficient (cfd.jl:411-424), whose generic method would reach `literal_pow`, which the broadcast
-# interpreter above does not take.
+# CFD.pressure_coefficient (cfd.jl:411-424) with M∞^2 folded on the host, as the Python mirror does.
 # ---------------------------------------------------------------------------------------------------
 const TA_DT_HOST, TA_DT_DEVICE, TA_DT_PER_VAR, TA_DT_ELEMENT = Cint.(0:3)
 const TA_F64, TA_FIRST = Cint(1), Cint(2)
