@@ -8,35 +8,12 @@ import pytest
 
 import ibamd
 from conftest import euler_field, rel_inf, seeded_field
+from percell import oracle_advection_residual, oracle_euler_residual  # noqa: F401  (smoke() imports them from here)
 from oracle import cfd as ocfd
-from oracle import domain as od
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
 f32 = np.float32
-
-
-def oracle_advection_residual(part, u, C):
-    """test/advection.jl:67-83 with ud starting from zero."""
-    ud = np.zeros_like(u)
-    D = od.JST_sensor(part, u)
-    for dim in range(1, part.ndims + 1):
-        Cf = od.at_faces(part, np.ascontiguousarray(C[:, dim - 1]), dim)
-        gu = od.cell_gradient(part, u, dim)
-        uL, uR = od.MUSCL(part, u, gu, dim, D=D, high_order=True)
-        ud -= od.green_gauss(part, (uL + uR) * Cf / f32(2) + np.abs(Cf) * (uL - uR) / f32(2), dim)
-    return ud
-
-
-def oracle_euler_residual(part, P, fluid):
-    R = np.zeros_like(P)
-    D = od.JST_sensor(part, np.ascontiguousarray(P[:, 0]))
-    for dim in range(1, part.ndims + 1):
-        gP = od.cell_gradient(part, P, dim)
-        PL, PR = od.MUSCL(part, P, gP, dim, D=D, high_order=True)
-        F = ocfd.inviscid_fluxes(fluid, PL, PR, dim)
-        R -= od.green_gauss(part, F, dim)  # Float64 flux, rounded on the in-place update
-    return R
 
 
 def _parts(domains):
