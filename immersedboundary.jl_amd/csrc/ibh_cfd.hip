@@ -12,11 +12,11 @@ int ibh_viscous_per_cell = 0;
 namespace {
 
 __device__ __forceinline__ float sutherland(const ibh_fluid& f, float T) {
-    T = fmaxf(T, 10.0f);
+    T = ibh_max(T, 10.0f);
     // mu_ref * ((T/Tref)^(2/3)) * (Tref + S) / (T + S)     (cfd.jl:75, exponent as in the reference)
-    // x^(2/3) = exp2(2/3 log2 x) on the transcendental unit (v_log_f32 / v_exp_f32, 1 ulp each; x = T / Tref in [0.03, 30]:
-    // inside 4e-7 of the correctly rounded power) instead of the ~100 instructions of the library's powf -- a third of a
-    // viscous face flux
+    // x^(2/3) = exp2(2/3 log2 x) on the transcendental unit (v_log_f32 / v_exp_f32, 1 ulp each) instead of the ~100
+    // instructions of the library's powf -- a third of a viscous face flux.  The whole viscosity stays within 10 ulps of
+    // the float64 evaluation for T in [10, 1e5] K (x in [0.037, 366]; tests/test_gpu_percell_closures.py::test_pointwise_edges)
     return f.mu_ref * __builtin_amdgcn_exp2f((2.0f / 3.0f) * __builtin_amdgcn_logf(T / f.Tref)) * (f.Tref + f.S) / (T + f.S);
 }
 
@@ -33,7 +33,7 @@ __device__ __forceinline__ float conductivity(const ibh_fluid& f, float T) {
 __global__ void k_pointwise(ibh_fluid f, int mode, int64_t n, const float* __restrict__ T, float* __restrict__ out) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         float t = T[i];
-        out[i] = mode == 0 ? sqrtf(f.gamma * f.R * fmaxf(t, 10.0f)) : mode == 1 ? sutherland(f, t) : conductivity(f, t);
+        out[i] = mode == 0 ? sqrtf(f.gamma * f.R * ibh_max(t, 10.0f)) : mode == 1 ? sutherland(f, t) : conductivity(f, t);
     }
 }
 
@@ -41,7 +41,7 @@ template <int ND>
 __global__ void k_p2s(ibh_fluid f, int64_t n, const float* __restrict__ P, int64_t ldp, float* __restrict__ Q,
                       int64_t ldq) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        float p = P[i], T = fmaxf(P[i + ldp], 10.0f);
+        float p = P[i], T = ibh_max(P[i + ldp], 10.0f);
         float k = P[i + 2 * ldp] * P[i + 2 * ldp];
 #pragma unroll
         for (int j = 1; j < ND; ++j) k = k + P[i + (2 + j) * ldp] * P[i + (2 + j) * ldp];
@@ -69,7 +69,7 @@ __global__ void k_s2p(ibh_fluid f, int64_t n, const float* __restrict__ Q, int64
         k = k / 2.0f;
         float p = (f.gamma - 1.0f) * (E - rho * k);
         P[i] = p;
-        P[i + ldp] = fmaxf(p / (rho * f.R), 10.0f);
+        P[i + ldp] = ibh_max(p / (rho * f.R), 10.0f);
 #pragma unroll
         for (int j = 0; j < ND; ++j) P[i + (2 + j) * ldp] = u[j];
     }
@@ -114,8 +114,8 @@ __global__ void k_sensor_flux(ibh_fluid f, int dim0, int64_t n, const float* __r
 #pragma unroll
         for (int v = 0; v < NV; ++v) Pm[v] = (l[v] + r[v]) / 2.0f;
         float u = Pm[2 + dim0];
-        float am = sqrtf(f.gamma * f.R * fmaxf(Pm[1], 10.0f));
-        float nu = fmaxf(nuL[i], nuR[i]);
+        float am = sqrtf(f.gamma * f.R * ibh_max(Pm[1], 10.0f));
+        float nu = ibh_max(nuL[i], nuR[i]);
         float diss = nu * (am + fabsf(u)) / 2.0f;
 #pragma unroll
         for (int v = 0; v < NV; ++v) {
@@ -450,6 +450,9 @@ __global__ __launch_bounds__(VISC_WG) VISC_ATTR void k_viscous_residual_shared(i
 inline dim3 visc_grid(int64_t n) { return dim3((unsigned)((n + VISC_WG - 1) / VISC_WG)); }
 inline dim3 grid1(int64_t n) { int g = ibh_grid(n, CFD_BLOCK); return dim3(g > 4096 ? 4096 : g); }
 
+// Julia's `b * y` for a Bool b: `false` is a strong zero (false * NaN == 0, with the sign of y); `b ? y : 0` otherwise
+__device__ __forceinline__ float jl_bool_times(bool b, float y) { return b ? y : copysignf(0.0f, y); }
+
 // FlowBC call, cfd.jl:243-300: characteristic-style boundary state from the image-point primitives
 template <int ND>
 __global__ void k_flow_bc(ibh_fluid f, int64_t n, const float* __restrict__ P, int64_t ldp,
@@ -475,11 +478,13 @@ __global__ void k_flow_bc(ibh_fluid f, int64_t n, const float* __restrict__ P, i
 #pragma unroll
             for (int j = 1; j < ND; ++j) un = un + nn[j] * uinf[j];
         }
-        const float a = sqrtf(f.gamma * f.R * fmaxf(T, 10.0f));
+        const float a = sqrtf(f.gamma * f.R * ibh_max(T, 10.0f));
         const float M = fabsf(un) / a;
-        // (un >= 0) * ((M > 1) * p_inf + (M <= 1) * p) + (un < 0) * ((M > 1) * p + (M <= 1) * p_inf)
-        const float pb = (un >= 0.0f) ? (M > 1.0f ? pinf : p) : (M > 1.0f ? p : pinf);
-        const float Tb = (un > 0.0f) ? Tinf : T;
+        // (un >= 0) * ((M > 1) * p_inf + (M <= 1) * p) + (un < 0) * ((M > 1) * p + (M <= 1) * p_inf) with Julia's Bool
+        // weights: a NaN Mach number (NaN temperature) makes every weight false and pb = 0, a NaN under a false weight is 0
+        const float pb = jl_bool_times(un >= 0.0f, jl_bool_times(M > 1.0f, pinf) + jl_bool_times(M <= 1.0f, p)) +
+                         jl_bool_times(un < 0.0f, jl_bool_times(M > 1.0f, p) + jl_bool_times(M <= 1.0f, pinf));
+        const float Tb = jl_bool_times(un > 0.0f, Tinf) + jl_bool_times(un <= 0.0f, T);
         float ub[ND];
         if (normal_flow) {
             const float tr = transp_v ? transp_v[i] : transp;

@@ -281,4 +281,10 @@ __device__ __forceinline__ int32_t ibh_xcd_chunk(int32_t wg, int32_t nwg) {
 #else
 #define IBH_WG_X() ((int64_t)ibh_xcd_chunk((int32_t)blockIdx.x, (int32_t)gridDim.x))
 #endif
+
+// Julia's max / min / clamp: NaN in, NaN out (fmaxf / fminf return the other operand).  For non-NaN operands the
+// result is fmaxf's / fminf's, bit for bit.
+__device__ __forceinline__ float ibh_max(float a, float b) { return (a != a || b != b) ? a + b : fmaxf(a, b); }
+__device__ __forceinline__ float ibh_min(float a, float b) { return (a != a || b != b) ? a + b : fminf(a, b); }
+__device__ __forceinline__ float ibh_clamp(float x, float lo, float hi) { return ibh_min(ibh_max(x, lo), hi); }
 #endif

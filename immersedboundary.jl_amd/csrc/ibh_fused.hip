@@ -1222,7 +1222,7 @@ __global__ __launch_bounds__(256) void k_wray_agarwal_of3(const BlockDesc3* __re
         const float src = C1 * r * s + C2 * dot * (r / (s + EPS32));
         nut[c] = r;
         nuR[c] = r * sigmaR;
-        Sout[c] = fminf(src, 10.0f * r);
+        Sout[c] = ibh_min(src, 10.0f * r);
     }
 }
 

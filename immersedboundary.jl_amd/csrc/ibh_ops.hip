@@ -267,7 +267,7 @@ __global__ void k_wray_agarwal_of_cells(int32_t nc, GradDims G, const float* __r
         const float src = C1 * r * s + C2 * dot * (r / (s + EPS32));
         nut[c] = r;
         nuR[c] = r * sigmaR;
-        Sout[c] = fminf(src, 10.0f * r);
+        Sout[c] = ibh_min(src, 10.0f * r);
     }
 }
 
@@ -323,9 +323,9 @@ __global__ void k_jst(int32_t nc, int nd, int dim, DimData D0, DimData D1, DimDa
             nu = jst_dim(D, spacing + (int64_t)(dim - 1) * nc, pv, (int32_t)c);
         } else {
             nu = 1e-7f;  // :1082-1086
-            nu = fmaxf(nu, jst_dim(D0, spacing, pv, (int32_t)c));
-            nu = fmaxf(nu, jst_dim(D1, spacing + (int64_t)nc, pv, (int32_t)c));
-            if (nd == 3) nu = fmaxf(nu, jst_dim(D2, spacing + 2 * (int64_t)nc, pv, (int32_t)c));
+            nu = ibh_max(nu, jst_dim(D0, spacing, pv, (int32_t)c));
+            nu = ibh_max(nu, jst_dim(D1, spacing + (int64_t)nc, pv, (int32_t)c));
+            if (nd == 3) nu = ibh_max(nu, jst_dim(D2, spacing + 2 * (int64_t)nc, pv, (int32_t)c));
         }
         out[c + v * ldo] = nu;
     }
@@ -333,7 +333,7 @@ __global__ void k_jst(int32_t nc, int nd, int dim, DimData D0, DimData D1, DimDa
 
 __device__ __forceinline__ float sgn(float x) { return (float)((x > 0.0f) - (x < 0.0f)); }
 __device__ __forceinline__ float minmod(float a, float b) {  // :1099
-    return fminf(fabsf(a), fabsf(b)) * (sgn(a) + sgn(b)) / 2.0f;
+    return ibh_min(fabsf(a), fabsf(b)) * (sgn(a) + sgn(b)) / 2.0f;
 }
 
 __global__ void k_muscl(int32_t nf, const int32_t* __restrict__ own, const int32_t* __restrict__ nei,
@@ -352,7 +352,7 @@ __global__ void k_muscl(int32_t nf, const int32_t* __restrict__ own, const int32
         float s = minmod(Du, gu);
         float l = uo + s, r = un - s;
         if (Dsens) {
-            float Df = fmaxf(fmaxf(Dsens[o], Dsens[n]), 1e-7f);
+            float Df = ibh_max(ibh_max(Dsens[o], Dsens[n]), 1e-7f);
             float uf = (uo * dn + un * dow) / (dow + dn);
             if (high_order) uf = uf + (duo * dow - dun * dn) / 8.0f;
             l = l * Df + (1.0f - Df) * uf;

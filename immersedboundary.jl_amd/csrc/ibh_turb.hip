@@ -15,7 +15,7 @@ struct GradPtrs {
 };
 
 __device__ __forceinline__ float von_karman(float yp, float kappa, float C) {
-    return fminf(logf(fmaxf(yp, 1.0f)) / kappa + C, yp);  // :11-16
+    return ibh_min(logf(ibh_max(yp, 1.0f)) / kappa + C, yp);  // :11-16
 }
 
 struct WallParams {
@@ -25,7 +25,7 @@ struct WallParams {
 
 __device__ __forceinline__ void wall_point(float Rey, const WallParams& w, float& yp, float& up, float& mup, float& kp,
                                            float& dudy) {
-    Rey = fminf(fmaxf(fabsf(Rey), EPS32), INFINITY);  // clamp(abs(Rey), eps, Inf32)
+    Rey = ibh_clamp(fabsf(Rey), EPS32, INFINITY);  // clamp(abs(Rey), eps, Inf32)
     yp = sqrtf(Rey);
     up = 0.0f;
     for (int it = 0; it < w.n_iter; ++it) {
@@ -36,7 +36,7 @@ __device__ __forceinline__ void wall_point(float Rey, const WallParams& w, float
     const float e = 1.0f - expf(-yp / w.A);
     mup = w.kappa * yp * (e * e);
     dudy = 1.0f / (1.0f + mup);
-    kp = fminf(yp * yp / (6.0f * w.betastar / w.beta - 2.0f), w.D * expf(-yp / w.Aplus));
+    kp = ibh_min(yp * yp / (6.0f * w.betastar / w.beta - 2.0f), w.D * expf(-yp / w.Aplus));
 }
 
 __global__ void k_wall_rey(int64_t n, const float* __restrict__ Rey, WallParams w, float* __restrict__ yp,
@@ -120,7 +120,7 @@ __global__ void k_wray_agarwal(int64_t n, const float* __restrict__ R, const flo
         const float src = C1 * r * s + C2 * dot * (r / (s + EPS32));
         nut[i] = r;
         nuR[i] = r * sigmaR;
-        Sout[i] = fminf(src, 10.0f * r);
+        Sout[i] = ibh_min(src, 10.0f * r);
     }
 }
 

@@ -166,6 +166,13 @@ def viscous_fluxes(fluid, P, Pgrad, dim, mu_t=f32(0.0)):
     return F
 
 
+def _jb(b, x):
+    """Julia's ``Bool * x``: ``false`` is a strong zero (``false * NaN == 0``, sign of ``x``); numpy's ``False * nan`` is nan.
+    The same bits as ``b * x`` for non-NaN ``x``."""
+    x = np.asarray(x)
+    return np.where(b, x, np.copysign(np.zeros((), x.dtype), x))
+
+
 class FlowBC:
     """cfd.jl:160-300 (characteristic-style far-field / slip / no-slip BC at image points)."""
 
@@ -189,12 +196,12 @@ class FlowBC:
             cur = cur + u[:, j] * normals[:, j]
         a = speed_of_sound(self.fluid, T)
         M = np.abs(un) / a
-        pb = (un >= 0.0) * ((M > 1.0) * p_inf + (M <= 1.0) * p) + (un < 0.0) * ((M > 1.0) * p + (M <= 1.0) * p_inf)
-        Tb = (un > 0.0) * T_inf + (un <= 0.0) * T
+        pb = _jb(un >= 0.0, _jb(M > 1.0, p_inf) + _jb(M <= 1.0, p)) + _jb(un < 0.0, _jb(M > 1.0, p) + _jb(M <= 1.0, p_inf))
+        Tb = _jb(un > 0.0, T_inf) + _jb(un <= 0.0, T)
         if self.normal_flow:
             ub = u + normals * (un - cur + transpiration)[:, None]
         else:
-            ub = (un < 0.0)[:, None] * u + (un >= 0.0)[:, None] * u_inf[None, :]
+            ub = _jb((un < 0.0)[:, None], u) + _jb((un >= 0.0)[:, None], np.broadcast_to(u_inf[None, :], u.shape))
         if (dudn is None) != (image_distances is None):
             raise ValueError("du!dn and image_distances must be passed together for BC imposition")
         if dudn is not None:

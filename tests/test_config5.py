@@ -48,7 +48,7 @@ def test_config5_fas_vcycle_with_turbulence_scalar():
     from oracle import domain as od
     from oracle import turbulence as ot
     from oracle.solver import FAS as oFAS
-    from test_gpu_residual import oracle_euler_residual
+    import percell as pc
     msh = Mesh(f32([-4, -4, -4]), f32([8, 8, 8]), ("sphere", bench.icosphere(subdiv=2), f32(0.2)), block_size=8)
     fam = [("farfield", [(d, sd) for d in (1, 2, 3) for sd in (False, True)])]
     dom = ibamd.Domain(msh, hypercube_families=fam, max_partition_size=10 ** 9)
@@ -98,31 +98,8 @@ def test_config5_fas_vcycle_with_turbulence_scalar():
         od.impose_bc(wall_bc, views[l], "sphere", P, R)
 
     def o_f(l, Q):
-        part = oparts[l]
         o_bcs(l, Q)
-        r = np.zeros_like(Q)
-        r[:, :5] = oracle_euler_residual(part, np.ascontiguousarray(Q[:, :5]), ocfd.Fluid())
-        R = np.ascontiguousarray(Q[:, 5])
-        gu = [[od.cell_gradient(part, np.ascontiguousarray(Q[:, 2 + i]), j + 1) for j in range(3)] for i in range(3)]
-        S = ot.shear_rate(gu)
-        gR = np.stack([od.cell_gradient(part, R, d + 1) for d in range(3)], axis=1)
-        gS = np.stack([od.cell_gradient(part, S, d + 1) for d in range(3)], axis=1)
-        wa = ot.Wray_Agarwal(R, S, gR, gS)
-        rt = wa["S"].copy()
-        for d in range(3):
-            conv = od.at_faces(part, np.ascontiguousarray(Q[:, 2 + d]) * R, d + 1)
-            diff = od.at_faces(part, NU + wa["nuR"], d + 1) * od.face_gradient(part, R, d + 1)
-            rt += od.green_gauss(part, diff - conv, d + 1)
-        r[:, 5] = rt
-        # viscous fluxes with the eddy viscosity
-        P = np.ascontiguousarray(Q[:, :5])
-        mut = (Q[:, 0] / (ofluid.R * Q[:, 1])) * wa["nut"]
-        gP = tuple(od.cell_gradient(part, P, d + 1) for d in range(3))
-        for d in (1, 2, 3):
-            Fv = ocfd.viscous_fluxes(ofluid, od.at_faces(part, P, d), od.face_gradient(part, P, gP, d), d,
-                                     mu_t=od.at_faces(part, mut, d))
-            r[:, :5] += od.green_gauss(part, Fv, d)
-        return r, omega
+        return pc.oracle_wa_residual(oparts[l], Q, NU, ofluid), omega
 
     def g_f(l, Q):
         from ibamd.closures import config5_boundary_conditions, navier_stokes_wray_agarwal_residual
