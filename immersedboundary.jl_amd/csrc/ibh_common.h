@@ -199,6 +199,17 @@ extern "C" int ibh_wray_agarwal_of_cells(const ibh_part* p, const float* R, cons
 extern "C" int ibh_scalar_transport_blocks(const ibh_part* p, const float* R, const float* nuR, float nu, const float* vel,
                                            int64_t ldv, const float* S, float* out, int* done);
 
+// internal: the boundary-condition set with the next step's time step beside it (ibh_ops.hip), called from ibh_fused.hip
+extern "C" int ibh_bcset_apply_with_dt(const ibh_bcset* s, float* a, ibh_part* p, const float* C, int64_t ldc, float scale,
+                                       float* dt_next, int partials_done);
+
+// tuning state owned by other translation units, set through ibh_set_tuning (ibh_fused.hip)
+extern "C" {
+extern int ibh_viscous_per_cell;  // ibh_cfd.hip
+extern int ibh_ew_scalar_only;    // ibh_ew.hip
+extern int ibh_time_average_nt;   // ibh_stats.hip
+}
+
 // thread-local state
 extern thread_local std::string ibh_err;
 extern thread_local hipStream_t ibh_stream;

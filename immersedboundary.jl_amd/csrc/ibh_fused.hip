@@ -1352,45 +1352,85 @@ __global__ __launch_bounds__(256) void k_scalar_transport_blocks3(const BlockDes
     }
 }
 
-// 1: wave-per-block form of the 3-D scalar pass A (IBH_3D_WAVE=0 for the 512-thread form, A/B)
-const int ibh_3d_wave = getenv("IBH_3D_WAVE") ? atoi(getenv("IBH_3D_WAVE")) : 1;
-// blocks per wave of the single-kernel sweep; 0 = automatic (IBH_SWEEP_ITERS overrides, for tuning)
-const int ibh_sweep_iters = getenv("IBH_SWEEP_ITERS") ? atoi(getenv("IBH_SWEEP_ITERS")) : 0;
-// IBH_QUAD=0: per-block single kernel everywhere (A/B runs)
-const int ibh_quad = getenv("IBH_QUAD") ? atoi(getenv("IBH_QUAD")) : 1;
-// row / column sweep (ibh_rows2d.h) where the partition qualifies: OFF by default -- measured slower than the quad sweep
-// (8.4 against 6.1 us at 0.87 M cells, 21.7 against 17.0 at 3.47 M: profiles/r3_final/probe_rows.json)
-int ibh_rows = getenv("IBH_ROWS") ? atoi(getenv("IBH_ROWS")) : 0;
-// ibh_set_tuning(key, v): "quad_variant" 4 = wave time stamps (scripts/wave_timeline.py); "quad_parts" 1 / 2 = only the
-// quads / only the single blocks of a quad sweep (measurement); "quad_singles_first" = grid order
-int ibh_quad_variant = getenv("IBH_QUAD_VARIANT") ? atoi(getenv("IBH_QUAD_VARIANT")) : 0;  // (profiling a variant under bench.py)
-int ibh_quad_parts = 3, ibh_quad_singles_iters = 1;
-int ibh_quad_singles_first = getenv("IBH_SINGLES_FIRST") ? atoi(getenv("IBH_SINGLES_FIRST")) : 0;
-int ibh_pairs = getenv("IBH_PAIRS") ? atoi(getenv("IBH_PAIRS")) : 1;  // pair tiles for the blocks outside quads ("pairs")
-int ibh_arith_ids = getenv("IBH_ARITH_IDS") ? atoi(getenv("IBH_ARITH_IDS")) : 1;  // quad sweep: halo ids from the companion rows
-int ibh_transport_blocks = 1;  // tuning key "transport_blocks" 0: the face-list transport kernel everywhere (A/B, tests)
-int ibh_rows_singles = getenv("IBH_ROWS_SINGLES") ? atoi(getenv("IBH_ROWS_SINGLES")) : -1;
+// ---------------------------------------------------------------------------------------------------------------------
+// Host side.  What a sweep call launches is decided in three steps, each written once: the tuning state and the partition
+// predicates below, advection_path() / euler_path() (the path of a (partition, flags, tuning) triple, nothing else), and
+// one launcher per path.  The entry points at the end are a switch over the path.
+
+int env_int(const char* name, int dflt) {
+    const char* s = getenv(name);
+    return s ? atoi(s) : dflt;
+}
+// Tuning state: ibh_set_tuning(key, v) at run time, the environment for the defaults (profiling a variant under bench.py)
+struct Tuning {
+    int wave3d = env_int("IBH_3D_WAVE", 1);  // 1: wave-per-block form of the 3-D scalar pass A (0: the 512-thread form, A/B)
+    int sweep_iters = env_int("IBH_SWEEP_ITERS", 0);  // blocks per wave of the per-block single-kernel sweep; 0 = automatic
+    int quad = env_int("IBH_QUAD", 1);                // 0: per-block single kernel everywhere (A/B runs)
+    // row / column sweep (ibh_rows2d.h) where the partition qualifies: OFF by default -- measured slower than the quad sweep
+    // (8.4 against 6.1 us at 0.87 M cells, 21.7 against 17.0 at 3.47 M: profiles/r3_final/probe_rows.json)
+    int rows = env_int("IBH_ROWS", 0);
+    int quad_variant = env_int("IBH_QUAD_VARIANT", 0);  // one of the QV_* forms below
+    // 1 / 2 = only the quads / only the single blocks of a quad sweep (measurement); single blocks per wave in a quad sweep
+    int quad_parts = 3, quad_singles_iters = 1;
+    int quad_singles_first = env_int("IBH_SINGLES_FIRST", 0);  // grid order of a quad sweep
+    int pairs = env_int("IBH_PAIRS", 1);          // pair tiles for the blocks outside quads
+    int arith_ids = env_int("IBH_ARITH_IDS", 1);  // quad sweep: halo ids from the companion rows
+    int transport_blocks = 1;  // 0: the face-list transport kernel everywhere (A/B, tests)
+    // blocks outside quads by the row sweep: -1 = by size, 0 / 1 = never / always a second launch, 2 = inside the quad launch
+    int rows_singles = env_int("IBH_ROWS_SINGLES", -1);
+} T;
 // measured (profiles/r3_final/rows_for_singles.json): 1 441 single blocks 5.96 -> 10.6 us, 5 937: 15.5 -> 19.0 us (a row wave
 // lives ~3 us whatever the load, and the second launch is serial), 47 272: 126.1 -> 119.0 us
 #define IBH_ROWS_SINGLES_MIN 24000
 
-PartView view(const ibh_part* p) {
-    PartView v;
-    v.nc = p->nc;
-    v.spacing = p->spacing;
-    for (int d = 0; d < IBH_MAXD; ++d) v.dim[d] = p->dim[d];
-    v.side = p->side;
-    return v;
-}
+// "quad_variant": the kernel form of a single-kernel sweep (0 = the default form of every path)
+enum : int {
+    QV_STAMPS = 4,            // wave time stamps (scripts/wave_timeline.py, scripts/wave_timeline_3d.py)
+    QV_GATHER_5 = 5, QV_GATHER_69 = 69, QV_GATHER_85 = 85, QV_GATHER_NONE = 100,  // measurement: subsets of the halo gathers
+    QV_GATHER_SEVEN = 126,    // A/B: seven 4-byte gathers
+    QV_THREAD_PER_CELL = 512, // A/B: thread-per-cell form of the 3-D sweeps
+    QV_STRIP_W2 = 515, QV_STRIP_W4 = 514, QV_STRIP_W3 = 518,  // A/B: the strip form (round 2) of the 3-D scalar sweep
+    QV_COLS_W4 = 519, QV_COLS_W5 = 520,  // columns at 4 (7 registers spilled: 46 against 41 us at 4.56 M cells) / 5 waves
+    QV_EULER_PERSISTENT = 514,  // 3-D Euler sweep, A/B: persistent waves (measured slower, see ibh_strip3d_euler.h)
+};
 
+// Flag groups of the eligibility conditions
+constexpr int F_LITERAL = IBH_FORCE_GENERAL | IBH_EXACT;                       // not the tuned block arithmetic
+constexpr int F_TWO_KERNEL = IBH_NO_FUSE | IBH_PASS_A_ONLY | IBH_PASS_B_ONLY;  // the workspace form is asked for
+constexpr int F_PHASES = IBH_PHASE_INTERIOR | IBH_PHASE_BOUNDARY;
+
+// Partition predicates.  The partition has a block structure (complete 8^nd blocks found by the analysis):
+bool has_blocks(const ibh_part* p) { return p->bs == 8 && p->nblk > 0 && (p->nd == 2 ? !!p->blocks2 : !!p->blocks3); }
+// ... and the call may take the tuned block kernels / the single-kernel sweeps
+bool tuned2(const ibh_part* p, int flags) { return p->nd == 2 && has_blocks(p) && !(flags & F_LITERAL); }
+bool tuned3(const ibh_part* p, int flags) { return p->nd == 3 && has_blocks(p) && !(flags & F_LITERAL); }
+bool fused2(const ibh_part* p, int flags) { return tuned2(p, flags) && !(flags & F_TWO_KERNEL); }
+bool whole3(const ibh_part* p, int flags) { return tuned3(p, flags) && !(flags & (F_TWO_KERNEL | F_PHASES)); }
+// 3-D, only the image cells wanted (a rank of a multi-GPU run) and every image block qualifies / every block qualifies
+bool image3(const ibh_part* p, int flags) { return whole3(p, flags) && (flags & IBH_IMAGE_ONLY) && p->img_all3; }
+bool single3(const ibh_part* p, int flags) { return whole3(p, flags) && !(flags & IBH_IMAGE_ONLY) && p->sweep3; }
+// every cell of the partition in a complete 8^3 block without a GENERAL side (what the fused closures need)
+bool all_blocks3(const ibh_part* p) {
+    return p->nd == 3 && has_blocks(p) && p->n_irr == 0 && (int64_t)p->nblk * 512 == p->nc && p->info[6] == 0;
+}
+// quad set `k` (0: all blocks, 1: image blocks) carries quads and the call may use them
+bool quads_usable(const ibh_part* p, int k, int flags) { return T.quad && !(flags & IBH_NO_QUAD) && p->nq[k] > 0; }
+
+// Overlap phases: INTERIOR = the leading n_int entries of a list (blocks independent of skirt data), BOUNDARY = the rest
+struct Range { int32_t first, last; int32_t count() const { return last - first; } };
+struct Phase {
+    bool interior, boundary;
+    explicit Phase(int flags) : interior((flags & IBH_PHASE_INTERIOR) != 0), boundary((flags & IBH_PHASE_BOUNDARY) != 0) {}
+    bool any() const { return interior || boundary; }
+    bool valid() const { return !(interior && boundary); }
+    Range of(int32_t n_int, int32_t n_all) const { return {boundary ? n_int : 0, interior ? n_int : n_all}; }
+};
+#define IBH_PHASES_EXCLUSIVE "IBH_PHASE_INTERIOR and IBH_PHASE_BOUNDARY are exclusive"
+
+PartView view(const ibh_part* p) { return {p->nc, p->spacing, {p->dim[0], p->dim[1], p->dim[2]}, p->side}; }
 // flattened records apply only when a launch walks exactly the partition's face-list cell list
 FlatRec flat_of(const ibh_part* p, const int32_t* cells) {
-    FlatRec r{nullptr, 0};
-    if (cells && cells == p->irr_cells && p->irr_rec) {
-        r.rec = p->irr_rec;
-        r.n = p->n_irr;
-    }
-    return r;
+    return cells && cells == p->irr_cells && p->irr_rec ? FlatRec{p->irr_rec, p->n_irr} : FlatRec{nullptr, 0};
 }
 
 // Gradient workspace of the two-kernel forms: allocated ONCE, on the first sweep that needs it, for the largest sweep
@@ -1409,7 +1449,355 @@ int ensure_G(ibh_part* p) {
     return 0;
 }
 
+struct AdvArgs { const float *u, *C; int64_t ldc; float* ud; };
+struct EulerArgs { const float* P; int64_t ldp; float* R; int64_t ldr; const ibh_fluid* fluid; };  // (the entries' fields)
+
+// ---- set-up shared by the advection and the Euler launchers (only the kernel and its physics arguments differ)
+// quad launch: the quads and the single blocks of quad set `k` in phase `ph`
+struct QuadRange { Range q, s; };
+QuadRange quad_range(const ibh_part* p, int k, Phase ph) {
+    QuadRange r{ph.of(p->nq_int[k], p->nq[k]), ph.of(p->nqs_int[k], p->nqs[k])};
+    if (T.quad_parts == 1) r.s.last = r.s.first;  // measurement: quads only / single blocks only
+    if (T.quad_parts == 2) r.q.last = r.q.first;
+    return r;
+}
+
+// per-block list launch: positions `r` of `list`, or of the block table itself (list == null), `wpb` blocks per workgroup
+struct BlockList { const BlockDesc2* bl; const int32_t *ht, *et, *ls; int32_t count, iters, nwg; };
+BlockList block_list(const ibh_part* p, const int32_t* list, Range r, int wpb, int max_iters) {
+    // blocks per wave: keep enough waves to fill the chip before a wave takes a second block
+    // (measured on 13.5 k and 54 k blocks, scripts/sweep_iters.sh: 2-3 and 4-6 blocks per wave are best)
+    const int32_t count = r.count(), iters = T.sweep_iters > 0 ? T.sweep_iters : std::min(max_iters, std::max(1, count / 6000));
+    return {list ? p->blocks2 : p->blocks2 + r.first, list ? p->htab : p->htab + (size_t)r.first * 64,
+            list ? p->etab : p->etab + (size_t)r.first * 16, list ? list + r.first : nullptr, count, iters,
+            (count + wpb * iters - 1) / (wpb * iters)};
+}
+
+// 3-D two-kernel block launch: block kernels over the block ranges of the phase + face-list threads over the rest
+// (a, b: pass A / pass B block range; nI, gI: face-list cells, their 512-thread workgroups)
+struct Blocks3 { Range a, b; int32_t nI, gI; bool doA, doB; PartView v; FlatRec flat; };
+Blocks3 blocks3_setup(const ibh_part* p, int flags, Phase ph) {
+    const Range a = ph.of(p->nA1, p->nblk), b = ph.of(p->nB1, p->nblk);
+    const int32_t nI = ph.interior ? 0 : p->n_irr, gI = (nI + 511) / 512;
+    return {a, b, nI, gI, !(flags & IBH_PASS_B_ONLY) && (a.count() > 0 || gI), !(flags & IBH_PASS_A_ONLY) && (b.count() > 0 || gI),
+            view(p), flat_of(p, p->irr_cells)};
+}
+
+// face-list threads of a two-kernel sweep: pass A over the cells outside blocks (`fast`; the interior phase has none) or
+// over every cell (skirt cells feed the faces of image cells), pass B over the same cells or over the image cells only
+struct CellLists { const int32_t *cellsA, *cellsB; int32_t nA, nB; };
+CellLists cell_lists(const ibh_part* p, int flags, bool fast, Phase ph) {
+    const bool image = (flags & IBH_IMAGE_ONLY) && !fast;
+    const int32_t* cellsA = fast ? p->irr_cells : nullptr;
+    const int32_t nA = fast ? (ph.interior ? 0 : p->n_irr) : p->nc;
+    return {cellsA, image ? p->image_in_domain : cellsA, nA, image ? p->n_image : nA};
+}
 }  // namespace
+
+// ---- advection: paths
+enum AdvPath {
+    ADV3_IMAGE_COLS,      // 3-D, image blocks only: one launch of the column sweep
+    ADV3_SINGLE,          // 3-D single-kernel sweep: columns, strip or thread-per-cell form by quad_variant
+    ADV3_BLOCKS,          // 3-D two-kernel block path
+    ADV2_IMAGE,           // 2-D, image blocks only: quads or per-block list
+    ADV2_FUSE_ALL,        // 2-D, every block eligible: rows, quads or per-block
+    ADV2_MIXED,           // 2-D: per-block sweep over fz_list + two-kernel form over ng_list / nf_list
+    ADV_GENERAL_2D,       // two-kernel form: 2-D (block kernels where tuned + face-list threads)
+    ADV_GENERAL_2D_EXACT, //                  2-D, literal arithmetic
+    ADV_GENERAL_3D,       //                  3-D face-list
+};
+static AdvPath advection_path(const ibh_part* p, int flags) {
+    if (tuned3(p, flags)) return image3(p, flags) ? ADV3_IMAGE_COLS : single3(p, flags) ? ADV3_SINGLE : ADV3_BLOCKS;
+    if (fused2(p, flags)) {
+        if ((flags & IBH_IMAGE_ONLY) && p->img_all_fz && !p->fuse_all) return ADV2_IMAGE;
+        if (p->fuse_all) return ADV2_FUSE_ALL;
+        // A mixed launch is three kernels where the two-kernel form is two: at ~3 us per launch it only pays when the
+        // single kernel saves more than that (0.26 ns per eligible block: scripts/mixed_ab.py).  The choice depends on
+        // the partition only, never on the phase flags: a sweep split in phases reproduces the whole sweep bit for bit.
+        const bool mixed_pays = p->n_fz >= 12000 || (flags & (IBH_FORCE_MIXED | IBH_SWEEP_ONLY));
+        if (p->fz_list && 4 * (int64_t)p->n_fz >= p->nblk && mixed_pays) return ADV2_MIXED;
+    }
+    return p->nd != 2 ? ADV_GENERAL_3D : (flags & IBH_EXACT) ? ADV_GENERAL_2D_EXACT : ADV_GENERAL_2D;
+}
+
+// only the image cells are wanted (a rank of a multi-GPU run) and every image block qualifies: no workspace, no skirt cells
+static void adv3_image_cols(const ibh_part* p, const AdvArgs& a) {
+    const int32_t nwg = (p->n_img3 + WPB3C - 1) / WPB3C;
+    hipLaunchKernelGGL((k_sweep3_cols<3, true>), dim3(nwg), dim3(64 * WPB3C), 0, ibh_stream, a.u, a.C, (uint32_t)a.ldc, a.ud,
+                       p->iblocks3, p->ihtab3, p->iftab3, p->irtab3, p->ir4tab3, p->n_img3, nwg, p->idtab3);
+}
+// (the strip and the column kernels differ in their last, defaulted parameter: no common function pointer type)
+#define SWEEP3_LAUNCH(K)                                                                                                 \
+    hipLaunchKernelGGL(K, dim3(nwg), dim3(64 * WPB3S), 0, ibh_stream, a.u, a.C, (uint32_t)a.ldc, a.ud, p->blocks3, p->htab3, \
+                       p->ftab3, p->rtab3, p->r4tab3, p->nblk, nwg)
+// every block qualifies for the single-kernel sweep: one launch, nothing through the workspace
+static void adv3_single(const ibh_part* p, const AdvArgs& a) {
+    static_assert(WPB3C == WPB3S, "one grid for both forms");
+    const int32_t nwg = (p->nblk + WPB3S - 1) / WPB3S;
+    switch (T.quad_variant) {
+    case QV_THREAD_PER_CELL:
+        hipLaunchKernelGGL(k_sweep3_adv, dim3(p->nblk), dim3(512), 0, ibh_stream, a.u, a.C, (uint32_t)a.ldc, a.ud, p->blocks3,
+                           p->htab3, p->ftab3, p->rtab3, p->r4tab3, p->nblk);
+        break;
+    case QV_STRIP_W2: SWEEP3_LAUNCH(k_sweep3_strip<2>); break;
+    case QV_STRIP_W4: SWEEP3_LAUNCH(k_sweep3_strip<4>); break;
+    case QV_STRIP_W3: SWEEP3_LAUNCH(k_sweep3_strip<3>); break;
+    case QV_COLS_W4: SWEEP3_LAUNCH(k_sweep3_cols<4>); break;
+    case QV_COLS_W5: SWEEP3_LAUNCH(k_sweep3_cols<5>); break;
+    default: SWEEP3_LAUNCH(k_sweep3_cols<3>);
+    }
+}
+#undef SWEEP3_LAUNCH
+
+static int adv3_blocks(ibh_part* p, const AdvArgs& a, int flags, Phase ph) {
+    if (const int rc = ensure_G(p)) return rc;
+    const Blocks3 s = blocks3_setup(p, flags, ph);
+    const int32_t na = s.a.count(), nb = s.b.count();
+    if (s.doA && T.wave3d) {
+        const int32_t nwgA = (na + 3) / 4, gIw = (s.nI + 255) / 256;
+        hipLaunchKernelGGL(k_passA3_wave, dim3(nwgA + gIw), dim3(256), 0, ibh_stream, s.v, a.u, p->G, p->blocks3 + s.a.first,
+                           p->htab3 + (size_t)s.a.first * 384, p->ftab3, na, nwgA, p->irr_cells, s.nI, s.flat,
+                           (const int32_t*)nullptr);
+    } else if (s.doA)
+        hipLaunchKernelGGL(k_passA3_blk, dim3(na + s.gI), dim3(512), 0, ibh_stream, s.v, a.u, p->G, p->blocks3 + s.a.first,
+                           p->htab3 + (size_t)s.a.first * 384, p->ftab3, na, p->irr_cells, s.nI, s.flat);
+    if (s.doB)
+        hipLaunchKernelGGL(k_passB3_adv_blk, dim3(nb + s.gI), dim3(512), 0, ibh_stream, s.v, a.u, a.C, a.ldc, p->G, a.ud,
+                           p->blocks3 + s.b.first, p->htab3 + (size_t)s.b.first * 384, p->ftab3, nb, p->irr_cells, s.nI,
+                           s.flat, (const int32_t*)nullptr);
+    return 0;
+}
+
+// single-kernel sweep (blk2::sweep_adv) over the eligible blocks: list positions `r`
+static void adv2_block_list(const ibh_part* p, const AdvArgs& a, const int32_t* list, Range r) {
+    if (r.count() <= 0) return;
+    const BlockList L = block_list(p, list, r, WPB, 6);
+    // <true>: some blocks take their deeper cells from the table (skirt fragments)
+    hipLaunchKernelGGL(p->n_dt > 0 ? k_sweep_adv<true> : k_sweep_adv<false>, dim3(L.nwg), dim3(64 * WPB), 0, ibh_stream, a.u,
+                       a.C, (uint32_t)a.ldc, a.ud, L.bl, L.ht, L.et, p->dtab, L.count, L.nwg, L.iters, L.ls);
+}
+
+// quad sweep over quad set `k` (0: all blocks, 1: image blocks), one phase of it or all
+static void adv2_quads(const ibh_part* p, const AdvArgs& a, int k, Phase ph) {
+    const Range q = quad_range(p, k, ph).q;
+    Range s = quad_range(p, k, ph).s;
+    // pair tiles (set 0, whole sweeps or the interior phase -- they exist only where every block is interior): the
+    // single blocks are then the ones outside quads AND pairs
+    const int32_t npair = (k == 0 && T.pairs && p->npair > 0 && !ph.boundary && q.first == 0 && q.last == p->nq[k] &&
+                           T.quad_parts == 3) ? p->npair : 0;
+    const int32_t* slist = p->qsingles[k];
+    if (npair) {
+        slist = p->qsingles2;
+        s = {0, p->nqs2};
+    } else if (k == 0 && p->npair > 0 && ph.boundary) {
+        s.last = s.first;  // (all blocks are interior blocks there: nothing in the boundary phase)
+    }
+    // The blocks outside quads by the row sweep (rows2::sweep_rows over the list: any eight complete blocks per wave,
+    // 110 vector instructions per block against 365 in the per-block kernel), as a SECOND launch where that is cheap
+    // against the sweep, or inside the quad launch ("rows_singles")
+    const bool rows_able = k == 0 && p->rows_ok && p->n_dt == 0 && T.quad_variant == 0 && s.count() > 0;
+    const bool rows_inside = rows_able && T.rows_singles == 2;
+    const bool rows_second = rows_able && !rows_inside &&
+                             (T.rows_singles < 0 ? s.count() >= IBH_ROWS_SINGLES_MIN : T.rows_singles > 0);
+    const Range rs = s;
+    if (rows_second) s.last = s.first;
+    const int32_t siters = T.quad_singles_iters > 0 ? T.quad_singles_iters : 1;
+    const int32_t nwgq = (q.count() + npair + WPB - 1) / WPB,
+                  nwgs = rows_inside ? (s.count() + WPB * 8 - 1) / (WPB * 8) : (s.count() + WPB * siters - 1) / (WPB * siters);
+    auto kq = k_sweep_quad<false, false>;
+    if (rows_inside) kq = k_sweep_quad<false, false, 127, false, true>;
+    else if (p->n_dt > 0) kq = k_sweep_quad<true, false>;
+    else if (T.quad_variant == QV_STAMPS) kq = k_sweep_quad<false, true>;
+    else if (T.quad_variant == QV_GATHER_SEVEN) kq = k_sweep_quad<false, false, 126>;
+    else if (T.quad_variant == QV_GATHER_85) kq = k_sweep_quad<false, false, 85>;
+    else if (T.quad_variant == QV_GATHER_69) kq = k_sweep_quad<false, false, 69>;
+    else if (T.quad_variant == QV_GATHER_5) kq = k_sweep_quad<false, false, 5>;
+    else if (T.quad_variant == QV_GATHER_NONE) kq = k_sweep_quad<false, false, 0>;
+    if (nwgq + nwgs > 0)
+        hipLaunchKernelGGL(kq, dim3(nwgq + nwgs), dim3(64 * WPB), 0, ibh_stream, a.u, a.C, (uint32_t)a.ldc, a.ud,
+                           p->qd[k] + q.first, p->qtab[k] + (size_t)q.first * IBH_QROW, q.count(), nwgq, p->blocks2, p->htab,
+                           p->etab, p->dtab, slist + s.first, s.count(), nwgs, T.quad_singles_first, siters,
+                           (const float*)nullptr, npair,
+                           T.arith_ids ? p->qaux[k] + (size_t)q.first * IBH_QAUX : (const int32_t*)nullptr);
+    if (rows_second) {
+        const int32_t nw = (rs.count() + 7) / 8, nwgr = (nw + WPBR - 1) / WPBR;
+        hipLaunchKernelGGL(k_sweep_rows, dim3(nwgr), dim3(64 * WPBR), 0, ibh_stream, a.u, a.C, (uint32_t)a.ldc, a.ud,
+                           p->blocks2, p->etab, 0, rs.count(), nwgr, slist + rs.first);
+    }
+}
+
+// One launch per phase, no workspace.  k = 0: every block is eligible, the whole sweep; k = 1: only the image cells are
+// wanted (a rank of a multi-GPU run) and every image block is eligible, nothing for the skirt fragments
+static void adv2_single(const ibh_part* p, const AdvArgs& a, int flags, Phase ph, int k) {
+    const Range b = k ? ph.of(p->n_img_int, p->n_img) : ph.of(p->nB1, p->nblk);
+    if (k == 0 && p->rows_ok && T.rows && !(flags & IBH_NO_QUAD) && T.quad_variant == 0) {
+        // row / column sweep: eight blocks per wavefront, arithmetic halo ids (`quad_variant` != 0: the quad forms)
+        const int32_t nw = (b.count() + 7) / 8, nwg = (nw + WPBR - 1) / WPBR;
+        if (nwg > 0)
+            hipLaunchKernelGGL(k_sweep_rows, dim3(nwg), dim3(64 * WPBR), 0, ibh_stream, a.u, a.C, (uint32_t)a.ldc, a.ud,
+                               p->blocks2, p->etab, b.first, b.count(), nwg, (const int32_t*)nullptr);
+    } else if (quads_usable(p, k, flags)) adv2_quads(p, a, k, ph);
+    else adv2_block_list(p, a, k ? p->img_list : nullptr, b);
+}
+
+// mixed: eligible blocks in one kernel; the rest (skirt blocks, blocks next to face-list cells) in the
+// two-kernel form, with the gradient workspace filled only where it is read (ng_list)
+static int adv2_mixed(ibh_part* p, const AdvArgs& a, int flags, Phase ph) {
+    // interior phase without blocks of the two-kernel form: nothing reads the workspace before the boundary
+    // phase, so all of pass A is done there and the interior phase is one launch
+    const bool defer = p->n_nf_int == 0;
+    const Range g = ph.of(defer ? 0 : p->n_ng_int, p->n_ng), r = ph.of(p->n_nf_int, p->n_nf);
+    const int32_t nI = ph.interior ? 0 : p->n_irr, gI = (nI + 64 * WPB - 1) / (64 * WPB);
+    if (const int rc = ensure_G(p)) return rc;
+    const int32_t nwgA = (g.count() + WPB - 1) / WPB, nwgB = (r.count() + WPB - 1) / WPB;
+    if (!(flags & IBH_SWEEP_ONLY)) {
+        const PartView v = view(p);
+        if (nwgA + gI)
+            hipLaunchKernelGGL((k_passA<2, 1, false>), dim3(nwgA + gI), dim3(64 * WPB), 0, ibh_stream, v, a.u, (int64_t)p->nc,
+                               p->G, p->blocks2, p->htab, g.count(), nwgA, p->irr_cells, nI, flat_of(p, p->irr_cells),
+                               p->ng_list + g.first);
+        if (nwgB + gI)
+            hipLaunchKernelGGL((k_passB_adv<2, false>), dim3(nwgB + gI), dim3(64 * WPB), 0, ibh_stream, v, a.u, a.C, a.ldc,
+                               p->G, a.ud, p->blocks2, p->htab, r.count(), nwgB, p->irr_cells, nI,
+                               flat_of(p, p->irr_cells), p->nf_list + r.first);
+    }
+    adv2_block_list(p, a, p->fz_list, ph.of(p->n_fz_int, p->n_fz));
+    return 0;
+}
+
+// two-kernel form through the gradient workspace: block kernels where the partition is 2-D with blocks (`fast`), face-list
+// threads for the other cells
+static int adv_general(ibh_part* p, const AdvArgs& a, int flags, Phase ph, AdvPath path) {
+    if (const int rc = ensure_G(p)) return rc;
+    const bool fast = p->nd == 2 && has_blocks(p) && !(flags & IBH_FORCE_GENERAL);
+    // overlap phases: INTERIOR = blocks independent of skirt data, BOUNDARY = the rest + face-list cells
+    IBH_REQUIRE(!ph.any() || fast, "overlap phases need the block path (2-D, block_size 8, domain given)");
+    const Range ra = ph.of(p->nA1, p->nblk), rb = ph.of(p->nB1, p->nblk);  // pass A / pass B block range
+    const int32_t nwgA = fast ? (ra.count() + WPB - 1) / WPB : 0, nwgB = fast ? (rb.count() + WPB - 1) / WPB : 0;
+    const CellLists c = cell_lists(p, flags, fast, ph);
+    const PartView v = view(p);
+    const dim3 blk(64 * WPB), gA(nwgA + (c.nA + 64 * WPB - 1) / (64 * WPB)), gB(nwgB + (c.nB + 64 * WPB - 1) / (64 * WPB));
+    const bool doA = gA.x && !(flags & IBH_PASS_B_ONLY), doB = gB.x && !(flags & IBH_PASS_A_ONLY);
+    // (without `fast` the block ranges are the whole, unused tables: null in 3-D)
+    const BlockDesc2 *blkA = p->blocks2 ? p->blocks2 + ra.first : nullptr, *blkB = p->blocks2 ? p->blocks2 + rb.first : nullptr;
+    const int32_t* htA = p->htab ? p->htab + (size_t)ra.first * 64 : nullptr;
+    const int32_t* htB = p->htab ? p->htab + (size_t)rb.first * 64 : nullptr;
+    const bool d3 = path == ADV_GENERAL_3D, exact = path == ADV_GENERAL_2D_EXACT;
+    auto kA = d3 ? k_passA<3, 1, true> : exact ? k_passA<2, 1, true> : k_passA<2, 1, false>;
+    auto kB = d3 ? k_passB_adv<3, true> : exact ? k_passB_adv<2, true> : k_passB_adv<2, false>;
+    if (doA)
+        hipLaunchKernelGGL(kA, gA, blk, 0, ibh_stream, v, a.u, (int64_t)p->nc, p->G, blkA, htA, ra.count(), nwgA, c.cellsA, c.nA,
+                           flat_of(p, c.cellsA), (const int32_t*)nullptr);
+    if (doB)
+        hipLaunchKernelGGL(kB, gB, blk, 0, ibh_stream, v, a.u, a.C, a.ldc, p->G, a.ud, blkB, htB, rb.count(), nwgB, c.cellsB,
+                           c.nB, flat_of(p, c.cellsB), (const int32_t*)nullptr);
+    return 0;
+}
+
+// ---- Euler: paths
+enum EulerPath {
+    EUL2_SINGLE,      // 2-D single launch per phase: quads or per-block
+    EUL3_IMAGE_COLS,  // 3-D, image blocks only: one launch of the column sweep
+    EUL3_SINGLE,      // 3-D single-kernel sweep: column / persistent / stamped / thread-per-cell form by quad_variant
+    EUL2_FAST,        // two-kernel form: 2-D block kernels + face-list threads
+    EUL2_FACE_LIST,   //                  2-D face-list
+    EUL3_BLOCKS,      //                  3-D block kernels + face-list threads
+    EUL3_FACE_LIST,   //                  3-D face-list
+};
+static EulerPath euler_path(const ibh_part* p, int flags) {
+    if (fused2(p, flags) && (p->fuse_all || ((flags & IBH_IMAGE_ONLY) && p->img_all_fz))) return EUL2_SINGLE;
+    if (image3(p, flags)) return EUL3_IMAGE_COLS;
+    if (single3(p, flags)) return EUL3_SINGLE;
+    // tuned block paths: not with IBH_EXACT (the literal arithmetic lives in the face-list body)
+    if (p->nd == 2) return tuned2(p, flags) ? EUL2_FAST : EUL2_FACE_LIST;
+    return tuned3(p, flags) ? EUL3_BLOCKS : EUL3_FACE_LIST;
+}
+
+// every block eligible, or only the image blocks wanted and all of them eligible: one launch per phase, no workspace
+static void euler2_single(const ibh_part* p, const EulerArgs& e, int flags, Phase ph) {
+    const int k = p->fuse_all ? 0 : 1;  // quad set; block list: all blocks / the image blocks
+    if (quads_usable(p, k, flags)) {
+        const QuadRange r = quad_range(p, k, ph);
+        const int32_t nwgq = (r.q.count() + WPBE - 1) / WPBE, nwgs = (r.s.count() + WPBE - 1) / WPBE;
+        if (nwgq + nwgs > 0)
+            hipLaunchKernelGGL(k_sweep_quad_euler, dim3(nwgq + nwgs), dim3(64 * WPBE), 0, ibh_stream, e.P, (uint32_t)e.ldp,
+                               e.R, (uint32_t)e.ldr, e.fluid->R, e.fluid->gamma, p->qd[k] + r.q.first,
+                               p->qtab[k] + (size_t)r.q.first * IBH_QROW, r.q.count(), nwgq, p->blocks2, p->htab, p->etab,
+                               p->dtab, p->qsingles[k] + r.s.first, r.s.count(), nwgs, T.quad_singles_first);
+        return;
+    }
+    const Range b = p->fuse_all ? ph.of(p->nB1, p->nblk) : ph.of(p->n_img_int, p->n_img);
+    if (b.count() <= 0) return;
+    const BlockList L = block_list(p, p->fuse_all ? nullptr : p->img_list, b, WPBE, 4);
+    hipLaunchKernelGGL(k_sweep_euler, dim3(L.nwg), dim3(64 * WPBE), 0, ibh_stream, e.P, (uint32_t)e.ldp, e.R, (uint32_t)e.ldr,
+                       e.fluid->R, e.fluid->gamma, L.bl, L.ht, L.et, p->dtab, L.count, L.nwg, L.iters, L.ls);
+}
+
+// image blocks of a partition with skirt fragments: one launch, nothing through the workspace
+static void euler3_image_cols(const ibh_part* p, const EulerArgs& e) {
+    const int32_t nwg = (p->n_img3 + WPB3E - 1) / WPB3E;
+    hipLaunchKernelGGL((k_sweep3_euler_cols<2, false, true, false>), dim3(nwg), dim3(64 * WPB3E), 0, ibh_stream, e.P,
+                       (uint32_t)e.ldp, e.R, (uint32_t)e.ldr, e.fluid->R, e.fluid->gamma, p->iblocks3, p->ihtab3, p->iftab3,
+                       p->irtab3, p->ir4tab3, p->n_img3, nwg, p->idtab3);
+}
+// 3-D, every block qualifies for the single-kernel sweep: one launch, nothing through the workspace
+static void euler3_single(const ibh_part* p, const EulerArgs& e) {
+    const bool persist = T.quad_variant == QV_EULER_PERSISTENT;
+    const int32_t nwg = persist ? s3e_persistent_wgs(p->nblk) : (p->nblk + WPB3E - 1) / WPB3E;
+    auto k = k_sweep3_euler_cols<2, false, false, false>;
+    if (persist) k = k_sweep3_euler_cols<2, false, false, true>;
+    else if (T.quad_variant == QV_STAMPS) k = k_sweep3_euler_cols<2, true, false, false>;
+    if (T.quad_variant == QV_THREAD_PER_CELL)
+        hipLaunchKernelGGL(k_sweep3_euler, dim3(p->nblk), dim3(512), 0, ibh_stream, e.P, (uint32_t)e.ldp, e.R, (uint32_t)e.ldr,
+                           e.fluid->R, e.fluid->gamma, p->blocks3, p->htab3, p->ftab3, p->rtab3, p->r4tab3, p->nblk);
+    else
+        hipLaunchKernelGGL(k, dim3(nwg), dim3(64 * WPB3E), 0, ibh_stream, e.P, (uint32_t)e.ldp, e.R, (uint32_t)e.ldr, e.fluid->R,
+                           e.fluid->gamma, p->blocks3, p->htab3, p->ftab3, p->rtab3, p->r4tab3, p->nblk, nwg,
+                           (const int32_t*)nullptr);
+}
+
+// 3-D block path: block kernels + the face-list kernels over the cells the analysis left out (whole sweeps only)
+static int euler3_blocks(ibh_part* p, const EulerArgs& e, int flags) {
+    if (const int rc = ensure_G(p)) return rc;
+    const Blocks3 s = blocks3_setup(p, flags, Phase(0));
+    if (s.doA && T.wave3d) {
+        const int32_t nwgA = (p->nblk + 3) / 4, gIw = (s.nI + 255) / 256;
+        hipLaunchKernelGGL(k_passA3e_wave, dim3(nwgA + gIw), dim3(256), 0, ibh_stream, s.v, e.P, e.ldp, p->G, p->blocks3,
+                           p->htab3, p->ftab3, p->nblk, nwgA, p->irr_cells, s.nI, s.flat);
+    } else if (s.doA)
+        hipLaunchKernelGGL(k_passA3e_blk, dim3(p->nblk + s.gI), dim3(512), 0, ibh_stream, s.v, e.P, e.ldp, p->G, p->blocks3,
+                           p->htab3, p->ftab3, p->nblk, p->irr_cells, s.nI, s.flat);
+    if (s.doB) {
+        hipLaunchKernelGGL(k_passB3e_blk, dim3(p->nblk), dim3(512), 0, ibh_stream, (uint32_t)p->nc, e.P, (uint32_t)e.ldp,
+                           p->G, e.R, (uint32_t)e.ldr, e.fluid->R, e.fluid->gamma, p->blocks3, p->htab3, p->ftab3, p->nblk);
+        if (s.nI)
+            hipLaunchKernelGGL((k_passB_euler<3>), dim3((s.nI + 64 * WPB - 1) / (64 * WPB)), dim3(64 * WPB), 0, ibh_stream,
+                               s.v, e.P, e.ldp, p->G, e.R, e.ldr, e.fluid->R, e.fluid->gamma, p->irr_cells, s.nI);
+    }
+    return 0;
+}
+
+// two-kernel form, 2-D (block kernels where `fast`) and 3-D face-list (whole sweeps only)
+static int euler_general(ibh_part* p, const EulerArgs& e, int flags, EulerPath path) {
+    if (const int rc = ensure_G(p)) return rc;
+    const PartView v = view(p);
+    const bool fast = path == EUL2_FAST;
+    const int32_t nwg_fast = fast ? (p->nblk + WPB - 1) / WPB : 0;
+    const CellLists c = cell_lists(p, flags, fast, Phase(0));
+    const dim3 blk(64 * WPB), gA(nwg_fast + (c.nA + 64 * WPB - 1) / (64 * WPB)), gB((c.nB + 64 * WPB - 1) / (64 * WPB));
+    const bool doA = gA.x && !(flags & IBH_PASS_B_ONLY), doB = !(flags & IBH_PASS_A_ONLY);
+    auto kA = fast ? k_passA<2, 4, false> : path == EUL2_FACE_LIST ? k_passA<2, 4, true> : k_passA<3, 5, true>;
+    if (doA)
+        hipLaunchKernelGGL(kA, gA, blk, 0, ibh_stream, v, e.P, e.ldp, p->G, p->blocks2, p->htab, p->nblk, nwg_fast, c.cellsA,
+                           c.nA, flat_of(p, c.cellsA), (const int32_t*)nullptr);
+    if (doB && nwg_fast)
+        hipLaunchKernelGGL(k_passB_euler_blk, dim3(nwg_fast), blk, 0, ibh_stream, (uint32_t)p->nc, e.P, (uint32_t)e.ldp, p->G,
+                           e.R, (uint32_t)e.ldr, e.fluid->R, e.fluid->gamma, p->blocks2, p->htab, p->nblk, nwg_fast);
+    if (doB && gB.x)
+        hipLaunchKernelGGL(path == EUL3_FACE_LIST ? k_passB_euler<3> : k_passB_euler<2>, gB, blk, 0, ibh_stream, v, e.P, e.ldp,
+                           p->G, e.R, e.ldr, e.fluid->R, e.fluid->gamma, c.cellsB, c.nB);
+    return 0;
+}
 
 extern "C" {
 
@@ -1419,303 +1807,72 @@ int ibh_debug_buffer(void* buf) {  // device buffer of 8 x uint64 per wave of th
     return 0;
 }
 
-extern int ibh_viscous_per_cell;   // ibh_cfd.hip
-extern int ibh_ew_scalar_only;     // ibh_ew.hip
-extern int ibh_time_average_nt;    // ibh_stats.hip
 int ibh_set_tuning(const char* key, int value) {
+    static const struct { const char* key; int* value; } keys[] = {
+        {"viscous_per_cell", &ibh_viscous_per_cell}, {"ew_scalar", &ibh_ew_scalar_only},  // ibh_cfd.hip, ibh_ew.hip
+        {"time_average_nt", &ibh_time_average_nt},                                        // ibh_stats.hip
+        {"quad_variant", &T.quad_variant}, {"quad_parts", &T.quad_parts}, {"quad_singles_first", &T.quad_singles_first},
+        {"quad_singles_iters", &T.quad_singles_iters}, {"rows", &T.rows}, {"rows_singles", &T.rows_singles},
+        {"transport_blocks", &T.transport_blocks}, {"pairs", &T.pairs}, {"arith_ids", &T.arith_ids}};
     IBH_REQUIRE(key, "ibh_set_tuning: null key");
-    if (!strcmp(key, "viscous_per_cell")) {
-        ibh_viscous_per_cell = value;
-        return 0;
-    }
-    if (!strcmp(key, "ew_scalar")) {
-        ibh_ew_scalar_only = value;
-        return 0;
-    }
-    if (!strcmp(key, "time_average_nt")) {
-        ibh_time_average_nt = value;
-        return 0;
-    }
-    if (!strcmp(key, "quad_variant")) ibh_quad_variant = value;
-    else if (!strcmp(key, "quad_parts")) ibh_quad_parts = value;
-    else if (!strcmp(key, "quad_singles_first")) ibh_quad_singles_first = value;
-    else if (!strcmp(key, "quad_singles_iters")) ibh_quad_singles_iters = value;
-    else if (!strcmp(key, "rows")) ibh_rows = value;
-    else if (!strcmp(key, "rows_singles")) ibh_rows_singles = value;
-    else if (!strcmp(key, "transport_blocks")) ibh_transport_blocks = value;
-    else if (!strcmp(key, "pairs")) ibh_pairs = value;
-    else if (!strcmp(key, "arith_ids")) ibh_arith_ids = value;
-    else return ibh_fail(-1, "ibh_set_tuning: unknown key", __FILE__, __LINE__);
-    return 0;
-}
-
-int ibh_residual_advection(ibh_part* p, const float* u, const float* C, int64_t ldc, float* ud, int flags);
-// n sweeps launched back to back from ONE call: the step loop of a compiled host (a Julia `for` around the ccall costs tens
-// of nanoseconds per iteration; from Python the interpreter and ctypes would be ten times the 6 us sweep)
-int ibh_residual_advection_n(ibh_part* p, const float* u, const float* C, int64_t ldc, float* ud, int flags, int n) {
-    for (int i = 0; i < n; ++i) {
-        const int rc = ibh_residual_advection(p, u, C, ldc, ud, flags);
-        if (rc) return rc;
-    }
-    return 0;
+    for (const auto& k : keys)
+        if (!strcmp(key, k.key)) {
+            *k.value = value;
+            return 0;
+        }
+    return ibh_fail(-1, "ibh_set_tuning: unknown key", __FILE__, __LINE__);
 }
 
 int ibh_residual_advection(ibh_part* p, const float* u, const float* C, int64_t ldc, float* ud, int flags) {
     IBH_REQUIRE(p && u && C && ud, "ibh_residual_advection: null argument");
     if (p->nc == 0) return 0;
+    const Phase ph(flags);
+    IBH_REQUIRE(ph.valid(), IBH_PHASES_EXCLUSIVE);
+    const AdvArgs a{u, C, ldc, ud};
+    const AdvPath path = advection_path(p, flags);
     int rc = 0;
-    if (p->nd == 3 && p->bs == 8 && p->blocks3 && p->nblk > 0 && !(flags & (IBH_FORCE_GENERAL | IBH_EXACT))) {
-        const bool ph1 = (flags & IBH_PHASE_INTERIOR) != 0, ph2 = (flags & IBH_PHASE_BOUNDARY) != 0;
-        IBH_REQUIRE(!(ph1 && ph2), "IBH_PHASE_INTERIOR and IBH_PHASE_BOUNDARY are exclusive");
-        if ((flags & IBH_IMAGE_ONLY) && p->img_all3 && !ph1 && !ph2 &&
-            !(flags & (IBH_NO_FUSE | IBH_PASS_A_ONLY | IBH_PASS_B_ONLY))) {
-            // only the image cells are wanted (a rank of a multi-GPU run) and every image block qualifies: one launch over
-            // the image blocks, no workspace, nothing for the skirt fragments
-            const int32_t nwg = (p->n_img3 + WPB3C - 1) / WPB3C;
-            hipLaunchKernelGGL((k_sweep3_cols<3, true>), dim3(nwg), dim3(64 * WPB3C), 0, ibh_stream, u, C, (uint32_t)ldc, ud,
-                               p->iblocks3, p->ihtab3, p->iftab3, p->irtab3, p->ir4tab3, p->n_img3, nwg, p->idtab3);
-            IBH_LAUNCH_CHECK();
-            return 0;
-        }
-        if (p->sweep3 && !ph1 && !ph2 &&
-            !(flags & (IBH_NO_FUSE | IBH_PASS_A_ONLY | IBH_PASS_B_ONLY | IBH_IMAGE_ONLY))) {
-            // every block qualifies for the single-kernel sweep: one launch, nothing through the workspace
-            if (ibh_quad_variant != 512) {
-                const int32_t nwg = (p->nblk + WPB3S - 1) / WPB3S;
-#define S3_LAUNCH(W)                                                                                                  \
-    hipLaunchKernelGGL(k_sweep3_strip<W>, dim3(nwg), dim3(64 * WPB3S), 0, ibh_stream, u, C, (uint32_t)ldc, ud, p->blocks3, \
-                       p->htab3, p->ftab3, p->rtab3, p->r4tab3, p->nblk, nwg)
-#define C3_LAUNCH(W)                                                                                                  \
-    hipLaunchKernelGGL(k_sweep3_cols<W>, dim3(nwg), dim3(64 * WPB3C), 0, ibh_stream, u, C, (uint32_t)ldc, ud, p->blocks3, \
-                       p->htab3, p->ftab3, p->rtab3, p->r4tab3, p->nblk, nwg)
-                static_assert(WPB3C == WPB3S, "one grid for both forms");
-                if (ibh_quad_variant == 515) S3_LAUNCH(2);
-                else if (ibh_quad_variant == 514) S3_LAUNCH(4);
-                else if (ibh_quad_variant == 518) S3_LAUNCH(3);   // A/B: the strip form (round 2)
-                else if (ibh_quad_variant == 519) C3_LAUNCH(4);   // (7 registers spilled: 46 against 41 us at 4.56 M cells)
-                else if (ibh_quad_variant == 520) C3_LAUNCH(5);
-                else C3_LAUNCH(3);
-#undef C3_LAUNCH
-#undef S3_LAUNCH
-            } else  // A/B: thread-per-cell form
-            hipLaunchKernelGGL(k_sweep3_adv, dim3(p->nblk), dim3(512), 0, ibh_stream, u, C, (uint32_t)ldc, ud, p->blocks3,
-                               p->htab3, p->ftab3, p->rtab3, p->r4tab3, p->nblk);
-            IBH_LAUNCH_CHECK();
-            return 0;
-        }
-        if ((rc = ensure_G(p))) return rc;
-        // 3-D block path: block kernels over the requested block range + face-list kernels over the rest
-        const int32_t a0 = ph2 ? p->nA1 : 0, a1 = ph1 ? p->nA1 : p->nblk;
-        const int32_t b0 = ph2 ? p->nB1 : 0, b1 = ph1 ? p->nB1 : p->nblk;
-        const int32_t nI = ph1 ? 0 : p->n_irr;
-        PartView v = view(p);
-        const bool doA = !(flags & IBH_PASS_B_ONLY), doB = !(flags & IBH_PASS_A_ONLY);
-        const int32_t gI = (nI + 511) / 512;
-        if (doA && (a1 > a0 || gI) && ibh_3d_wave) {
-            const int32_t nwgA = (a1 - a0 + 3) / 4, gIw = (nI + 255) / 256;
-            hipLaunchKernelGGL(k_passA3_wave, dim3(nwgA + gIw), dim3(256), 0, ibh_stream, v, u, p->G, p->blocks3 + a0,
-                               p->htab3 + (size_t)a0 * 384, p->ftab3, a1 - a0, nwgA, p->irr_cells, nI,
-                               flat_of(p, p->irr_cells), (const int32_t*)nullptr);
-        } else if (doA && (a1 > a0 || gI))
-            hipLaunchKernelGGL(k_passA3_blk, dim3(a1 - a0 + gI), dim3(512), 0, ibh_stream, v, u, p->G, p->blocks3 + a0,
-                               p->htab3 + (size_t)a0 * 384, p->ftab3, a1 - a0, p->irr_cells, nI, flat_of(p, p->irr_cells));
-        if (doB && (b1 > b0 || gI))
-            hipLaunchKernelGGL(k_passB3_adv_blk, dim3(b1 - b0 + gI), dim3(512), 0, ibh_stream, v, u, C, ldc, p->G, ud,
-                               p->blocks3 + b0, p->htab3 + (size_t)b0 * 384, p->ftab3, b1 - b0, p->irr_cells, nI,
-                               flat_of(p, p->irr_cells), (const int32_t*)nullptr);
-        IBH_LAUNCH_CHECK();
-        return 0;
+    switch (path) {
+    case ADV3_IMAGE_COLS: adv3_image_cols(p, a); break;
+    case ADV3_SINGLE: adv3_single(p, a); break;
+    case ADV3_BLOCKS: rc = adv3_blocks(p, a, flags, ph); break;
+    case ADV2_IMAGE: adv2_single(p, a, flags, ph, 1); break;
+    case ADV2_FUSE_ALL: adv2_single(p, a, flags, ph, 0); break;
+    case ADV2_MIXED: rc = adv2_mixed(p, a, flags, ph); break;
+    default: rc = adv_general(p, a, flags, ph, path);
     }
-    const bool tuned2 = p->nd == 2 && p->bs == 8 && p->nblk > 0 &&
-                        !(flags & (IBH_FORCE_GENERAL | IBH_EXACT | IBH_NO_FUSE | IBH_PASS_A_ONLY | IBH_PASS_B_ONLY));
-    // single-kernel sweep (blk2::sweep_adv) over the eligible blocks: `count` list positions from `first`
-    auto launch_sweep = [&](const int32_t* list, int32_t first, int32_t count) {
-        if (count <= 0) return;
-        // blocks per wave: keep enough waves to fill the chip before a wave takes a second block
-        // (measured on 13.5 k and 54 k blocks, scripts/sweep_iters.sh: 2-3 and 4-6 blocks per wave are best)
-        const int32_t iters = ibh_sweep_iters > 0 ? ibh_sweep_iters : std::min(6, std::max(1, count / 6000));
-        const int32_t nwg = (count + WPB * iters - 1) / (WPB * iters);
-        const BlockDesc2* bl = list ? p->blocks2 : p->blocks2 + first;
-        const int32_t* ht = list ? p->htab : p->htab + (size_t)first * 64;
-        const int32_t* et = list ? p->etab : p->etab + (size_t)first * 16;
-        const int32_t* ls = list ? list + first : nullptr;
-        if (p->n_dt > 0)  // some blocks take their deeper cells from the table (skirt fragments)
-            hipLaunchKernelGGL(k_sweep_adv<true>, dim3(nwg), dim3(64 * WPB), 0, ibh_stream, u, C, (uint32_t)ldc, ud, bl, ht,
-                               et, p->dtab, count, nwg, iters, ls);
-        else
-            hipLaunchKernelGGL(k_sweep_adv<false>, dim3(nwg), dim3(64 * WPB), 0, ibh_stream, u, C, (uint32_t)ldc, ud, bl, ht,
-                               et, p->dtab, count, nwg, iters, ls);
-    };
-    // quad sweep over quad set `k` (0: all blocks, 1: image blocks): `ph1`/`ph2` select the interior / boundary part
-    auto quads_ok = [&](int k) {
-        return ibh_quad && !(flags & IBH_NO_QUAD) && p->nq[k] > 0;
-    };
-    auto launch_quads = [&](int k, bool ph1, bool ph2) {
-        int32_t q0 = ph2 ? p->nq_int[k] : 0, q1 = ph1 ? p->nq_int[k] : p->nq[k];
-        int32_t s0 = ph2 ? p->nqs_int[k] : 0, s1 = ph1 ? p->nqs_int[k] : p->nqs[k];
-        if (q1 - q0 + s1 - s0 <= 0) return;
-        if (ibh_quad_parts == 1) s1 = s0;  // measurement: quads only / single blocks only
-        if (ibh_quad_parts == 2) q1 = q0;
-        // The blocks outside quads as a SECOND launch of the row sweep (rows2::sweep_rows over the list: any eight complete
-        // blocks per wave, 110 vector instructions per block against 365 in the per-block kernel) where a second launch
-        // is cheap against the sweep ("rows_singles": -1 = by size, 0 / 1 = never / always)
-        // pair tiles (set 0, whole sweeps or the interior phase -- they exist only where every block is interior): the
-        // single blocks are then the ones outside quads AND pairs
-        const int32_t npair =
-            (k == 0 && ibh_pairs && p->npair > 0 && !ph2 && q0 == 0 && q1 == p->nq[k] && ibh_quad_parts == 3) ? p->npair : 0;
-        const int32_t* slist = p->qsingles[k];
-        if (npair) {
-            slist = p->qsingles2;
-            s0 = 0;
-            s1 = p->nqs2;
-        } else if (k == 0 && p->npair > 0 && ph2) {
-            s1 = s0;  // (all blocks are interior blocks there: nothing in the boundary phase)
-        }
-        const bool rows_singles = k == 0 && p->rows_ok && p->n_dt == 0 && ibh_quad_variant == 0 && s1 > s0 &&
-                                  (ibh_rows_singles < 0 ? s1 - s0 >= IBH_ROWS_SINGLES_MIN : ibh_rows_singles > 0);
-        const int32_t rs0 = s0, rs1 = s1;
-        const bool rows_inside = k == 0 && p->rows_ok && p->n_dt == 0 && ibh_quad_variant == 0 && s1 > s0 && ibh_rows_singles == 2;
-        if (rows_singles && !rows_inside) s1 = s0;
-        const int32_t siters = ibh_quad_singles_iters > 0 ? ibh_quad_singles_iters : 1;
-        const int32_t nwgq = (q1 - q0 + npair + WPB - 1) / WPB,
-                      nwgs = rows_inside ? (s1 - s0 + WPB * 8 - 1) / (WPB * 8) : (s1 - s0 + WPB * siters - 1) / (WPB * siters);
-        if (nwgq + nwgs == 0 && !rows_singles) return;
-#define QUAD_LAUNCH(DT, STAMP, ...)                                                                                    \
-    hipLaunchKernelGGL((k_sweep_quad<DT, STAMP, ##__VA_ARGS__>), dim3(nwgq + nwgs), dim3(64 * WPB), 0, ibh_stream, u, C,              \
-                       (uint32_t)ldc, ud, p->qd[k] + q0, p->qtab[k] + (size_t)q0 * IBH_QROW, q1 - q0, nwgq,            \
-                       p->blocks2, p->htab, p->etab, p->dtab, slist + s0, s1 - s0, nwgs, ibh_quad_singles_first, siters,          \
-                       (const float*)nullptr, npair, ibh_arith_ids ? p->qaux[k] + (size_t)q0 * IBH_QAUX : (const int32_t*)nullptr)
-        if (rows_inside) QUAD_LAUNCH(false, false, 127, false, true);
-        else if (p->n_dt > 0) QUAD_LAUNCH(true, false);
-        else if (ibh_quad_variant == 4) QUAD_LAUNCH(false, true);
-        else if (ibh_quad_variant == 126) QUAD_LAUNCH(false, false, 126);  // A/B: seven 4-byte gathers
-        else if (ibh_quad_variant == 85) QUAD_LAUNCH(false, false, 85);  // measurement: subsets of the halo gathers
-        else if (ibh_quad_variant == 69) QUAD_LAUNCH(false, false, 69);
-        else if (ibh_quad_variant == 5) QUAD_LAUNCH(false, false, 5);
-        else if (ibh_quad_variant == 100) QUAD_LAUNCH(false, false, 0);
-        else if (nwgq + nwgs > 0) QUAD_LAUNCH(false, false);
-#undef QUAD_LAUNCH
-        if (rows_singles && !rows_inside) {
-            const int32_t nw = (rs1 - rs0 + 7) / 8, nwgr = (nw + WPBR - 1) / WPBR;
-            hipLaunchKernelGGL(k_sweep_rows, dim3(nwgr), dim3(64 * WPBR), 0, ibh_stream, u, C, (uint32_t)ldc, ud, p->blocks2,
-                               p->etab, 0, rs1 - rs0, nwgr, slist + rs0);
-        }
-    };
-    if (tuned2 && (flags & IBH_IMAGE_ONLY) && p->img_all_fz && !p->fuse_all) {
-        // only the image cells are wanted (a rank of a multi-GPU run) and every image block is eligible: one launch
-        // per phase over the image blocks, no workspace, nothing for the skirt fragments
-        const bool ph1 = (flags & IBH_PHASE_INTERIOR) != 0, ph2 = (flags & IBH_PHASE_BOUNDARY) != 0;
-        IBH_REQUIRE(!(ph1 && ph2), "IBH_PHASE_INTERIOR and IBH_PHASE_BOUNDARY are exclusive");
-        const int32_t i0 = ph2 ? p->n_img_int : 0, i1 = ph1 ? p->n_img_int : p->n_img;
-        if (quads_ok(1)) launch_quads(1, ph1, ph2);
-        else launch_sweep(p->img_list, i0, i1 - i0);
-        IBH_LAUNCH_CHECK();
-        return 0;
+    if (!rc) IBH_LAUNCH_CHECK();
+    return rc;
+}
+
+// n sweeps launched back to back from ONE call: the step loop of a compiled host (a Julia `for` around the ccall costs tens
+// of nanoseconds per iteration; from Python the interpreter and ctypes would be ten times the 6 us sweep)
+int ibh_residual_advection_n(ibh_part* p, const float* u, const float* C, int64_t ldc, float* ud, int flags, int n) {
+    int rc = 0;
+    for (int i = 0; i < n && !rc; ++i) rc = ibh_residual_advection(p, u, C, ldc, ud, flags);
+    return rc;
+}
+
+int ibh_residual_euler_hll(ibh_part* p, const float* P, int64_t ldp, float* R, int64_t ldr, const ibh_fluid* fluid,
+                           int flags) {
+    IBH_REQUIRE(p && P && R && fluid, "ibh_residual_euler_hll: null argument");
+    if (p->nc == 0) return 0;
+    const Phase ph(flags);
+    const EulerArgs e{P, ldp, R, ldr, fluid};
+    const EulerPath path = euler_path(p, flags);
+    if (path == EUL2_SINGLE) IBH_REQUIRE(ph.valid(), IBH_PHASES_EXCLUSIVE);
+    else  // the other forms run the whole sweep: they have no overlap phases
+        IBH_REQUIRE(!ph.any(), "ibh_residual_euler_hll: overlap phases need a partition whose (image) blocks are all "
+                               "eligible for the single-kernel sweep; run the sweep unphased after the exchange");
+    int rc = 0;
+    switch (path) {
+    case EUL2_SINGLE: euler2_single(p, e, flags, ph); break;
+    case EUL3_IMAGE_COLS: euler3_image_cols(p, e); break;
+    case EUL3_SINGLE: euler3_single(p, e); break;
+    case EUL3_BLOCKS: rc = euler3_blocks(p, e, flags); break;
+    default: rc = euler_general(p, e, flags, path);
     }
-    if (tuned2 && p->fuse_all) {
-        // every block is eligible: the whole sweep (or one overlap phase of it) is one launch
-        const bool ph1 = (flags & IBH_PHASE_INTERIOR) != 0, ph2 = (flags & IBH_PHASE_BOUNDARY) != 0;
-        IBH_REQUIRE(!(ph1 && ph2), "IBH_PHASE_INTERIOR and IBH_PHASE_BOUNDARY are exclusive");
-        const int32_t b0 = ph2 ? p->nB1 : 0, b1 = ph1 ? p->nB1 : p->nblk;
-        if (p->rows_ok && ibh_rows && !(flags & IBH_NO_QUAD) && ibh_quad_variant == 0) {
-            // row / column sweep: eight blocks per wavefront, arithmetic halo ids (`quad_variant` != 0: the quad forms)
-            const int32_t nw = (b1 - b0 + 7) / 8, nwg = (nw + WPBR - 1) / WPBR;
-            if (nwg > 0)
-                hipLaunchKernelGGL(k_sweep_rows, dim3(nwg), dim3(64 * WPBR), 0, ibh_stream, u, C, (uint32_t)ldc, ud,
-                                   p->blocks2, p->etab, b0, b1 - b0, nwg, (const int32_t*)nullptr);
-        } else if (quads_ok(0)) launch_quads(0, ph1, ph2);
-        else launch_sweep(nullptr, b0, b1 - b0);
-        IBH_LAUNCH_CHECK();
-        return 0;
-    }
-    // A mixed launch is three kernels where the two-kernel form is two: at ~3 us per launch it only pays when the
-    // single kernel saves more than that (0.26 ns per eligible block: scripts/mixed_ab.py).  The choice depends on
-    // the partition only, never on the phase flags: a sweep split in phases reproduces the whole sweep bit for bit.
-    const bool mixed_pays = p->n_fz >= 12000 || (flags & (IBH_FORCE_MIXED | IBH_SWEEP_ONLY));
-    if (tuned2 && p->fz_list && 4 * (int64_t)p->n_fz >= p->nblk && mixed_pays) {
-        // mixed: eligible blocks in one kernel; the rest (skirt blocks, blocks next to face-list cells) in the
-        // two-kernel form, with the gradient workspace filled only where it is read (ng_list)
-        const bool ph1 = (flags & IBH_PHASE_INTERIOR) != 0, ph2 = (flags & IBH_PHASE_BOUNDARY) != 0;
-        IBH_REQUIRE(!(ph1 && ph2), "IBH_PHASE_INTERIOR and IBH_PHASE_BOUNDARY are exclusive");
-        const int32_t f0 = ph2 ? p->n_fz_int : 0, f1 = ph1 ? p->n_fz_int : p->n_fz;
-        // interior phase without blocks of the two-kernel form: nothing reads the workspace before the boundary
-        // phase, so all of pass A is done there and the interior phase is one launch
-        const bool defer = p->n_nf_int == 0;
-        const int32_t g0 = ph2 ? (defer ? 0 : p->n_ng_int) : 0, g1 = ph1 ? (defer ? 0 : p->n_ng_int) : p->n_ng;
-        const int32_t r0 = ph2 ? p->n_nf_int : 0, r1 = ph1 ? p->n_nf_int : p->n_nf;
-        const int32_t nI = ph1 ? 0 : p->n_irr;
-        const int32_t gI = (nI + 64 * WPB - 1) / (64 * WPB);
-        PartView v = view(p);
-        if ((rc = ensure_G(p))) return rc;
-        const int32_t nwgA = (g1 - g0 + WPB - 1) / WPB, nwgB = (r1 - r0 + WPB - 1) / WPB;
-        if (!(flags & IBH_SWEEP_ONLY)) {
-            if (nwgA + gI)
-                hipLaunchKernelGGL((k_passA<2, 1, false>), dim3(nwgA + gI), dim3(64 * WPB), 0, ibh_stream, v, u,
-                                   (int64_t)p->nc, p->G, p->blocks2, p->htab, g1 - g0, nwgA, p->irr_cells, nI,
-                                   flat_of(p, p->irr_cells), p->ng_list + g0);
-            if (nwgB + gI)
-                hipLaunchKernelGGL((k_passB_adv<2, false>), dim3(nwgB + gI), dim3(64 * WPB), 0, ibh_stream, v, u, C, ldc,
-                                   p->G, ud, p->blocks2, p->htab, r1 - r0, nwgB, p->irr_cells, nI,
-                                   flat_of(p, p->irr_cells), p->nf_list + r0);
-        }
-        launch_sweep(p->fz_list, f0, f1 - f0);
-        IBH_LAUNCH_CHECK();
-        return 0;
-    }
-    if ((rc = ensure_G(p))) return rc;
-    const bool fast = p->bs == 8 && p->nd == 2 && p->nblk > 0 && !(flags & IBH_FORCE_GENERAL);
-    const int bpwg = WPB;  // blocks per workgroup
-    // overlap phases: INTERIOR = blocks independent of skirt data, BOUNDARY = the rest + face-list cells
-    const bool ph1 = (flags & IBH_PHASE_INTERIOR) != 0, ph2 = (flags & IBH_PHASE_BOUNDARY) != 0;
-    IBH_REQUIRE(!(ph1 && ph2), "IBH_PHASE_INTERIOR and IBH_PHASE_BOUNDARY are exclusive");
-    IBH_REQUIRE(!(ph1 || ph2) || fast, "overlap phases need the block path (2-D, block_size 8, domain given)");
-    const int32_t a0 = ph2 ? p->nA1 : 0, a1 = ph1 ? p->nA1 : p->nblk;  // pass A block range
-    const int32_t b0 = ph2 ? p->nB1 : 0, b1 = ph1 ? p->nB1 : p->nblk;  // pass B block range
-    const int32_t nwgA_fast = fast ? (a1 - a0 + bpwg - 1) / bpwg : 0;
-    const int32_t nwgB_fast = fast ? (b1 - b0 + bpwg - 1) / bpwg : 0;
-    // pass A always covers every cell of the partition (skirt cells feed the faces of image cells)
-    const int32_t* cellsA = fast ? p->irr_cells : nullptr;
-    const int32_t nA = fast ? (ph1 ? 0 : p->n_irr) : p->nc;
-    // pass B: every cell, or image cells only
-    const int32_t* cellsB = cellsA;
-    int32_t nB = nA;
-    if ((flags & IBH_IMAGE_ONLY) && !fast) {
-        cellsB = p->image_in_domain;
-        nB = p->n_image;
-    }
-    PartView v = view(p);
-    dim3 blk(64 * WPB);
-    dim3 gA(nwgA_fast + (nA + 64 * WPB - 1) / (64 * WPB)), gB(nwgB_fast + (nB + 64 * WPB - 1) / (64 * WPB));
-    const bool exact = (flags & IBH_EXACT) != 0;
-    const bool doA = gA.x && !(flags & IBH_PASS_B_ONLY), doB = gB.x && !(flags & IBH_PASS_A_ONLY);
-    const BlockDesc2* blkA = p->blocks2 ? p->blocks2 + a0 : nullptr;
-    const BlockDesc2* blkB = p->blocks2 ? p->blocks2 + b0 : nullptr;
-    const int32_t* htA = p->htab ? p->htab + (size_t)a0 * 64 : nullptr;
-    const int32_t* htB = p->htab ? p->htab + (size_t)b0 * 64 : nullptr;
-    if (p->nd == 2 && exact) {
-        if (doA)
-            hipLaunchKernelGGL((k_passA<2, 1, true>), gA, blk, 0, ibh_stream, v, u, (int64_t)p->nc, p->G, blkA, htA,
-                               a1 - a0, nwgA_fast, cellsA, nA, flat_of(p, cellsA), nullptr);
-        if (doB)
-            hipLaunchKernelGGL((k_passB_adv<2, true>), gB, blk, 0, ibh_stream, v, u, C, ldc, p->G, ud, blkB, htB,
-                               b1 - b0, nwgB_fast, cellsB, nB, flat_of(p, cellsB), nullptr);
-    } else if (p->nd == 2) {
-        if (doA)
-            hipLaunchKernelGGL((k_passA<2, 1, false>), gA, blk, 0, ibh_stream, v, u, (int64_t)p->nc, p->G, blkA, htA,
-                               a1 - a0, nwgA_fast, cellsA, nA, flat_of(p, cellsA), nullptr);
-        if (doB)
-            hipLaunchKernelGGL((k_passB_adv<2, false>), gB, blk, 0, ibh_stream, v, u, C, ldc, p->G, ud, blkB, htB,
-                               b1 - b0, nwgB_fast, cellsB, nB, flat_of(p, cellsB), nullptr);
-    } else {
-        if (doA)
-            hipLaunchKernelGGL((k_passA<3, 1, true>), gA, blk, 0, ibh_stream, v, u, (int64_t)p->nc, p->G, p->blocks2,
-                               p->htab, p->nblk, 0, cellsA, nA, flat_of(p, cellsA), nullptr);
-        if (doB)
-            hipLaunchKernelGGL((k_passB_adv<3, true>), gB, blk, 0, ibh_stream, v, u, C, ldc, p->G, ud, p->blocks2,
-                               p->htab, p->nblk, 0, cellsB, nB, flat_of(p, cellsB), nullptr);
-    }
-    IBH_LAUNCH_CHECK();
-    return 0;
+    if (!rc) IBH_LAUNCH_CHECK();
+    return rc;
 }
 
 // One step of a rank in one launch: xGMI halo exchange of u + image-only quad sweep (k_step_quad).  Needs a partition
@@ -1726,15 +1883,15 @@ int ibh_step_advection(ibh_part* p, const float* u, float* u_out, const float* C
     IBH_REQUIRE(p && u && u_out && C && dt_dev && u != u_out, "ibh_step_advection: null or aliased argument");
     if (p->nc == 0) return 0;
     int rc = 0;
-    if (p->nd == 2 && p->bs == 8 && p->nblk > 0 && p->fuse_all && ibh_quad && p->nq[0] > 0 && p->n_dt == 0) {
+    if (fused2(p, 0) && p->fuse_all && quads_usable(p, 0, 0) && p->n_dt == 0) {
         // sweep and update in one launch: the quad sweep stores u + dt * residual (its cells of u are in registers)
-        const int32_t npair = ibh_pairs ? p->npair : 0;
+        const int32_t npair = T.pairs ? p->npair : 0;
         const int32_t nq = p->nq[0], ns = npair ? p->nqs2 : p->nqs[0];
         const int32_t nwgq = (nq + npair + WPB - 1) / WPB, nwgs = (ns + WPB - 1) / WPB;
         hipLaunchKernelGGL((k_sweep_quad<false, false, 127, true>), dim3(nwgq + nwgs), dim3(64 * WPB), 0, ibh_stream, u, C,
                            (uint32_t)ldc, u_out, p->qd[0], p->qtab[0], nq, nwgq, p->blocks2, p->htab, p->etab, p->dtab,
-                           npair ? p->qsingles2 : p->qsingles[0], ns, nwgs, ibh_quad_singles_first, 1, dt_dev, npair,
-                           ibh_arith_ids ? p->qaux[0] : (const int32_t*)nullptr);
+                           npair ? p->qsingles2 : p->qsingles[0], ns, nwgs, T.quad_singles_first, 1, dt_dev, npair,
+                           T.arith_ids ? p->qaux[0] : (const int32_t*)nullptr);
         IBH_LAUNCH_CHECK();
     } else {
         if ((rc = ibh_residual_advection(p, u, C, ldc, u_out, 0))) return rc;
@@ -1749,8 +1906,6 @@ int ibh_step_advection(ibh_part* p, const float* u, float* u_out, const float* C
 // set instead of standing in front of the next sweep.  dt_next may be dt_dev (the sweep has read it by then).
 // (Tried and dropped: the partial maxima beside the SWEEP instead -- its workgroups then carry the sweep's 27 KB of LDS and
 // its register budget, and the launch takes longer than the two side by side save: 26.8 against 26.1 us per step.)
-extern "C" int ibh_bcset_apply_with_dt(const ibh_bcset* s, float* a, ibh_part* p, const float* C, int64_t ldc, float scale,
-                                       float* dt_next, int partials_done);
 int ibh_step_advection_dt(ibh_part* p, const float* u, float* u_out, const float* C, int64_t ldc, const float* dt_dev,
                           const ibh_bcset* bcs, float scale, float* dt_next) {
     IBH_REQUIRE(dt_next, "ibh_step_advection_dt: null dt_next");
@@ -1766,7 +1921,7 @@ int ibh_step_advection_xgmi(ibh_part* p, float* u, const float* C, int64_t ldc, 
                             int n_recv_peers, const int32_t* recv_seg, const uint32_t* const* recv_flags,
                             uint32_t* state, uint32_t max_spins, unsigned long long* fstate) {
     IBH_REQUIRE(p && u && C && ud && state && fstate, "ibh_step_advection_xgmi: null argument");
-    IBH_REQUIRE(p->nd == 2 && p->bs == 8 && p->nblk > 0 && p->img_all_fz && !p->fuse_all && p->nq[1] > 0 && ibh_quad,
+    IBH_REQUIRE(fused2(p, 0) && p->img_all_fz && !p->fuse_all && quads_usable(p, 1, 0),
                 "ibh_step_advection_xgmi: needs a 2-D partition with skirt fragments whose image blocks are all eligible "
                 "for the quad sweep");
     IBH_REQUIRE(n_send_peers >= 0 && n_send_peers <= IBH_MAX_PEERS && n_recv_peers >= 0 && n_recv_peers <= IBH_MAX_PEERS &&
@@ -1800,16 +1955,21 @@ int ibh_step_advection_xgmi(ibh_part* p, float* u, const float* C, int64_t ldc, 
     const int32_t nq = p->nq[1], nqi = p->nq_int[1], ns = p->nqs[1], nsi = p->nqs_int[1];
     const int32_t nwg = (nqi + WPB - 1) / WPB + (nsi + WPB - 1) / WPB + (nq - nqi + WPB - 1) / WPB + (ns - nsi + WPB - 1) / WPB;
     static_assert(WPB == 4, "the exchange workgroups of k_step_quad are 256 threads");
-    if (p->n_dt > 0)
-        hipLaunchKernelGGL(k_step_quad<true>, dim3(E + nwg), dim3(64 * WPB), 0, ibh_stream, u, C, (uint32_t)ldc, ud, p->qd[1],
-                           p->qtab[1], nqi, nq, p->blocks2, p->htab, p->etab, p->dtab, p->qsingles[1], nsi, ns, send_all,
-                           recv_all, src0, src1, A, state, max_spins, E, fstate);
-    else
-        hipLaunchKernelGGL(k_step_quad<false>, dim3(E + nwg), dim3(64 * WPB), 0, ibh_stream, u, C, (uint32_t)ldc, ud,
-                           p->qd[1], p->qtab[1], nqi, nq, p->blocks2, p->htab, p->etab, p->dtab, p->qsingles[1], nsi, ns,
-                           send_all, recv_all, src0, src1, A, state, max_spins, E, fstate);
+    hipLaunchKernelGGL(p->n_dt > 0 ? k_step_quad<true> : k_step_quad<false>, dim3(E + nwg), dim3(64 * WPB), 0, ibh_stream, u, C,
+                       (uint32_t)ldc, ud, p->qd[1], p->qtab[1], nqi, nq, p->blocks2, p->htab, p->etab, p->dtab, p->qsingles[1],
+                       nsi, ns, send_all, recv_all, src0, src1, A, state, max_spins, E, fstate);
     IBH_LAUNCH_CHECK();
     return 0;
+}
+
+// pass A of the scalar sweep over field `uv`, written to `G` = [grad_1 .. grad_nd, sensor], each nc floats (velocity / output
+// are not touched): `G` is the workspace for the duration of the call, so the partition's own is not even allocated
+static int pass_A_into(ibh_part* p, const float* uv, float* G) {
+    float* const own = p->G;
+    p->G = G;
+    const int rc = ibh_residual_advection(p, uv, uv, p->nc, G, IBH_PASS_A_ONLY | IBH_NO_FUSE);
+    p->G = own;
+    return rc;
 }
 
 // cell_gradient(part, u) -- the tuple form (ImmersedBoundary.jl:980-988): the gradients of `nv` fields along ALL
@@ -1824,28 +1984,17 @@ int ibh_cell_gradient_nd(ibh_part* p, const float* u, int nv, int64_t ldu, float
     IBH_REQUIRE(p && u && out && nv >= 1, "ibh_cell_gradient_nd: bad argument");
     if (p->nc == 0) return 0;
     const int nd = p->nd;
-    const bool blocks = p->bs == 8 && p->nblk > 0 && (nd == 2 ? p->blocks2 != nullptr : p->blocks3 != nullptr);
-    if (!blocks) {
+    if (!has_blocks(p)) {
         // no block structure (e.g. the coarse levels of multigrid()): every dimension in one face-list launch
-        const int rc = ibh_cell_gradient_all(p, u, nv, ldu, out, ldo);
-        if (rc) return rc;
-        if (sensor) return ibh_jst_sensor(p, 0, u, nv, ldu, sensor, lds);
-        return 0;
+        if (const int rc = ibh_cell_gradient_all(p, u, nv, ldu, out, ldo)) return rc;
+        return sensor ? ibh_jst_sensor(p, 0, u, nv, ldu, sensor, lds) : 0;
     }
-    if (nv == 1 && ldo == p->nc && sensor == out + (size_t)nd * ldo && lds == ldo) {
-        // one field, gradients and sensor back to back: pass A writes them in place (the output IS its workspace for the
-        // duration of the call: no copy, and the partition's own workspace is not even allocated)
-        float* const own = p->G;
-        p->G = out;
-        const int rc1 = ibh_residual_advection(p, u, u, p->nc, out, IBH_PASS_A_ONLY | IBH_NO_FUSE);
-        p->G = own;
-        return rc1;
-    }
+    // one field, gradients and sensor back to back: pass A writes them in place (no copy)
+    if (nv == 1 && ldo == p->nc && sensor == out + (size_t)nd * ldo && lds == ldo) return pass_A_into(p, u, out);
     int rc = ensure_G(p);
     if (rc) return rc;
     for (int v = 0; v < nv; ++v) {
         const float* uv = u + (size_t)v * ldu;
-        // pass A of the scalar sweep: G = [grad_1 .. grad_nd, sensor], each nc floats (velocity / output are not touched)
         if ((rc = ibh_residual_advection(p, uv, uv, p->nc, p->G, IBH_PASS_A_ONLY | IBH_NO_FUSE))) return rc;
         for (int d = 0; d < nd; ++d)
             IBH_HIP(hipMemcpyAsync(out + (size_t)(d * nv + v) * ldo, p->G + (size_t)d * p->nc, sizeof(float) * p->nc,
@@ -1867,35 +2016,21 @@ int ibh_cell_gradient_fields(ibh_part* p, const float* u, int nv, int64_t ldu, f
     IBH_REQUIRE(p && u && out && nv >= 1, "ibh_cell_gradient_fields: bad argument");
     if (p->nc == 0) return 0;
     const int nd = p->nd;
-    const bool blocks = p->bs == 8 && p->nblk > 0 && (nd == 2 ? p->blocks2 != nullptr : p->blocks3 != nullptr);
     for (int v = 0; v < nv; ++v) {
         const float* uv = u + (size_t)v * ldu;
         float* ov = out + (size_t)v * (nd + 1) * p->nc;
-        int rc;
-        if (blocks) {
-            float* const own = p->G;
-            p->G = ov;
-            rc = ibh_residual_advection(p, uv, uv, p->nc, ov, IBH_PASS_A_ONLY | IBH_NO_FUSE);
-            p->G = own;
-        } else {
-            rc = ibh_cell_gradient_all(p, uv, 1, p->nc, ov, p->nc);
-            if (!rc) rc = ibh_jst_sensor(p, 0, uv, 1, p->nc, ov + (size_t)nd * p->nc, p->nc);
-        }
+        int rc = has_blocks(p) ? pass_A_into(p, uv, ov) : ibh_cell_gradient_all(p, uv, 1, p->nc, ov, p->nc);
+        if (!rc && !has_blocks(p)) rc = ibh_jst_sensor(p, 0, uv, 1, p->nc, ov + (size_t)nd * p->nc, p->nc);
         if (rc) return rc;
     }
     return 0;
 }
 
-// every cell of the partition in a complete 8^3 block without a GENERAL side (what the fused closures below need)
-static bool all_blocks3(const ibh_part* p) {
-    return p->nd == 3 && p->bs == 8 && p->blocks3 && p->nblk > 0 && p->n_irr == 0 && (int64_t)p->nblk * 512 == p->nc &&
-           p->info[6] == 0;
-}
 // ibh_scalar_transport on an all-block 3-D partition (dispatched from ibh_turb.hip; 0 = not applicable here)
 int ibh_scalar_transport_blocks(const ibh_part* p, const float* R, const float* nuR, float nu, const float* vel, int64_t ldv,
                                 const float* S, float* out, int* done) {
     *done = 0;
-    if (!all_blocks3(p) || !ibh_transport_blocks) return 0;
+    if (!all_blocks3(p) || !T.transport_blocks) return 0;
     const int32_t nwg = (p->nblk + 3) / 4;
     hipLaunchKernelGGL(k_scalar_transport_blocks3, dim3(nwg), dim3(256), 0, ibh_stream, p->blocks3, p->htab3, p->ftab3,
                        p->nblk, nwg, (uint32_t)p->nc, p->spacing, R, nuR, nu, vel, (uint32_t)ldv, S, out);
@@ -1904,15 +2039,13 @@ int ibh_scalar_transport_blocks(const ibh_part* p, const float* R, const float* 
     return 0;
 }
 
-// no block structure at all: the tuple cell_gradient is the face-list kernel there (ibh_cell_gradient_nd)
-static bool no_blocks(const ibh_part* p) {
-    return !(p->bs == 8 && p->nblk > 0 && (p->nd == 2 ? p->blocks2 != nullptr : p->blocks3 != nullptr));
-}
+// The fused closures: face-list kernels on a partition without block structure (the tuple cell_gradient is the face-list
+// kernel there: ibh_cell_gradient_nd), block kernels on one made of complete blocks
 int ibh_shear_rate_of_velocity_grad(ibh_part* p, const float* vel, int64_t ldv, float* S, float* G, int64_t ldg) {
     IBH_REQUIRE(p && vel && S, "ibh_shear_rate_of_velocity: null argument");
     IBH_REQUIRE(!G || ldg >= p->nc, "ibh_shear_rate_of_velocity_grad: ldg < nc");
     if (p->nc == 0) return 0;
-    if (no_blocks(p)) return ibh_shear_rate_of_velocity_cells(p, vel, ldv, S, G, ldg);
+    if (!has_blocks(p)) return ibh_shear_rate_of_velocity_cells(p, vel, ldv, S, G, ldg);
     IBH_REQUIRE(all_blocks3(p), "ibh_shear_rate_of_velocity: needs a 3-D partition made of complete blocks or one without "
                                 "block structure (compose cell_gradient and shear_rate otherwise)");
     FieldPtrs<3> V{{vel, vel + ldv, vel + 2 * ldv}};
@@ -1929,148 +2062,13 @@ int ibh_wray_agarwal_of(ibh_part* p, const float* R, const float* S, float sigma
                         float* nuR, float* Sout) {
     IBH_REQUIRE(p && R && S && nut && nuR && Sout, "ibh_wray_agarwal_of: null argument");
     if (p->nc == 0) return 0;
-    if (no_blocks(p)) return ibh_wray_agarwal_of_cells(p, R, S, sigmaR, C1, kappa, nut, nuR, Sout);
+    if (!has_blocks(p)) return ibh_wray_agarwal_of_cells(p, R, S, sigmaR, C1, kappa, nut, nuR, Sout);
     IBH_REQUIRE(all_blocks3(p), "ibh_wray_agarwal_of: needs a 3-D partition made of complete blocks or one without block "
                                 "structure (compose cell_gradient and Wray_Agarwal otherwise)");
     FieldPtrs<2> RS{{R, S}};
     const int32_t nwg = (p->nblk + 3) / 4;
     hipLaunchKernelGGL(k_wray_agarwal_of3, dim3(nwg), dim3(256), 0, ibh_stream, p->blocks3, p->htab3, p->ftab3, p->nblk, nwg,
                        RS, sigmaR, C1, kappa, nut, nuR, Sout);
-    IBH_LAUNCH_CHECK();
-    return 0;
-}
-
-int ibh_residual_euler_hll(ibh_part* p, const float* P, int64_t ldp, float* R, int64_t ldr, const ibh_fluid* fluid,
-                           int flags) {
-    IBH_REQUIRE(p && P && R && fluid, "ibh_residual_euler_hll: null argument");
-    if (p->nc == 0) return 0;
-    const bool tuned2e = p->nd == 2 && p->bs == 8 && p->nblk > 0 &&
-                         !(flags & (IBH_FORCE_GENERAL | IBH_EXACT | IBH_NO_FUSE | IBH_PASS_A_ONLY | IBH_PASS_B_ONLY));
-    if (tuned2e && (p->fuse_all || ((flags & IBH_IMAGE_ONLY) && p->img_all_fz))) {
-        // every block eligible (or only the image blocks wanted and all of them eligible: a rank of a multi-GPU run):
-        // the Euler sweep is one launch per phase, nothing goes through the workspace
-        const bool ph1 = (flags & IBH_PHASE_INTERIOR) != 0, ph2 = (flags & IBH_PHASE_BOUNDARY) != 0;
-        IBH_REQUIRE(!(ph1 && ph2), "IBH_PHASE_INTERIOR and IBH_PHASE_BOUNDARY are exclusive");
-        const int32_t* list = p->fuse_all ? nullptr : p->img_list;
-        const int32_t nall = p->fuse_all ? p->nblk : p->n_img, nint = p->fuse_all ? p->nB1 : p->n_img_int;
-        const int32_t i0 = ph2 ? nint : 0, i1 = ph1 ? nint : nall;
-        const int32_t count = i1 - i0;
-        const int k = p->fuse_all ? 0 : 1;
-        if (ibh_quad && !(flags & IBH_NO_QUAD) && p->nq[k] > 0) {
-            int32_t s0 = ph2 ? p->nqs_int[k] : 0, s1 = ph1 ? p->nqs_int[k] : p->nqs[k];
-            int32_t q0 = ph2 ? p->nq_int[k] : 0, q1 = ph1 ? p->nq_int[k] : p->nq[k];
-            if (ibh_quad_parts == 1) s1 = s0;  // measurement: quads only / single blocks only
-            if (ibh_quad_parts == 2) q1 = q0;
-            const int32_t nwgq = (q1 - q0 + WPBE - 1) / WPBE, nwgs = (s1 - s0 + WPBE - 1) / WPBE;
-            if (nwgq + nwgs > 0)
-                hipLaunchKernelGGL(k_sweep_quad_euler, dim3(nwgq + nwgs), dim3(64 * WPBE), 0, ibh_stream, P, (uint32_t)ldp,
-                                   R, (uint32_t)ldr, fluid->R, fluid->gamma, p->qd[k] + q0,
-                                   p->qtab[k] + (size_t)q0 * IBH_QROW, q1 - q0, nwgq, p->blocks2, p->htab, p->etab, p->dtab,
-                                   p->qsingles[k] + s0, s1 - s0, nwgs, ibh_quad_singles_first);
-        } else if (count > 0) {
-            const int32_t iters = ibh_sweep_iters > 0 ? ibh_sweep_iters : std::min(4, std::max(1, count / 6000));
-            const int32_t nwg = (count + WPBE * iters - 1) / (WPBE * iters);
-            const BlockDesc2* bl = list ? p->blocks2 : p->blocks2 + i0;
-            const int32_t* ht = list ? p->htab : p->htab + (size_t)i0 * 64;
-            const int32_t* et = list ? p->etab : p->etab + (size_t)i0 * 16;
-            hipLaunchKernelGGL(k_sweep_euler, dim3(nwg), dim3(64 * WPBE), 0, ibh_stream, P, (uint32_t)ldp, R, (uint32_t)ldr,
-                               fluid->R, fluid->gamma, bl, ht, et, p->dtab, count, nwg, iters, list ? list + i0 : nullptr);
-        }
-        IBH_LAUNCH_CHECK();
-        return 0;
-    }
-    if (p->nd == 3 && p->img_all3 && (flags & IBH_IMAGE_ONLY) && p->bs == 8 &&
-        !(flags & (IBH_FORCE_GENERAL | IBH_EXACT | IBH_NO_FUSE | IBH_PASS_A_ONLY | IBH_PASS_B_ONLY | IBH_PHASE_INTERIOR |
-                   IBH_PHASE_BOUNDARY))) {
-        // image blocks of a partition with skirt fragments: one launch, nothing through the workspace
-        const int32_t nwg = (p->n_img3 + WPB3E - 1) / WPB3E;
-        hipLaunchKernelGGL((k_sweep3_euler_cols<2, false, true, false>), dim3(nwg), dim3(64 * WPB3E), 0, ibh_stream, P,
-                           (uint32_t)ldp, R, (uint32_t)ldr, fluid->R, fluid->gamma, p->iblocks3, p->ihtab3, p->iftab3,
-                           p->irtab3, p->ir4tab3, p->n_img3, nwg, p->idtab3);
-        IBH_LAUNCH_CHECK();
-        return 0;
-    }
-    if (p->nd == 3 && p->sweep3 && p->bs == 8 && p->blocks3 && p->nblk > 0 &&
-        !(flags & (IBH_FORCE_GENERAL | IBH_EXACT | IBH_NO_FUSE | IBH_PASS_A_ONLY | IBH_PASS_B_ONLY | IBH_IMAGE_ONLY |
-                   IBH_PHASE_INTERIOR | IBH_PHASE_BOUNDARY))) {
-        // 3-D, every block qualifies for the single-kernel sweep: one launch, nothing through the workspace
-        if (ibh_quad_variant != 512) {
-            const bool persist = ibh_quad_variant == 514;  // A/B: persistent waves (measured slower, see above)
-            const int32_t nwg = persist ? s3e_persistent_wgs(p->nblk) : (p->nblk + WPB3E - 1) / WPB3E;
-#define S3E_LAUNCH(W, ST, PE)                                                                                         \
-    hipLaunchKernelGGL((k_sweep3_euler_cols<W, ST, false, PE>), dim3(nwg), dim3(64 * WPB3E), 0, ibh_stream, P,         \
-                       (uint32_t)ldp, R, (uint32_t)ldr, fluid->R, fluid->gamma, p->blocks3, p->htab3, p->ftab3,        \
-                       p->rtab3, p->r4tab3, p->nblk, nwg)
-            if (persist) S3E_LAUNCH(2, false, true);
-            else if (ibh_quad_variant == 4) S3E_LAUNCH(2, true, false);  // wave time stamps (scripts/wave_timeline_3d.py)
-            else S3E_LAUNCH(2, false, false);
-#undef S3E_LAUNCH
-        } else  // A/B: thread-per-cell form
-        hipLaunchKernelGGL(k_sweep3_euler, dim3(p->nblk), dim3(512), 0, ibh_stream, P, (uint32_t)ldp, R, (uint32_t)ldr,
-                           fluid->R, fluid->gamma, p->blocks3, p->htab3, p->ftab3, p->rtab3, p->r4tab3, p->nblk);
-        IBH_LAUNCH_CHECK();
-        return 0;
-    }
-    // the forms below run the whole sweep: they have no overlap phases (the single-kernel branch above does)
-    IBH_REQUIRE(!(flags & (IBH_PHASE_INTERIOR | IBH_PHASE_BOUNDARY)),
-                "ibh_residual_euler_hll: overlap phases need a partition whose (image) blocks are all eligible for the "
-                "single-kernel sweep; run the sweep unphased after the exchange");
-    int rc = ensure_G(p);
-    if (rc) return rc;
-    PartView v = view(p);
-    dim3 blk(64 * WPB);
-    // tuned block path: 2-D only and not with IBH_EXACT (the literal arithmetic lives in the face-list body)
-    const bool fast = p->bs == 8 && p->nd == 2 && p->nblk > 0 && !(flags & (IBH_FORCE_GENERAL | IBH_EXACT));
-    const int32_t nwg_fast = fast ? (p->nblk + WPB - 1) / WPB : 0;
-    const int32_t* cellsA = fast ? p->irr_cells : nullptr;
-    const int32_t nA = fast ? p->n_irr : p->nc;
-    const int32_t* cellsB = cellsA;
-    int32_t nB = nA;
-    if ((flags & IBH_IMAGE_ONLY) && !fast) {
-        cellsB = p->image_in_domain;
-        nB = p->n_image;
-    }
-    dim3 gA(nwg_fast + (nA + 64 * WPB - 1) / (64 * WPB)), gB((nB + 64 * WPB - 1) / (64 * WPB));
-    const bool doA = gA.x && !(flags & IBH_PASS_B_ONLY), doB = !(flags & IBH_PASS_A_ONLY);
-    if (p->nd == 2) {
-        if (doA && fast)
-            hipLaunchKernelGGL((k_passA<2, 4, false>), gA, blk, 0, ibh_stream, v, P, ldp, p->G, p->blocks2, p->htab,
-                               p->nblk, nwg_fast, cellsA, nA, flat_of(p, cellsA), nullptr);
-        else if (doA)
-            hipLaunchKernelGGL((k_passA<2, 4, true>), gA, blk, 0, ibh_stream, v, P, ldp, p->G, p->blocks2, p->htab,
-                               p->nblk, 0, cellsA, nA, flat_of(p, cellsA), nullptr);
-        if (doB && nwg_fast)
-            hipLaunchKernelGGL(k_passB_euler_blk, dim3(nwg_fast), blk, 0, ibh_stream, (uint32_t)p->nc, P, (uint32_t)ldp,
-                               p->G, R, (uint32_t)ldr, fluid->R, fluid->gamma, p->blocks2, p->htab, p->nblk, nwg_fast);
-        if (doB && gB.x)
-            hipLaunchKernelGGL((k_passB_euler<2>), gB, blk, 0, ibh_stream, v, P, ldp, p->G, R, ldr, fluid->R,
-                               fluid->gamma, cellsB, nB);
-    } else if (p->bs == 8 && p->blocks3 && p->nblk > 0 && !(flags & (IBH_FORCE_GENERAL | IBH_EXACT))) {
-        // 3-D block path: block kernels + the face-list kernels over the cells the analysis left out
-        const int32_t nI = p->n_irr;
-        const int32_t gI = (nI + 511) / 512;
-        if (!(flags & IBH_PASS_B_ONLY) && ibh_3d_wave) {
-            const int32_t nwgA = (p->nblk + 3) / 4, gIw = (nI + 255) / 256;
-            hipLaunchKernelGGL(k_passA3e_wave, dim3(nwgA + gIw), dim3(256), 0, ibh_stream, v, P, ldp, p->G, p->blocks3,
-                               p->htab3, p->ftab3, p->nblk, nwgA, p->irr_cells, nI, flat_of(p, p->irr_cells));
-        } else if (!(flags & IBH_PASS_B_ONLY))
-            hipLaunchKernelGGL(k_passA3e_blk, dim3(p->nblk + gI), dim3(512), 0, ibh_stream, v, P, ldp, p->G, p->blocks3,
-                               p->htab3, p->ftab3, p->nblk, p->irr_cells, nI, flat_of(p, p->irr_cells));
-        if (!(flags & IBH_PASS_A_ONLY)) {
-            hipLaunchKernelGGL(k_passB3e_blk, dim3(p->nblk), dim3(512), 0, ibh_stream, (uint32_t)p->nc, P, (uint32_t)ldp,
-                               p->G, R, (uint32_t)ldr, fluid->R, fluid->gamma, p->blocks3, p->htab3, p->ftab3, p->nblk);
-            if (nI)
-                hipLaunchKernelGGL((k_passB_euler<3>), dim3((nI + 64 * WPB - 1) / (64 * WPB)), blk, 0, ibh_stream, v, P,
-                                   ldp, p->G, R, ldr, fluid->R, fluid->gamma, p->irr_cells, nI);
-        }
-    } else {
-        if (doA)
-            hipLaunchKernelGGL((k_passA<3, 5, true>), gA, blk, 0, ibh_stream, v, P, ldp, p->G, p->blocks2, p->htab,
-                               p->nblk, 0, cellsA, nA, flat_of(p, cellsA), nullptr);
-        if (doB && gB.x)
-            hipLaunchKernelGGL((k_passB_euler<3>), gB, blk, 0, ibh_stream, v, P, ldp, p->G, R, ldr, fluid->R,
-                               fluid->gamma, cellsB, nB);
-    }
     IBH_LAUNCH_CHECK();
     return 0;
 }
