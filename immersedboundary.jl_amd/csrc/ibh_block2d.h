@@ -1,6 +1,6 @@
 // Block fast path, 2-D, 8x8 blocks: one 64-lane wavefront per block, lane = cell (x fastest).
 //
-// This is the tuned form of the fast path (the literal IEEE form lives in ibh_fused.hip and is
+// This is the tuned form of the fast path (the literal IEEE form lives in ibh_facelist.h and is
 // selected with IBH_EXACT).  Differences, all within the 1e-5 norm-wise parity tolerance:
 //   * the divisions of the reference formulas are replaced by per-block reciprocals (1/hx, 1/hy
 //     are wave-uniform, stored in the block descriptor) and per-side weights: inside a block and
@@ -20,6 +20,10 @@
 // LDS per wave and field: tile[64] followed by halo[64] (slot = (side*8 + t)*2 + k).
 #pragma once
 #include "ibh_common.h"
+
+#ifndef WPB
+#define WPB 4  // waves (= blocks) per workgroup of 64*WPB threads: the 2-D block kernels and the face-list kernels
+#endif
 
 namespace blk2 {
 
@@ -110,7 +114,7 @@ __device__ __forceinline__ void cell_G(const float* f, const Lane& L, const Bloc
 
 // ------------------------------------------------------------------------------------------
 // pass A: gradients of NV variables along x and y + JST sensor of variable 0
-// G layout as in ibh_fused.hip: grad of var v along dim d at G[(d*NV+v)*nc + c], sensor at G[2*NV*nc + c]
+// G layout as in ibh_facelist.h: grad of var v along dim d at G[(d*NV+v)*nc + c], sensor at G[2*NV*nc + c]
 // LDS per wave: NV * 128 floats
 // ------------------------------------------------------------------------------------------
 template <int NV>

@@ -1366,7 +1366,7 @@ __device__ __forceinline__ void passA_wave_nv(const BlockDesc3* __restrict__ blo
 
 // gradients of NV cell fields of one block in registers, g[v][k][d] (plane k of this lane's column, dimension d): the
 // arithmetic of passA_wave_nv without the stores and the sensor -- for kernels that consume the gradients where they
-// are made (shear rate of a velocity field, the Wray-Agarwal closure: ibh_fused.hip).  Blocks without GENERAL sides only.
+// are made (shear rate of a velocity field, the Wray-Agarwal closure: ibh_turb.hip).  Blocks without GENERAL sides only.
 template <int NV>
 __device__ __forceinline__ void wave_gradients(const BlockDesc3& bb, const int32_t* __restrict__ htab,
                                                const int32_t* __restrict__ ftab, int32_t blk, const float* const* F,

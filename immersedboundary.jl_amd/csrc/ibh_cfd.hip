@@ -1,7 +1,7 @@
 // libibhip: CFD pointwise physics (cfd.jl) as standalone kernels, one thread per row, literal
 // Float32 arithmetic in the reference's evaluation order (-ffp-contract=off).  These exist so that
 // operator-granularity closures (`CFD.inviscid_fluxes(fluid, PL, PR, dim)` etc.) run on device arrays;
-// the fused sweeps of ibh_fused.hip inline the same formulas (ibh_flux.h).
+// the fused sweeps (ibh_fused*.hip) inline the same formulas (ibh_flux.h).
 #include "ibh_common.h"
 #include "ibh_flux.h"
 

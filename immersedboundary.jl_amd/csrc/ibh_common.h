@@ -190,14 +190,11 @@ struct ibh_bcset {
     int32_t* mode = nullptr;
 };
 
-// internal: face-list forms of the fused turbulence closures (ibh_ops.hip), dispatched from ibh_fused.hip
+// internal: face-list forms of the fused turbulence closures (ibh_ops.hip), dispatched from ibh_turb.hip
 extern "C" int ibh_shear_rate_of_velocity_cells(const ibh_part* p, const float* vel, int64_t ldv, float* S, float* Gout,
                                                 int64_t ldg);
 extern "C" int ibh_wray_agarwal_of_cells(const ibh_part* p, const float* R, const float* S, float sigmaR, float C1,
                                          float kappa, float* nut, float* nuR, float* Sout);
-
-extern "C" int ibh_scalar_transport_blocks(const ibh_part* p, const float* R, const float* nuR, float nu, const float* vel,
-                                           int64_t ldv, const float* S, float* out, int* done);
 
 // internal: the boundary-condition set with the next step's time step beside it (ibh_ops.hip), called from ibh_fused.hip
 extern "C" int ibh_bcset_apply_with_dt(const ibh_bcset* s, float* a, ibh_part* p, const float* C, int64_t ldc, float scale,
@@ -285,6 +282,14 @@ static inline int ibh_grid(int64_t n, int block) {
 __device__ __forceinline__ int32_t ibh_xcd_chunk(int32_t wg, int32_t nwg) {
     const int32_t q = nwg >> 3, r = nwg & 7, xcd = wg & 7, idx = wg >> 3;
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
+// the same for kernels that run over blocks (IBH_NO_XCD_REMAP: A/B builds); placement only affects speed
+__device__ __forceinline__ int32_t xcd_remap(int32_t wg, int32_t nwg) {
+#ifdef IBH_NO_XCD_REMAP
+    return wg;
+#else
+    return ibh_xcd_chunk(wg, nwg);
+#endif
 }
 // the workgroup's position along x for kernels that run over cells (or output rows) and gather from neighbouring cells
 #ifdef IBH_NO_XCD_CELLS   // (A/B builds)

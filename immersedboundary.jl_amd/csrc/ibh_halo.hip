@@ -126,7 +126,7 @@ __global__ void k_halo_pull(float* __restrict__ f, int nv, int64_t ld, const int
     }
 }
 
-// push and pull in ONE launch (body: ibh_halo_dev.h, shared with the fused step kernel of ibh_fused.hip)
+// push and pull in ONE launch (body: ibh_halo_dev.h, shared with the fused step kernel of ibh_fused2d.hip)
 __global__ void k_halo_exchange(float* __restrict__ f, int nv, int64_t ld, const int32_t* __restrict__ send_all,
                                 const int32_t* __restrict__ recv_all, const float* __restrict__ src0,
                                 const float* __restrict__ src1, XchgArgs A, uint32_t* __restrict__ state,

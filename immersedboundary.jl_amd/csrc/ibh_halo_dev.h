@@ -1,4 +1,4 @@
-// Device side of the one-launch xGMI halo exchange (ibh_halo.hip: k_halo_exchange; ibh_fused.hip: the fused
+// Device side of the one-launch xGMI halo exchange (ibh_halo.hip: k_halo_exchange; ibh_fused2d.hip: the fused
 // exchange + sweep step).  `wg` of `nwg` workgroups of 256 threads run the body; all of them must be resident.
 #pragma once
 #include "ibh_common.h"

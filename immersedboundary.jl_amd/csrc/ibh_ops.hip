@@ -730,7 +730,7 @@ int ibh_cell_gradient_all(const ibh_part* p, const float* u, int nv, int64_t ldu
     return 0;
 }
 
-// face-list forms of ibh_shear_rate_of_velocity / ibh_wray_agarwal_of (ibh_fused.hip dispatches here on partitions
+// face-list forms of ibh_shear_rate_of_velocity / ibh_wray_agarwal_of (ibh_turb.hip dispatches here on partitions
 // without block structure)
 int ibh_shear_rate_of_velocity_cells(const ibh_part* p, const float* vel, int64_t ldv, float* S, float* Gout, int64_t ldg) {
     const GradDims G = grad_dims(p);

@@ -3,7 +3,9 @@
 // Wray_Agarwal :222-241, Ducros_sensor :252-282, WALE_νSGS :291-337.  Float32, the reference's operation order
 // (-ffp-contract=off); log/exp/pow come from the device math library (a few ulp from Julia's).
 // Velocity gradients: an nd x nd table of device pointers, g[i*nd + j] = d u_i / d x_j (the reference's Matrix of vectors).
+// At the end: the closures on an all-block 3-D partition with the gradients made where they are consumed (block kernels).
 #include "ibh_common.h"
+#include "ibh_fused_int.h"
 
 namespace {
 
@@ -237,6 +239,211 @@ __global__ void k_scalar_transport(int32_t nc, TransportDims T, const float* __r
     }
 }
 
+}  // namespace
+
+#include "ibh_block3d.h"  // (here, not at the top: the pointwise kernels above are compiled as before without it)
+
+namespace {
+
+// ---- closures of a turbulence model on an all-block 3-D partition, gradients consumed where they are made (one wavefront
+// per 8^3 block, blk3::wave_gradients: the arithmetic of the tuple cell_gradient's block sweep; the pointwise formulas are
+// those of k_shear / k_wray_agarwal above, evaluated without contraction):
+//   k_shear_of_velocity3: S = shear_rate(cell_gradient(u), cell_gradient(v), cell_gradient(w))      (turbulence.jl:110-124)
+//   k_wray_agarwal_of3:   (nut, nuR, S) = Wray_Agarwal(R, S, cell_gradient(R), cell_gradient(S))    (turbulence.jl:222-241)
+// 12 B in + 4 B out per cell instead of 3 x (4 in + 16 out) + 36 in + 4 out; 8 in + 12 out instead of 2 x 20 + 44.
+template <int NV>
+struct FieldPtrs {
+    const float* f[NV];
+};
+__global__ __launch_bounds__(256) void k_shear_of_velocity3(const BlockDesc3* __restrict__ blocks,
+                                                            const int32_t* __restrict__ htab,
+                                                            const int32_t* __restrict__ ftab, int32_t nblk, int32_t nwg,
+                                                            FieldPtrs<3> V, float* __restrict__ S,
+                                                            float* __restrict__ Gout, uint32_t ldg) {
+    // Gout (or null): the nine gradients on the way, d u_i / d x_j in column 3 j + i (the tuple cell_gradient's layout) --
+    // a Navier-Stokes closure needs them again for its viscous fluxes (three pass-A sweeps otherwise)
+    __shared__ float lds[4 * BLK3W_PASSA_LDS];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int32_t blk = __builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x, nwg) * 4 + wave);
+    if (blk >= nblk) return;
+    const BlockDesc3 bb = blocks[blk];
+    float g[3][8][3];
+    blk3::wave_gradients<3>(bb, htab, ftab, blk, V.f, lds + wave * BLK3W_PASSA_LDS, lane, g);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        float s = 0.0f;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const float t = (g[i][k][j] + g[j][k][i]) / 2.0f;
+                s = s + t * t;
+            }
+        S[(uint32_t)bb.base + lane + 64 * k] = sqrtf(2.0f * s);
+        if (Gout) {  // (uniform)
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = 0; j < 3; ++j)
+                    __builtin_nontemporal_store(g[i][k][j], Gout + (size_t)(3 * j + i) * ldg + (uint32_t)bb.base + lane + 64 * k);
+        }
+    }
+}
+__global__ __launch_bounds__(256) void k_wray_agarwal_of3(const BlockDesc3* __restrict__ blocks,
+                                                          const int32_t* __restrict__ htab,
+                                                          const int32_t* __restrict__ ftab, int32_t nblk, int32_t nwg,
+                                                          FieldPtrs<2> RS, float sigmaR, float C1, float kappa,
+                                                          float* __restrict__ nut, float* __restrict__ nuR,
+                                                          float* __restrict__ Sout) {
+    __shared__ float lds[4 * BLK3W_PASSA_LDS];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int32_t blk = __builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x, nwg) * 4 + wave);
+    if (blk >= nblk) return;
+    const BlockDesc3 bb = blocks[blk];
+    float g[2][8][3];
+    blk3::wave_gradients<2>(bb, htab, ftab, blk, RS.f, lds + wave * BLK3W_PASSA_LDS, lane, g);
+    const float C2 = sigmaR + C1 / (kappa * kappa);
+    constexpr float EPS32 = 1.1920929e-07f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const uint32_t c = (uint32_t)bb.base + lane + 64 * k;
+        float dot = g[0][k][0] * g[1][k][0];
+        dot = dot + g[0][k][1] * g[1][k][1];
+        dot = dot + g[0][k][2] * g[1][k][2];
+        const float r = RS.f[0][c], s = RS.f[1][c];
+        const float src = C1 * r * s + C2 * dot * (r / (s + EPS32));
+        nut[c] = r;
+        nuR[c] = r * sigmaR;
+        Sout[c] = ibh_min(src, 10.0f * r);
+    }
+}
+
+// ---- transport of a scalar with variable diffusivity on an all-block 3-D partition (k_scalar_transport above is
+// the face-list form): out = S + sum_d green_gauss(at_faces(nu + nuR, d) .* face_gradient(R, d) .- at_faces(u_d .* R, d), d).
+// One wavefront per 8^3 block, lane = (i, j) with its z-column of R, nu + nuR and u_d R in registers; x / y neighbours from
+// four LDS tiles; lane t also owns slot t of the six sides: it gathers the cell(s) across, evaluates the side's face flux(es)
+// -- one, or the mean of four behind a FINE side -- and leaves it for the boundary cell.  The expressions and their order
+// are those of the face-list kernel (no contraction): equal bit for bit wherever a side has one face.
+#define TR3_LDS (4 * 512 + 384)
+__device__ __forceinline__ float tr3_avg(float uo, float un, float ho, float hn) { return (uo * hn + un * ho) / (hn + ho); }
+__device__ __forceinline__ float tr3_flux(float Ro, float Rn, float To, float Tn, float Ao, float An, float ho, float hn) {
+    const float conv = tr3_avg(Ao, An, ho, hn);   // at_faces(u_d .* R)
+    const float nuf = tr3_avg(To, Tn, ho, hn);    // at_faces(nu .+ nuR)
+    const float fd = (ho + hn) / 2.0f;            // face_distance
+    const float fg = (Rn - Ro) / fd;              // face_gradient(R)
+    return nuf * fg - conv;
+}
+__global__ __launch_bounds__(256) void k_scalar_transport_blocks3(const BlockDesc3* __restrict__ blocks,
+                                                                  const int32_t* __restrict__ htab,
+                                                                  const int32_t* __restrict__ ftab, int32_t nblk,
+                                                                  int32_t nwg, uint32_t nc, const float* __restrict__ hsp,
+                                                                  const float* __restrict__ R, const float* __restrict__ nuR,
+                                                                  float nu, const float* __restrict__ vel, uint32_t ldv,
+                                                                  const float* __restrict__ S, float* __restrict__ out) {
+    using blk2::ldg;
+    __shared__ float lds_all[4 * TR3_LDS];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int32_t blk = __builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x, nwg) * 4 + wave);
+    if (blk >= nblk) return;
+    float* lds = lds_all + wave * TR3_LDS;
+    float *tR = lds, *tT = lds + 512, *tAx = lds + 1024, *tAy = lds + 1536, *Hf = lds + 2048;
+    const BlockDesc3 bb = blocks[blk];
+    const uint32_t base = (uint32_t)bb.base;
+    const float h[3] = {hsp[base], hsp[nc + base], hsp[2 * (size_t)nc + base]};   // the block's spacing as the cells hold it
+    float Rk[8], Tk[8], Ak[3][8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const uint32_t c = base + lane + 64 * k;
+        Rk[k] = ldg(R, c);
+        Tk[k] = nu + ldg(nuR, c);
+#pragma unroll
+        for (int d = 0; d < 3; ++d) Ak[d][k] = ldg(vel + (size_t)d * ldv, c) * Rk[k];
+    }
+    uint32_t hid[6];
+    hid[0] = blk3::halo_cell3s<0>(bb, htab, blk, lane);
+    hid[1] = blk3::halo_cell3s<1>(bb, htab, blk, lane);
+    hid[2] = blk3::halo_cell3s<2>(bb, htab, blk, lane);
+    hid[3] = blk3::halo_cell3s<3>(bb, htab, blk, lane);
+    hid[4] = blk3::halo_cell3s<4>(bb, htab, blk, lane);
+    hid[5] = blk3::halo_cell3s<5>(bb, htab, blk, lane);
+    float hR[6], hT[6], hA[6], hh[6];
+#pragma unroll
+    for (int s = 0; s < 6; ++s) {
+        const int d = s >> 1;
+        hR[s] = ldg(R, hid[s]);
+        hT[s] = nu + ldg(nuR, hid[s]);
+        hA[s] = ldg(vel + (size_t)d * ldv, hid[s]) * hR[s];
+        hh[s] = ldg(hsp + (size_t)d * nc, hid[s]);
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        tR[k * 64 + lane] = Rk[k];
+        tT[k * 64 + lane] = Tk[k];
+        tAx[k * 64 + lane] = Ak[0][k];
+        tAy[k * 64 + lane] = Ak[1][k];
+    }
+    blk2::wave_lds_sync();
+    // side fluxes: slot t = lane of side s belongs to boundary cell pos(s, t) of the tile
+#pragma unroll
+    for (int s = 0; s < 6; ++s) {
+        const int d = s >> 1;
+        const bool low = (s & 1) == 0;
+        const int sd = d == 0 ? 1 : d == 1 ? 8 : 64, sa = d == 0 ? 8 : 1, sb = d == 2 ? 8 : 64;
+        const int pos = (low ? 0 : 7) * sd + (lane & 7) * sa + (lane >> 3) * sb;
+        const float Rb = tR[pos], Tb = tT[pos];
+        const float Ab = d == 0 ? tAx[pos] : d == 1 ? tAy[pos] : (low ? Ak[2][0] : Ak[2][7]);
+        const float hb = h[d];
+        // the halo cell is the owner on a low side, the neighbour on a high side
+        float F = low ? tr3_flux(hR[s], Rb, hT[s], Tb, hA[s], Ab, hh[s], hb) : tr3_flux(Rb, hR[s], Tb, hT[s], Ab, hA[s], hb, hh[s]);
+        if (bb.type[s] == SIDE_FINE) {  // wave-uniform: three more faces behind this slot, mean of the four fluxes
+            const int32_t* ft = ftab + (((size_t)bb.fine * 6 + s) * 64 + lane) * 3;
+            F = F * 0.25f;
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                const uint32_t x = (uint32_t)ft[q];
+                const float Rx = ldg(R, x), Tx = nu + ldg(nuR, x), Ax = ldg(vel + (size_t)d * ldv, x) * Rx;
+                const float hx = ldg(hsp + (size_t)d * nc, x);
+                const float Fq = low ? tr3_flux(Rx, Rb, Tx, Tb, Ax, Ab, hx, hb) : tr3_flux(Rb, Rx, Tb, Tx, Ab, Ax, hb, hx);
+                F = F + Fq * 0.25f;
+            }
+        } else {
+            F = F * 1.0f;
+        }
+        Hf[s * 64 + lane] = F;
+    }
+    blk2::wave_lds_sync();
+    const int i = lane & 7, j = lane >> 3;
+    const bool e0 = i == 0, e1 = i == 7, e2 = j == 0, e3 = j == 7;
+    const float fzl = Hf[4 * 64 + lane], fzh = Hf[5 * 64 + lane];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const uint32_t c = base + lane + 64 * k;
+        const float *r = tR + k * 64, *t = tT + k * 64, *ax = tAx + k * 64, *ay = tAy + k * 64;
+        const float Rc = Rk[k], Tc = Tk[k];
+        float fl[3], fr[3];
+        // x and y: inside the plane or the side's flux (x sides: slot j + 8 k, y sides: slot i + 8 k)
+        const int xl = e0 ? lane : lane - 1, xr = e1 ? lane : lane + 1, yl = e2 ? lane : lane - 8, yr = e3 ? lane : lane + 8;
+        const float fxl = tr3_flux(r[xl], Rc, t[xl], Tc, ax[xl], Ak[0][k], h[0], h[0]) * 1.0f;
+        const float fxr = tr3_flux(Rc, r[xr], Tc, t[xr], Ak[0][k], ax[xr], h[0], h[0]) * 1.0f;
+        const float fyl = tr3_flux(r[yl], Rc, t[yl], Tc, ay[yl], Ak[1][k], h[1], h[1]) * 1.0f;
+        const float fyr = tr3_flux(Rc, r[yr], Tc, t[yr], Ak[1][k], ay[yr], h[1], h[1]) * 1.0f;
+        fl[0] = e0 ? Hf[0 * 64 + j + 8 * k] : fxl;
+        fr[0] = e1 ? Hf[1 * 64 + j + 8 * k] : fxr;
+        fl[1] = e2 ? Hf[2 * 64 + i + 8 * k] : fyl;
+        fr[1] = e3 ? Hf[3 * 64 + i + 8 * k] : fyr;
+        // z: registers
+        const int kl = k > 0 ? k - 1 : 0, kh = k < 7 ? k + 1 : 7;
+        const float fzl_in = tr3_flux(Rk[kl], Rc, Tk[kl], Tc, Ak[2][kl], Ak[2][k], h[2], h[2]) * 1.0f;
+        const float fzr_in = tr3_flux(Rc, Rk[kh], Tc, Tk[kh], Ak[2][k], Ak[2][kh], h[2], h[2]) * 1.0f;
+        fl[2] = k == 0 ? fzl : fzl_in;
+        fr[2] = k == 7 ? fzh : fzr_in;
+        float rt = ldg(S, c);
+#pragma unroll
+        for (int d = 0; d < 3; ++d) rt = rt + (fr[d] - fl[d]) / h[d];
+        out[c] = rt;
+    }
+}
+
 inline int tgrid(int64_t n) {
     int g = ibh_grid(n, TB);
     return g > 4096 ? 4096 : g;
@@ -316,12 +523,24 @@ int ibh_turb_wray_agarwal(int nd, int64_t n, const float* R, const float* S, con
     IBH_LAUNCH_CHECK();
     return 0;
 }
+// ibh_scalar_transport on an all-block 3-D partition (*done = 0: not applicable here)
+int ibh_scalar_transport_blocks(const ibh_part* p, const float* R, const float* nuR, float nu, const float* vel, int64_t ldv,
+                                const float* S, float* out, int* done) {
+    *done = 0;
+    if (!fused::all_blocks3(p) || !fused::T.transport_blocks) return 0;
+    const int32_t nwg = (p->nblk + 3) / 4;
+    hipLaunchKernelGGL(k_scalar_transport_blocks3, dim3(nwg), dim3(256), 0, ibh_stream, p->blocks3, p->htab3, p->ftab3,
+                       p->nblk, nwg, (uint32_t)p->nc, p->spacing, R, nuR, nu, vel, (uint32_t)ldv, S, out);
+    IBH_LAUNCH_CHECK();
+    *done = 1;
+    return 0;
+}
 int ibh_scalar_transport(const ibh_part* p, const float* R, const float* nuR, float nu, const float* vel, int64_t ldv,
                          const float* S, float* out) {
     IBH_REQUIRE(p && R && nuR && vel && S && out && (p->nd == 2 || p->nd == 3), "ibh_scalar_transport: bad argument");
     if (p->nc == 0) return 0;
     {
-        int done = 0;   // all-block 3-D partitions: the block kernel (ibh_fused.hip)
+        int done = 0;   // all-block 3-D partitions: the block kernel
         const int rc = ibh_scalar_transport_blocks(p, R, nuR, nu, vel, ldv, S, out, &done);
         if (rc || done) return rc;
     }
@@ -357,6 +576,40 @@ int ibh_turb_wale(int64_t n, const float* Delta, const float* const* g, float Cw
     if (rc) return rc;
     IBH_REQUIRE(Delta && out, "ibh_turb_wale: null argument");
     hipLaunchKernelGGL(k_wale, dim3(tgrid(n)), dim3(TB), 0, ibh_stream, n, Delta, G, Cw, out);
+    IBH_LAUNCH_CHECK();
+    return 0;
+}
+
+// The fused closures: face-list kernels on a partition without block structure (the tuple cell_gradient is the face-list
+// kernel there: ibh_cell_gradient_nd), block kernels on one made of complete blocks
+int ibh_shear_rate_of_velocity_grad(ibh_part* p, const float* vel, int64_t ldv, float* S, float* G, int64_t ldg) {
+    IBH_REQUIRE(p && vel && S, "ibh_shear_rate_of_velocity: null argument");
+    IBH_REQUIRE(!G || ldg >= p->nc, "ibh_shear_rate_of_velocity_grad: ldg < nc");
+    if (p->nc == 0) return 0;
+    if (!fused::has_blocks(p)) return ibh_shear_rate_of_velocity_cells(p, vel, ldv, S, G, ldg);
+    IBH_REQUIRE(fused::all_blocks3(p), "ibh_shear_rate_of_velocity: needs a 3-D partition made of complete blocks or one without "
+                                "block structure (compose cell_gradient and shear_rate otherwise)");
+    FieldPtrs<3> V{{vel, vel + ldv, vel + 2 * ldv}};
+    const int32_t nwg = (p->nblk + 3) / 4;
+    hipLaunchKernelGGL(k_shear_of_velocity3, dim3(nwg), dim3(256), 0, ibh_stream, p->blocks3, p->htab3, p->ftab3, p->nblk, nwg,
+                       V, S, G, (uint32_t)ldg);
+    IBH_LAUNCH_CHECK();
+    return 0;
+}
+int ibh_shear_rate_of_velocity(ibh_part* p, const float* vel, int64_t ldv, float* S) {
+    return ibh_shear_rate_of_velocity_grad(p, vel, ldv, S, nullptr, 0);
+}
+int ibh_wray_agarwal_of(ibh_part* p, const float* R, const float* S, float sigmaR, float C1, float kappa, float* nut,
+                        float* nuR, float* Sout) {
+    IBH_REQUIRE(p && R && S && nut && nuR && Sout, "ibh_wray_agarwal_of: null argument");
+    if (p->nc == 0) return 0;
+    if (!fused::has_blocks(p)) return ibh_wray_agarwal_of_cells(p, R, S, sigmaR, C1, kappa, nut, nuR, Sout);
+    IBH_REQUIRE(fused::all_blocks3(p), "ibh_wray_agarwal_of: needs a 3-D partition made of complete blocks or one without block "
+                                "structure (compose cell_gradient and Wray_Agarwal otherwise)");
+    FieldPtrs<2> RS{{R, S}};
+    const int32_t nwg = (p->nblk + 3) / 4;
+    hipLaunchKernelGGL(k_wray_agarwal_of3, dim3(nwg), dim3(256), 0, ibh_stream, p->blocks3, p->htab3, p->ftab3, p->nblk, nwg,
+                       RS, sigmaR, C1, kappa, nut, nuR, Sout);
     IBH_LAUNCH_CHECK();
     return 0;
 }

@@ -1,4 +1,5 @@
-"""What the fused-sweep dispatch of csrc/ibh_fused.hip launches and computes, for comparing two builds of libibhip.so.
+"""What the fused-sweep dispatch of csrc/ibh_fused.hip (kernels and launchers: csrc/ibh_fused2d.hip, ibh_fused3d.hip,
+ibh_fused_general.hip, the block closures of ibh_turb.hip) launches and computes, for comparing two builds of libibhip.so.
 
     IBHIP_LIB=<build> python scripts/dispatch_trace.py --out run.json
         runs every sweep entry point on five kinds of partition (2-D single, 2-D with skirt fragments, 3-D all-block, 3-D

@@ -2,7 +2,7 @@
 
 The checker is tests/percell.py (bounds, scales and the per-class report); tests/test_percell.py calibrates it and shows
 that it sees errors the norm-wise checks cannot.  Each test builds one float64 reference per mesh and field and runs
-every form of ``ibh_residual_advection`` / ``ibh_residual_euler_hll`` (csrc/ibh_fused.hip) that computes the residual on
+every form of ``ibh_residual_advection`` / ``ibh_residual_euler_hll`` (csrc/ibh_fused*.hip) that computes the residual on
 that kind of partition against it, with the same bound.  ``dpart.info`` pins the coverage: a mesh change that empties a
 block or side class fails here instead of silently dropping it.
 
