@@ -531,7 +531,7 @@ __global__ void k_bc_blend(int32_t ng, const int32_t* __restrict__ ghost, const 
 }
 
 __global__ void k_axpy_clamped(int64_t n, float omega, const float* __restrict__ r, float* __restrict__ q) {
-    float w = fminf(fmaxf(omega, 0.0f), 1.0f);
+    float w = ibh_clamp(omega, 0.0f, 1.0f);   // Julia's clamp: a NaN omega stays NaN
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
         q[i] = q[i] + w * r[i];
 }
@@ -583,7 +583,7 @@ __global__ void k_sumsq(int64_t n, const float* __restrict__ x, double* __restri
 // q += clamp(omega, 0, 1) * r and out += sum r^2 in one pass over r (solver.jl:82 and the norm of :84 on the same array)
 __global__ void k_axpy_clamped_sumsq(int64_t n, float omega, const float* __restrict__ r, float* __restrict__ q,
                                      double* __restrict__ out) {
-    const float w = fminf(fmaxf(omega, 0.0f), 1.0f);
+    const float w = ibh_clamp(omega, 0.0f, 1.0f);   // Julia's clamp: a NaN omega stays NaN
     double s = 0.0;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const float ri = r[i];
@@ -607,7 +607,7 @@ __global__ void k_axpy_clamped_sumsq(int64_t n, float omega, const float* __rest
 template <bool SRC, bool UPD, bool NRM>
 __global__ void k_fas_update(int64_t n, float omega, const float* __restrict__ r, const float* __restrict__ src,
                              float* __restrict__ q, double* __restrict__ out) {
-    const float w = fminf(fmaxf(omega, 0.0f), 1.0f);
+    const float w = ibh_clamp(omega, 0.0f, 1.0f);   // Julia's clamp: a NaN omega stays NaN
     double s = 0.0;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         float ri = r[i];

@@ -168,11 +168,13 @@ __global__ void k_dot(int64_t n, const float* __restrict__ a, const float* __res
     }
 }
 __global__ void k_maxabs(int64_t n, const float* __restrict__ a, uint32_t* __restrict__ out) {
+    // Julia's maximum(abs, a) propagates NaN (ibh_max); the bits of |NaN| are above those of Inf, so the integer
+    // maximum keeps it
     float m = 0.0f;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        m = fmaxf(m, fabsf(a[i]));
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_down(m, o, 64));
-    if ((threadIdx.x & 63) == 0) atomicMax(out, __float_as_uint(m));
+        m = ibh_max(m, fabsf(a[i]));
+    for (int o = 32; o > 0; o >>= 1) m = ibh_max(m, __shfl_down(m, o, 64));
+    if ((threadIdx.x & 63) == 0) atomicMax(out, __float_as_uint(m) & 0x7fffffffu);
 }
 
 // x += alpha s ; r -= alpha As  with  alpha = AvB / (AvAv + eps)  read from device memory (:231-236, :291-294)
