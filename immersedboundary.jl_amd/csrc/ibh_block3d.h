@@ -91,58 +91,6 @@ __device__ __forceinline__ uint32_t halo_cell3(const BlockDesc3& bb, const int32
 }
 
 // ------------------------------------------------------------------------------------------
-// pass A (scalar field): gradients along x, y, z + JST sensor.  LDS: 896 floats.
-// ------------------------------------------------------------------------------------------
-__device__ __forceinline__ void passA(const BlockDesc3* __restrict__ blocks, const int32_t* __restrict__ htab,
-                                      const int32_t* __restrict__ ftab, int32_t blk, uint32_t nc,
-                                      const float* __restrict__ u, float* __restrict__ G, float* lds, int tid) {
-    const BlockDesc3 bb = blocks[blk];
-    const uint32_t c = (uint32_t)bb.base + tid;
-    const uint32_t hidx = halo_cell3(bb, htab, blk, tid);
-    const float uc = ldg(u, c);
-    const float hv = ldg(u, hidx);
-    lds[tid] = uc;
-    if (tid < 384) lds[512 + tid] = hv;
-    const Lane3 L = lane_info(bb, tid);
-    __syncthreads();
-    float g[3], D = 1e-7f;
-    const int tt[3] = {L.j + 8 * L.k, L.i + 8 * L.k, L.i + 8 * L.j};
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        const float rh = bb.rh[d];
-        float vm[2], am[2];  // mean neighbour value and mean |difference| towards the low / high side
-#pragma unroll
-        for (int side = 0; side < 2; ++side) {
-            const int s = 2 * d + side;
-            const float v0 = lds[L.nidx[s]];
-            vm[side] = v0;
-            am[side] = fabsf(v0 - uc);
-            if (bb.type[s] == SIDE_FINE) {  // wave-uniform: 4 fine cells behind every boundary cell of this side
-                if (L.edge[s]) {
-                    const int32_t* ft = ftab + (((size_t)bb.fine * 6 + s) * 64 + tt[d]) * 3;
-                    const float v1 = ldg(u, (uint32_t)ft[0]), v2 = ldg(u, (uint32_t)ft[1]), v3 = ldg(u, (uint32_t)ft[2]);
-                    vm[side] = 0.25f * (v0 + v1 + v2 + v3);
-                    am[side] = 0.25f * (fabsf(v0 - uc) + fabsf(v1 - uc) + fabsf(v2 - uc) + fabsf(v3 - uc));
-                }
-            }
-        }
-        const float fr = uc + L.q[2 * d + 1] * (vm[1] - uc);  // at_faces: (1-q)*u_self + q*u_nb
-        const float fl = uc + L.q[2 * d] * (vm[0] - uc);
-        g[d] = (fr - fl) * rh;
-        const float dr = vm[1] - uc, dl = uc - vm[0];
-        const float gg = (dr - dl) * rh;
-        const float ugg = (am[1] + am[0]) * rh;
-        D = fmaxf(D, (1e-7f + fabsf(gg)) * __builtin_amdgcn_rcpf(1e-7f + ugg));
-    }
-    if (!L.general) {
-        stg(G, c, g[0]);
-        stg(G + nc, c, g[1]);
-        stg(G + (size_t)2 * nc, c, g[2]);
-        stg(G + (size_t)3 * nc, c, D);
-    }
-}
-
-// ------------------------------------------------------------------------------------------
 // pass B, advection.  LDS (floats): fU 896 | fD 896 | tG 3x512 | hG 384 | tC 3x512 | hC 384 | ex 192 | F 3x512
 // ------------------------------------------------------------------------------------------
 #define BLK3_PASSB_LDS (896 * 2 + 1536 + 384 + 1536 + 384 + 192 + 1536)
@@ -503,82 +451,9 @@ __device__ __forceinline__ void sweep_adv(const BlockDesc3* __restrict__ blocks,
 
 // ------------------------------------------------------------------------------------------
 // Euler sweep in 3-D (P = [p T u v w], cfd.jl:106-151 / :459-508), the block form of the R2 residual.
-// pass A: gradients of the NV primitives along x, y, z + JST sensor of the pressure.
+// pass A (passA_wave_nv below): gradients of the NV primitives along x, y, z + JST sensor of the pressure.
 //   G layout as the face-list kernels: grad of var v along dim d at G[(d*NV + v)*nc + c], sensor at G[3*NV*nc + c].
-//   LDS: NV x 896 floats.
 // ------------------------------------------------------------------------------------------
-template <int NV>
-__device__ __forceinline__ void passA_nv(const BlockDesc3* __restrict__ blocks, const int32_t* __restrict__ htab,
-                                         const int32_t* __restrict__ ftab, int32_t blk, uint32_t nc,
-                                         const float* __restrict__ P, uint32_t ldp, float* __restrict__ G, float* lds,
-                                         int tid) {
-    const BlockDesc3 bb = blocks[blk];
-    const uint32_t c = (uint32_t)bb.base + tid;
-    const uint32_t hidx = halo_cell3(bb, htab, blk, tid);
-    float self[NV];
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        self[v] = ldg(P + (size_t)v * ldp, c);
-        const float hv = ldg(P + (size_t)v * ldp, hidx);
-        lds[v * 896 + tid] = self[v];
-        if (tid < 384) lds[v * 896 + 512 + tid] = hv;
-    }
-    const Lane3 L = lane_info(bb, tid);
-    __syncthreads();
-    const int tt[3] = {L.j + 8 * L.k, L.i + 8 * L.k, L.i + 8 * L.j};
-    float D = 1e-7f;
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        const float rh = bb.rh[d];
-        // the three extra fine cells behind a boundary cell of a FINE side (workgroup-uniform branch)
-        uint32_t fc[2][3];
-        bool fine[2];
-#pragma unroll
-        for (int side = 0; side < 2; ++side) {
-            const int s = 2 * d + side;
-            fine[side] = false;
-            if (bb.type[s] == SIDE_FINE) {
-                if (L.edge[s]) {
-                    const int32_t* ft = ftab + (((size_t)bb.fine * 6 + s) * 64 + tt[d]) * 3;
-                    fc[side][0] = (uint32_t)ft[0];
-                    fc[side][1] = (uint32_t)ft[1];
-                    fc[side][2] = (uint32_t)ft[2];
-                    fine[side] = true;
-                }
-            }
-        }
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-            const float uc = self[v];
-            float vm[2], am[2];
-#pragma unroll
-            for (int side = 0; side < 2; ++side) {
-                const int s = 2 * d + side;
-                const float v0 = lds[v * 896 + L.nidx[s]];
-                vm[side] = v0;
-                am[side] = fabsf(v0 - uc);
-                if (bb.type[s] == SIDE_FINE) {
-                    if (fine[side]) {
-                        const float* Pv = P + (size_t)v * ldp;
-                        const float v1 = ldg(Pv, fc[side][0]), v2 = ldg(Pv, fc[side][1]), v3 = ldg(Pv, fc[side][2]);
-                        vm[side] = 0.25f * (v0 + v1 + v2 + v3);
-                        am[side] = 0.25f * (fabsf(v0 - uc) + fabsf(v1 - uc) + fabsf(v2 - uc) + fabsf(v3 - uc));
-                    }
-                }
-            }
-            const float fr = uc + L.q[2 * d + 1] * (vm[1] - uc);
-            const float fl = uc + L.q[2 * d] * (vm[0] - uc);
-            if (!L.general) stg(G + (size_t)(d * NV + v) * nc, c, (fr - fl) * rh);
-            if (v == 0) {
-                const float gg = ((vm[1] - uc) - (uc - vm[0])) * rh;
-                const float ugg = (am[1] + am[0]) * rh;
-                D = fmaxf(D, (1e-7f + fabsf(gg)) * __builtin_amdgcn_rcpf(1e-7f + ugg));
-            }
-        }
-    }
-    if (!L.general) stg(G + (size_t)(3 * NV) * nc, c, D);
-}
-
 struct Gas3 {
     float R, gamma;
 };

@@ -7,7 +7,7 @@
 //
 //   order: u as z-columns -> sensor z, y, x (numerator / denominator carried: one reciprocal per cell) -> fluxes x, y, z ->
 //   the z pass stores coalesced dwords.
-// Same arithmetic and tables as strip3::sweep_strip (ibh_strip3d.h).
+// Same arithmetic and tables as blk3::sweep_adv (ibh_block3d.h: thread per cell).
 #pragma once
 #include "ibh_strip3d_euler.h"
 
@@ -104,7 +104,7 @@ __device__ __forceinline__ void sensor_cols(const Diffs& D, float ha0, float ha1
 }
 
 // ---- halo cell(s) of slot `lane` of side S: slope along the normal (towards +) and sensor; on a FINE side the mean
-// flux through the four sub-faces instead (strip3::side_flux with the boundary cell in the lane's own registers)
+// flux through the four sub-faces instead (the boundary cell is in the lane's own registers)
 template <int S>
 __device__ __forceinline__ void side_eval(const BlockDesc3& bb, const LaneGeo& LG, const int32_t* __restrict__ ftab,
                                           const int32_t* __restrict__ r4tab, const float* __restrict__ u,

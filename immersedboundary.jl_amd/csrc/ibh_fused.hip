@@ -5,7 +5,7 @@
 // and one launcher per path.  The entry points are a switch over the path.  The kernels and their launchers live in one
 // unit per family:
 //   ibh_fused2d.hip        2-D single-kernel sweeps: per-block, quad, row and step kernels, scalar and Euler
-//   ibh_fused3d.hip        3-D sweeps: column, strip and thread-per-cell forms, the 3-D block kernels of the two-kernel form
+//   ibh_fused3d.hip        3-D sweeps: column and thread-per-cell forms, the 3-D block kernels of the two-kernel form
 //   ibh_fused_general.hip  the two-kernel form through the gradient workspace (face-list threads + 2-D block bodies)
 // and the block closures of the turbulence model in ibh_turb.hip.  No kernel and no kernel header here.
 #include <string.h>
@@ -60,6 +60,9 @@ int ibh_set_tuning(const char* key, int value) {
     IBH_REQUIRE(key, "ibh_set_tuning: null key");
     for (const auto& k : keys)
         if (!strcmp(key, k.key)) {
+            // a value that named a retired kernel form must not quietly time the default one
+            IBH_REQUIRE(k.value != &T.quad_variant || quad_variant_known(value),
+                        "ibh_set_tuning: quad_variant takes 0, 4 (wave time stamps) or 512 (thread per cell)");
             *k.value = value;
             return 0;
         }

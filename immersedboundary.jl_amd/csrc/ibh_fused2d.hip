@@ -58,7 +58,7 @@ __device__ __forceinline__ void dbg_stamp(int32_t slot, int k, unsigned long lon
 
 // RS: the blocks outside quads take the row sweep, EIGHT per wave (rows2::sweep_rows over the list), instead of the per-block
 // body -- `nwgs`, `siters` then count waves of eight
-template <bool DT, bool STAMP, int GM = 127, bool STEP = false, bool RS = false>
+template <bool DT, bool STAMP, bool STEP = false, bool RS = false>
 #ifndef QS_WAVES
 #define QS_WAVES 5
 #endif
@@ -88,11 +88,11 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(QS_WAV
     if (isq) {
         const int32_t q = __builtin_amdgcn_readfirstlane(xcd_remap(wgq, nwgq) * WPB + wave);
         if (q < nq)
-            quad2::sweep_quad<STAMP, GM, STEP>(qd, qtab, q, u, C, ldc, ud, lds + wave * QUAD_LDS, lane,
-                                               STAMP && ibh_dbg_buf ? ibh_dbg_buf + (size_t)slot * 8 : nullptr, dt, qaux);
+            quad2::sweep_quad<STAMP, STEP>(qd, qtab, q, u, C, ldc, ud, lds + wave * QUAD_LDS, lane,
+                                           STAMP && ibh_dbg_buf ? ibh_dbg_buf + (size_t)slot * 8 : nullptr, dt, qaux);
         else if (q < nq + npair)  // pair tiles: entries nq .. of the same arrays, the HALF form of the same wave code
-            quad2::sweep_quad<STAMP, GM, STEP, true>(qd, qtab, q, u, C, ldc, ud, lds + wave * QUAD_LDS, lane,
-                                                     STAMP && ibh_dbg_buf ? ibh_dbg_buf + (size_t)slot * 8 : nullptr, dt, qaux);
+            quad2::sweep_quad<STAMP, STEP, true>(qd, qtab, q, u, C, ldc, ud, lds + wave * QUAD_LDS, lane,
+                                                 STAMP && ibh_dbg_buf ? ibh_dbg_buf + (size_t)slot * 8 : nullptr, dt, qaux);
     } else {
         const int32_t wgs = singles_first ? (int32_t)blockIdx.x : (int32_t)blockIdx.x - nwgq;
         if constexpr (RS) {
@@ -197,7 +197,7 @@ __global__ __launch_bounds__(64 * WPB) void k_step_quad(float* __restrict__ u, c
     const int32_t nws = boundary ? nwg_sb : nwg_si, s0 = boundary ? ns_int : 0, s1 = boundary ? ns : ns_int;
     if (b < nwq) {
         const int32_t q = __builtin_amdgcn_readfirstlane(q0 + xcd_remap(b, nwq) * WPB + wave);
-        if (q < q1) quad2::sweep_quad<false, 127>(qd, qtab, q, u, C, ldc, ud, lds + wave * QUAD_LDS, lane);
+        if (q < q1) quad2::sweep_quad<false>(qd, qtab, q, u, C, ldc, ud, lds + wave * QUAD_LDS, lane);
     } else {
         const int32_t first = __builtin_amdgcn_readfirstlane(s0 + xcd_remap(b - nwq, nws) * WPB + wave);
         if (first < s1)
@@ -332,14 +332,9 @@ static void adv2_quads(const ibh_part* p, const AdvArgs& a, int k, Phase ph) {
     const int32_t nwgq = (q.count() + npair + WPB - 1) / WPB,
                   nwgs = rows_inside ? (s.count() + WPB * 8 - 1) / (WPB * 8) : (s.count() + WPB * siters - 1) / (WPB * siters);
     auto kq = k_sweep_quad<false, false>;
-    if (rows_inside) kq = k_sweep_quad<false, false, 127, false, true>;
+    if (rows_inside) kq = k_sweep_quad<false, false, false, true>;
     else if (p->n_dt > 0) kq = k_sweep_quad<true, false>;
     else if (T.quad_variant == QV_STAMPS) kq = k_sweep_quad<false, true>;
-    else if (T.quad_variant == QV_GATHER_SEVEN) kq = k_sweep_quad<false, false, 126>;
-    else if (T.quad_variant == QV_GATHER_85) kq = k_sweep_quad<false, false, 85>;
-    else if (T.quad_variant == QV_GATHER_69) kq = k_sweep_quad<false, false, 69>;
-    else if (T.quad_variant == QV_GATHER_5) kq = k_sweep_quad<false, false, 5>;
-    else if (T.quad_variant == QV_GATHER_NONE) kq = k_sweep_quad<false, false, 0>;
     if (nwgq + nwgs > 0)
         hipLaunchKernelGGL(kq, dim3(nwgq + nwgs), dim3(64 * WPB), 0, ibh_stream, a.u, a.C, (uint32_t)a.ldc, a.ud,
                            p->qd[k] + q.first, p->qtab[k] + (size_t)q.first * IBH_QROW, q.count(), nwgq, p->blocks2, p->htab,
@@ -392,7 +387,7 @@ void adv2_step_quads(const ibh_part* p, const float* u, float* u_out, const floa
     const int32_t npair = T.pairs ? p->npair : 0;
     const int32_t nq = p->nq[0], ns = npair ? p->nqs2 : p->nqs[0];
     const int32_t nwgq = (nq + npair + WPB - 1) / WPB, nwgs = (ns + WPB - 1) / WPB;
-    hipLaunchKernelGGL((k_sweep_quad<false, false, 127, true>), dim3(nwgq + nwgs), dim3(64 * WPB), 0, ibh_stream, u, C,
+    hipLaunchKernelGGL((k_sweep_quad<false, false, true>), dim3(nwgq + nwgs), dim3(64 * WPB), 0, ibh_stream, u, C,
                        (uint32_t)ldc, u_out, p->qd[0], p->qtab[0], nq, nwgq, p->blocks2, p->htab, p->etab, p->dtab,
                        npair ? p->qsingles2 : p->qsingles[0], ns, nwgs, T.quad_singles_first, 1, dt_dev, npair,
                        T.arith_ids ? p->qaux[0] : (const int32_t*)nullptr);

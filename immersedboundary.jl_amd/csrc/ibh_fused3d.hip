@@ -2,13 +2,11 @@
 //   single-kernel sweeps, no gradient workspace:
 //     k_sweep3_cols / k_sweep3_euler_cols   one wavefront per block, columns of eight cells per lane (ibh_cols3d.h,
 //                                           ibh_strip3d_euler.h): the default forms
-//     k_sweep3_strip                        the strip form of the scalar sweep (ibh_strip3d.h), A/B
 //     k_sweep3_adv / k_sweep3_euler         thread per cell, one 512-thread workgroup per block (ibh_block3d.h), A/B
 //   two-kernel form through the workspace, the face-list cells (ibh_facelist.h) in the same launch as the blocks:
-//     k_passA3_wave / k_passA3_blk, k_passB3_adv_blk, k_passA3e_wave / k_passA3e_blk, k_passB3e_blk
+//     k_passA3_wave, k_passB3_adv_blk, k_passA3e_wave, k_passB3e_blk
 // and their launchers (adv3_*, euler3_*; ibh_fused.hip decides which one runs).
 #include "ibh_facelist.h"
-#include "ibh_strip3d.h"
 #include "ibh_strip3d_euler.h"
 #include "ibh_cols3d.h"
 #include "ibh_block3d.h"
@@ -19,29 +17,10 @@ using namespace fused;
 
 namespace {
 
-// 3-D block kernels: one 512-thread workgroup per 8x8x8 block (the face-list cells get their own launch)
+// 3-D pass B block kernels: one 512-thread workgroup per 8x8x8 block
 // grid = [face-list workgroups over `cells` | nblk block workgroups]: the face-list cells (sides facing finer
 // blocks, partial skirt blocks) are few but latency-bound (a ~20 us chain of dependent loads); dispatched FIRST
 // in the same launch they run underneath the block work instead of forming a tail.
-__global__ __launch_bounds__(512) void k_passA3_blk(PartView p, const float* __restrict__ u, float* __restrict__ G,
-                                                    const BlockDesc3* __restrict__ blocks,
-                                                    const int32_t* __restrict__ htab,
-                                                    const int32_t* __restrict__ ftab, int32_t nblk,
-                                                    const int32_t* __restrict__ cells, int32_t ncells, FlatRec flat) {
-    __shared__ float lds[896];
-    const int32_t gI = (ncells + 511) / 512;
-    if ((int32_t)blockIdx.x >= gI) {
-        const int32_t blk = xcd_remap(blockIdx.x - gI, nblk);
-        blk3::passA(blocks, htab, ftab, blk, (uint32_t)p.nc, u, G, lds, threadIdx.x);
-        return;
-    }
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < ncells) {
-        if (flat.rec) passA_flat<3, 1>(p, flat, (int32_t)t, cells[t], u, (int64_t)p.nc, G);
-        else passA_cell<3, 1>(p, u, (int64_t)p.nc, G, cells[t]);
-    }
-}
-
 __global__ __launch_bounds__(512) void k_passB3_adv_blk(PartView p, const float* __restrict__ u,
                                                         const float* __restrict__ C, int64_t ldc,
                                                         const float* __restrict__ G, float* __restrict__ ud,
@@ -89,24 +68,6 @@ __global__ __launch_bounds__(512) void k_sweep3_euler(const float* __restrict__ 
                       threadIdx.x);
 }
 
-// Strip form of the 3-D scalar sweep (strip3::sweep_strip): one wavefront per block
-#ifndef WPB3S
-#define WPB3S 2
-#endif
-template <int WAVES>
-__global__ __launch_bounds__(64 * WPB3S) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void k_sweep3_strip(const float* __restrict__ u, const float* __restrict__ C,
-                                                             uint32_t ldc, float* __restrict__ ud,
-                                                             const BlockDesc3* __restrict__ blocks,
-                                                             const int32_t* __restrict__ htab,
-                                                             const int32_t* __restrict__ ftab,
-                                                             const int32_t* __restrict__ rtab,
-                                                             const int32_t* __restrict__ r4tab, int32_t n, int32_t nwg) {
-    __shared__ __attribute__((aligned(16))) float lds[WPB3S * S3_LDS];
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int32_t blk = __builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x, nwg) * WPB3S + wave);
-    if (blk < n) strip3::sweep_strip(blocks, htab, ftab, rtab, r4tab, blk, u, C, ldc, ud, lds + wave * S3_LDS, lane);
-}
-
 // Column form of the 3-D scalar sweep (cols3::sweep_cols): one wavefront per block
 #ifndef WPB3C
 #define WPB3C 2
@@ -127,65 +88,25 @@ __global__ __launch_bounds__(64 * WPB3C) __attribute__((amdgpu_waves_per_eu(WAVE
                           TAB ? dtab : nullptr);
 }
 
-// Column form of the 3-D Euler sweep (strip3e::sweep_euler_chain): one wavefront per 8^3 block.
-// PERSIST = false, the default of every path: one block per wave, grid = blocks.
-// PERSIST = true, the A/B form ("quad_variant" 514 on the Euler entry): the grid is the 2 048 wave slots of the chip at two
-// waves per SIMD (8 per CU), and each wave works through a chain of blocks with the first loads of its next block in flight
-// during the z fluxes of the one in hand.  Every XCD gets one contiguous chunk of the block list (depth-first order: a
-// compact patch of the mesh), and the waves of an XCD walk their chunk side by side (wave i: blocks c0 + i, c0 + i + W, ...),
-// so the blocks in flight on an XCD at any time are W consecutive ones.  Measured slower than one block per wave (see
-// ibh_strip3d_euler.h).
-// (Round 3 measured a persistent form slower, 143 against 107 us at 4.56 M cells: at 256 VGPRs the registers of the
-// prefetch spilled.  Round 4 first freed the registers -- nothing of a later pass is held through a flux loop, lane-only
-// integers and the block descriptor are derived / read again per pass: 190 VGPRs -- and tried them as a third wave per
-// SIMD: 168 VGPRs with 17 spilled words, 11 waves per CU resident (wave timeline), and slower: 755 against 695 us at 33.6 M
-// cells on the same box.  As prefetch registers they pay: see profiles/r4_*/README.md.)
+// Column form of the 3-D Euler sweep (strip3e::sweep_euler_cols): one wavefront per 8^3 block, grid = blocks.
+// (Persistent waves with the next block's first loads in flight were tried in rounds 3 and 4 and measured slower; the
+// record is in DESIGN.md and profiles/r4_final/README.md.)
 #ifndef WPB3E
 #define WPB3E 1
 #endif
-#define S3E_SLOTS_PER_CU 8
 // wave timeline of a launch (STAMP, ibh_debug_buffer), as in ibh_fused2d.hip: this code object's own pointer
 __device__ unsigned long long* ibh_dbg_buf = nullptr;
-template <int WAVES, bool STAMP = false, bool TAB = false, bool PERSIST = false>
+template <int WAVES, bool STAMP = false, bool TAB = false>
 __global__ __launch_bounds__(64 * WPB3E) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void k_sweep3_euler_cols(
     const float* __restrict__ P, uint32_t ldp, float* __restrict__ R, uint32_t ldr, float Rgas, float gamma,
     const BlockDesc3* __restrict__ blocks, const int32_t* __restrict__ htab, const int32_t* __restrict__ ftab,
     const int32_t* __restrict__ rtab, const int32_t* __restrict__ r4tab, int32_t n, int32_t nwg,
     const int32_t* __restrict__ dtab = nullptr) {
     __shared__ __attribute__((aligned(16))) float lds[WPB3E * S3E_LDS];
-    __shared__ __attribute__((aligned(16))) float nextbuf[PERSIST ? WPB3E * S3E_NEXT : 1];  // (the LDS-DMA rows)
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    int32_t first, stride, end;
-    if constexpr (PERSIST) {
-        // nwg = workgroups of the launch, a multiple of 8; workgroup w belongs to XCD w & 7 (placement affects speed only)
-        const int32_t xcd = blockIdx.x & 7, idx = (blockIdx.x >> 3) * WPB3E + wave;
-        const int32_t q = n >> 3, r = n & 7;
-        const int32_t c0 = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-        first = __builtin_amdgcn_readfirstlane(c0 + idx);
-        stride = (nwg >> 3) * WPB3E;
-        end = c0 + q + (xcd < r ? 1 : 0);
-    } else {
-        first = __builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x, nwg) * WPB3E + wave);
-        stride = n;
-        end = n;
-    }
-    strip3e::sweep_euler_chain<STAMP, PERSIST>(blocks, htab, ftab, rtab, r4tab, first, stride, end, P, ldp, R, ldr,
-                                      blk3::Gas3{Rgas, gamma}, lds + wave * S3E_LDS, nextbuf + (PERSIST ? wave * S3E_NEXT : 0), lane,
-                                      STAMP ? ibh_dbg_buf : nullptr,
-                                      TAB ? dtab : nullptr);
-}
-// workgroups of the persistent launch: the chip's wave slots (or fewer, for few blocks), a multiple of 8
-static int32_t s3e_persistent_wgs(int32_t nblk) {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-        if (cus <= 0) cus = 256;
-    }
-    const int32_t slots = cus * S3E_SLOTS_PER_CU / WPB3E;
-    const int32_t want = ((nblk + WPB3E - 1) / WPB3E + 7) & ~7;
-    return want < slots ? want : slots;
+    const int32_t blk = __builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x, nwg) * WPB3E + wave);
+    strip3e::sweep_euler_cols<STAMP>(blocks, htab, ftab, rtab, r4tab, blk, n, P, ldp, R, ldr, blk3::Gas3{Rgas, gamma},
+                                     lds + wave * S3E_LDS, lane, STAMP ? ibh_dbg_buf : nullptr, TAB ? dtab : nullptr);
 }
 
 // wave-per-block form of the 3-D scalar pass A (blk3::passA_wave): 4 blocks per 256-thread workgroup
@@ -236,26 +157,7 @@ __global__ __launch_bounds__(256) void k_passA3e_wave(PartView p, const float* _
     }
 }
 
-// 3-D Euler block kernels (5 primitives): same launch layout as the scalar 3-D kernels
-__global__ __launch_bounds__(512) void k_passA3e_blk(PartView p, const float* __restrict__ P, int64_t ldp,
-                                                     float* __restrict__ G, const BlockDesc3* __restrict__ blocks,
-                                                     const int32_t* __restrict__ htab,
-                                                     const int32_t* __restrict__ ftab, int32_t nblk,
-                                                     const int32_t* __restrict__ cells, int32_t ncells, FlatRec flat) {
-    __shared__ float lds[5 * 896];
-    const int32_t gI = (ncells + 511) / 512;
-    if ((int32_t)blockIdx.x >= gI) {
-        const int32_t blk = xcd_remap(blockIdx.x - gI, nblk);
-        blk3::passA_nv<5>(blocks, htab, ftab, blk, (uint32_t)p.nc, P, (uint32_t)ldp, G, lds, threadIdx.x);
-        return;
-    }
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < ncells) {
-        if (flat.rec) passA_flat<3, 5>(p, flat, (int32_t)t, cells[t], P, ldp, G);
-        else passA_cell<3, 5>(p, P, ldp, G, cells[t]);
-    }
-}
-
+// 3-D Euler pass B block kernel (5 primitives)
 __global__ __launch_bounds__(512) void k_passB3e_blk(uint32_t nc, const float* __restrict__ P, uint32_t ldp,
                                                      const float* __restrict__ G, float* __restrict__ R, uint32_t ldr,
                                                      float Rgas, float gamma, const BlockDesc3* __restrict__ blocks,
@@ -293,41 +195,28 @@ void adv3_image_cols(const ibh_part* p, const AdvArgs& a) {
     hipLaunchKernelGGL((k_sweep3_cols<3, true>), dim3(nwg), dim3(64 * WPB3C), 0, ibh_stream, a.u, a.C, (uint32_t)a.ldc, a.ud,
                        p->iblocks3, p->ihtab3, p->iftab3, p->irtab3, p->ir4tab3, p->n_img3, nwg, p->idtab3);
 }
-// (the strip and the column kernels differ in their last, defaulted parameter: no common function pointer type)
-#define SWEEP3_LAUNCH(K)                                                                                                 \
-    hipLaunchKernelGGL(K, dim3(nwg), dim3(64 * WPB3S), 0, ibh_stream, a.u, a.C, (uint32_t)a.ldc, a.ud, p->blocks3, p->htab3, \
-                       p->ftab3, p->rtab3, p->r4tab3, p->nblk, nwg)
 // every block qualifies for the single-kernel sweep: one launch, nothing through the workspace
 void adv3_single(const ibh_part* p, const AdvArgs& a) {
-    static_assert(WPB3C == WPB3S, "one grid for both forms");
-    const int32_t nwg = (p->nblk + WPB3S - 1) / WPB3S;
-    switch (T.quad_variant) {
-    case QV_THREAD_PER_CELL:
+    if (T.quad_variant == QV_THREAD_PER_CELL) {
         hipLaunchKernelGGL(k_sweep3_adv, dim3(p->nblk), dim3(512), 0, ibh_stream, a.u, a.C, (uint32_t)a.ldc, a.ud, p->blocks3,
                            p->htab3, p->ftab3, p->rtab3, p->r4tab3, p->nblk);
-        break;
-    case QV_STRIP_W2: SWEEP3_LAUNCH(k_sweep3_strip<2>); break;
-    case QV_STRIP_W4: SWEEP3_LAUNCH(k_sweep3_strip<4>); break;
-    case QV_STRIP_W3: SWEEP3_LAUNCH(k_sweep3_strip<3>); break;
-    case QV_COLS_W4: SWEEP3_LAUNCH(k_sweep3_cols<4>); break;
-    case QV_COLS_W5: SWEEP3_LAUNCH(k_sweep3_cols<5>); break;
-    default: SWEEP3_LAUNCH(k_sweep3_cols<3>);
+        return;
     }
+    const int32_t nwg = (p->nblk + WPB3C - 1) / WPB3C;
+    hipLaunchKernelGGL((k_sweep3_cols<3>), dim3(nwg), dim3(64 * WPB3C), 0, ibh_stream, a.u, a.C, (uint32_t)a.ldc, a.ud,
+                       p->blocks3, p->htab3, p->ftab3, p->rtab3, p->r4tab3, p->nblk, nwg);
 }
-#undef SWEEP3_LAUNCH
 
 int adv3_blocks(ibh_part* p, const AdvArgs& a, int flags, Phase ph) {
     if (const int rc = ensure_G(p)) return rc;
     const Blocks3 s = blocks3_setup(p, flags, ph);
     const int32_t na = s.a.count(), nb = s.b.count();
-    if (s.doA && T.wave3d) {
+    if (s.doA) {
         const int32_t nwgA = (na + 3) / 4, gIw = (s.nI + 255) / 256;
         hipLaunchKernelGGL(k_passA3_wave, dim3(nwgA + gIw), dim3(256), 0, ibh_stream, s.v, a.u, p->G, p->blocks3 + s.a.first,
                            p->htab3 + (size_t)s.a.first * 384, p->ftab3, na, nwgA, p->irr_cells, s.nI, s.flat,
                            (const int32_t*)nullptr);
-    } else if (s.doA)
-        hipLaunchKernelGGL(k_passA3_blk, dim3(na + s.gI), dim3(512), 0, ibh_stream, s.v, a.u, p->G, p->blocks3 + s.a.first,
-                           p->htab3 + (size_t)s.a.first * 384, p->ftab3, na, p->irr_cells, s.nI, s.flat);
+    }
     if (s.doB)
         hipLaunchKernelGGL(k_passB3_adv_blk, dim3(nb + s.gI), dim3(512), 0, ibh_stream, s.v, a.u, a.C, a.ldc, p->G, a.ud,
                            p->blocks3 + s.b.first, p->htab3 + (size_t)s.b.first * 384, p->ftab3, nb, p->irr_cells, s.nI,
@@ -338,17 +227,14 @@ int adv3_blocks(ibh_part* p, const AdvArgs& a, int flags, Phase ph) {
 // image blocks of a partition with skirt fragments: one launch, nothing through the workspace
 void euler3_image_cols(const ibh_part* p, const EulerArgs& e) {
     const int32_t nwg = (p->n_img3 + WPB3E - 1) / WPB3E;
-    hipLaunchKernelGGL((k_sweep3_euler_cols<2, false, true, false>), dim3(nwg), dim3(64 * WPB3E), 0, ibh_stream, e.P,
+    hipLaunchKernelGGL((k_sweep3_euler_cols<2, false, true>), dim3(nwg), dim3(64 * WPB3E), 0, ibh_stream, e.P,
                        (uint32_t)e.ldp, e.R, (uint32_t)e.ldr, e.fluid->R, e.fluid->gamma, p->iblocks3, p->ihtab3, p->iftab3,
                        p->irtab3, p->ir4tab3, p->n_img3, nwg, p->idtab3);
 }
 // 3-D, every block qualifies for the single-kernel sweep: one launch, nothing through the workspace
 void euler3_single(const ibh_part* p, const EulerArgs& e) {
-    const bool persist = T.quad_variant == QV_EULER_PERSISTENT;
-    const int32_t nwg = persist ? s3e_persistent_wgs(p->nblk) : (p->nblk + WPB3E - 1) / WPB3E;
-    auto k = k_sweep3_euler_cols<2, false, false, false>;
-    if (persist) k = k_sweep3_euler_cols<2, false, false, true>;
-    else if (T.quad_variant == QV_STAMPS) k = k_sweep3_euler_cols<2, true, false, false>;
+    const int32_t nwg = (p->nblk + WPB3E - 1) / WPB3E;
+    const auto k = T.quad_variant == QV_STAMPS ? k_sweep3_euler_cols<2, true, false> : k_sweep3_euler_cols<2, false, false>;
     if (T.quad_variant == QV_THREAD_PER_CELL)
         hipLaunchKernelGGL(k_sweep3_euler, dim3(p->nblk), dim3(512), 0, ibh_stream, e.P, (uint32_t)e.ldp, e.R, (uint32_t)e.ldr,
                            e.fluid->R, e.fluid->gamma, p->blocks3, p->htab3, p->ftab3, p->rtab3, p->r4tab3, p->nblk);
@@ -362,13 +248,11 @@ void euler3_single(const ibh_part* p, const EulerArgs& e) {
 int euler3_blocks(ibh_part* p, const EulerArgs& e, int flags) {
     if (const int rc = ensure_G(p)) return rc;
     const Blocks3 s = blocks3_setup(p, flags, Phase(0));
-    if (s.doA && T.wave3d) {
+    if (s.doA) {
         const int32_t nwgA = (p->nblk + 3) / 4, gIw = (s.nI + 255) / 256;
         hipLaunchKernelGGL(k_passA3e_wave, dim3(nwgA + gIw), dim3(256), 0, ibh_stream, s.v, e.P, e.ldp, p->G, p->blocks3,
                            p->htab3, p->ftab3, p->nblk, nwgA, p->irr_cells, s.nI, s.flat);
-    } else if (s.doA)
-        hipLaunchKernelGGL(k_passA3e_blk, dim3(p->nblk + s.gI), dim3(512), 0, ibh_stream, s.v, e.P, e.ldp, p->G, p->blocks3,
-                           p->htab3, p->ftab3, p->nblk, p->irr_cells, s.nI, s.flat);
+    }
     if (s.doB) {
         hipLaunchKernelGGL(k_passB3e_blk, dim3(p->nblk), dim3(512), 0, ibh_stream, (uint32_t)p->nc, e.P, (uint32_t)e.ldp,
                            p->G, e.R, (uint32_t)e.ldr, e.fluid->R, e.fluid->gamma, p->blocks3, p->htab3, p->ftab3, p->nblk);

@@ -14,15 +14,23 @@ inline int env_int(const char* name, int dflt) {
     const char* s = getenv(name);
     return s ? atoi(s) : dflt;
 }
+// "quad_variant": the kernel form of a single-kernel sweep (0 = the default form of every path).  These are all the values
+// there are: ibh_set_tuning rejects any other, and any other in the environment counts as 0.
+enum : int {
+    QV_STAMPS = 4,             // wave time stamps (scripts/wave_timeline.py, scripts/wave_timeline_3d.py)
+    QV_THREAD_PER_CELL = 512,  // A/B: thread-per-cell form of the 3-D sweeps
+};
+inline bool quad_variant_known(int v) { return v == 0 || v == QV_STAMPS || v == QV_THREAD_PER_CELL; }
+inline int quad_variant_or_0(int v) { return quad_variant_known(v) ? v : 0; }
+
 // Tuning state: ibh_set_tuning(key, v) at run time, the environment for the defaults (profiling a variant under bench.py)
 struct Tuning {
-    int wave3d = env_int("IBH_3D_WAVE", 1);  // 1: wave-per-block form of the 3-D scalar pass A (0: the 512-thread form, A/B)
     int sweep_iters = env_int("IBH_SWEEP_ITERS", 0);  // blocks per wave of the per-block single-kernel sweep; 0 = automatic
     int quad = env_int("IBH_QUAD", 1);                // 0: per-block single kernel everywhere (A/B runs)
     // row / column sweep (ibh_rows2d.h) where the partition qualifies: OFF by default -- measured slower than the quad sweep
     // (8.4 against 6.1 us at 0.87 M cells, 21.7 against 17.0 at 3.47 M: profiles/r3_final/probe_rows.json)
     int rows = env_int("IBH_ROWS", 0);
-    int quad_variant = env_int("IBH_QUAD_VARIANT", 0);  // one of the QV_* forms below
+    int quad_variant = quad_variant_or_0(env_int("IBH_QUAD_VARIANT", 0));  // 0 or one of the QV_* forms above
     // 1 / 2 = only the quads / only the single blocks of a quad sweep (measurement); single blocks per wave in a quad sweep
     int quad_parts = 3, quad_singles_iters = 1;
     int quad_singles_first = env_int("IBH_SINGLES_FIRST", 0);  // grid order of a quad sweep
@@ -33,17 +41,6 @@ struct Tuning {
     int rows_singles = env_int("IBH_ROWS_SINGLES", -1);
 };
 extern Tuning T;  // (ibh_fused.hip)
-
-// "quad_variant": the kernel form of a single-kernel sweep (0 = the default form of every path)
-enum : int {
-    QV_STAMPS = 4,            // wave time stamps (scripts/wave_timeline.py, scripts/wave_timeline_3d.py)
-    QV_GATHER_5 = 5, QV_GATHER_69 = 69, QV_GATHER_85 = 85, QV_GATHER_NONE = 100,  // measurement: subsets of the halo gathers
-    QV_GATHER_SEVEN = 126,    // A/B: seven 4-byte gathers
-    QV_THREAD_PER_CELL = 512, // A/B: thread-per-cell form of the 3-D sweeps
-    QV_STRIP_W2 = 515, QV_STRIP_W4 = 514, QV_STRIP_W3 = 518,  // A/B: the strip form (round 2) of the 3-D scalar sweep
-    QV_COLS_W4 = 519, QV_COLS_W5 = 520,  // columns at 4 (7 registers spilled: 46 against 41 us at 4.56 M cells) / 5 waves
-    QV_EULER_PERSISTENT = 514,  // 3-D Euler sweep, A/B: persistent waves (measured slower, see ibh_strip3d_euler.h)
-};
 
 // Flag groups of the eligibility conditions
 constexpr int F_LITERAL = IBH_FORCE_GENERAL | IBH_EXACT;                       // not the tuned block arithmetic
@@ -84,7 +81,7 @@ struct EulerArgs { const float* P; int64_t ldp; float* R; int64_t ldr; const ibh
 // ---- advection: paths
 enum AdvPath {
     ADV3_IMAGE_COLS,      // 3-D, image blocks only: one launch of the column sweep
-    ADV3_SINGLE,          // 3-D single-kernel sweep: columns, strip or thread-per-cell form by quad_variant
+    ADV3_SINGLE,          // 3-D single-kernel sweep: column or thread-per-cell form by quad_variant
     ADV3_BLOCKS,          // 3-D two-kernel block path
     ADV2_IMAGE,           // 2-D, image blocks only: quads or per-block list
     ADV2_FUSE_ALL,        // 2-D, every block eligible: rows, quads or per-block
@@ -98,7 +95,7 @@ enum AdvPath {
 enum EulerPath {
     EUL2_SINGLE,      // 2-D single launch per phase: quads or per-block
     EUL3_IMAGE_COLS,  // 3-D, image blocks only: one launch of the column sweep
-    EUL3_SINGLE,      // 3-D single-kernel sweep: column / persistent / stamped / thread-per-cell form by quad_variant
+    EUL3_SINGLE,      // 3-D single-kernel sweep: column / stamped / thread-per-cell form by quad_variant
     EUL2_FAST,        // two-kernel form: 2-D block kernels + face-list threads
     EUL2_FACE_LIST,   //                  2-D face-list
     EUL3_BLOCKS,      //                  3-D block kernels + face-list threads

@@ -266,25 +266,8 @@ __device__ __forceinline__ QuadOwn quad_load_own(const QuadLane& G, const QuadTa
 // as the first -- a wave-uniform branch, a second code path for quads without a FINE side, exec-masked loads, a paired
 // 8-byte load of halo + deeper cell -- measured equal or slower than gathering everything: the sweep ends with its
 // slowest waves, and those are the quads with a FINE side either way.
-// GM: which of the seven gathers are performed (127 = all; anything else: measurement only, wrong results)
-template <int GM = 127>
-__device__ __forceinline__ QuadHalo quad_load_halo(const QuadLane& G, const QuadTab& T, const float* __restrict__ u,
-                                                   const float* __restrict__ C, uint32_t ldc) {
-    using blk2::ldg;
-    QuadHalo H;
-    const float* Cn = C + (G.dny ? ldc : 0u);
-    const float z = (float)(T.hid.x + T.hid.y + (int)T.eid) * 1e-30f;  // keeps the table loads alive
-    H.hu.x = (GM & 1) ? ldg(u, (uint32_t)T.hid.x) : z;
-    H.hu.y = (GM & 2) ? ldg(u, (uint32_t)T.hid.y) : H.hu.x;
-    H.hd.x = (GM & 4) ? ldg(u, (uint32_t)(T.hid.x + G.delta)) : z;
-    H.hd.y = (GM & 8) ? ldg(u, (uint32_t)(T.hid.y + G.delta)) : H.hd.x;
-    H.hc.x = (GM & 16) ? ldg(Cn, (uint32_t)T.hid.x) : 1.0f + z;
-    H.hc.y = (GM & 32) ? ldg(Cn, (uint32_t)T.hid.y) : H.hc.x;
-    H.eu = (GM & 64) ? ldg(u, T.eid) : z;
-    return H;
-}
-
-// The same seven values with FOUR full gathers and one that only the lanes of FINE left / right half-sides issue:
+//
+// The seven values with FOUR full gathers and one that only the lanes of FINE left / right half-sides issue:
 // every gather is 8 bytes per lane.  Left / right lanes: the halo cell and the cell one step deeper are x neighbours
 // (one pair per sub-face slot).  Bottom / top lanes: the two sub-face cells of a FINE half-side are x neighbours (the
 // builder checks it: ibh_build_quads2), so (slot 0, slot 1) of the halo cells, of the deeper cells and of the velocity
@@ -493,7 +476,7 @@ __device__ __forceinline__ void quad_compute(const QuadLane& G, const QuadTab& T
 // ---- one quad by one wave.  (Sweeping several quads per wave with the next quad's loads in flight was measured and
 // dropped: the prefetch registers cost a wave per SIMD -- 124 VGPRs against 89 -- and the sweep lives on wave-level
 // parallelism: 6.1 us against 5.5 us at 0.87 M cells, no gain at 3.47 M.)
-template <bool STAMP, int GM = 127, bool STEP = false, bool HALF = false>
+template <bool STAMP, bool STEP = false, bool HALF = false>
 __device__ __forceinline__ void sweep_quad(const QuadDesc2* __restrict__ qd, const int32_t* __restrict__ qtab, int32_t q,
                                            const float* __restrict__ u, const float* __restrict__ C, uint32_t ldc,
                                            float* __restrict__ ud, float* lds, int lane,
@@ -502,7 +485,7 @@ __device__ __forceinline__ void sweep_quad(const QuadDesc2* __restrict__ qd, con
     const QuadLane G = quad_lane<HALF>(lds, lane);
     const QuadTab T = quad_load_tab(qd, qtab, q, lane, qaux);  // everything that needs the quad's index only is in flight
     const QuadOwn O = quad_load_own(G, T, u, C, ldc);
-    const QuadHalo H = GM == 127 ? quad_load_halo_paired(G, T, u, C, ldc) : quad_load_halo<GM == 126 ? 127 : GM>(G, T, u, C, ldc);
+    const QuadHalo H = quad_load_halo_paired(G, T, u, C, ldc);
     quad_compute<STAMP, STEP, HALF>(G, T, O, H, ud, stamps, dt);
 }
 

@@ -8,7 +8,7 @@
 //   layout d (columns along d): lane = ta + 8 tb, (ta, tb) = the two other coordinates in increasing dim order -- which is
 //   exactly the slot numbering of the block sides normal to d (htab3 / rtab3, ibh_analyze3.cpp): the lane of a column IS
 //   the lane of the halo slots at its two ends.  Halo cell(s), the cell one step deeper, slope along the normal and the
-//   pressure sensor of the halo cell (lateral neighbours: the side's plane + rim table, as strip3::side_flux) are
+//   pressure sensor of the halo cell (lateral neighbours: the side's plane + rim table, ibh_strip3d.h) are
 //   computed where they are used.
 //
 //   column registers: e[j] = (c[j - 1], c[j + 4]), j = 0..4, c[0..7] the cells, c[-1] / c[8] the halo ends.  Faces
@@ -45,8 +45,7 @@ using strip3::LaneGeo;
 #define S3E_PLANE 0                     // [18 x 18] pressure of the halo cells of one side + rim
 #define S3E_PLANEA (S3E_PLANE + 324)    // [64] rim: mean |difference| to the halo cell next to it
 #define S3E_R 576                       // [5][576] residual
-#define S3E_LDS (S3E_R + 5 * 576)       // 3 456 floats = 13.5 KB per wave (+ 5 KB for the first loads of the next block)
-
+#define S3E_LDS (S3E_R + 5 * 576)       // 3 456 floats = 13.5 KB per wave
 
 struct Col {
     v2f e[5];
@@ -237,7 +236,7 @@ __device__ __forceinline__ float dpp_xor8(float v) {  // lane i <- lane i ^ 8 (r
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128, 0xf, 0xf, true));
 }
 
-// pressure sensor of ONE halo cell (strip3::slot_eval without the flux).  GROUP: the halo cell is coarser, four of the
+// pressure sensor of ONE halo cell.  GROUP: the halo cell is coarser, four of the
 // block's cells (m0..m3) face it; otherwise one (m0)
 template <bool GROUP>
 __device__ __forceinline__ float slot_sensor(const float* pl, const float* pA, float h, float hde, float m0, float m1,
@@ -678,7 +677,7 @@ __device__ __forceinline__ void flux_pass(const BlockDesc3& bb, const int32_t* _
         for (int v = 0; v < 5; ++v) park[64 * v] = Sh1[v];
     }
     __builtin_amdgcn_sched_barrier(0);
-    hook();  // (the halo registers are free from here on: the first loads of the wave's next block go out in the last pass)
+    hook();  // (the halo registers are free from here on: the halo loads of the next pass go out here)
     __builtin_amdgcn_sched_barrier(0);
     // column ends
     Dc.e[0].x = Dh0;
@@ -748,55 +747,15 @@ __device__ __forceinline__ void load_zcol(const float* __restrict__ p, Col& c) {
     }
 }
 
-// ---- the first loads of a block -- those its sensor needs, and the rim ids: the pressure as z-columns (8 rows of 64), the
-// halo pressures (6), the rim ids of the six sides (6) -- go to a wave-private LDS buffer by LDS-DMA (global_load_lds_dword:
-// a per-lane global address, row base + 4 * lane in LDS, no VGPR for the data).  In a chain of blocks they are requested
-// during the z fluxes of the block before and cost that block neither registers nor a wait.
-#define S3E_NEXT_ROWS 20
-#define S3E_NEXT (64 * S3E_NEXT_ROWS)  // floats per wave
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-// row[lane] = base[idx] (4-byte elements; uniform base + 32-bit lane offset: the SGPR-base form of the instruction)
-__device__ __forceinline__ void dma_row(const void* base, uint32_t idx, float* row) {
-    __builtin_amdgcn_global_load_lds((gptr_t)((const char*)base + (size_t)(idx << 2)), (lptr_t)row, 4, 0, 0);
-}
-__device__ __forceinline__ void request_first(const BlockDesc3* __restrict__ blocks, const int32_t* __restrict__ htab,
-                                              const int32_t* __restrict__ rtab, const float* __restrict__ P, int32_t blk,
-                                              int lane, float* nextbuf) {
-    const BlockDesc3 bn = blocks[blk];
-    // halo cell ids first (a table load where a side is FINE or faces a fragment)
-    uint32_t hid[6];
-    hid[0] = halo_cell3s<0>(bn, htab, blk, lane);
-    hid[1] = halo_cell3s<1>(bn, htab, blk, lane);
-    hid[2] = halo_cell3s<2>(bn, htab, blk, lane);
-    hid[3] = halo_cell3s<3>(bn, htab, blk, lane);
-    hid[4] = halo_cell3s<4>(bn, htab, blk, lane);
-    hid[5] = halo_cell3s<5>(bn, htab, blk, lane);
-#ifdef S3E_ABLATE_HALO
-#pragma unroll
-    for (int s = 0; s < 6; ++s) hid[s] = (uint32_t)bn.base + 64u * s + (uint32_t)lane;
-#endif
-    const uint32_t c0 = (uint32_t)bn.base + (uint32_t)lane;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) dma_row(P, c0 + 64u * i, nextbuf + 64 * i);
-#pragma unroll
-    for (int s = 0; s < 6; ++s) dma_row(P, hid[s], nextbuf + 64 * (8 + s));
-    const int32_t* rt = rtab + (size_t)blk * 384;  // (uniform)
-#pragma unroll
-    for (int s = 0; s < 6; ++s) dma_row(rt, (uint32_t)(64 * s + lane), nextbuf + 64 * (14 + s));
-}
-
-// One block whose first loads are in (or on their way to) `nextbuf`; `next` requests those of the wave's next block
-// (called in the z pass, when the buffer has long been read).
+// One block.
 // STAMP: phase time stamps of the wave (100 MHz ticks) for scripts/wave_timeline_3d.py: 0 start, 1 first loads landed,
 // 2 sensor done, 3 x fluxes, 4 transposed, 5 y fluxes, 6 transposed, 7 end
-template <bool STAMP, bool DMA, class Next>
+template <bool STAMP>
 __device__ __forceinline__ void sweep_block(const BlockDesc3* __restrict__ blocks, const int32_t* __restrict__ htab,
                                             const int32_t* __restrict__ ftab, const int32_t* __restrict__ rtab,
                                             const int32_t* __restrict__ r4tab, int32_t blk, const float* __restrict__ P,
                                             uint32_t ldp, float* __restrict__ Rr, uint32_t ldr, const Gas3& gas, float* lds,
-                                            int lane, unsigned long long* stamps, const int32_t* __restrict__ dtab,
-                                            const float* nextbuf, Next&& next) {
+                                            int lane, unsigned long long* stamps, const int32_t* __restrict__ dtab) {
     auto stamp = [&](int k) {
         if constexpr (STAMP) {
             __builtin_amdgcn_sched_barrier(0);
@@ -809,13 +768,11 @@ __device__ __forceinline__ void sweep_block(const BlockDesc3* __restrict__ block
     const BlockDesc3 bb = blocks[blk];
     const int ta = lane & 7, tb = lane >> 3;
     float* buf = lds + S3E_BUF;
-    // ---- DMA = false (one block per wave: nothing to prefetch for): the first loads of the block -- rim ids, the pressure
-    // as z-columns, the halo pressures -- as plain loads, ahead of everything else (the LDS-DMA form costs ~100 vector and
-    // ~400 scalar instructions of address and M0 handling per block)
+    // ---- the first loads of the block -- rim ids, the pressure as z-columns, the halo pressures -- ahead of everything else
     int32_t ridk[6] = {0, 0, 0, 0, 0, 0};
     Col pz;
     float hp[6];
-    if constexpr (!DMA) {
+    {
         uint32_t hid[6];
         hid[0] = halo_cell3s<0>(bb, htab, blk, lane);
         hid[1] = halo_cell3s<1>(bb, htab, blk, lane);
@@ -850,23 +807,7 @@ __device__ __forceinline__ void sweep_block(const BlockDesc3* __restrict__ block
         }
     }
     __builtin_amdgcn_sched_barrier(0);
-    // ---- the buffer of the first loads: the DMA rows are older than the loads just issued (vector memory operations
-    // complete in order): at least 5 + 5 halo gathers and 10 x-column loads
-    int32_t rid0, rid1;
-    if constexpr (DMA) {
-        asm volatile("s_waitcnt vmcnt(20)" ::: "memory");
-        const int32_t* nrid = (const int32_t*)(nextbuf + 64 * 14) + lane;
-        rid0 = nrid[0];
-        rid1 = nrid[64];
-        const float* np_ = nextbuf + lane;
-        set_cell<0>(pz, np_[0]); set_cell<1>(pz, np_[64]); set_cell<2>(pz, np_[128]); set_cell<3>(pz, np_[192]);
-        set_cell<4>(pz, np_[256]); set_cell<5>(pz, np_[320]); set_cell<6>(pz, np_[384]); set_cell<7>(pz, np_[448]);
-#pragma unroll
-        for (int s = 0; s < 6; ++s) hp[s] = np_[64 * (8 + s)];
-    } else {
-        rid0 = ridk[0];
-        rid1 = ridk[1];
-    }
+    int32_t rid0 = ridk[0], rid1 = ridk[1];
     h0.rv = ldg(P, (uint32_t)(rid0 >= 0 ? rid0 : bb.base));
     h1.rv = ldg(P, (uint32_t)(rid1 >= 0 ? rid1 : bb.base));
     __builtin_amdgcn_sched_barrier(0);
@@ -912,8 +853,8 @@ __device__ __forceinline__ void sweep_block(const BlockDesc3* __restrict__ block
     Slot tl0, tl1;
     int32_t tid0, tid1;
     flux_pass<0, 0>(bx, ftab, r4tab, P, ldp, lds, lane, gas, Pc, Dc, sl0, sl1, rid0, rid1, h0, h1, Rr, ldr, [&]() {
-        tid0 = DMA ? ((const int32_t*)(nextbuf + 64 * 16))[lane] : ridk[2];
-        tid1 = DMA ? ((const int32_t*)(nextbuf + 64 * 17))[lane] : ridk[3];
+        tid0 = ridk[2];
+        tid1 = ridk[3];
         tl0 = slot_of<2>(bx, htab, blk, lane, dtab);
         tl1 = slot_of<3>(bx, htab, blk, lane, dtab);
         halo_load<2>(bx, lane, P, ldp, tl0, tid0, g0);
@@ -928,8 +869,8 @@ __device__ __forceinline__ void sweep_block(const BlockDesc3* __restrict__ block
     transpose<0, 1>(buf, ta, tb, Dc);
     stamp(4);
     flux_pass<1, 1>(by, ftab, r4tab, P, ldp, lds, lane, gas, Pc, Dc, tl0, tl1, tid0, tid1, g0, g1, Rr, ldr, [&]() {
-        rid0 = DMA ? ((const int32_t*)(nextbuf + 64 * 18))[lane] : ridk[4];
-        rid1 = DMA ? ((const int32_t*)(nextbuf + 64 * 19))[lane] : ridk[5];
+        rid0 = ridk[4];
+        rid1 = ridk[5];
         sl0 = slot_of<4>(by, htab, blk, lane, dtab);
         sl1 = slot_of<5>(by, htab, blk, lane, dtab);
         halo_load<4>(by, lane, P, ldp, sl0, rid0, h0);
@@ -943,35 +884,22 @@ __device__ __forceinline__ void sweep_block(const BlockDesc3* __restrict__ block
     for (int v = 0; v < 5; ++v) transpose<1, 2>(buf, ta, tb, Pc[v]);
     transpose<1, 2>(buf, ta, tb, Dc);
     stamp(6);
-    flux_pass<2, 2>(bz, ftab, r4tab, P, ldp, lds, lane, gas, Pc, Dc, sl0, sl1, rid0, rid1, h0, h1, Rr, ldr, next);
+    flux_pass<2, 2>(bz, ftab, r4tab, P, ldp, lds, lane, gas, Pc, Dc, sl0, sl1, rid0, rid1, h0, h1, Rr, ldr, []() {});
     stamp(7);
 }
 
-// A chain of blocks first, first + stride, ... < end for one wave: the first loads of a block are requested while the z
-// fluxes of the block before are computed.
-template <bool STAMP = false, bool DMA = true>
-__device__ __forceinline__ void sweep_euler_chain(const BlockDesc3* __restrict__ blocks, const int32_t* __restrict__ htab,
-                                                  const int32_t* __restrict__ ftab, const int32_t* __restrict__ rtab,
-                                                  const int32_t* __restrict__ r4tab, int32_t first, int32_t stride,
-                                                  int32_t end, const float* __restrict__ P, uint32_t ldp,
-                                                  float* __restrict__ Rr, uint32_t ldr, Gas3 gas, float* lds,
-                                                  float* nextbuf, int lane, unsigned long long* stamps = nullptr,
-                                                  const int32_t* __restrict__ dtab = nullptr) {
-    if (first >= end) return;
-    if constexpr (!DMA) {   // one block per wave
-        sweep_block<STAMP, false>(blocks, htab, ftab, rtab, r4tab, first, P, ldp, Rr, ldr, gas, lds, lane,
-                                  STAMP && stamps ? stamps + (size_t)first * 8 : nullptr, dtab, nextbuf, []() {});
-        return;
-    }
-    request_first(blocks, htab, rtab, P, first, lane, nextbuf);
-#pragma unroll 1
-    for (int32_t blk = first; blk < end; blk += stride) {
-        const int32_t nb = blk + stride;
-        sweep_block<STAMP, true>(blocks, htab, ftab, rtab, r4tab, blk, P, ldp, Rr, ldr, gas, lds, lane,
-                           STAMP && stamps ? stamps + (size_t)blk * 8 : nullptr, dtab, nextbuf, [&]() {
-                               if (nb < end) request_first(blocks, htab, rtab, P, nb, lane, nextbuf);  // wave-uniform
-                           });
-    }
+// Block `blk` of `n` by one wave (a wave past the end of the list does nothing)
+template <bool STAMP = false>
+__device__ __forceinline__ void sweep_euler_cols(const BlockDesc3* __restrict__ blocks, const int32_t* __restrict__ htab,
+                                                 const int32_t* __restrict__ ftab, const int32_t* __restrict__ rtab,
+                                                 const int32_t* __restrict__ r4tab, int32_t blk, int32_t n,
+                                                 const float* __restrict__ P, uint32_t ldp, float* __restrict__ Rr,
+                                                 uint32_t ldr, Gas3 gas, float* lds, int lane,
+                                                 unsigned long long* stamps = nullptr,
+                                                 const int32_t* __restrict__ dtab = nullptr) {
+    if (blk >= n) return;
+    sweep_block<STAMP>(blocks, htab, ftab, rtab, r4tab, blk, P, ldp, Rr, ldr, gas, lds, lane,
+                       STAMP && stamps ? stamps + (size_t)blk * 8 : nullptr, dtab);
 }
 
 #pragma clang fp contract(off)

@@ -142,7 +142,8 @@ enum { IBH_EW_CLAMP = 112, IBH_EW_IFELSE = 113 };
 int ibh_ew_reduce_rows(int64_t n, int nv, const float* a, float* out);
 
 /* Measurement switches of the kernels (A/B runs inside one process, no effect on results beyond rounding):
- *   "quad_variant"  variant of the quad / 3-D sweeps (4: wave time stamps; 512, 518: round-2 3-D kernels; ...)
+ *   "quad_variant"  kernel form of the single-kernel sweeps: 0 the default, 4 wave time stamps, 512 the thread-per-cell form
+ *                   of the 3-D sweeps; any other value is an error and leaves the setting as it was
  *   "quad_parts" 1 / 2 only the quads / only the single blocks; "quad_singles_first" grid order; "quad_singles_iters"
  *   "rows" 1: the row sweep instead of the quad sweep; "rows_singles" -1 by size / 0 / 1 second launch / 2 inside the launch
  *   "pairs" 0: no pair tiles; "arith_ids" 0: halo ids from the table rows; "transport_blocks" 0: face-list transport kernel */

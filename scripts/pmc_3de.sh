@@ -1,4 +1,4 @@
-# PMC passes over the 3-D Euler column sweep for one variant: bash scripts/pmc_3de.sh <name> <quad_variant> [workload]
+# PMC passes over the 3-D Euler single-kernel sweep: bash scripts/pmc_3de.sh <name> <quad_variant: 0 columns, 512 thread per cell> [workload]
 export TMPDIR=/tmp
 N=$1; V=$2; W=${3:-sphere3d_4.6M}
 export IBH_QUAD_VARIANT=$V

@@ -1,6 +1,5 @@
 """A/B of the 3-D Euler sweep forms on one workload (run on the GPU box): python scripts/probe_3d_euler.py [workload]
-column form (strip3e::sweep_block) as one block per wave / persistent chains, thread-per-cell single kernel, two-kernel
-form."""
+column form (strip3e::sweep_block, one block per wave), thread-per-cell single kernel, two-kernel form."""
 import json
 import os
 import sys
@@ -56,9 +55,7 @@ def timed(fn, n=10, reps=15):
 out = {"workload": name, "cells": int(dpart.nc), "blocks": int(dpart.info["full_blocks"]),
        "single_kernel_blocks": int(dpart.info["fusable_blocks"])}
 ref = None
-# (round 4: 0 = one block per wave at two waves per SIMD, the default; 514 = persistent waves, each working through a chain of
-# blocks with the first loads of the next block requested by LDS-DMA during the z fluxes)
-for key, var in (("thread_per_cell_us", 512), ("cols_block_per_wave_us", 0), ("cols_persistent_chain_us", 514)):
+for key, var in (("thread_per_cell_us", 512), ("cols_block_per_wave_us", 0)):
     _lib.call("ibh_set_tuning", b"quad_variant", var)
     R.zero_()
     out[key] = round(timed(lambda: ibamd.residual_euler_hll(dpart, P, out=R)), 3)

@@ -7,10 +7,7 @@ that kind of partition against it, with the same bound.  ``dpart.info`` pins the
 block or side class fails here instead of silently dropping it.
 
 Not run here, on purpose:
-- ``quad_variant`` 4, 85, 69, 5 and 100: measurement variants (wave time stamps, subsets of the halo gathers -- some of
-  them skip gathers by design);
-- ``quad_variant`` 514 on the Euler entry: the persistent LDS-DMA form (its hard-coded ``vmcnt(20)`` wait is an open
-  finding).  On the scalar entry 514 is a strip width and is run.
+- ``quad_variant`` 4: the measurement variant (wave time stamps).
 """
 import numpy as np
 import pytest
@@ -177,7 +174,6 @@ def test_2d_scalar_one_partition(one_part, case):
         c.check_adv("2d scalar NO_QUAD phases", _adv(c.dpart, u, c.C, NO_QUAD, phases=True), kind)
         c.check_adv("2d scalar rows", _tuned({"rows": 1}, lambda: _adv(c.dpart, u, c.C)), kind)
         c.check_adv("2d scalar rows phases", _tuned({"rows": 1}, lambda: _adv(c.dpart, u, c.C, phases=True)), kind)
-        c.check_adv("2d scalar quad_variant 126", _tuned({"quad_variant": 126}, lambda: _adv(c.dpart, u, c.C)), kind)
         c.check_adv("2d scalar NO_FUSE", _adv(c.dpart, u, c.C, NO_FUSE), kind)
         c.check_adv("2d scalar NO_FUSE phases", _adv(c.dpart, u, c.C, NO_FUSE, phases=True), kind)
         c.check_adv("2d scalar EXACT", _adv(c.dpart, u, c.C, EXACT), kind)
@@ -299,8 +295,8 @@ def test_3d_scalar(octrees):
             c.check_adv("3d scalar partition NO_FUSE", _adv(c.dpart, u, c.C, NO_FUSE), "smooth")
             continue
         c.check_adv("3d scalar cols (default)", _adv(c.dpart, u, c.C), "smooth")
-        # 519 / 520: column forms; 518 / 515 / 514: strip forms (514: strip width 4 on this entry); 512: thread per cell
-        for v in (519, 520, 518, 515, 514, 512):
+        # 512: thread per cell
+        for v in (512,):
             c.check_adv(f"3d scalar quad_variant {v}", _tuned({"quad_variant": v}, lambda: _adv(c.dpart, u, c.C)), "smooth")
         c.check_adv("3d scalar NO_FUSE", _adv(c.dpart, u, c.C, NO_FUSE), "smooth")
         c.check_adv("3d scalar NO_FUSE phases", _adv(c.dpart, u, c.C, NO_FUSE, phases=True), "smooth")
@@ -319,3 +315,28 @@ def test_3d_euler(octrees):
         c.check_euler("3d euler quad_variant 512", _tuned({"quad_variant": 512}, lambda: _euler(c.dpart, c.P)))
         c.check_euler("3d euler NO_FUSE", _euler(c.dpart, c.P, NO_FUSE))
         c.check_euler("3d euler FORCE_GENERAL", _euler(c.dpart, c.P, GENERAL))
+
+
+# the kernel forms that lost their A/B and were removed (gather subsets and the seven 4-byte gathers of the quad sweep, the
+# persistent Euler sweep, the strip form and the 4- and 5-wave column forms of the 3-D scalar sweep), and one value never defined
+RETIRED_QUAD_VARIANTS = (5, 69, 85, 100, 126, 514, 515, 518, 519, 520, 7)
+
+
+def test_retired_quad_variants_are_rejected(octrees, one_part):
+    """``ibh_set_tuning("quad_variant", v)`` takes 0, 4 and 512 only: a value of a removed form is an error that leaves
+    the setting as it was -- it must not quietly run (and let a probe script time) the default form."""
+    lib = _lib.load()
+    c3, c2 = octrees["corner"], one_part["adv"]
+    try:
+        for v in RETIRED_QUAD_VARIANTS:
+            rc = lib.ibh_set_tuning(b"quad_variant", v)   # (the raw entry: _lib.call raises on a non-zero code)
+            msg = lib.ibh_last_error().decode()
+            assert rc != 0, v
+            assert "quad_variant" in msg, (v, msg)
+        # the setting is still 0: the default forms, with the bound they pass in test_3d_scalar / test_2d_scalar_one_partition
+        c3.check_adv("3d scalar cols (default) after rejected quad_variant", _adv(c3.dpart, c3.u["smooth"], c3.C), "smooth")
+        c2.check_adv("2d scalar quad (default) after rejected quad_variant", _adv(c2.dpart, c2.u["smooth"], c2.C), "smooth")
+        for v in (0, 4, 512):
+            assert lib.ibh_set_tuning(b"quad_variant", v) == 0, v
+    finally:
+        _lib.call("ibh_set_tuning", b"quad_variant", 0)
