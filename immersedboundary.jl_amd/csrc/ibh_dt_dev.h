@@ -3,6 +3,7 @@
 // march step (ibh_ops.hip: k_bcinterp_dt / k_bcscatter_dt).
 #pragma once
 #include "ibh_common.h"
+#include "ibh_reduce_dev.h"
 
 #define DT_BLOCK 256
 
@@ -81,28 +82,12 @@ __device__ __forceinline__ void dt_partial_wg(int wg, int nwg, int32_t nc, const
             m = fmaxf(m, (ar + al) / hc);
         }
     }
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    __shared__ float wm[DT_BLOCK / 64];
-    if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float b = wm[0];
-        for (int w = 1; w < DT_BLOCK / 64; ++w) b = fmaxf(b, wm[w]);
-        partial[wg] = b;
-    }
+    m = ibh_red::wg_reduce<DT_BLOCK, ibh_red::FMax>(m);
+    if (threadIdx.x == 0) partial[wg] = m;
 }
 __device__ __forceinline__ void dt_final_wg(int n, const float* __restrict__ partial, float scale, float* __restrict__ dt) {
-    float m = -INFINITY;
-    for (int i = threadIdx.x; i < n; i += DT_BLOCK) m = fmaxf(m, partial[i]);
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    __shared__ float wm[DT_BLOCK / 64];
-    if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float b = wm[0];
-        for (int w = 1; w < DT_BLOCK / 64; ++w) b = fmaxf(b, wm[w]);
-        *dt = (0.5f / b) * scale;  // advection.jl:53 and :65
-    }
+    const float b = ibh_red::wg_reduce_partials<DT_BLOCK, ibh_red::FMax>(n, partial);
+    if (threadIdx.x == 0) *dt = (0.5f / b) * scale;  // advection.jl:53 and :65
 }
 
 }  // namespace dt_dev

@@ -5,6 +5,7 @@
 // vector (n,) broadcast over the columns, or a scalar.
 #include "ibh_common.h"
 #include "ibh_ew_math.h"
+#include "ibh_reduce_dev.h"
 
 namespace {
 
@@ -215,42 +216,21 @@ __global__ __launch_bounds__(256) void k_ew_reduce_rows(int64_t n, int nv, const
     }
 }
 
-template <int OP>
-__device__ __forceinline__ float red2(float a, float b) {
-    return OP == IBH_EW_SUM ? a + b : OP == IBH_EW_MAX ? fmaxf(a, b) : fminf(a, b);
-}
-template <int OP>
-__device__ __forceinline__ float red_identity() {
-    return OP == IBH_EW_SUM ? 0.0f : OP == IBH_EW_MAX ? -INFINITY : INFINITY;
-}
-template <int OP>
-__device__ __forceinline__ float block_reduce(float v, float* sm) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = red2<OP>(v, __shfl_down(v, o, 64));
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) sm[w] = v;
-    __syncthreads();
-    v = threadIdx.x < (blockDim.x >> 6) ? sm[threadIdx.x] : red_identity<OP>();
-    if (w == 0) {
-#pragma unroll
-        for (int o = 2; o > 0; o >>= 1) v = red2<OP>(v, __shfl_down(v, o, 64));
-    }
-    return v;
-}
-// every block reduces its stride of the array; with ONE block the result is written at once, with more (`two_stage`) only
-// the partials are -- a second one-block launch over them finishes (many blocks meeting at one counter serialise: ~20 ns
-// per arrival across the XCDs, 20 us for 1 024 blocks; a launch costs a tenth of that)
-template <int OP>
+// sum / maximum / minimum of a flat array (ibh_reduce_dev.h): every workgroup reduces its stride of the array.  Without a
+// counter it writes out[blockIdx.x]: the result of a one-workgroup launch, or the partials that the same kernel, launched
+// with one workgroup over them, finishes.  With a counter (2 - 8 workgroups: the last last-workgroup-out reduction of the
+// library, kept until a measurement shows that one workgroup is no slower there) the partials go to
+// `part` and the workgroup that arrives last reduces them into out[0].  maximum / minimum keep fmaxf / fminf.
+template <class OP>
 __global__ __launch_bounds__(256) void k_ew_reduce(int64_t total, const float* __restrict__ a, float* part,
-                                                   unsigned int* counter, float* out, int two_stage) {
-    __shared__ float sm[4];
+                                                   unsigned int* counter, float* out) {
     __shared__ bool last;
-    float v = red_identity<OP>();
+    float v = OP::identity();
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x)
-        v = red2<OP>(v, a[t]);
-    v = block_reduce<OP>(v, sm);
-    if (two_stage) {
-        if (threadIdx.x == 0) part[blockIdx.x] = v;
+        v = OP::op(v, a[t]);
+    v = ibh_red::wg_reduce<256, OP>(v);
+    if (!counter) {
+        if (threadIdx.x == 0) out[blockIdx.x] = v;
         return;
     }
     if (threadIdx.x == 0) {
@@ -261,29 +241,14 @@ __global__ __launch_bounds__(256) void k_ew_reduce(int64_t total, const float* _
     __syncthreads();
     if (!last) return;
     __threadfence();
-    v = red_identity<OP>();
-    for (unsigned t = threadIdx.x; t < gridDim.x; t += blockDim.x) v = red2<OP>(v, ((volatile float*)part)[t]);
-    __syncthreads();
-    v = block_reduce<OP>(v, sm);
+    v = OP::identity();
+    for (unsigned t = threadIdx.x; t < gridDim.x; t += 256) v = OP::op(v, ((volatile float*)part)[t]);
+    __syncthreads();   // thread 0 has read the slots of the first wg_reduce
+    v = ibh_red::wg_reduce<256, OP>(v);
     if (threadIdx.x == 0) {
         *out = v;
         *counter = 0;  // ready for the next launch on this stream
     }
-}
-
-// scratch of the reductions: partials of up to 1024 blocks + the arrival counter (one per host thread)
-struct RedScratch {
-    float* part = nullptr;
-    unsigned int* counter = nullptr;
-};
-thread_local RedScratch red_scratch;
-
-int ensure_scratch() {
-    if (red_scratch.part) return 0;
-    IBH_HIP(hipMalloc((void**)&red_scratch.part, 1032 * sizeof(float)));
-    IBH_HIP(hipMalloc((void**)&red_scratch.counter, sizeof(unsigned int)));
-    IBH_HIP(hipMemset(red_scratch.counter, 0, sizeof(unsigned int)));
-    return 0;
 }
 
 }  // namespace
@@ -474,21 +439,21 @@ int ibh_ew_fill(int64_t total, float value, float* out) {
 
 int ibh_ew_reduce(int op, int64_t total, const float* a, float* out_device) {
     IBH_REQUIRE(a && out_device && total >= 1, "ibh_ew_reduce: bad argument (an empty reduction has no value)");
-    int rc = ensure_scratch();
-    if (rc) return rc;
-    const dim3 grid(std::min(1024, ibh_grid(total, 256 * 8))), blk(256);
-    float* part = red_scratch.part;
-    unsigned int* cnt = red_scratch.counter;
-    const int two = grid.x > 8;
-    const int64_t nparts = (int64_t)grid.x;
-    // (the second stage reads the first `nparts` partials and writes its own one partial behind them)
+    float* part = (float*)ibh_red_scratch(IBH_RED_EW);
+    IBH_REQUIRE(part, "ibh_ew_reduce: no scratch");
+    // 8 elements per thread in up to 1 024 workgroups: one writes the result, 2 - 8 meet at the counter behind the partials,
+    // more write partials and a second launch reduces them
+    const int nwg = ibh_grid_cap(total, 256 * 8, 1024);
+    unsigned int* cnt = nwg > 1 && nwg <= 8 ? (unsigned int*)(part + 1024) : nullptr;
 #define EW_REDUCE(OP)                                                                                                  \
-    hipLaunchKernelGGL(k_ew_reduce<OP>, grid, blk, 0, ibh_stream, total, a, part, cnt, out_device, two);               \
-    if (two) hipLaunchKernelGGL(k_ew_reduce<OP>, dim3(1), blk, 0, ibh_stream, nparts, (const float*)part, part + 1024, cnt, out_device, 0)
+    hipLaunchKernelGGL(k_ew_reduce<OP>, dim3(nwg), dim3(256), 0, ibh_stream, total, a, part, cnt,                      \
+                       nwg > 8 ? part : out_device);                                                                   \
+    if (nwg > 8) hipLaunchKernelGGL(k_ew_reduce<OP>, dim3(1), dim3(256), 0, ibh_stream, (int64_t)nwg, (const float*)part, \
+                                    part, cnt, out_device)
     switch (op) {
-        case IBH_EW_SUM: EW_REDUCE(IBH_EW_SUM); break;
-        case IBH_EW_MAX: EW_REDUCE(IBH_EW_MAX); break;
-        case IBH_EW_MIN: EW_REDUCE(IBH_EW_MIN); break;
+        case IBH_EW_SUM: EW_REDUCE(ibh_red::Sum<float>); break;
+        case IBH_EW_MAX: EW_REDUCE(ibh_red::FMax); break;
+        case IBH_EW_MIN: EW_REDUCE(ibh_red::FMin); break;
         default: return ibh_fail(-1, "ibh_ew_reduce: unknown operation", __FILE__, __LINE__);
     }
 #undef EW_REDUCE

@@ -541,69 +541,20 @@ __global__ void k_axpy(int64_t n, float a, const float* __restrict__ x, float* _
         y[i] = a * x[i] + y[i];
 }
 
-// final step of the two-stage reductions below: one workgroup adds the workgroup sums (in index order: a fixed order for a
-// fixed grid) -- no atomics: 1 024 - 2 048 arrivals at ONE address cost 20 - 40 us on this part (they serialise across the XCDs)
-__global__ __launch_bounds__(OPS_BLOCK) void k_sum_partials(int n, const double* __restrict__ part, double* __restrict__ out) {
-    __shared__ double sh[OPS_BLOCK];
-    double s = 0.0;
-    for (int i = threadIdx.x; i < n; i += OPS_BLOCK) s += part[i];
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = OPS_BLOCK / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *out = sh[0];
-}
-// scratch of the two-stage reductions (per host thread: one stream of reductions at a time)
-static double* red_scratch() {
-    static thread_local double* buf = nullptr;
-    if (!buf && hipMalloc((void**)&buf, 4096 * sizeof(double)) != hipSuccess) buf = nullptr;
-    return buf;
-}
-
+// sum x^2 in double: workgroup sums (ibh_reduce_dev.h), added by k_sum_partials (ibh_reduce.hip)
 __global__ void k_sumsq(int64_t n, const float* __restrict__ x, double* __restrict__ out) {
     double s = 0.0;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         double t = (double)x[i];
         s += t * t;
     }
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-    __shared__ double part[OPS_BLOCK / 64];
-    int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) part[w] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int i = 0; i < OPS_BLOCK / 64; ++i) t += part[i];
-        out[blockIdx.x] = t;    // (workgroup sums: k_sum_partials adds them)
-    }
-}
-
-// q += clamp(omega, 0, 1) * r and out += sum r^2 in one pass over r (solver.jl:82 and the norm of :84 on the same array)
-__global__ void k_axpy_clamped_sumsq(int64_t n, float omega, const float* __restrict__ r, float* __restrict__ q,
-                                     double* __restrict__ out) {
-    const float w = ibh_clamp(omega, 0.0f, 1.0f);   // Julia's clamp: a NaN omega stays NaN
-    double s = 0.0;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float ri = r[i];
-        q[i] = q[i] + w * ri;
-        s += (double)ri * (double)ri;
-    }
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-    __shared__ double part[OPS_BLOCK / 64];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0) part[wv] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int i = 0; i < OPS_BLOCK / 64; ++i) t += part[i];
-        out[blockIdx.x] = t;    // (workgroup sums: k_sum_partials adds them)
-    }
+    s = ibh_red::wg_reduce<OPS_BLOCK, ibh_red::Sum<double>>(s);
+    if (threadIdx.x == 0) out[blockIdx.x] = s;
 }
 
 // One pass of `FAS!` over a residual array (solver.jl:80-84): rr = r [+ source]; [q += clamp(omega, 0, 1) * rr]; [sum rr^2]
 // -- `r .+= source`, the fixed-point update and the norm on ONE read of r (round 3 had the sum as an ATen kernel).
+// <false, true, true> is ibh_axpy_clamped_sumsq (solver.jl:82 and the norm of :84 on the same array).
 template <bool SRC, bool UPD, bool NRM>
 __global__ void k_fas_update(int64_t n, float omega, const float* __restrict__ r, const float* __restrict__ src,
                              float* __restrict__ q, double* __restrict__ out) {
@@ -616,20 +567,12 @@ __global__ void k_fas_update(int64_t n, float omega, const float* __restrict__ r
         if (NRM) s += (double)ri * (double)ri;
     }
     if (NRM) {
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-        __shared__ double part[OPS_BLOCK / 64];
-        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-        if (lane == 0) part[wv] = s;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double t = 0.0;
-            for (int i = 0; i < OPS_BLOCK / 64; ++i) t += part[i];
-            out[blockIdx.x] = t;
-        }
+        s = ibh_red::wg_reduce<OPS_BLOCK, ibh_red::Sum<double>>(s);
+        if (threadIdx.x == 0) out[blockIdx.x] = s;
     }
 }
 
-inline dim3 grid2(int64_t n, int nv) { return dim3(ibh_grid(n, OPS_BLOCK) > 4096 ? 4096 : ibh_grid(n, OPS_BLOCK), nv); }
+inline dim3 grid2(int64_t n, int nv) { return dim3(ibh_grid_cap(n, OPS_BLOCK, 4096), nv); }
 
 // launch of the accumulation kernels: per (row, field) for one field, per row over blocks of up to 4 fields otherwise
 static inline void launch_accumulate(int32_t n_out, const int32_t* off, const int32_t* idx, const float* w,
@@ -754,16 +697,22 @@ int ibh_wray_agarwal_of_cells(const ibh_part* p, const float* R, const float* S,
     return 0;
 }
 
+// the workgroup maxima of the time step live with the partition, not in the per-thread scratch: a march step launches them
+// in one call and reduces them in the next (partials_done below)
+static hipError_t ensure_march_tmp(ibh_part* p) {
+    if (p->march_tmp) return hipSuccess;
+    const hipError_t e = hipMalloc((void**)&p->march_tmp, 8192 * sizeof(float));
+    if (e == hipSuccess) p->march_tmp_n = 8192;
+    return e;
+}
+
 int ibh_timestep_advection(ibh_part* p, const float* C, int64_t ldc, float scale, float* dt_dev) {
     IBH_REQUIRE(p && C && dt_dev && (p->nd == 2 || p->nd == 3) && p->nc > 0, "ibh_timestep_advection: bad argument");
-    if (!p->march_tmp) {  // workgroup maxima
-        IBH_HIP(hipMalloc((void**)&p->march_tmp, 8192 * sizeof(float)));
-        p->march_tmp_n = 8192;
-    }
+    IBH_HIP(ensure_march_tmp(p));
     const GradDims G = grad_dims(p);
     // one cell per thread up to 2 M cells (every load of a cell in flight at once: the kernel is two dependent round trips,
     // not bandwidth; with 1 024 workgroups and 3-4 cells per thread it took 18.6 us at 0.87 M cells)
-    const int nwg = std::min(ibh_grid(p->nc, OPS_BLOCK), 8192);
+    const int nwg = ibh_grid_cap(p->nc, OPS_BLOCK, 8192);
     const bool tiled = p->info[20] != 0;   // complete blocks in order (ibh_api.hip)
 #define DT_LAUNCH(ND_, T_) \
     hipLaunchKernelGGL((k_timestep_advection<ND_, T_>), dim3(nwg), dim3(OPS_BLOCK), 0, ibh_stream, p->nc, G, C, ldc, p->march_tmp)
@@ -788,18 +737,15 @@ int ibh_timestep_advection(ibh_part* p, const float* C, int64_t ldc, float scale
 int ibh_bcset_apply_with_dt(const ibh_bcset* s, float* a, ibh_part* p, const float* C, int64_t ldc, float scale,
                             float* dt_next, int partials_done) {
     IBH_REQUIRE(s && a && p && C && dt_next && (p->nd == 2 || p->nd == 3) && p->nc > 0, "ibh_bcset_apply_with_dt: bad argument");
-    if (!p->march_tmp) {
-        IBH_HIP(hipMalloc((void**)&p->march_tmp, 8192 * sizeof(float)));
-        p->march_tmp_n = 8192;
-    }
+    IBH_HIP(ensure_march_tmp(p));
     const GradDims G = grad_dims(p);
-    const int nwg_dt = std::min(ibh_grid(p->nc, OPS_BLOCK), 8192);
+    const int nwg_dt = ibh_grid_cap(p->nc, OPS_BLOCK, 8192);
     const bool tiled = p->info[20] != 0;
     int stage = partials_done ? 1 : 0;   // 0: partial maxima not launched yet, 1: final reduction not launched yet, 2: done
     for (int lv = 0; lv < s->nlev; ++lv) {
         const int32_t g0 = s->seg[lv], g1 = s->seg[lv + 1];
         if (g1 == g0) continue;
-        const int nwg = std::min(ibh_grid(g1 - g0, OPS_BLOCK), 2048);
+        const int nwg = ibh_grid_cap(g1 - g0, OPS_BLOCK, 2048);
         BcLaunch B{g0, g1, s->eta, s->w, s->value, s->off, s->donor, s->bidx, s->mode, s->direct[lv] ? s->ghost : nullptr,
                    s->ghost, s->gval};
         // the interpolation launch of the level
@@ -990,35 +936,24 @@ int ibh_bc_apply(const ibh_bc* b, float* a, int nv, int64_t lda, int mode, const
 
 int ibh_axpy_clamped(int64_t n, float omega, const float* r, float* q) {
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(k_axpy_clamped, dim3(ibh_grid(n, OPS_BLOCK) > 2048 ? 2048 : ibh_grid(n, OPS_BLOCK)),
-                       dim3(OPS_BLOCK), 0, ibh_stream, n, omega, r, q);
+    hipLaunchKernelGGL(k_axpy_clamped, dim3(ibh_grid_cap(n, OPS_BLOCK, 2048)), dim3(OPS_BLOCK), 0, ibh_stream, n, omega, r, q);
     IBH_LAUNCH_CHECK();
     return 0;
 }
 int ibh_axpy_clamped_sumsq(int64_t n, float omega, const float* r, float* q, double* out) {
     IBH_REQUIRE(out, "ibh_axpy_clamped_sumsq: null argument");
-    double* part = red_scratch();
-    IBH_REQUIRE(part, "ibh_axpy_clamped_sumsq: no scratch");
-    if (n <= 0) {
-        IBH_HIP(hipMemsetAsync(out, 0, sizeof(double), ibh_stream));
-        return 0;
-    }
-    const int nwg = ibh_grid(n, OPS_BLOCK) > 2048 ? 2048 : ibh_grid(n, OPS_BLOCK);
-    hipLaunchKernelGGL(k_axpy_clamped_sumsq, dim3(nwg), dim3(OPS_BLOCK), 0, ibh_stream, n, omega, r, q, part);
-    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(OPS_BLOCK), 0, ibh_stream, nwg, part, out);
-    IBH_LAUNCH_CHECK();
-    return 0;
+    return ibh_fas_update(n, omega, r, nullptr, q, out);   // k_fas_update<false, true, true>
 }
 int ibh_fas_update(int64_t n, float omega, const float* r, const float* source, float* q, double* out_sumsq) {
     IBH_REQUIRE(r || n <= 0, "ibh_fas_update: null residual");
-    double* part = out_sumsq ? red_scratch() : nullptr;
+    double* part = out_sumsq ? (double*)ibh_red_scratch(IBH_RED_FAS) : nullptr;
     IBH_REQUIRE(!out_sumsq || part, "ibh_fas_update: no scratch");
     if (n <= 0) {
         if (out_sumsq) IBH_HIP(hipMemsetAsync(out_sumsq, 0, sizeof(double), ibh_stream));
         return 0;
     }
     if (!q && !out_sumsq) return 0;
-    const int nwg = ibh_grid(n, OPS_BLOCK) > 2048 ? 2048 : ibh_grid(n, OPS_BLOCK);
+    const int nwg = ibh_grid_cap(n, OPS_BLOCK, 2048);
 #define FAS_LAUNCH(S, U, N) \
     hipLaunchKernelGGL((k_fas_update<S, U, N>), dim3(nwg), dim3(OPS_BLOCK), 0, ibh_stream, n, omega, r, source, q, part)
     if (source) {
@@ -1031,27 +966,26 @@ int ibh_fas_update(int64_t n, float omega, const float* r, const float* source, 
         else FAS_LAUNCH(false, false, true);
     }
 #undef FAS_LAUNCH
-    if (out_sumsq) hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(OPS_BLOCK), 0, ibh_stream, nwg, part, out_sumsq);
+    if (out_sumsq) ibh_launch_sum_partials(nwg, part, out_sumsq);
     IBH_LAUNCH_CHECK();
     return 0;
 }
 int ibh_axpy(int64_t n, float a, const float* x, float* y) {
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(k_axpy, dim3(ibh_grid(n, OPS_BLOCK) > 2048 ? 2048 : ibh_grid(n, OPS_BLOCK)), dim3(OPS_BLOCK), 0,
-                       ibh_stream, n, a, x, y);
+    hipLaunchKernelGGL(k_axpy, dim3(ibh_grid_cap(n, OPS_BLOCK, 2048)), dim3(OPS_BLOCK), 0, ibh_stream, n, a, x, y);
     IBH_LAUNCH_CHECK();
     return 0;
 }
 int ibh_sumsq(int64_t n, const float* x, double* out) {
-    double* part = red_scratch();
+    double* part = (double*)ibh_red_scratch(IBH_RED_SUMSQ);
     IBH_REQUIRE(out && part, "ibh_sumsq: null argument or no scratch");
     if (n <= 0) {
         IBH_HIP(hipMemsetAsync(out, 0, sizeof(double), ibh_stream));
         return 0;
     }
-    const int nwg = ibh_grid(n, OPS_BLOCK) > 1024 ? 1024 : ibh_grid(n, OPS_BLOCK);
-    hipLaunchKernelGGL(k_sumsq, dim3(nwg), dim3(OPS_BLOCK), 0, ibh_stream, n, x, part + 2048);
-    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(OPS_BLOCK), 0, ibh_stream, nwg, part + 2048, out);
+    const int nwg = ibh_grid_cap(n, OPS_BLOCK, 1024);
+    hipLaunchKernelGGL(k_sumsq, dim3(nwg), dim3(OPS_BLOCK), 0, ibh_stream, n, x, part);
+    ibh_launch_sum_partials(nwg, part, out);
     IBH_LAUNCH_CHECK();
     return 0;
 }

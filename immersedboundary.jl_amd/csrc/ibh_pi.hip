@@ -8,6 +8,7 @@
 // Block layout: D (n, nv, nv) column-major like the reference's stack(): D[p + n*(k + nv*i)] = d f_k / d x_i at
 // point p, so every access is coalesced over p.
 #include "ibh_common.h"
+#include "ibh_reduce_dev.h"
 
 namespace {
 
@@ -152,29 +153,26 @@ __global__ void k_mul(int64_t n, const float* __restrict__ a, const float* __res
         out[i] = a[i] * b[i];
 }
 
-// block reduction helpers: out[0] += sum a*b (double), out[0] = max |a| (float bits, non-negative: integer max)
-__global__ void k_dot(int64_t n, const float* __restrict__ a, const float* __restrict__ b, double* __restrict__ out) {
-    __shared__ double sh[PB / 64];
+// the two-stage reductions (ibh_reduce_dev.h): workgroup sums of a*b in double, added by k_sum_partials (ibh_reduce.hip);
+// workgroup maxima of |a|, reduced by k_maxabs_partials
+__global__ void k_dot(int64_t n, const float* __restrict__ a, const float* __restrict__ b, double* __restrict__ part) {
     double s = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
         s += (double)a[i] * (double)b[i];
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int k = 0; k < PB / 64; ++k) t += sh[k];
-        atomicAdd(out, t);
-    }
+    s = ibh_red::wg_reduce<PB, ibh_red::Sum<double>>(s);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
-__global__ void k_maxabs(int64_t n, const float* __restrict__ a, uint32_t* __restrict__ out) {
-    // Julia's maximum(abs, a) propagates NaN (ibh_max); the bits of |NaN| are above those of Inf, so the integer
-    // maximum keeps it
+__global__ void k_maxabs(int64_t n, const float* __restrict__ a, float* __restrict__ part) {
+    // Julia's maximum(abs, a) propagates NaN (ibh_max)
     float m = 0.0f;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
         m = ibh_max(m, fabsf(a[i]));
-    for (int o = 32; o > 0; o >>= 1) m = ibh_max(m, __shfl_down(m, o, 64));
-    if ((threadIdx.x & 63) == 0) atomicMax(out, __float_as_uint(m) & 0x7fffffffu);
+    m = ibh_red::wg_reduce<PB, ibh_red::NanMax>(m);
+    if (threadIdx.x == 0) part[blockIdx.x] = m;
+}
+__global__ __launch_bounds__(PB) void k_maxabs_partials(int n, const float* __restrict__ part, float* __restrict__ out) {
+    const float m = ibh_red::wg_reduce_partials<PB, ibh_red::NanMax>(n, part);
+    if (threadIdx.x == 0) *out = m;
 }
 
 // x += alpha s ; r -= alpha As  with  alpha = AvB / (AvAv + eps)  read from device memory (:231-236, :291-294)
@@ -187,17 +185,14 @@ __global__ void k_pi_update(int64_t n, const double* __restrict__ dots, float ep
     }
 }
 // s = r / (eps + max|r|)   (:297-299)
-__global__ void k_pi_normalize(int64_t n, const float* __restrict__ r, const uint32_t* __restrict__ mx, float eps,
+__global__ void k_pi_normalize(int64_t n, const float* __restrict__ r, const float* __restrict__ mx, float eps,
                                float* __restrict__ s) {
-    const float d = eps + __uint_as_float(mx[0]);
+    const float d = eps + mx[0];
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
         s[i] = r[i] / d;
 }
 
-inline int grid_for(int64_t n) {
-    int g = ibh_grid(n, PB);
-    return g > 4096 ? 4096 : g;
-}
+inline int grid_for(int64_t n) { return ibh_grid_cap(n, PB, 4096); }
 
 }  // namespace
 
@@ -275,21 +270,30 @@ int ibh_pi_apply_blocks(int64_t n, int nv, const float* invD, const float* v, fl
     return 0;
 }
 int ibh_dot(int64_t n, const float* a, const float* b, double* out) {
-    IBH_REQUIRE(out, "ibh_dot: null argument");
-    IBH_HIP(hipMemsetAsync(out, 0, sizeof(double), ibh_stream));
-    if (n <= 0) return 0;
+    double* part = (double*)ibh_red_scratch(IBH_RED_DOT);
+    IBH_REQUIRE(out && part, "ibh_dot: null argument or no scratch");
+    if (n <= 0) {
+        IBH_HIP(hipMemsetAsync(out, 0, sizeof(double), ibh_stream));
+        return 0;
+    }
     IBH_REQUIRE(a && b, "ibh_dot: null argument");
-    hipLaunchKernelGGL(k_dot, dim3(grid_for(n) > 1024 ? 1024 : grid_for(n)), dim3(PB), 0, ibh_stream, n, a, b, out);
+    const int nwg = ibh_grid_cap(n, PB, 1024);
+    hipLaunchKernelGGL(k_dot, dim3(nwg), dim3(PB), 0, ibh_stream, n, a, b, part);
+    ibh_launch_sum_partials(nwg, part, out);
     IBH_LAUNCH_CHECK();
     return 0;
 }
 int ibh_maxabs(int64_t n, const float* a, float* out) {
-    IBH_REQUIRE(out, "ibh_maxabs: null argument");
-    IBH_HIP(hipMemsetAsync(out, 0, sizeof(float), ibh_stream));
-    if (n <= 0) return 0;
+    float* part = (float*)ibh_red_scratch(IBH_RED_MAXABS);
+    IBH_REQUIRE(out && part, "ibh_maxabs: null argument or no scratch");
+    if (n <= 0) {
+        IBH_HIP(hipMemsetAsync(out, 0, sizeof(float), ibh_stream));
+        return 0;
+    }
     IBH_REQUIRE(a, "ibh_maxabs: null argument");
-    hipLaunchKernelGGL(k_maxabs, dim3(grid_for(n) > 1024 ? 1024 : grid_for(n)), dim3(PB), 0, ibh_stream, n, a,
-                       reinterpret_cast<uint32_t*>(out));
+    const int nwg = ibh_grid_cap(n, PB, 1024);
+    hipLaunchKernelGGL(k_maxabs, dim3(nwg), dim3(PB), 0, ibh_stream, n, a, part);
+    hipLaunchKernelGGL(k_maxabs_partials, dim3(1), dim3(PB), 0, ibh_stream, nwg, (const float*)part, out);
     IBH_LAUNCH_CHECK();
     return 0;
 }
@@ -303,8 +307,7 @@ int ibh_pi_update(int64_t n, const double* dots, float eps, const float* s, cons
 int ibh_pi_normalize(int64_t n, const float* r, const float* maxabs, float eps, float* s) {
     if (n <= 0) return 0;
     IBH_REQUIRE(r && maxabs && s, "ibh_pi_normalize: null argument");
-    hipLaunchKernelGGL(k_pi_normalize, dim3(grid_for(n)), dim3(PB), 0, ibh_stream, n, r,
-                       reinterpret_cast<const uint32_t*>(maxabs), eps, s);
+    hipLaunchKernelGGL(k_pi_normalize, dim3(grid_for(n)), dim3(PB), 0, ibh_stream, n, r, maxabs, eps, s);
     IBH_LAUNCH_CHECK();
     return 0;
 }

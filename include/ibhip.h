@@ -532,7 +532,8 @@ int ibh_pi_div_scalar(int64_t n, float d, float* s);
 int ibh_pi_invert_blocks(int64_t n, int nv, float* D);
 /* out[p,k] = sum_i v[p,i] * invD[p,k,i]  (:153-161; nv == 1: out = v .* invD :141-146) */
 int ibh_pi_apply_blocks(int64_t n, int nv, const float* invD, const float* v, float* out);
-/* *out (device, double) = sum(a .* b);  *out (device, float) = maximum(abs, a) */
+/* *out (device, double) = sum(a .* b);  *out (device, float) = maximum(abs, a).  Both are two-stage reductions without
+ * atomics: the result of ibh_dot is reproducible -- the same input gives the same bits in every call. */
 int ibh_dot(int64_t n, const float* a, const float* b, double* out);
 int ibh_maxabs(int64_t n, const float* a, float* out);
 /* alpha = dots[0] / (dots[1] + eps) read on the device; x += s*alpha; r -= As*alpha  (:229-236, :291-294) */

@@ -26,6 +26,8 @@ requires it to stay at or below half of each bound; it prints the maxima quoted 
 - Sums (``ibh_sumsq``, ``ibh_dot``, the norm halves): 1e-13 x sum |t_i| against ``math.fsum`` (``BOUND_SUM``): a product of
   two floats is exact in double, a term passes through fewer than 100 additions (thread stride, wave shuffle, four waves,
   partials stride, tree), 100 x 2^-53 = 1.1e-14, times 10.
+- Float32 sum of ``ibh_ew_reduce``: D x 2^-24 x sum |a_i| against ``math.fsum`` (``check_sum32``), D = ``ew_sum_depth`` the
+  number of additions a term passes through.  The Float32 model of the same order measures 0.06 of the bound at most.
 - Time step: relative 4 ulp (``BOUND_DT``): one face average, one sum and two divisions; the maximum itself is exact.
 """
 import math
@@ -397,6 +399,61 @@ def check_sum(got, a, b=None, what=""):
     err = abs(float(got) - ref)
     assert err <= BOUND_SUM * mag, f"{what}: sum {float(got)!r}, fsum {ref!r}, error {err:.3e} > {BOUND_SUM * mag:.3e}"
     return err / mag if mag else 0.0
+
+
+# ibh_ew_reduce (sum / maximum / minimum of a flat Float32 array): its totals cover one wave, one workgroup, both sides of
+# the one-to-several-workgroups threshold, both sides of the counter / two-launch threshold and the 1 024-workgroup cap
+EW_REDUCE_TOTALS = (1, 63, 64, 65, 255, 256, 257, 2048, 2049, 16384, 16385, 256 * 8 * 1024 + 1)
+
+
+def ew_reduce_stages(total):
+    """[(elements, workgroups)] of the stages of ``ibh_ew_reduce``, from the grid formula of ibh_ew.hip: 8 elements per
+    thread in at most 1 024 workgroups of 256 threads; more than one workgroup leaves partials that one workgroup reduces
+    (the last one to arrive for 2 - 8 workgroups, a second launch above)."""
+    nwg = min(1024, -(-total // (256 * 8)))
+    return [(total, nwg)] + ([(nwg, 1)] if nwg > 1 else [])
+
+
+def ew_sum_depth(total):
+    """Additions a term of the Float32 sum can pass through, read from the code: per stage the chain of a thread
+    (ceil(elements / (workgroups * 256))), 6 shuffle steps and 4 wave slots."""
+    return sum(-(-n // (g * 256)) + 6 + 4 for n, g in ew_reduce_stages(total))
+
+
+def ew_sum_model32(a):
+    """The Float32 sum in the order of ibh_reduce_dev.h: per thread its strided chain from 0, the shuffle tree with offsets
+    32 ... 1 (lane 0), the wave slots in order; then the same over the workgroup values."""
+    v = np.asarray(a, f32)
+    for n, g in ew_reduce_stages(v.size):
+        t = g * 256
+        pad = np.zeros(-(-n // t) * t, f32)
+        pad[:n] = v
+        acc = np.zeros(t, f32)
+        for row in pad.reshape(-1, t):                 # (a thread past the end adds nothing: x + 0 = x)
+            acc = acc + row
+        w = acc.reshape(g, 4, 64).copy()
+        for o in (32, 16, 8, 4, 2, 1):
+            w[:, :, :o] = w[:, :, :o] + w[:, :, o:2 * o]
+        slot = w[:, :, 0]
+        v = ((slot[:, 0] + slot[:, 1]) + slot[:, 2]) + slot[:, 3]
+    return v[0]
+
+
+def check_sum32(got, a, what=""):
+    """|got - math.fsum(a)| <= D 2^-24 sum |a_i| with D = ``ew_sum_depth``: every addition rounds by at most 2^-24 of its
+    result, which is at most sum |a_i|.  Returns the error relative to the bound."""
+    a64 = np.asarray(a, f32).astype(f64)
+    ref, mag = math.fsum(a64.tolist()), math.fsum(np.abs(a64).tolist())
+    bound = ew_sum_depth(a64.size) * 2.0 ** -24 * mag
+    err = abs(float(got) - ref)
+    assert err <= bound, f"{what}: sum {float(got)!r}, fsum {ref!r}, error {err:.3e} > {bound:.3e} (depth {ew_sum_depth(a64.size)})"
+    return err / bound if bound else 0.0
+
+
+def extreme_places(n):
+    """Where ``test_maxabs`` puts the largest element: first, last, at 63 / 64 and at the start of the last partial
+    workgroup."""
+    return sorted({0, n - 1, min(63, n - 1), min(64, n - 1), max(0, n - 1 - (n - 1) % 256)})
 
 
 def clamp_julia(x, lo, hi):

@@ -23,6 +23,7 @@ import percell_steps as ps
 from conftest import ADV_FAMILIES, RAE_FAMILIES, oracle_view
 from ibamd import _lib
 from ibamd import backend as B
+from ibamd import hiparray as H
 from ibamd.accumulator import Accumulator
 
 pytestmark = pytest.mark.gpu
@@ -636,6 +637,38 @@ def test_maxabs(n):
     a = base.copy()
     a[0] = np.nan
     assert np.isnan(_maxabs(a)), "maxabs dropped a NaN"
+
+
+@pytest.mark.parametrize("n", ps.EW_REDUCE_TOTALS)
+def test_ew_reduce(n):
+    """sum / maximum / minimum of a flat array (``ibh_ew_reduce``), each twice into the same output.  The extremes are
+    exact, with the extreme element at the places of ``test_maxabs``; the Float32 sum is within ``check_sum32``'s bound of
+    ``math.fsum`` (depth from the grid formula; the Float32 model of the same order measures 0.06 of the bound)."""
+    out = torch.full((1,), float("nan"), dtype=torch.float32, device="cuda")
+    for x in (ps.seeded(n, 1), ps.seeded(n, 2, 0.0, 1.0)):
+        call("ibh_ew_reduce", H.SUM, n, B._ptr(keep(x)), B._ptr(out))
+        _record("ew_reduce sum / bound", ps.check_sum32(out.item(), x, f"ew_reduce sum n={n}"))
+    d = keep(ps.seeded(n, 6))
+    for op, sign in ((H.MAX, 1.0), (H.MIN, -1.0)):
+        for p in ps.extreme_places(n):
+            old = d[p].item()
+            for big in (3.25, 1.5):                                 # the second call into the same output is less extreme
+                d[p] = sign * big                                   # (both exact in Float32)
+                call("ibh_ew_reduce", op, n, B._ptr(d), B._ptr(out))
+                assert out.item() == sign * big, (op, n, p, big)
+            d[p] = old
+
+
+@pytest.mark.parametrize("n", [256 * 1024 + 1, 256 * 2048 + 3])
+def test_dot_reproducible(n):
+    """Two calls of ``ibh_dot`` on the same input give the same bits: workgroup sums in an array and one workgroup that adds
+    them in a fixed order (no arrival order)."""
+    x, y = keep(ps.seeded(n, 1)), keep(ps.seeded(n, 3))
+    o1, o2 = _dbl(), _dbl()
+    call("ibh_dot", n, B._ptr(x), B._ptr(y), B._ptr(o1))
+    call("ibh_dot", n, B._ptr(x), B._ptr(y), B._ptr(o2))
+    a, b = o1.cpu().numpy().view(np.uint64)[0], o2.cpu().numpy().view(np.uint64)[0]
+    assert a == b, (n, hex(a), hex(b))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -168,6 +168,29 @@ def test_sensitivity_reduction_skips_its_last_element():
         ps.check_sum(float(np.sum(x[:-1].astype(f64) ** 2)), x, what="skipped")
 
 
+def test_calibration_ew_sum():
+    """The Float32 model of the two-stage sum (the order of ibh_reduce_dev.h) stays at or below half of ``check_sum32``'s
+    bound at every total of the device test; the depth is the one read from the code."""
+    assert [ps.ew_sum_depth(n) for n in (1, 256, 257, 2048, 2049, 16384, 16385, 256 * 8 * 1024 + 1)] == [11, 11, 12, 18, 26, 29, 29, 33]
+    assert ps.ew_reduce_stages(16385) == [(16385, 9), (9, 1)] and ps.ew_reduce_stages(256 * 8 * 1024 + 1)[0][1] == 1024
+    worst = 0.0
+    for n in ps.EW_REDUCE_TOTALS:
+        for seed, lo in ((1, -1.0), (2, 0.0)):                      # mixed signs, and all positive (the sum grows)
+            x = ps.seeded(n, seed, lo, 1.0)
+            worst = max(worst, ps.check_sum32(ps.ew_sum_model32(x), x, f"model n={n}"))
+    print(f"Float32 model of the two-stage sum against fsum: {worst:.2f} of the bound")
+    assert worst <= 0.5
+
+
+def test_sensitivity_ew_sum_drops_one_element():
+    for n in (257, 2049, 16385):
+        x = ps.seeded(n, 3)
+        x[-1] = f32(0.75)
+        ps.check_sum32(ps.ew_sum_model32(x), x, "intact")
+        with pytest.raises(AssertionError, match="fsum"):
+            ps.check_sum32(ps.ew_sum_model32(x[:-1]), x, "dropped")
+
+
 def test_sensitivity_time_step_wrong_in_one_coarse_side_cell():
     """A probe of a cell with a face to a coarser cell whose value is evaluated as if the neighbour had its own spacing."""
     from conftest import ADV_FAMILIES, advection_mesh, oracle_view
