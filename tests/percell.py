@@ -25,6 +25,13 @@ f32, f64 = np.float32, np.float64
 # error on the coarsest level alone reads 3e-5 (tests/test_percell.py::test_sensitivity).
 BOUND = 2e-6
 BOUND_EULER = 2.5e-6
+# Bounds across flow regimes (tests/regimes.py), with the scales ``scalar_scale_c`` / ``euler_scale_waves``: 4 x the worst
+# Float32-oracle / C-restatement figure over every regime and case of tests/test_percell_regimes.py::test_calibration
+# (scalar 4.3e-7 at the tiny C on the smooth u, Euler 3.9e-7 at rest), rounded up to one digit and capped at BOUND /
+# BOUND_EULER.  4 x: the tuned device forms measure about 1 x the literal Float32 arithmetic under the present scales; the
+# factor leaves room for their reciprocal and regrouped HLL combine without admitting a wrong term.
+BOUND_SCALAR_REGIMES = 2e-6   # 4 x 4.3e-7 = 1.7e-6
+BOUND_EULER_REGIMES = 2e-6    # 4 x 3.9e-7 = 1.6e-6
 # Bounds per kernel family against the float64 references below, each with the scales of ``*_scale``: the Float32 oracle
 # stays at or below half of each on every case of tests/test_percell_closures.py::test_calibration, which prints the
 # measured maxima (2-D RAE2822 / advection partitions and the 3-D octree: operators 1.1e-7, viscous sum 6.1e-8, shear rate
@@ -98,6 +105,37 @@ def euler_scale(part, P, ref, fluid=None):
     m = _face_max(part, _face_max(part, F))
     h = np.asarray(part.spacing).min(axis=1).astype(f64)
     return np.abs(np.asarray(ref, dtype=f64)) + m / h[:, None]
+
+
+def euler_scale_waves(part, P, ref, fluid=None):
+    """(nc, nv) scale of the Euler residual that holds in every flow regime: |ref_v| + max over the two-deep face
+    neighbourhood of sum_d [|Q_v| (|u_d| + a) + pressure terms] / h, with Q = primitive2state(P), a = speed_of_sound(T)
+    and the pressure terms p in the momentum row of direction d and p |u_d| in the energy row -- the HLL flux with every
+    difference turned into a sum.  ``euler_scale``'s physical flux vanishes with the velocity; the dissipation term
+    SL SR (QR - QL) / (SL - SR) ~ a dQ does not."""
+    fluid = fluid or ocfd.Fluid()
+    P64 = np.asarray(P).astype(f64)
+    Q = np.abs(ocfd.primitive2state(fluid, P64))
+    a = ocfd.speed_of_sound(fluid, P64[:, 1]).astype(f64)
+    p = np.abs(P64[:, 0])
+    W = np.zeros_like(P64)
+    for d in range(1, part.ndims + 1):
+        ud = np.abs(P64[:, 1 + d])
+        W += Q * (ud + a)[:, None]
+        W[:, 1] += p * ud
+        W[:, 1 + d] += p
+    m = _face_max(part, _face_max(part, W))
+    h = np.asarray(part.spacing).min(axis=1).astype(f64)
+    return np.abs(np.asarray(ref, dtype=f64)) + m / h[:, None]
+
+
+def scalar_scale_c(part, u, C, ref):
+    """Scale of the advection residual that carries the advecting velocity: |ref| + (max over the cell and its face
+    neighbours of sum_d |C_d|) (max over the same cells of |u|) / h.  ``scalar_scale`` is this with sum_d |C_d| = 1."""
+    c = _face_max(part, np.abs(np.asarray(C).astype(f64)).sum(axis=1))
+    m = _face_max(part, np.abs(np.asarray(u).astype(f64)))
+    h = np.asarray(part.spacing).min(axis=1).astype(f64)
+    return np.abs(np.asarray(ref, dtype=f64)) + c * m / h
 
 
 def percell_error(got, ref, scale):

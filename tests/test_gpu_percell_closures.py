@@ -445,6 +445,51 @@ def _ulps(got, ref):
     return int(ulp_distance(g, r).max())
 
 
+def test_inviscid_fluxes_wave_speed_edges():
+    """Pointwise ``inviscid_fluxes`` where the clamps of SR = min(uR - aR, 0) and SL = max(uL + aL, 0) bind or nearly do:
+    both sides supersonic to the right (F = FL) and to the left (F = FR), uR - aR and uL + aL one Float32 step either side
+    of 0 (the flux is continuous there, so the device's own rounding of a may fall on either side), both sides at rest,
+    and the clear 0 / 0 (uL = -3 a, uR = +3 a: SL = SR = 0), NaN in every variable in the float64 oracle and on the
+    device alike.  Magnitude scale and bound of ``test_pointwise_edges``."""
+    fl, ofl = cfd.Fluid(), ocfd.Fluid()
+    TL, TR, pL, pR = f32(300.0), f32(280.0), f32(1.1e5), f32(0.9e5)
+    aL, aR = (f32(np.sqrt(f64(ofl.gamma) * f64(ofl.R) * f64(T))) for T in (TL, TR))
+    up, dn = (lambda v: np.nextafter(f32(v), f32(np.inf))), (lambda v: np.nextafter(f32(v), f32(-np.inf)))
+    # (uL, uR) along the flux direction; the other component is 20 / -15
+    rows = {"supersonic right": (2 * aL, 3 * aR), "supersonic left": (-3 * aL, -2 * aR),
+            "uR - aR = +1 step": (f32(50.0), up(aR)), "uR - aR = 0": (f32(50.0), aR), "uR - aR = -1 step": (f32(50.0), dn(aR)),
+            "uL + aL = +1 step": (up(-aL), f32(-50.0)), "uL + aL = 0": (-aL, f32(-50.0)),
+            "uL + aL = -1 step": (dn(-aL), f32(-50.0)), "at rest": (f32(0.0), f32(0.0)), "0/0": (-3 * aL, 3 * aR)}
+    names = list(rows)
+    for d in (1, 2):
+        PL = np.array([[pL, TL, 20.0, -15.0]] * len(rows), f32)
+        PR = np.array([[pR, TR, 20.0, -15.0]] * len(rows), f32)
+        PL[:, 1 + d] = [rows[k][0] for k in names]
+        PR[:, 1 + d] = [rows[k][1] for k in names]
+        PL[names.index("at rest"), 2:] = 0
+        PR[names.index("at rest"), 2:] = 0
+        got = _h(cfd.inviscid_fluxes(fl, ibamd.hip(PL), ibamd.hip(PR), d))
+        L, Rr = PL.astype(f64), PR.astype(f64)
+        with np.errstate(all="ignore"):
+            ref = ocfd.inviscid_fluxes(ofl, L, Rr, d)
+        nan = names.index("0/0")
+        assert np.isnan(ref[nan]).all() and np.isfinite(np.delete(ref, nan, axis=0)).all()
+        assert np.allclose(ref[0], ocfd.inviscid_fluxes(ofl, L[:1], L[:1], d)[0], rtol=1e-14, atol=0)        # F = FL
+        assert np.allclose(ref[1], ocfd.inviscid_fluxes(ofl, Rr[1:2], Rr[1:2], d)[0], rtol=1e-14, atol=0)    # F = FR
+        assert np.array_equal(np.isnan(got), np.isnan(ref)), (d, got, ref)
+        sc = np.abs(ref)
+        for X in (L, Rr):
+            sc = sc + np.abs(ocfd.inviscid_fluxes(ofl, X, X, d)) + \
+                ((ocfd.speed_of_sound(ofl, X[:, 1]) + np.abs(X[:, 1 + d]))[:, None] * np.abs(ocfd.primitive2state(ofl, X)))
+        fin = np.arange(len(rows)) != nan
+        # at rest the transverse momentum row has scale 0: the flux must be exactly 0 there (percell_error: 0, else inf)
+        err = pc.percell_error(got[fin], ref[fin], sc[fin])
+        worst = int(np.argmax(err.max(axis=1)))
+        e = float(err.max())
+        _record("pointwise inviscid_fluxes, wave-speed edges (per-element, magnitude scale)", e)
+        assert e <= pc.BOUND_EULER, (d, np.array(names)[fin][worst], e, got[fin][worst], ref[fin][worst])
+
+
 def test_pointwise_edges():
     """Per element against the float64 oracle: finite values within a few ulps, NaN exactly where Julia has NaN."""
     fl, ofl = cfd.Fluid(), ocfd.Fluid()
