@@ -745,6 +745,32 @@ def residual_euler_hll(part, P, fluid_R=283.0, fluid_gamma=1.4, out=None, flags=
     return R
 
 
+@_hipaware
+def residual_euler_sensor(part, P, nu=None, out=None, flags=0, fluid=None):
+    """Fused Euler residual with the sensor-scaled central + Rusanov flux (cfd.jl:516-554): JST(p) + cell_gradient +
+    MUSCL(high_order) + ``inviscid_fluxes(fluid, PL, PR, at_owners(nu), at_neighbors(nu), dim)`` + green_gauss.  ``nu``:
+    ``(nc,)`` Float32 device array, or None for the pressure sensor ``JST_sensor(part, P[:, 0])`` (one kernel per sweep
+    where ``residual_euler_hll`` has one; a given ``nu`` takes the face-list form)."""
+    part = _part(part)
+    P, nv, ldp = _field(P, part.nc)
+    if nv != part.nd + 2:
+        raise ValueError("P must be (nc, nd+2) = [p T u v (w)]")
+    if nu is not None:
+        if isinstance(nu, torch.Tensor) and nu.ndim != 1:
+            raise ValueError("nu must be (nc,)")
+        nu, _, _ = _field(nu, part.nc)
+    R = out if out is not None else torch.zeros((nv, part.nc), dtype=torch.float32, device=P.device).T
+    R, nvr, ldr = _field_inplace(R, part.nc, "out")
+    if nvr != nv:
+        raise ValueError(f"out must be (nc, {nv})")
+    fluid_R, fluid_gamma = (fluid.R, fluid.gamma) if fluid is not None else (283.0, 1.4)
+    fl = _lib.ibh_fluid(float(fluid_R), float(fluid_gamma), 0.0, 1.0, 0.0, 0)
+    _stream()
+    call("ibh_residual_euler_sensor", part.handle, _ptr(P), ldp, _ptr(nu) if nu is not None else c_vp(None), _ptr(R), ldr,
+         C.byref(fl), flags)
+    return R
+
+
 # ---------------------------------------------------------------------------
 # partition runtime and ghost-cell BC
 # ---------------------------------------------------------------------------

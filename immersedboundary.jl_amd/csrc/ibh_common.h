@@ -207,6 +207,10 @@ extern int ibh_ew_scalar_only;    // ibh_ew.hip
 extern int ibh_time_average_nt;   // ibh_stats.hip
 }
 
+// Flux scheme of an Euler sweep: HLL (cfd.jl:459-508) or the central flux with sensor-scaled Rusanov dissipation (:516-554).
+// A field of the host dispatch and a compile-time parameter of every flux function and of the kernels that call them.
+enum EulerScheme : int { EULER_HLL = 0, EULER_SENSOR = 1 };
+
 // thread-local state
 extern thread_local std::string ibh_err;
 extern thread_local hipStream_t ibh_stream;

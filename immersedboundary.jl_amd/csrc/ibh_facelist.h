@@ -185,13 +185,16 @@ __device__ __forceinline__ void passB_adv_cell(const PartView& p, const float* _
     ud[c] = r;
 }
 
-template <int ND>
+// EULER_SENSOR: nu per face from `nu` (nc values), or from the sensor column of the workspace when `nu` is null
+template <int ND, int SCH = EULER_HLL>
 __device__ __forceinline__ void passB_euler_cell(const PartView& p, const float* __restrict__ P, int64_t ldp,
                                                  const float* __restrict__ G, float* __restrict__ Rr, int64_t ldr,
-                                                 float Rgas, float gamma, int32_t c) {
+                                                 float Rgas, float gamma, int32_t c, const float* __restrict__ nu = nullptr) {
     constexpr int NV = ND + 2;
+    typedef typename flux_of<SCH>::type FT;
     const int64_t nc = p.nc;
     const float* Ds = G + (int64_t)(ND * NV) * nc;
+    const float* Nu = SCH == EULER_SENSOR && nu ? nu : Ds;
     float res[NV], Pc[NV];
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
@@ -199,21 +202,23 @@ __device__ __forceinline__ void passB_euler_cell(const PartView& p, const float*
         Pc[v] = P[c + v * ldp];
     }
     const float Dc = Ds[c];
+    float Nc = 0.0f;
+    if constexpr (SCH == EULER_SENSOR) Nc = Nu[c];
 #pragma unroll
     for (int d = 0; d < ND; ++d) {
         const DimData& dd = p.dim[d];
         const float* h = p.spacing + d * nc;
-        double fr[NV], fl[NV];
+        FT fr[NV], fl[NV];
         float dPc[NV];
 #pragma unroll
         for (int v = 0; v < NV; ++v) {
-            fr[v] = fl[v] = 0.0;
+            fr[v] = fl[v] = 0;
             dPc[v] = G[(int64_t)(d * NV + v) * nc + c];
         }
         const float hcf = h[c];
 #pragma unroll
         for (int side = 0; side < 2; ++side) {
-            double* acc = side ? fr : fl;
+            FT* acc = side ? fr : fl;
             const SideIter it = side_iter(p, d, side, c);
             if (it.direct) {
                 // one face: the cell's own values are in registers, only the cell across is gathered (weight 1.0f / 1)
@@ -225,11 +230,13 @@ __device__ __forceinline__ void passB_euler_cell(const PartView& p, const float*
                     dPx[v] = G[(int64_t)(d * NV + v) * nc + x];
                 }
                 const float Dx = Ds[x], hx = h[x];
-                double F[NV];
-                if (side) euler_face_flux<ND>(Pc, Px, dPc, dPx, Dc, Dx, hcf, hx, d, Rgas, gamma, F);
-                else euler_face_flux<ND>(Px, Pc, dPx, dPc, Dx, Dc, hx, hcf, d, Rgas, gamma, F);
+                float Nx = 0.0f;
+                if constexpr (SCH == EULER_SENSOR) Nx = Nu[x];
+                FT F[NV];
+                if (side) euler_face_flux<ND, SCH>(Pc, Px, dPc, dPx, Dc, Dx, hcf, hx, d, Rgas, gamma, F, Nc, Nx);
+                else euler_face_flux<ND, SCH>(Px, Pc, dPx, dPc, Dx, Dc, hx, hcf, d, Rgas, gamma, F, Nx, Nc);
 #pragma unroll
-                for (int v = 0; v < NV; ++v) acc[v] = F[v] * (double)1.0f;
+                for (int v = 0; v < NV; ++v) acc[v] = F[v] * (FT)1.0f;
                 continue;
             }
             const int32_t b = it.b, e = it.e;
@@ -245,18 +252,23 @@ __device__ __forceinline__ void passB_euler_cell(const PartView& p, const float*
                     dPo[v] = G[(int64_t)(d * NV + v) * nc + o];
                     dPn[v] = G[(int64_t)(d * NV + v) * nc + n];
                 }
-                double F[NV];
-                euler_face_flux<ND>(Po, Pn, dPo, dPn, Ds[o], Ds[n], h[o], h[n], d, Rgas, gamma, F);
+                float No = 0.0f, Nn = 0.0f;
+                if constexpr (SCH == EULER_SENSOR) {
+                    No = Nu[o];
+                    Nn = Nu[n];
+                }
+                FT F[NV];
+                euler_face_flux<ND, SCH>(Po, Pn, dPo, dPn, Ds[o], Ds[n], h[o], h[n], d, Rgas, gamma, F, No, Nn);
 #pragma unroll
                 for (int v = 0; v < NV; ++v) {
-                    double t = F[v] * (double)w;
+                    FT t = F[v] * (FT)w;
                     acc[v] = (k == b) ? t : acc[v] + t;
                 }
             }
         }
-        double hc = (double)hcf;
+        FT hc = (FT)hcf;
 #pragma unroll
-        for (int v = 0; v < NV; ++v) res[v] = (float)((double)res[v] - (fr[v] - fl[v]) / hc);
+        for (int v = 0; v < NV; ++v) res[v] = (float)((FT)res[v] - (fr[v] - fl[v]) / hc);
     }
 #pragma unroll
     for (int v = 0; v < NV; ++v) Rr[c + v * ldr] = res[v];

@@ -84,18 +84,62 @@ __device__ __forceinline__ void hll_flux(const float* PL, const float* PR, int d
         F[v] = (SL * (double)FL[v] - SR * (double)FR[v] + SR * SL * (double)(QR[v] - QL[v])) / (SL - SR);
 }
 
-// Full Euler face flux: MUSCL(high_order) on every primitive with the pressure sensor, then HLL.
+// primitive2state with the pressure parcel in the energy row (cfd.jl:521-525): Uc = [rho, E + p, rho u ..]
 template <int ND>
+__device__ __forceinline__ void state_pe(const float* P, float R, float gamma, float* Uc) {
+    float p = P[0];
+    float T = fmaxf(P[1], 10.0f);
+    float k = P[2] * P[2];
+#pragma unroll
+    for (int j = 1; j < ND; ++j) k = k + P[2 + j] * P[2 + j];
+    k = k / 2.0f;
+    float rho = p / (R * T);
+    float E = rho * (R / (gamma - 1.0f) * T + k);
+    Uc[0] = rho;
+    Uc[1] = E + p;
+#pragma unroll
+    for (int j = 0; j < ND; ++j) Uc[2 + j] = rho * P[2 + j];
+}
+
+// Central flux with Rusanov dissipation scaled by the sensors nuL, nuR (cfd.jl:516-554), operation by operation in the
+// reference's order.  Float32 throughout: this method has no `0.0` literal.
+template <int ND>
+__device__ __forceinline__ void sensor_flux(const float* PL, const float* PR, float nuL, float nuR, int dim0, float R,
+                                            float gamma, float* F) {
+    constexpr int NV = ND + 2;
+    float UL[NV], UR[NV], Pm[NV];
+    state_pe<ND>(PL, R, gamma, UL);
+    state_pe<ND>(PR, R, gamma, UR);
+#pragma unroll
+    for (int v = 0; v < NV; ++v) Pm[v] = (PL[v] + PR[v]) / 2.0f;
+    const float p = Pm[0], u = Pm[2 + dim0];
+    const float a = sqrtf(gamma * R * ibh_max(Pm[1], 10.0f));   // (ibh_max, as k_sensor_flux of ibh_cfd.hip)
+#pragma unroll
+    for (int v = 0; v < NV; ++v) F[v] = (UL[v] + UR[v]) * u / 2.0f;
+    F[2 + dim0] = F[2 + dim0] + p;
+    const float k = ibh_max(nuL, nuR) * (a + fabsf(u)) / 2.0f;   // (Julia's max: a NaN in a caller's nu stays a NaN)
+#pragma unroll
+    for (int v = 0; v < NV; ++v) F[v] = F[v] + (UL[v] - UR[v]) * k;
+}
+
+// flux, face accumulators and Green-Gauss update: Float64 for HLL (its flux is), Float32 for the sensor scheme
+template <int SCH> struct flux_of { typedef double type; };
+template <> struct flux_of<EULER_SENSOR> { typedef float type; };
+
+// Full Euler face flux: MUSCL(high_order) on every primitive with the pressure sensor, then HLL or (EULER_SENSOR) the
+// sensor-scaled flux with nu_o, nu_n = at_owners / at_neighbors of nu.
+template <int ND, int SCH = EULER_HLL>
 __device__ __forceinline__ void euler_face_flux(const float* Po, const float* Pn, const float* dPo, const float* dPn,
                                                 float Do, float Dn, float ho, float hn, int dim0, float R, float gamma,
-                                                double* F) {
+                                                typename flux_of<SCH>::type* F, float nuo = 0.0f, float nun = 0.0f) {
     constexpr int NV = ND + 2;
     float PL[NV], PR[NV];
     float Df = fmaxf(fmaxf(Do, Dn), 1e-7f);
     float dO = ho / 2.0f, dN = hn / 2.0f;
 #pragma unroll
     for (int v = 0; v < NV; ++v) muscl_ho(Po[v], Pn[v], dPo[v], dPn[v], Df, dO, dN, PL[v], PR[v]);
-    hll_flux<ND>(PL, PR, dim0, R, gamma, F);
+    if constexpr (SCH == EULER_SENSOR) sensor_flux<ND>(PL, PR, nuo, nun, dim0, R, gamma, F);
+    else hll_flux<ND>(PL, PR, dim0, R, gamma, F);
 }
 
 }  // namespace ibhf

@@ -33,10 +33,16 @@ static AdvPath advection_path(const ibh_part* p, int flags) {
 }
 
 // ---- Euler: path
-static EulerPath euler_path(const ibh_part* p, int flags) {
-    if (fused2(p, flags) && (p->fuse_all || ((flags & IBH_IMAGE_ONLY) && p->img_all_fz))) return EUL2_SINGLE;
-    if (image3(p, flags)) return EUL3_IMAGE_COLS;
-    if (single3(p, flags)) return EUL3_SINGLE;
+// The sensor scheme has the single-kernel forms and the face-list form: an external nu (one more field with halos), the
+// tuned two-kernel block bodies (EUL2_FAST, EUL3_BLOCKS) and IBH_NO_FUSE all take the face-list form there.
+static EulerPath euler_path(const ibh_part* p, int flags, const EulerArgs& e) {
+    const bool sensor = e.scheme == EULER_SENSOR;
+    if (!(sensor && e.nu)) {
+        if (fused2(p, flags) && (p->fuse_all || ((flags & IBH_IMAGE_ONLY) && p->img_all_fz))) return EUL2_SINGLE;
+        if (image3(p, flags)) return EUL3_IMAGE_COLS;
+        if (single3(p, flags)) return EUL3_SINGLE;
+    }
+    if (sensor) return p->nd == 2 ? EUL2_FACE_LIST : EUL3_FACE_LIST;
     // tuned block paths: not with IBH_EXACT (the literal arithmetic lives in the face-list body)
     if (p->nd == 2) return tuned2(p, flags) ? EUL2_FAST : EUL2_FACE_LIST;
     return tuned3(p, flags) ? EUL3_BLOCKS : EUL3_FACE_LIST;
@@ -98,17 +104,18 @@ int ibh_residual_advection_n(ibh_part* p, const float* u, const float* C, int64_
     return rc;
 }
 
-int ibh_residual_euler_hll(ibh_part* p, const float* P, int64_t ldp, float* R, int64_t ldr, const ibh_fluid* fluid,
-                           int flags) {
-    IBH_REQUIRE(p && P && R && fluid, "ibh_residual_euler_hll: null argument");
+// the Euler entries: one body, the scheme in `e`
+static int residual_euler(ibh_part* p, const EulerArgs& e, int flags, const char* phase_msg) {
     if (p->nc == 0) return 0;
     const Phase ph(flags);
-    const EulerArgs e{P, ldp, R, ldr, fluid};
-    const EulerPath path = euler_path(p, flags);
+    const EulerPath path = euler_path(p, flags, e);
     if (path == EUL2_SINGLE) IBH_REQUIRE(ph.valid(), IBH_PHASES_EXCLUSIVE);
     else  // the other forms run the whole sweep: they have no overlap phases
-        IBH_REQUIRE(!ph.any(), "ibh_residual_euler_hll: overlap phases need a partition whose (image) blocks are all "
-                               "eligible for the single-kernel sweep; run the sweep unphased after the exchange");
+        IBH_REQUIRE(!ph.any(), phase_msg);
+    // the stamped and the thread-per-cell 3-D forms are HLL only: a variant must not quietly time another kernel
+    IBH_REQUIRE(!(e.scheme == EULER_SENSOR && path == EUL3_SINGLE && T.quad_variant != 0),
+                "ibh_residual_euler_sensor: quad_variant 4 (wave time stamps) and 512 (thread per cell) are forms of the "
+                "HLL sweep only; set quad_variant 0");
     int rc = 0;
     switch (path) {
     case EUL2_SINGLE: euler2_single(p, e, flags, ph); break;
@@ -119,6 +126,24 @@ int ibh_residual_euler_hll(ibh_part* p, const float* P, int64_t ldp, float* R, i
     }
     if (!rc) IBH_LAUNCH_CHECK();
     return rc;
+}
+
+int ibh_residual_euler_hll(ibh_part* p, const float* P, int64_t ldp, float* R, int64_t ldr, const ibh_fluid* fluid,
+                           int flags) {
+    IBH_REQUIRE(p && P && R && fluid, "ibh_residual_euler_hll: null argument");
+    return residual_euler(p, EulerArgs{P, ldp, R, ldr, fluid}, flags,
+                          "ibh_residual_euler_hll: overlap phases need a partition whose (image) blocks are all "
+                          "eligible for the single-kernel sweep; run the sweep unphased after the exchange");
+}
+
+// The same closure with CFD.inviscid_fluxes(fluid, PL, PR, at_owners(nu), at_neighbors(nu), dim) (cfd.jl:516-554) for the
+// flux; nu = null: the pressure sensor D the sweep computes for MUSCL.  Same flags as ibh_residual_euler_hll.
+int ibh_residual_euler_sensor(ibh_part* p, const float* P, int64_t ldp, const float* nu, float* R, int64_t ldr,
+                              const ibh_fluid* fluid, int flags) {
+    IBH_REQUIRE(p && P && R && fluid, "ibh_residual_euler_sensor: null argument");
+    return residual_euler(p, EulerArgs{P, ldp, R, ldr, fluid, EULER_SENSOR, nu}, flags,
+                          "ibh_residual_euler_sensor: overlap phases need a partition whose (image) blocks are all "
+                          "eligible for the single-kernel sweep; run the sweep unphased after the exchange");
 }
 
 // One step, u_out = u + dt * residual: in one launch where the quad sweep covers the whole partition (it stores the update,

@@ -210,6 +210,7 @@ __global__ __launch_bounds__(64 * WPB) void k_step_quad(float* __restrict__ u, c
 #ifndef WPBE
 #define WPBE 4
 #endif
+template <int SCH = EULER_HLL>
 __global__ __launch_bounds__(64 * WPBE) void k_sweep_euler(const float* __restrict__ P, uint32_t ldp,
                                                            float* __restrict__ R, uint32_t ldr, float Rgas, float gamma,
                                                            const BlockDesc2* __restrict__ blocks,
@@ -222,7 +223,7 @@ __global__ __launch_bounds__(64 * WPBE) void k_sweep_euler(const float* __restri
     const int32_t first = __builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x, nwg) * (WPBE * iters) + wave);
     if (first >= nblk) return;
     const int32_t nb = __builtin_amdgcn_readfirstlane(min(iters, (nblk - first + WPBE - 1) / WPBE));
-    blk2::sweep_euler(blocks, htab, etab, dtab, blist, first, WPBE, nb, P, ldp, R, ldr, blk2::Gas{Rgas, gamma},
+    blk2::sweep_euler<SCH>(blocks, htab, etab, dtab, blist, first, WPBE, nb, P, ldp, R, ldr, blk2::Gas{Rgas, gamma},
                       lds + wave * BLK2_SWEEP_EULER_LDS, lane);
 }
 
@@ -237,6 +238,7 @@ __global__ __launch_bounds__(64 * WPBE) void k_sweep_euler(const float* __restri
 #ifndef QE_WAVES
 #define QE_WAVES 3
 #endif
+template <int SCH = EULER_HLL>
 __global__ __launch_bounds__(64 * WPBE) __attribute__((amdgpu_waves_per_eu(QE_WAVES, QE_WAVES))) void k_sweep_quad_euler(const float* __restrict__ P, uint32_t ldp,
                                                                 float* __restrict__ R, uint32_t ldr, float Rgas,
                                                                 float gamma, const QuadDesc2* __restrict__ qd,
@@ -253,12 +255,12 @@ __global__ __launch_bounds__(64 * WPBE) __attribute__((amdgpu_waves_per_eu(QE_WA
                                      : (int32_t)blockIdx.x;
     if (wg < nwgq) {
         const int32_t q = __builtin_amdgcn_readfirstlane(xcd_remap(wg, nwgq) * WPBE + wave);
-        if (q < nq) quad2::sweep_quad_euler(qd, qtab, q, P, ldp, R, ldr, blk2::Gas{Rgas, gamma}, lds + wave * QE_LDS, lane);
+        if (q < nq) quad2::sweep_quad_euler<SCH>(qd, qtab, q, P, ldp, R, ldr, blk2::Gas{Rgas, gamma}, lds + wave * QE_LDS, lane);
     } else {
         const int32_t first = __builtin_amdgcn_readfirstlane(xcd_remap(wg - nwgq, nwgs) * WPBE + wave);
 #ifndef IBH_QE_NO_SINGLES  // (instruction counts of the quad path alone: scripts/isa_count.py)
         if (first < ns)
-            blk2::sweep_euler(blocks, htab, etab, dtab, singles, first, WPBE, 1, P, ldp, R, ldr, blk2::Gas{Rgas, gamma},
+            blk2::sweep_euler<SCH>(blocks, htab, etab, dtab, singles, first, WPBE, 1, P, ldp, R, ldr, blk2::Gas{Rgas, gamma},
                               lds + wave * BLK2_SWEEP_EULER_LDS, lane);
 #endif
     }
@@ -365,11 +367,12 @@ void adv2_single(const ibh_part* p, const AdvArgs& a, int flags, Phase ph, int k
 // every block eligible, or only the image blocks wanted and all of them eligible: one launch per phase, no workspace
 void euler2_single(const ibh_part* p, const EulerArgs& e, int flags, Phase ph) {
     const int k = p->fuse_all ? 0 : 1;  // quad set; block list: all blocks / the image blocks
+    const bool sensor = e.scheme == EULER_SENSOR;
     if (quads_usable(p, k, flags)) {
         const QuadRange r = quad_range(p, k, ph);
         const int32_t nwgq = (r.q.count() + WPBE - 1) / WPBE, nwgs = (r.s.count() + WPBE - 1) / WPBE;
         if (nwgq + nwgs > 0)
-            hipLaunchKernelGGL(k_sweep_quad_euler, dim3(nwgq + nwgs), dim3(64 * WPBE), 0, ibh_stream, e.P, (uint32_t)e.ldp,
+            hipLaunchKernelGGL(sensor ? k_sweep_quad_euler<EULER_SENSOR> : k_sweep_quad_euler<EULER_HLL>, dim3(nwgq + nwgs), dim3(64 * WPBE), 0, ibh_stream, e.P, (uint32_t)e.ldp,
                                e.R, (uint32_t)e.ldr, e.fluid->R, e.fluid->gamma, p->qd[k] + r.q.first,
                                p->qtab[k] + (size_t)r.q.first * IBH_QROW, r.q.count(), nwgq, p->blocks2, p->htab, p->etab,
                                p->dtab, p->qsingles[k] + r.s.first, r.s.count(), nwgs, T.quad_singles_first);
@@ -378,8 +381,8 @@ void euler2_single(const ibh_part* p, const EulerArgs& e, int flags, Phase ph) {
     const Range b = p->fuse_all ? ph.of(p->nB1, p->nblk) : ph.of(p->n_img_int, p->n_img);
     if (b.count() <= 0) return;
     const BlockList L = block_list(p, p->fuse_all ? nullptr : p->img_list, b, WPBE, 4);
-    hipLaunchKernelGGL(k_sweep_euler, dim3(L.nwg), dim3(64 * WPBE), 0, ibh_stream, e.P, (uint32_t)e.ldp, e.R, (uint32_t)e.ldr,
-                       e.fluid->R, e.fluid->gamma, L.bl, L.ht, L.et, p->dtab, L.count, L.nwg, L.iters, L.ls);
+    hipLaunchKernelGGL(sensor ? k_sweep_euler<EULER_SENSOR> : k_sweep_euler<EULER_HLL>, dim3(L.nwg), dim3(64 * WPBE), 0,
+                       ibh_stream, e.P, (uint32_t)e.ldp, e.R, (uint32_t)e.ldr, e.fluid->R, e.fluid->gamma, L.bl, L.ht, L.et, p->dtab, L.count, L.nwg, L.iters, L.ls);
 }
 
 // sweep and update in one launch: the quad sweep stores u + dt * residual (its cells of u are in registers)

@@ -96,7 +96,7 @@ __global__ __launch_bounds__(64 * WPB3C) __attribute__((amdgpu_waves_per_eu(WAVE
 #endif
 // wave timeline of a launch (STAMP, ibh_debug_buffer), as in ibh_fused2d.hip: this code object's own pointer
 __device__ unsigned long long* ibh_dbg_buf = nullptr;
-template <int WAVES, bool STAMP = false, bool TAB = false>
+template <int WAVES, bool STAMP = false, bool TAB = false, int SCH = EULER_HLL>
 __global__ __launch_bounds__(64 * WPB3E) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void k_sweep3_euler_cols(
     const float* __restrict__ P, uint32_t ldp, float* __restrict__ R, uint32_t ldr, float Rgas, float gamma,
     const BlockDesc3* __restrict__ blocks, const int32_t* __restrict__ htab, const int32_t* __restrict__ ftab,
@@ -105,7 +105,7 @@ __global__ __launch_bounds__(64 * WPB3E) __attribute__((amdgpu_waves_per_eu(WAVE
     __shared__ __attribute__((aligned(16))) float lds[WPB3E * S3E_LDS];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int32_t blk = __builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x, nwg) * WPB3E + wave);
-    strip3e::sweep_euler_cols<STAMP>(blocks, htab, ftab, rtab, r4tab, blk, n, P, ldp, R, ldr, blk3::Gas3{Rgas, gamma},
+    strip3e::sweep_euler_cols<STAMP, SCH>(blocks, htab, ftab, rtab, r4tab, blk, n, P, ldp, R, ldr, blk3::Gas3{Rgas, gamma},
                                      lds + wave * S3E_LDS, lane, STAMP ? ibh_dbg_buf : nullptr, TAB ? dtab : nullptr);
 }
 
@@ -227,14 +227,20 @@ int adv3_blocks(ibh_part* p, const AdvArgs& a, int flags, Phase ph) {
 // image blocks of a partition with skirt fragments: one launch, nothing through the workspace
 void euler3_image_cols(const ibh_part* p, const EulerArgs& e) {
     const int32_t nwg = (p->n_img3 + WPB3E - 1) / WPB3E;
-    hipLaunchKernelGGL((k_sweep3_euler_cols<2, false, true>), dim3(nwg), dim3(64 * WPB3E), 0, ibh_stream, e.P,
-                       (uint32_t)e.ldp, e.R, (uint32_t)e.ldr, e.fluid->R, e.fluid->gamma, p->iblocks3, p->ihtab3, p->iftab3,
+    const auto k = e.scheme == EULER_SENSOR ? k_sweep3_euler_cols<2, false, true, EULER_SENSOR>
+                                            : k_sweep3_euler_cols<2, false, true>;
+    hipLaunchKernelGGL(k, dim3(nwg), dim3(64 * WPB3E), 0, ibh_stream, e.P, (uint32_t)e.ldp, e.R, (uint32_t)e.ldr, e.fluid->R,
+                       e.fluid->gamma, p->iblocks3, p->ihtab3, p->iftab3,
                        p->irtab3, p->ir4tab3, p->n_img3, nwg, p->idtab3);
 }
 // 3-D, every block qualifies for the single-kernel sweep: one launch, nothing through the workspace
 void euler3_single(const ibh_part* p, const EulerArgs& e) {
     const int32_t nwg = (p->nblk + WPB3E - 1) / WPB3E;
-    const auto k = T.quad_variant == QV_STAMPS ? k_sweep3_euler_cols<2, true, false> : k_sweep3_euler_cols<2, false, false>;
+    // (the sensor scheme has the column form alone: residual_euler() in ibh_fused.hip has refused every other value of
+    // quad_variant before this is reached, so the tests on quad_variant below see the HLL scheme only)
+    const auto k = e.scheme == EULER_SENSOR      ? k_sweep3_euler_cols<2, false, false, EULER_SENSOR>
+                   : T.quad_variant == QV_STAMPS ? k_sweep3_euler_cols<2, true, false>
+                                                 : k_sweep3_euler_cols<2, false, false>;
     if (T.quad_variant == QV_THREAD_PER_CELL)
         hipLaunchKernelGGL(k_sweep3_euler, dim3(p->nblk), dim3(512), 0, ibh_stream, e.P, (uint32_t)e.ldp, e.R, (uint32_t)e.ldr,
                            e.fluid->R, e.fluid->gamma, p->blocks3, p->htab3, p->ftab3, p->rtab3, p->r4tab3, p->nblk);

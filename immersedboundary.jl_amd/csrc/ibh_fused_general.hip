@@ -117,15 +117,16 @@ __global__ __launch_bounds__(64 * WPB) void k_passB_euler_blk(uint32_t nc, const
 
 // (127 VGPRs = four waves per SIMD.  Six and eight waves per SIMD by capping the registers -- what paid in the viscous sum --
 // were measured here: 216 and 293 against 171 us on 1.67 M cells; this pass is arithmetic in Float64, the spills cost more.)
-template <int ND>
+// EULER_SENSOR (Float32 flux and accumulators): nu from `nu`, or the sensor column of G when `nu` is null
+template <int ND, int SCH = EULER_HLL>
 __global__ __launch_bounds__(64 * WPB) void k_passB_euler(PartView p, const float* __restrict__ P, int64_t ldp,
                                                      const float* __restrict__ G, float* __restrict__ R, int64_t ldr,
                                                      float Rgas, float gamma, const int32_t* __restrict__ cells,
-                                                     int32_t ncells) {
+                                                     int32_t ncells, const float* __restrict__ nu) {
     int64_t t = IBH_WG_X() * blockDim.x + threadIdx.x;
     if (t >= ncells) return;
     int32_t c = cells ? cells[t] : (int32_t)t;
-    passB_euler_cell<ND>(p, P, ldp, G, R, ldr, Rgas, gamma, c);
+    passB_euler_cell<ND, SCH>(p, P, ldp, G, R, ldr, Rgas, gamma, c, nu);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -218,8 +219,11 @@ int adv_general(ibh_part* p, const AdvArgs& a, int flags, Phase ph, AdvPath path
 // the 3-D block path (ibh_fused3d.hip)
 void euler_passB_cells(const ibh_part* p, const EulerArgs& e, const int32_t* cells, int32_t n) {
     if (n <= 0) return;
-    hipLaunchKernelGGL(p->nd == 3 ? k_passB_euler<3> : k_passB_euler<2>, dim3((n + 64 * WPB - 1) / (64 * WPB)), dim3(64 * WPB), 0,
-                       ibh_stream, view(p), e.P, e.ldp, p->G, e.R, e.ldr, e.fluid->R, e.fluid->gamma, cells, n);
+    const bool d3 = p->nd == 3;
+    const auto k = e.scheme == EULER_SENSOR ? (d3 ? k_passB_euler<3, EULER_SENSOR> : k_passB_euler<2, EULER_SENSOR>)
+                                            : (d3 ? k_passB_euler<3> : k_passB_euler<2>);
+    hipLaunchKernelGGL(k, dim3((n + 64 * WPB - 1) / (64 * WPB)), dim3(64 * WPB), 0, ibh_stream, view(p), e.P, e.ldp, p->G, e.R,
+                       e.ldr, e.fluid->R, e.fluid->gamma, cells, n, e.nu);
 }
 
 // two-kernel form, 2-D (block kernels where `fast`) and 3-D face-list (whole sweeps only)

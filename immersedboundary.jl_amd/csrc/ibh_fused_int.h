@@ -76,7 +76,11 @@ struct Phase {
 #define IBH_PHASES_EXCLUSIVE "IBH_PHASE_INTERIOR and IBH_PHASE_BOUNDARY are exclusive"
 
 struct AdvArgs { const float *u, *C; int64_t ldc; float* ud; };
-struct EulerArgs { const float* P; int64_t ldp; float* R; int64_t ldr; const ibh_fluid* fluid; };  // (the entries' fields)
+// `nu`: the caller's sensor of the sensor scheme (nc values), or null = the pressure JST sensor the sweep computes anyway
+struct EulerArgs {  // (the entries' fields)
+    const float* P; int64_t ldp; float* R; int64_t ldr; const ibh_fluid* fluid;
+    EulerScheme scheme = EULER_HLL; const float* nu = nullptr;
+};
 
 // ---- advection: paths
 enum AdvPath {

@@ -69,6 +69,9 @@ __device__ __forceinline__ void euler_side_pm2(const v2f* P, bool dn, const blk2
 // pressure terms, regrouped by state (as strip3e::euler_flux): F = QL (wL unL - c) + QR (c - wR unR) + pressure terms,
 // wL = SL / (SL - SR), wR = SR / (SL - SR), c = SL wR -- two instructions per variable instead of five, and the physical
 // fluxes of the two sides are never held
+// EULER_SENSOR: the sensor-scaled central + Rusanov flux grouped by state (blk2::euler_flux_w), packed like the HLL form;
+// Df's floor of 1e-7 never binds on a JST sensor, which is >= 1e-7 itself (see there)
+template <int SCH = EULER_HLL>
 __device__ __forceinline__ void euler_flux_w2(const v2f* Pa, const v2f* Pb, const v2f* Sa, const v2f* Sb, v2f Da, v2f Db,
                                               float wa, bool dn, const blk2::Gas& gas, v2f* F) {
     v2f PL[4], PR[4];
@@ -85,6 +88,26 @@ __device__ __forceinline__ void euler_flux_w2(const v2f* Pa, const v2f* Pb, cons
         PL[v] = uf + Df * ((s - wa * d) - t16);
         // PR = uf + Df ((wb d - s) - t16) = PL + Df (d - 2 s)   (wa + wb = 1; round 4, as strip3e::euler_flux)
         PR[v] = PL[v] + Df * (d - 2.0f * s);
+    }
+    if constexpr (SCH == EULER_SENSOR) {
+        const v2f ten = v2f{10.0f, 10.0f};
+        const v2f TL = max2(PL[1], ten), TR = max2(PR[1], ten);
+        const v2f rL = PL[0] * rcp2(gas.R * TL), rR = PR[0] * rcp2(gas.R * TR);
+        const float cp = gas.R / (gas.gamma - 1.0f) + gas.R;
+        const v2f hL = cp * TL + 0.5f * (PL[2] * PL[2] + PL[3] * PL[3]);
+        const v2f hR = cp * TR + 0.5f * (PR[2] * PR[2] + PR[3] * PR[3]);
+        const v2f hu = 0.25f * ((dn ? PL[3] : PL[2]) + (dn ? PR[3] : PR[2]));   // um / 2
+        const v2f a = sqrt2((gas.gamma * gas.R) * max2(0.5f * (PL[1] + PR[1]), ten));
+        const v2f k = (0.5f * Df) * (a + 2.0f * v2f{fabsf(hu.x), fabsf(hu.y)});
+        const v2f AL = rL * (hu + k), AR = rR * (hu - k);
+        F[0] = AL + AR;
+        F[1] = AL * hL + AR * hR;
+        F[2] = AL * PL[2] + AR * PR[2];
+        F[3] = AL * PL[3] + AR * PR[3];
+        const v2f pm = 0.5f * (PL[0] + PR[0]), z = v2f{0.0f, 0.0f};
+        F[2] += dn ? z : pm;
+        F[3] += dn ? pm : z;
+        return;
     }
     // with Q = rho (1, e, u, v) the conserved states are never formed: F = AL (1, eL, uL, vL) + AR (1, eR, uR, vR), A = rho c
     v2f rL, eL, pL, uL, aL, rR, eR, pR, uR, aR;
@@ -108,6 +131,7 @@ __device__ __forceinline__ void euler_flux_w2(const v2f* Pa, const v2f* Pb, cons
     F[1] += mL * uL - mR * uR;
 }
 
+template <int SCH = EULER_HLL>
 __device__ __forceinline__ void sweep_quad_euler(const QuadDesc2* __restrict__ qd, const int32_t* __restrict__ qtab,
                                                  int32_t q, const float* __restrict__ P, uint32_t ldp,
                                                  float* __restrict__ Rr, uint32_t ldr, blk2::Gas gas, float* lds,
@@ -296,7 +320,7 @@ __device__ __forceinline__ void sweep_quad_euler(const QuadDesc2* __restrict__ q
             Sb[v] = high ? Sh[v] : so;
         }
         const v2f dov = v2f{Do, Do};
-        euler_flux_w2(Pa, Pb, Sa, Sb, high ? dov : Dh, high ? Dh : dov, wa, dny, gas, F);
+        euler_flux_w2<SCH>(Pa, Pb, Sa, Sb, high ? dov : Dh, high ? Dh : dov, wa, dny, gas, F);
 #pragma unroll
         for (int v = 0; v < QE_NV; ++v) edge[v] = 0.5f * (F[v].x + F[v].y);
     }
@@ -324,7 +348,7 @@ __device__ __forceinline__ void sweep_quad_euler(const QuadDesc2* __restrict__ q
             Pb[v] = U[v].yz;
             Sb[v] = SX[v].yz;
         }
-        euler_flux_w2(Pa, Pb, Sa, Sb, D.xy, D.yz, 0.5f, false, gas, F);
+        euler_flux_w2<SCH>(Pa, Pb, Sa, Sb, D.xy, D.yz, 0.5f, false, gas, F);
 #pragma unroll
         for (int v = 0; v < QE_NV; ++v) {
             FR[v].xy = F[v];
@@ -333,7 +357,7 @@ __device__ __forceinline__ void sweep_quad_euler(const QuadDesc2* __restrict__ q
             Pb[v] = v2f{U[v].w, nP[v]};
             Sb[v] = v2f{SX[v].w, nS[v]};
         }
-        euler_flux_w2(Pa, Pb, Sa, Sb, D.zw, v2f{D.w, nD}, 0.5f, false, gas, F);
+        euler_flux_w2<SCH>(Pa, Pb, Sa, Sb, D.zw, v2f{D.w, nD}, 0.5f, false, gas, F);
 #pragma unroll
         for (int v = 0; v < QE_NV; ++v) {
             FR[v].zw = F[v];
@@ -362,7 +386,7 @@ __device__ __forceinline__ void sweep_quad_euler(const QuadDesc2* __restrict__ q
                 }
                 Dbt[k] = dpp_shl1(D[c], D[c]);
             }
-            euler_flux_w2(Pa, Pb, Sa, Sb, h ? D.zw : D.xy, Dbt, 0.5f, true, gas, F);
+            euler_flux_w2<SCH>(Pa, Pb, Sa, Sb, h ? D.zw : D.xy, Dbt, 0.5f, true, gas, F);
 #pragma unroll
             for (int v = 0; v < QE_NV; ++v) {
                 if (h) FT[v].zw = F[v];

@@ -181,7 +181,9 @@ __device__ __forceinline__ void euler_side_pm(const T* P, const Gas3& gas, T& rh
 
 // MUSCL states from undivided slopes, then HLL (blk3::euler_flux_w3); a = owner (towards -), b = neighbour,
 // wa = h_a / (h_a + h_b)
-template <class T, int DN>
+// EULER_SENSOR: the sensor-scaled central + Rusanov flux grouped by state (blk2::euler_flux_w) with five primitives;
+// Df's floor of 1e-7 never binds on a JST sensor, which is >= 1e-7 itself (see there)
+template <class T, int DN, int SCH = EULER_HLL>
 __device__ __forceinline__ void euler_flux(const T* Pa, const T* Pb, const T* Sa, const T* Sb, T Da, T Db, T wa,
                                            const Gas3& gas, T* F) {
 #ifdef S3E_ABLATE_FLUX  // (timing diagnostic, wrong results: the flux arithmetic removed, everything else in place)
@@ -203,6 +205,24 @@ __device__ __forceinline__ void euler_flux(const T* Pa, const T* Pb, const T* Sa
         PL[v] = uf + Df * ((s - wa * d) - t16);
         // PR = uf + Df ((wb d - s) - t16) = PL + Df (d - 2 s)   (wa + wb = 1)
         PR[v] = PL[v] + Df * (d - 2.0f * s);
+    }
+    if constexpr (SCH == EULER_SENSOR) {
+        const T ten = bc<T>(10.0f);
+        const T TL = maxT(PL[1], ten), TR = maxT(PR[1], ten);
+        const T rL = PL[0] * rcpT(gas.R * TL), rR = PR[0] * rcpT(gas.R * TR);
+        const float cp = gas.R / (gas.gamma - 1.0f) + gas.R;
+        const T hL = cp * TL + 0.5f * (PL[2] * PL[2] + PL[3] * PL[3] + PL[4] * PL[4]);
+        const T hR = cp * TR + 0.5f * (PR[2] * PR[2] + PR[3] * PR[3] + PR[4] * PR[4]);
+        const T hu = 0.25f * (PL[2 + DN] + PR[2 + DN]);   // um / 2
+        const T a = sqrtT((gas.gamma * gas.R) * maxT(0.5f * (PL[1] + PR[1]), ten));
+        const T k = (0.5f * Df) * (a + 2.0f * maxT(hu, -hu));
+        const T AL = rL * (hu + k), AR = rR * (hu - k);
+        F[0] = AL + AR;
+        F[1] = AL * hL + AR * hR;
+#pragma unroll
+        for (int v = 2; v < 5; ++v) F[v] = AL * PL[v] + AR * PR[v];
+        F[2 + DN] += 0.5f * (PL[0] + PR[0]);
+        return;
     }
     // HLL: F = (SL FL - SR FR + SL SR (QR - QL)) / (SL - SR) with FL = QL unL + pressure terms regrouped by state:
     // F = QL (wL unL - c) + QR (c - wR unR) + pressure terms, wL = SL / (SL - SR), wR = SR / (SL - SR), c = SL wR; with
@@ -352,7 +372,7 @@ __device__ __forceinline__ void sensor_pass(const BlockDesc3& bb, const int32_t*
 
 // ---- halo cells of slot `lane` of side S: slopes of the five primitives along the side normal (towards +) and
 // pressure sensor; on a FINE side instead the mean flux through the four sub-faces (Ff)
-template <int S>
+template <int S, int SCH = EULER_HLL>
 __device__ __forceinline__ void side_eval(const BlockDesc3& bb, const LaneGeo& LG, const int32_t* __restrict__ ftab,
                                           const int32_t* __restrict__ r4tab, const float* __restrict__ P, uint32_t ldp,
                                           float* lds, int lane, const Slot& sl, const float* hu, const float* hde,
@@ -456,8 +476,8 @@ __device__ __forceinline__ void side_eval(const BlockDesc3& bb, const LaneGeo& L
                 const float x = (1.0f - qs) * (Pb[v] - hk[v]) - 0.5f * (hdk[v] - hk[v]);
                 shk[v] = low ? x : -x;
             }
-            if (low) euler_flux<float, d>(hk, Pb, shk, Sb, dhk, Db, 1.0f - qs, gas, X);
-            else euler_flux<float, d>(Pb, hk, Sb, shk, Db, dhk, qs, gas, X);
+            if (low) euler_flux<float, d, SCH>(hk, Pb, shk, Sb, dhk, Db, 1.0f - qs, gas, X);
+            else euler_flux<float, d, SCH>(Pb, hk, Sb, shk, Db, dhk, qs, gas, X);
 #pragma unroll
             for (int v = 0; v < 5; ++v) acc[v] += X[v];
         }
@@ -536,7 +556,7 @@ constexpr int rstride() {
 // a later pass is held in registers while the flux loop runs (168 VGPRs = three waves per SIMD).  Order: face 4 (needs no
 // halo value: covers the halo loads), the two sides, then the packed faces.  The mean flux through a FINE side goes
 // straight into the residual of its boundary cell in LDS (the packed evaluation of that face is zeroed).
-template <int D, int MODE, class Hook>
+template <int D, int MODE, int SCH, class Hook>
 __device__ __forceinline__ void flux_pass(const BlockDesc3& bb, const int32_t* __restrict__ ftab,
                                           const int32_t* __restrict__ r4tab, const float* __restrict__ P, uint32_t ldp,
                                           float* lds, int lane, const Gas3& gas, Col* Pc, Col& Dc, const Slot& sl0,
@@ -586,7 +606,7 @@ __device__ __forceinline__ void flux_pass(const BlockDesc3& bb, const int32_t* _
             Sa[v] = 0.5f * d4 + 0.5f * (p.e[4].x - p.e[3].x);
             Sbb[v] = 0.5f * (p.e[1].y - p.e[0].y) + 0.5f * d4;
         }
-        euler_flux<float, D>(Pa, Pbb, Sa, Sbb, Dc.e[4].x, Dc.e[0].y, 0.5f, gas, F4);
+        euler_flux<float, D, SCH>(Pa, Pbb, Sa, Sbb, Dc.e[4].x, Dc.e[0].y, 0.5f, gas, F4);
 #ifndef S3E_ABLATE_R
 #pragma unroll
         for (int v = 0; v < 5; ++v) {
@@ -645,7 +665,7 @@ __device__ __forceinline__ void flux_pass(const BlockDesc3& bb, const int32_t* _
             Pb[v] = p.e[1].x;
             Sb[v] = 0.5f * (p.e[2].x - p.e[1].x) + qlo * (p.e[1].x - hm0[v]);
         }
-        side_eval<S0>(bb, LG, ftab, r4tab, P, ldp, lds, lane, sl0, h0.hu, h0.hd, rid0, h0.rv, Pb, Sb, Dc.e[1].x, gas, Sh0,
+        side_eval<S0, SCH>(bb, LG, ftab, r4tab, P, ldp, lds, lane, sl0, h0.hu, h0.hd, rid0, h0.rv, Pb, Sb, Dc.e[1].x, gas, Sh0,
                       Dh0, Ff);
         if (isF0) {  // cell 0: R -= (F1 - Ff) / h  (the packed value of face 0 is taken out again in the flux loop)
 #pragma unroll
@@ -662,7 +682,7 @@ __device__ __forceinline__ void flux_pass(const BlockDesc3& bb, const int32_t* _
             Pb[v] = p.e[3].y;
             Sb[v] = qhi * (hm1[v] - p.e[3].y) + 0.5f * (p.e[3].y - p.e[2].y);
         }
-        side_eval<S1>(bb, LG, ftab, r4tab, P, ldp, lds, lane, sl1, h1.hu, h1.hd, rid1, h1.rv, Pb, Sb, Dc.e[3].y, gas, Sh1,
+        side_eval<S1, SCH>(bb, LG, ftab, r4tab, P, ldp, lds, lane, sl1, h1.hu, h1.hd, rid1, h1.rv, Pb, Sb, Dc.e[3].y, gas, Sh1,
                       Dh1, Ff);
         if (isF1) {  // cell 7: R -= (Ff - F7) / h
 #pragma unroll
@@ -720,7 +740,7 @@ __device__ __forceinline__ void flux_pass(const BlockDesc3& bb, const int32_t* _
             Pbb[v] = Pc[v].e[j + 1];
         }
         const v2f wa = j == 0 ? v2f{1.0f - qlo, 0.5f} : j == 3 ? v2f{0.5f, qhi} : v2f{0.5f, 0.5f};
-        euler_flux<v2f, D>(Pa, Pbb, Sc, Sn, Dc.e[j], Dc.e[j + 1], wa, gas, F);
+        euler_flux<v2f, D, SCH>(Pa, Pbb, Sc, Sn, Dc.e[j], Dc.e[j + 1], wa, gas, F);
 #pragma unroll
         for (int v = 0; v < 5; ++v) {
             if (j == 0 && isF0) lds_add(Rl + v * 576, -(F[v].x * rh));                        // wave-uniform, rare
@@ -750,7 +770,7 @@ __device__ __forceinline__ void load_zcol(const float* __restrict__ p, Col& c) {
 // One block.
 // STAMP: phase time stamps of the wave (100 MHz ticks) for scripts/wave_timeline_3d.py: 0 start, 1 first loads landed,
 // 2 sensor done, 3 x fluxes, 4 transposed, 5 y fluxes, 6 transposed, 7 end
-template <bool STAMP>
+template <bool STAMP, int SCH>
 __device__ __forceinline__ void sweep_block(const BlockDesc3* __restrict__ blocks, const int32_t* __restrict__ htab,
                                             const int32_t* __restrict__ ftab, const int32_t* __restrict__ rtab,
                                             const int32_t* __restrict__ r4tab, int32_t blk, const float* __restrict__ P,
@@ -852,7 +872,7 @@ __device__ __forceinline__ void sweep_block(const BlockDesc3* __restrict__ block
     HaloRegs g0, g1;  // the halo registers of the next pass: requested before the flux loop of the pass in hand
     Slot tl0, tl1;
     int32_t tid0, tid1;
-    flux_pass<0, 0>(bx, ftab, r4tab, P, ldp, lds, lane, gas, Pc, Dc, sl0, sl1, rid0, rid1, h0, h1, Rr, ldr, [&]() {
+    flux_pass<0, 0, SCH>(bx, ftab, r4tab, P, ldp, lds, lane, gas, Pc, Dc, sl0, sl1, rid0, rid1, h0, h1, Rr, ldr, [&]() {
         tid0 = ridk[2];
         tid1 = ridk[3];
         tl0 = slot_of<2>(bx, htab, blk, lane, dtab);
@@ -868,7 +888,7 @@ __device__ __forceinline__ void sweep_block(const BlockDesc3* __restrict__ block
     for (int v = 0; v < 5; ++v) transpose<0, 1>(buf, ta, tb, Pc[v]);
     transpose<0, 1>(buf, ta, tb, Dc);
     stamp(4);
-    flux_pass<1, 1>(by, ftab, r4tab, P, ldp, lds, lane, gas, Pc, Dc, tl0, tl1, tid0, tid1, g0, g1, Rr, ldr, [&]() {
+    flux_pass<1, 1, SCH>(by, ftab, r4tab, P, ldp, lds, lane, gas, Pc, Dc, tl0, tl1, tid0, tid1, g0, g1, Rr, ldr, [&]() {
         rid0 = ridk[4];
         rid1 = ridk[5];
         sl0 = slot_of<4>(by, htab, blk, lane, dtab);
@@ -884,12 +904,12 @@ __device__ __forceinline__ void sweep_block(const BlockDesc3* __restrict__ block
     for (int v = 0; v < 5; ++v) transpose<1, 2>(buf, ta, tb, Pc[v]);
     transpose<1, 2>(buf, ta, tb, Dc);
     stamp(6);
-    flux_pass<2, 2>(bz, ftab, r4tab, P, ldp, lds, lane, gas, Pc, Dc, sl0, sl1, rid0, rid1, h0, h1, Rr, ldr, []() {});
+    flux_pass<2, 2, SCH>(bz, ftab, r4tab, P, ldp, lds, lane, gas, Pc, Dc, sl0, sl1, rid0, rid1, h0, h1, Rr, ldr, []() {});
     stamp(7);
 }
 
 // Block `blk` of `n` by one wave (a wave past the end of the list does nothing)
-template <bool STAMP = false>
+template <bool STAMP = false, int SCH = EULER_HLL>
 __device__ __forceinline__ void sweep_euler_cols(const BlockDesc3* __restrict__ blocks, const int32_t* __restrict__ htab,
                                                  const int32_t* __restrict__ ftab, const int32_t* __restrict__ rtab,
                                                  const int32_t* __restrict__ r4tab, int32_t blk, int32_t n,
@@ -898,7 +918,7 @@ __device__ __forceinline__ void sweep_euler_cols(const BlockDesc3* __restrict__ 
                                                  unsigned long long* stamps = nullptr,
                                                  const int32_t* __restrict__ dtab = nullptr) {
     if (blk >= n) return;
-    sweep_block<STAMP>(blocks, htab, ftab, rtab, r4tab, blk, P, ldp, Rr, ldr, gas, lds, lane,
+    sweep_block<STAMP, SCH>(blocks, htab, ftab, rtab, r4tab, blk, P, ldp, Rr, ldr, gas, lds, lane,
                        STAMP && stamps ? stamps + (size_t)blk * 8 : nullptr, dtab);
 }
 

@@ -330,7 +330,12 @@ __device__ __forceinline__ void euler_side_pm(const float* P, int dn, const Gas&
     a = __builtin_amdgcn_sqrtf((gas.gamma * gas.R) * T);
 }
 
-// MUSCL states from undivided slopes (see flux_w), then the HLL flux of blk2::euler_flux
+// MUSCL states from undivided slopes (see flux_w), then the HLL flux of blk2::euler_flux, or (EULER_SENSOR) the central flux
+// with Rusanov dissipation scaled by nu = the pressure sensor: max(nu_a, nu_b) is the Df of MUSCL.  Df carries MUSCL's floor,
+// max(D_a, D_b, 1e-7), which the reference's max(nuL, nuR) does not have; it never binds here, because JST_sensor starts its
+// maximum from 1e-7 (ImmersedBoundary.jl:1082) and so Da, Db >= 1e-7: Df == max(nu_a, nu_b) exactly.  A nu that can go below
+// 1e-7 (nu = 0, the pure central flux) is a caller's nu, and that takes the face-list form (ibhf::sensor_flux: no floor).
+template <int SCH = EULER_HLL>
 __device__ __forceinline__ void euler_flux_w(const float* Pa, const float* Pb, const float* Sa, const float* Sb, float Da,
                                              float Db, float wa, int dn, const Gas& gas, float* F) {
     float PL[4], PR[4];
@@ -346,6 +351,29 @@ __device__ __forceinline__ void euler_flux_w(const float* Pa, const float* Pb, c
         const float uf = (Pa[v] + wa * d) + t16;
         PL[v] = uf + Df * ((s - wa * d) - t16);   // (Pa + s) - uf
         PR[v] = PL[v] + Df * (d - 2.0f * s);      // uf + Df ((wb d - s) - t16) = PL + Df (d - 2 s)
+    }
+    if constexpr (SCH == EULER_SENSOR) {
+        // cfd.jl:516-554 grouped by state, operation for operation what quad2::euler_flux_w2 does on pairs: with
+        // Uc = rho (1, h, u, v), h = e + R max(T, 10) (the raw p over rho), F = (UcL + UcR) um / 2 + (UcL - UcR) k
+        // = AL (1, hL, uL, vL) + AR (1, hR, uR, vR) + pm in the momentum row, k = Df (a + |um|) / 2, AL = rhoL (um / 2 + k),
+        // AR = rhoR (um / 2 - k): one square root and two reciprocals per face
+        const float TL = fmaxf(PL[1], 10.0f), TR = fmaxf(PR[1], 10.0f);
+        const float rL = PL[0] * __builtin_amdgcn_rcpf(gas.R * TL), rR = PR[0] * __builtin_amdgcn_rcpf(gas.R * TR);
+        const float cp = gas.R / (gas.gamma - 1.0f) + gas.R;
+        const float hL = cp * TL + 0.5f * (PL[2] * PL[2] + PL[3] * PL[3]);
+        const float hR = cp * TR + 0.5f * (PR[2] * PR[2] + PR[3] * PR[3]);
+        const float hu = 0.25f * ((dn ? PL[3] : PL[2]) + (dn ? PR[3] : PR[2]));   // um / 2
+        const float a = __builtin_amdgcn_sqrtf((gas.gamma * gas.R) * fmaxf(0.5f * (PL[1] + PR[1]), 10.0f));
+        const float k = (0.5f * Df) * (a + 2.0f * fabsf(hu));
+        const float AL = rL * (hu + k), AR = rR * (hu - k);
+        F[0] = AL + AR;
+        F[1] = AL * hL + AR * hR;
+        F[2] = AL * PL[2] + AR * PR[2];
+        F[3] = AL * PL[3] + AR * PR[3];
+        const float pm = 0.5f * (PL[0] + PR[0]);
+        F[2] += dn ? 0.0f : pm;
+        F[3] += dn ? pm : 0.0f;
+        return;
     }
     // HLL regrouped by state, operation for operation what quad2::euler_flux_w2 does on pairs (ibh_quad2d_euler.h): a block
     // gives the same bits whether a quad wave or a single-block wave sweeps it.  Q = rho (1, e, u, v) is never formed:
@@ -398,6 +426,7 @@ __device__ __forceinline__ SweepPreE sweep_prefetch_e(const BlockDesc2* __restri
     return T;
 }
 
+template <int SCH = EULER_HLL>
 __device__ __forceinline__ void sweep_euler(const BlockDesc2* __restrict__ blocks, const int32_t* __restrict__ htab,
                                             const int32_t* __restrict__ etab, const int32_t* __restrict__ dtab,
                                             const int32_t* __restrict__ blist, int32_t blk0, int32_t stride, int32_t nb,
@@ -531,13 +560,13 @@ __device__ __forceinline__ void sweep_euler(const BlockDesc2* __restrict__ block
                 Pb[v] = fP[v * 128 + n1];
                 Sb[v] = fSX[v * 128 + n1];
             }
-            euler_flux_w(T.Pc, Pb, Sx, Sb, Dc, fD[n1], q1, 0, gas, FR);
+            euler_flux_w<SCH>(T.Pc, Pb, Sx, Sb, Dc, fD[n1], q1, 0, gas, FR);
 #pragma unroll
             for (int v = 0; v < 4; ++v) {
                 Pb[v] = fP[v * 128 + n3];
                 Sb[v] = fSY[v * 128 + n3];
             }
-            euler_flux_w(T.Pc, Pb, Sy, Sb, Dc, fD[n3], q3, 1, gas, FT);
+            euler_flux_w<SCH>(T.Pc, Pb, Sy, Sb, Dc, fD[n3], q3, 1, gas, FT);
         }
         {   // low sides: the halo cell is the owner, this block's cell the neighbour
             float Pa[4], Pb[4], Sa[4], Sb[4], X[4];
@@ -548,7 +577,7 @@ __device__ __forceinline__ void sweep_euler(const BlockDesc2* __restrict__ block
                 Sa[v] = xS[v * 128 + xslot];
                 Sb[v] = xS[v * 128 + xpos];
             }
-            euler_flux_w(Pa, Pb, Sa, Sb, fD[xslot], fD[xpos], 1.0f - (xd ? bb.q[2] : bb.q[0]), xd, gas, X);
+            euler_flux_w<SCH>(Pa, Pb, Sa, Sb, fD[xslot], fD[xpos], 1.0f - (xd ? bb.q[2] : bb.q[0]), xd, gas, X);
 #pragma unroll
             for (int v = 0; v < 4; ++v) ex[v * 64 + lane] = X[v];
         }
@@ -564,7 +593,7 @@ __device__ __forceinline__ void sweep_euler(const BlockDesc2* __restrict__ block
                 Pb[v] = fP[v * 128 + n1 + 1];
                 Sb[v] = fSX[v * 128 + n1 + 1];
             }
-            euler_flux_w(T.Pc, Pb, Sx, Sb, Dc, fD[n1 + 1], bb.q[1], 0, gas, FR1);
+            euler_flux_w<SCH>(T.Pc, Pb, Sx, Sb, Dc, fD[n1 + 1], bb.q[1], 0, gas, FR1);
         }
         if (bb.type[3] == SIDE_FINE) {
             float Pb[4], Sb[4];
@@ -573,7 +602,7 @@ __device__ __forceinline__ void sweep_euler(const BlockDesc2* __restrict__ block
                 Pb[v] = fP[v * 128 + n3 + 1];
                 Sb[v] = fSY[v * 128 + n3 + 1];
             }
-            euler_flux_w(T.Pc, Pb, Sy, Sb, Dc, fD[n3 + 1], bb.q[3], 1, gas, FT1);
+            euler_flux_w<SCH>(T.Pc, Pb, Sy, Sb, Dc, fD[n3 + 1], bb.q[3], 1, gas, FT1);
         }
         float FLs[4], FBs[4];
 #pragma unroll

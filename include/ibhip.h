@@ -272,6 +272,15 @@ int ibh_copy_rows(const int32_t* dst_rows, const int32_t* src_rows, int32_t n,
  *     D = JST_sensor(part,P[:,1]); per dim: gP = cell_gradient(P,dim);
  *     PL,PR = MUSCL(P,gP,dim; D, high_order=true); F = inviscid_fluxes(fluid,PL,PR,dim)
  *     (cfd.jl:459-508); R -= green_gauss(F,dim), R starting from 0;  P = [p T u v (w)].
+ * ibh_residual_euler_sensor: the same closure with the second inviscid_fluxes method, the central flux with Rusanov
+ *     dissipation scaled by sensors (cfd.jl:516-554), all Float32:
+ *     F = inviscid_fluxes(fluid,PL,PR, at_owners(part,nu,dim), at_neighbors(part,nu,dim), dim)
+ *     with `nu` nc values, or NULL for nu = D (the pressure sensor MUSCL uses).  One kernel per sweep where the HLL entry
+ *     has one and nu is NULL (quad_variant must be 0 in 3-D); the literal face-list form through the gradient workspace
+ *     wherever nu is given, with IBH_NO_FUSE / IBH_EXACT / IBH_FORCE_GENERAL, and on partitions whose blocks do not all
+ *     qualify for a single-kernel sweep.  Same flags and phase rules as ibh_residual_euler_hll.
+ *     D >= 1e-7 (JST_sensor starts its maximum there), so max(nuL,nuR) with nu = NULL is MUSCL's max(D_o,D_n,1e-7) exactly;
+ *     a given nu has no floor (nu = 0 is the pure central flux) and a NaN in it stays a NaN, as through Julia's max.
  * flags: bit0 = force the general face-list kernels (no block fast path);
  *        bit1 = image cells only (skirt rows of the output are left untouched);
  *        bit2 / bit3 = run only pass A / only pass B of the two-kernel sweep.
@@ -292,6 +301,8 @@ int ibh_residual_advection(ibh_part*, const float* u, const float* C, int64_t ld
 int ibh_residual_advection_n(ibh_part*, const float* u, const float* C, int64_t ldc, float* ud, int flags, int n);
 int ibh_residual_euler_hll(ibh_part*, const float* P, int64_t ldp, float* R, int64_t ldr,
                            const ibh_fluid* fluid, int flags);
+int ibh_residual_euler_sensor(ibh_part*, const float* P, int64_t ldp, const float* nu /* nc values or NULL */,
+                              float* R, int64_t ldr, const ibh_fluid* fluid, int flags);
 
 /* ---- CFD pointwise physics that residual closures call (cfd.jl), rows of P are [p T u v (w)],
  * rows of Q are [rho E rho*u rho*v (rho*w)]; all arrays (n, nd+2) column-major, `dim` 1-based. ---- */

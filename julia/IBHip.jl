@@ -748,6 +748,18 @@ function residual_euler_hll!(R::HipArray, part::HipPartition, P::HipArray, fluid
     R
 end
 
+"The same closure with `CFD.inviscid_fluxes(fluid, PL, PR, at_owners(part, ν, dim), at_neighbors(part, ν, dim), dim)`
+(cfd.jl:516): central flux + Rusanov dissipation scaled by the sensor `ν` (`nc` values), or by the pressure JST sensor when
+`ν === nothing`."
+function residual_euler_sensor!(R::HipArray, part::HipPartition, P::HipArray, fluid;
+        ν::Union{HipArray, Nothing} = nothing, flags::Integer = 0)
+    f = Ref(IbhFluid(fluid))
+    check(ccall((:ibh_residual_euler_sensor, lib), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{IbhFluid}, Cint),
+        part.handle, P.ptr, ld(P), isnothing(ν) ? C_NULL : ν.ptr, R.ptr, ld(R), f, flags))
+    R
+end
+
 # ---------------------------------------------------------------------------------------------------
 # an explicit solver step, device resident: the body of `march!` (test/advection.jl:61-89)
 # ---------------------------------------------------------------------------------------------------
