@@ -124,6 +124,8 @@ def inviscid_fluxes(fluid, PL, PR, *args):
     ``inviscid_fluxes(fluid, PL, PR, nuL, nuR, dim)`` (sensor/Rusanov, cfd.jl:516-554)."""
     PL, _, ld = B._field(PL)
     PR, _, ld2 = B._field(PR)
+    if PR.shape != PL.shape:   # the kernel takes PR's extent from PL
+        raise ValueError(f"inviscid_fluxes: PR of shape {tuple(PR.shape)}, PL of shape {tuple(PL.shape)}")
     if ld2 != ld:
         PR = PR.T.contiguous().T
         PL = PL.T.contiguous().T
@@ -145,14 +147,26 @@ def inviscid_fluxes(fluid, PL, PR, *args):
     return F
 
 
+def _check_gradients(what, grads, nd, ncol):
+    """The viscous kernels take the extent of every gradient array from ``nd``: one (n, ncol) array per dimension, or they
+    would read past the allocation."""
+    if len(grads) != nd:
+        raise ValueError(f"{what}: Pgrad needs one array per dimension")
+    for g in grads:
+        if g.ndim != 2 or g.shape[1] != ncol:
+            raise ValueError(f"{what}: every gradient array must be (n, {ncol}), got {tuple(g.shape)}"
+                             + (" (gradients of the velocities alone need velocity_gradients_only=True)"
+                                if g.ndim == 2 and g.shape[1] == nd and ncol == nd + 2 else ""))
+
+
 def viscous_fluxes(fluid, P, Pgrad, dim, mu_t=0.0):
     """cfd.jl:664-736 (Cartesian ``dim``); ``Pgrad`` = tuple of the gradients of P along each axis."""
     P, _, ldp = B._field(P)
     nd = _nd(P)
     n = P.shape[0]
-    grads = [B._field(g, n)[0].T.contiguous().T for g in Pgrad]
-    if len(grads) != nd:
-        raise ValueError("Pgrad needs one array per dimension")
+    grads = [B._field(g, n)[0] for g in Pgrad]
+    _check_gradients("viscous_fluxes", grads, nd, nd + 2)
+    grads = [g.T.contiguous().T for g in grads]
     ptrs = (B.c_vp * nd)(*[g.data_ptr() for g in grads])
     F = B._like(P, n)
     f = fluid._c()
@@ -177,9 +191,10 @@ def viscous_residual(part, fluid, P, Pgrad, mu_t, R, velocity_gradients_only=Fal
     part = B._part(part)
     P, _, ldp = B._field(P, part.nc)
     nd = _nd(P)
+    if nd != part.nd:   # the kernel takes the column counts of P, Pgrad and R from the partition
+        raise ValueError(f"viscous_residual: P must be (nc, nd + 2) with the partition's nd = {part.nd}")
     grads = [B._field(g, part.nc)[0] for g in Pgrad]
-    if len(grads) != nd:
-        raise ValueError("Pgrad needs one array per dimension")
+    _check_gradients("viscous_residual", grads, nd, nd if velocity_gradients_only else nd + 2)
     ldg = {g.stride(1) for g in grads}
     if len(ldg) != 1:
         grads = [g.T.contiguous().T for g in grads]

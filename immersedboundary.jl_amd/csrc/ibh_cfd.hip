@@ -514,10 +514,11 @@ __global__ void k_flow_bc(ibh_fluid f, int64_t n, const float* __restrict__ P, i
 // CFD.JST_sensor(Pim1, Pi, Pip1), cfd.jl:563-573: (|Pim1 + Pip1 - 2 Pi| + eps) / (|Pim1 - Pi| + |Pip1 - Pi| + eps), eps = 1f-14
 __global__ __launch_bounds__(CFD_BLOCK) void k_jst3(int64_t n, const float* __restrict__ a, const float* __restrict__ b,
                                                     const float* __restrict__ c, float* __restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float e = 1e-14f, pm = a[i], p0 = b[i], pp = c[i];
-    out[i] = (fabsf(pm + pp - 2.0f * p0) + e) / (fabsf(pm - p0) + fabsf(pp - p0) + e);
+    // (grid-stride, like every kernel launched on grid1: the grid is capped at 4096 workgroups)
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float e = 1e-14f, pm = a[i], p0 = b[i], pp = c[i];
+        out[i] = (fabsf(pm + pp - 2.0f * p0) + e) / (fabsf(pm - p0) + fabsf(pp - p0) + e);
+    }
 }
 // CFD.shock_sensor(velocity_gradients), cfd.jl:575-617: (div^2 + eps) / (div^2 + |curl|^2 + eps); g[i * nd + j] = d u_i / d x_j
 struct ShockGradPtrs {
@@ -525,18 +526,18 @@ struct ShockGradPtrs {
 };
 template <int ND>
 __global__ __launch_bounds__(CFD_BLOCK) void k_shock(int64_t n, ShockGradPtrs G, float* __restrict__ out) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    float divu = 0.0f, vort2 = 0.0f;
+    for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x) {
+        float divu = 0.0f, vort2 = 0.0f;
 #pragma unroll
-    for (int i = 0; i < ND; ++i) {
-        const int in = (i + 1) % ND, inn = (in + 1) % ND;
-        divu = divu + G.g[i * ND + i][p];
-        const float w = G.g[inn * ND + in][p] - G.g[in * ND + inn][p];
-        vort2 = vort2 + w * w;
+        for (int i = 0; i < ND; ++i) {   // in 2-D both trips visit the one vorticity component: 2 w^2, as the reference
+            const int in = (i + 1) % ND, inn = (in + 1) % ND;
+            divu = divu + G.g[i * ND + i][p];
+            const float w = G.g[inn * ND + in][p] - G.g[in * ND + inn][p];
+            vort2 = vort2 + w * w;
+        }
+        divu = divu * divu;
+        out[p] = (divu + 1e-14f) / (divu + vort2 + 1e-14f);
     }
-    divu = divu * divu;
-    out[p] = (divu + 1e-14f) / (divu + vort2 + 1e-14f);
 }
 }  // namespace
 

@@ -192,7 +192,8 @@ def Ducros_sensor(velocity_gradient):
 def WALE_nuSGS(Delta, velocity_gradient, Cw=0.325):
     """:291-337 (3-D only, like the reference's @assert)."""
     nd, n, keep, tab = _grad_table(velocity_gradient)
-    assert nd == 3, "WALE model only implemented for 3D"
+    if nd != 3:   # (the reference's @assert; the kernel reads a 3 x 3 table)
+        raise ValueError("WALE model only implemented for 3D")
     Delta = _vec(Delta, n)
     out = B.colmajor_empty(n)
     B._stream()

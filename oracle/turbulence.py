@@ -2,7 +2,12 @@
 
 numpy restatement of /root/reference/src/turbulence.jl (Float32, the reference's operation order).  No reference test
 exercises these closures: parity is pinned only by the analytic properties in tests/test_turbulence.py (law of the
-wall limits, pure shear / pure rotation, model constants) -- "parity unpinned" against Julia's libm otherwise."""
+wall limits, pure shear / pure rotation, model constants) -- "parity unpinned" against Julia's libm otherwise.
+
+Promotion kept literally: in ``WALE_nuSGS`` the reference's ``δ / 3`` (Bool / Int, turbulence.jl:329-331) is a Float64, so
+every term of ``SdijSdij`` is formed and squared in Float64 and rounded when it is added into the Float32 accumulator.
+The device kernel (csrc/ibh_turb.hip, ``k_wale``) keeps Float32 there; the difference lies inside the per-element bound
+of tests/pointwise_model.py (``BOUND_POINTWISE`` on the scale that carries the magnitudes of ``g . g``)."""
 import numpy as np
 
 f32 = np.float32
@@ -101,5 +106,8 @@ def WALE_nuSGS(Delta, g, Cw=f32(0.325)):
     for i in range(nd):
         for j in range(nd):
             SS = SS + ((g[i][j] + g[j][i]) / f32(2)) ** 2
-            SdSd = SdSd + ((g2[i][j] + g2[j][i]) / f32(2) - g2[i][j] * f32((1.0 if i == j else 0.0) / 3)) ** 2
+            # delta / 3 is a Float64 in Julia: the term and its square are Float64, the sum rounds into SdSd's type
+            third = (1.0 if i == j else 0.0) / 3
+            q = ((g2[i][j] + g2[j][i]) / f32(2)).astype(np.float64) - g2[i][j].astype(np.float64) * third
+            SdSd = (SdSd.astype(np.float64) + q ** 2).astype(SdSd.dtype)
     return Cw * Delta ** 2 * SdSd ** f32(1.5) / (SS ** f32(2.5) + SdSd ** f32(1.25) + EPS)
