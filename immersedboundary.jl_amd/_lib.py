@@ -25,6 +25,12 @@ class ibh_fluid(C.Structure):
                 ("S", C.c_float), ("nk", C.c_int32), ("k", C.c_float * 4)]
 
 
+class ibh_flow_bc_spec(C.Structure):
+    _fields_ = [("normal_flow", C.c_int32), ("p_inf", C.c_float), ("T_inf", C.c_float), ("u_inf", C.c_float * 3),
+                ("transpiration", C.c_float), ("wall_function", C.c_int32), ("wall_params", C.c_float * 8),
+                ("n_iter", C.c_int32)]
+
+
 _SIGS = {
     "ibh_init": [c_int],
     "ibh_set_stream": [c_vp],
@@ -67,6 +73,9 @@ _SIGS = {
     "ibh_bc_interp": [c_vp, c_vp, c_int, c_i64, c_vp, c_i64],
     "ibh_bc_blend": [c_vp, c_vp, c_int, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp],
     "ibh_bc_apply": [c_vp, c_vp, c_int, c_i64, c_int, c_vp],
+    "ibh_bc_flow_info": [c_vp, C.POINTER(C.c_int32)],
+    "ibh_bc_flow": [c_vp, C.POINTER(ibh_fluid), c_int, c_vp, c_i64, c_vp, c_vp, c_i64, C.POINTER(ibh_flow_bc_spec), c_int,
+                    C.POINTER(c_vp), c_vp, c_vp, c_vp],
     "ibh_gather_rows": [c_vp, C.c_int32, c_vp, c_int, c_i64, c_vp, c_i64],
     "ibh_scatter_rows": [c_vp, C.c_int32, c_vp, c_int, c_i64, c_vp, c_i64],
     "ibh_copy_rows": [c_vp, c_vp, C.c_int32, c_vp, c_int, c_i64, c_vp, c_i64],

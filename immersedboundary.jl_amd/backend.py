@@ -961,6 +961,103 @@ def impose_bc(f, dom, bname, *args, conv_to_backend=None, conv_from_backend=None
                 h[...] = conv_from_backend(a)
 
 
+_FLOW_BC_SCALAR_MODES = {"copy": 1, "nut": 2, "k": 3, "omega": 4, "epsilon": 5}   # IBH_BC_SCALAR_* of include/ibhip.h
+_WALL_PARAMS = ("kappa", "C_", "A", "beta", "betastar", "D", "Aplus", "omega_fixed_point")
+
+
+def impose_flow_bc(dom, bname, bc, P, scalars=(), wall_function=None, transpiration=0.0):
+    """``impose_bc!`` with a ``FlowBC`` closure in ONE launch per boundary partition (``ibh_bc_flow``): what
+
+        impose_bc(lambda b, Pi, *si: (bc(Pi, b.normals, [du_dn=wf["du_dn"], image_distances=b.image_distances,]
+                                         transpiration=transpiration), *values), dom, bname, P, *fields)
+
+    computes, bit for bit, where with ``wall_function`` (``None``, or a dict of ``turbulence.wall_function``'s keywords, ``{}``
+    for its defaults) ``wf = wall_function(b.image_distances, ut, nu)`` at the image points with ``ut`` the tangential speed
+    and ``nu = dynamic_viscosity(T) / rho`` (turbulence.jl:72-98).
+
+    ``bc`` is a ``cfd.FlowBC``; ``P`` the global ``(n, nd + 2)`` device array ``[p T u v (w)]``; ``scalars`` a sequence of up to
+    four ``(field, spec)`` pairs, ``field`` a global device vector and ``spec`` its boundary value: a float, ``"copy"`` (the
+    interpolated value), or -- with ``wall_function`` -- one of ``"nut"``, ``"k"``, ``"omega"``, ``"epsilon"``.  The arrays
+    (``torch`` or ``HipArray``) are updated in place, boundary partitions in ``dom.boundaries[bname]`` order, each seeing the
+    previous one's writes.  Every ghost cell is interpolated from the arrays as they were before any ghost cell of its
+    partition is written: a boundary with ghost cells among its donors goes through a staging buffer and a second launch."""
+    from .hiparray import HipArray
+    from . import turbulence
+    nd = dom.ndims
+    if nd not in (2, 3):
+        raise ValueError("impose_flow_bc: the domain must have 2 or 3 dimensions")
+    n = len(dom)
+    bparts = dom.boundaries[bname]
+    scalars = [tuple(s) for s in scalars]
+    if len(scalars) > 4:
+        raise ValueError("impose_flow_bc: at most 4 scalar fields")
+    if any(len(s) != 2 for s in scalars):
+        raise ValueError("impose_flow_bc: scalars are (field, spec) pairs")
+    wpar, n_iter = [0.0] * 8, 0
+    if wall_function is not None:
+        kw = dict(turbulence.wall_function.__kwdefaults__)
+        unknown = set(wall_function) - set(kw)
+        if unknown:
+            raise ValueError(f"impose_flow_bc: wall_function has no keyword {sorted(unknown)}")
+        kw.update(wall_function)
+        wpar, n_iter = [float(kw[k]) for k in _WALL_PARAMS], int(kw["n_iter"])
+        if n_iter < 0:
+            raise ValueError("impose_flow_bc: n_iter must not be negative")
+    modes, values = [], []
+    for _, spec in scalars:
+        if isinstance(spec, str):
+            if spec not in _FLOW_BC_SCALAR_MODES:
+                raise ValueError(f"impose_flow_bc: scalar spec {spec!r}: a float, 'copy', 'nut', 'k', 'omega' or 'epsilon'")
+            if spec != "copy" and wall_function is None:
+                raise ValueError(f"impose_flow_bc: scalar spec {spec!r} needs wall_function")
+            modes.append(_FLOW_BC_SCALAR_MODES[spec])
+            values.append(0.0)
+        else:
+            modes.append(0)
+            values.append(float(spec))
+    if bc.normal_flow:
+        if bc.u_inf.size != 1:
+            raise ValueError("Only 3 parcels in P (p, T and normal flow) allowed for normal_flow = true BC")
+    elif bc.u_inf.size != nd:
+        raise ValueError("FlowBC needs one free-stream velocity component per dimension")
+    arrays = [P] + [f for f, _ in scalars]
+    tens = [a.t if isinstance(a, HipArray) else a for a in arrays]
+    Pt, nvp, ldp = _field_inplace(tens[0], n, "impose_flow_bc: P")
+    if tens[0].ndim != 2 or nvp != nd + 2:
+        raise ValueError(f"impose_flow_bc: P must be (n, {nd + 2}) = [p T u v (w)]")
+    fields = []
+    for t in tens[1:]:
+        f, nv, _ = _field_inplace(t, n, "impose_flow_bc: scalar field")
+        if f.ndim != 1:
+            raise ValueError("impose_flow_bc: scalar fields are vectors of n values")
+        fields.append(f)
+    for a in arrays:
+        if isinstance(a, HipArray):
+            a._flush_readers()   # the arrays are written in place: pending broadcasts that read them go first
+    ns = len(fields)
+    u_inf = [float(x) for x in bc.u_inf] + [0.0] * (3 - bc.u_inf.size)
+    spec = _lib.ibh_flow_bc_spec(int(bc.normal_flow), bc.p_inf, bc.T_inf, (C.c_float * 3)(*u_inf), float(transpiration),
+                                 int(wall_function is not None), (C.c_float * 8)(*wpar), n_iter)
+    fluid = bc.fluid._c()
+    ptrs = (c_vp * ns)(*[f.data_ptr() for f in fields]) if ns else None
+    cmodes = (C.c_int32 * max(ns, 1))(*modes)
+    cvalues = (C.c_float * max(ns, 1))(*values)
+    for ipart in bparts:
+        bdry = to_backend(bparts[ipart])
+        _stream()
+        direct = getattr(bdry, "flow_direct", None)
+        if direct is None:
+            d = C.c_int32()
+            call("ibh_bc_flow_info", bdry.handle, C.byref(d))
+            direct = bdry.flow_direct = bool(d.value)
+        # (torch's allocator: in a graph capture the buffer comes from the graph's pool)
+        staging = None if direct or bdry.ng == 0 else torch.empty(bdry.ng * (nd + 2 + ns), dtype=torch.float32,
+                                                                  device=Pt.device)
+        nrm, _, ldn = _field(bdry.normals, bdry.ng)
+        call("ibh_bc_flow", bdry.handle, C.byref(fluid), nd, _ptr(nrm), ldn, _ptr(bdry.image_distances), _ptr(Pt), ldp,
+             C.byref(spec), ns, ptrs, C.cast(cmodes, c_vp), C.cast(cvalues, c_vp), _ptr(staging))
+
+
 class GraphedClosure:
     """A user closure at operator granularity captured ONCE in a HIP graph and replayed.
 

@@ -32,7 +32,7 @@ def euler_wray_agarwal_residual(part, Q, nu=1.5e-5, out=None):
     return r
 
 
-def config5_boundary_conditions(dom, Q, far, wall_name="sphere", far_name="farfield", fluid=None, R_inf=None):
+def config5_boundary_conditions(dom, Q, far, wall_name="sphere", far_name="farfield", fluid=None, R_inf=None, fused=False):
     """The boundary conditions of a level of BASELINE.json configs[4], ``impose_bc!`` on THAT level's own ``Boundary``
     structs (``multigrid`` builds every coarse ``Domain`` with its boundaries, ImmersedBoundary.jl:1381-1382), in the order a
     solver script would write them:
@@ -43,7 +43,9 @@ def config5_boundary_conditions(dom, Q, far, wall_name="sphere", far_name="farfi
       ``wall_function(y, u, nu)`` (turbulence.jl:72-98) at the image points -- ``y`` = image distance, ``u`` = tangential
       speed at the image point, ``nu = mu(T) / rho`` -- and the wall function's ``nu_t`` as the value of the scalar.
 
-    ``Q = [p T u v w R]`` (global device array of the level, updated in place)."""
+    ``Q = [p T u v w R]`` (global device array of the level, updated in place).  ``fused``: each of the two calls as one launch
+    per boundary partition (``impose_flow_bc``: ``ibh_bc_flow``), bit-identical to the composition where the glue lines of
+    the wall closure are evaluated left to right in Float32."""
     from . import cfd
     fluid = fluid or cfd.Fluid()
     nd = dom.ndims
@@ -51,6 +53,10 @@ def config5_boundary_conditions(dom, Q, far, wall_name="sphere", far_name="farfi
     free = cfd.FlowBC(fluid, far)
     wall = cfd.FlowBC(fluid, [far[0], far[1], 0.0], normal_flow=True)
     R_inf = float(R_inf if R_inf is not None else 3 * 1.5e-5)
+    if fused:
+        B.impose_flow_bc(dom, far_name, free, P, scalars=[(R, R_inf)])
+        B.impose_flow_bc(dom, wall_name, wall, P, scalars=[(R, "nut")], wall_function={})
+        return
     B.impose_bc(lambda b, Pi, Ri: (free(Pi, b.normals), R_inf), dom, far_name, P, R)
 
     def wall_bc(b, Pi, Ri):

@@ -4,6 +4,7 @@
 // the fused sweeps (ibh_fused*.hip) inline the same formulas (ibh_flux.h).
 #include "ibh_common.h"
 #include "ibh_flux.h"
+#include "ibh_flowbc_dev.h"
 
 #define CFD_BLOCK 256
 
@@ -11,14 +12,7 @@
 int ibh_viscous_per_cell = 0;
 namespace {
 
-__device__ __forceinline__ float sutherland(const ibh_fluid& f, float T) {
-    T = ibh_max(T, 10.0f);
-    // mu_ref * ((T/Tref)^(2/3)) * (Tref + S) / (T + S)     (cfd.jl:75, exponent as in the reference)
-    // x^(2/3) = exp2(2/3 log2 x) on the transcendental unit (v_log_f32 / v_exp_f32, 1 ulp each) instead of the ~100
-    // instructions of the library's powf -- a third of a viscous face flux.  The whole viscosity stays within 10 ulps of
-    // the float64 evaluation for T in [10, 1e5] K (x in [0.037, 366]; tests/test_gpu_percell_closures.py::test_pointwise_edges)
-    return f.mu_ref * __builtin_amdgcn_exp2f((2.0f / 3.0f) * __builtin_amdgcn_logf(T / f.Tref)) * (f.Tref + f.S) / (T + f.S);
-}
+using flowbc_dev::sutherland;
 
 __device__ __forceinline__ float conductivity(const ibh_fluid& f, float T) {
     float k = 0.0f * T;
@@ -450,9 +444,6 @@ __global__ __launch_bounds__(VISC_WG) VISC_ATTR void k_viscous_residual_shared(i
 inline dim3 visc_grid(int64_t n) { return dim3((unsigned)((n + VISC_WG - 1) / VISC_WG)); }
 inline dim3 grid1(int64_t n) { int g = ibh_grid(n, CFD_BLOCK); return dim3(g > 4096 ? 4096 : g); }
 
-// Julia's `b * y` for a Bool b: `false` is a strong zero (false * NaN == 0, with the sign of y); `b ? y : 0` otherwise
-__device__ __forceinline__ float jl_bool_times(bool b, float y) { return b ? y : copysignf(0.0f, y); }
-
 // FlowBC call, cfd.jl:243-300: characteristic-style boundary state from the image-point primitives
 template <int ND>
 __global__ void k_flow_bc(ibh_fluid f, int64_t n, const float* __restrict__ P, int64_t ldp,
@@ -468,42 +459,10 @@ __global__ void k_flow_bc(ibh_fluid f, int64_t n, const float* __restrict__ P, i
             nn[j] = nrm[i + j * ldn];
         }
         const float p = P[i], T = P[i + ldp];
-        float un, cur = u[0] * nn[0];
-#pragma unroll
-        for (int j = 1; j < ND; ++j) cur = cur + u[j] * nn[j];
-        if (normal_flow) {
-            un = u0;
-        } else {
-            un = nn[0] * uinf[0];
-#pragma unroll
-            for (int j = 1; j < ND; ++j) un = un + nn[j] * uinf[j];
-        }
-        const float a = sqrtf(f.gamma * f.R * ibh_max(T, 10.0f));
-        const float M = fabsf(un) / a;
-        // (un >= 0) * ((M > 1) * p_inf + (M <= 1) * p) + (un < 0) * ((M > 1) * p + (M <= 1) * p_inf) with Julia's Bool
-        // weights: a NaN Mach number (NaN temperature) makes every weight false and pb = 0, a NaN under a false weight is 0
-        const float pb = jl_bool_times(un >= 0.0f, jl_bool_times(M > 1.0f, pinf) + jl_bool_times(M <= 1.0f, p)) +
-                         jl_bool_times(un < 0.0f, jl_bool_times(M > 1.0f, p) + jl_bool_times(M <= 1.0f, pinf));
-        const float Tb = jl_bool_times(un > 0.0f, Tinf) + jl_bool_times(un <= 0.0f, T);
-        float ub[ND];
-        if (normal_flow) {
-            const float tr = transp_v ? transp_v[i] : transp;
-            const float d = un - cur + tr;
-#pragma unroll
-            for (int j = 0; j < ND; ++j) ub[j] = u[j] + nn[j] * d;
-        } else {
-#pragma unroll
-            for (int j = 0; j < ND; ++j) ub[j] = (un < 0.0f) ? u[j] : uinf[j];
-        }
-        if (dudn) {
-            float V = ub[0] * ub[0];
-#pragma unroll
-            for (int j = 1; j < ND; ++j) V = V + ub[j] * ub[j];
-            V = sqrtf(V) + 1.1920929e-07f;
-            const float sc = (V - dudn[i] * imd[i]) / V;
-#pragma unroll
-            for (int j = 0; j < ND; ++j) ub[j] = ub[j] * sc;
-        }
+        const float tr = (normal_flow && transp_v) ? transp_v[i] : transp;
+        float pb, Tb, ub[ND];
+        flowbc_dev::flow_bc_point<ND>(f, p, T, u, nn, pinf, Tinf, uinf, normal_flow, dudn != nullptr,
+                                      dudn ? dudn[i] : 0.0f, dudn ? imd[i] : 0.0f, tr, pb, Tb, ub);
         out[i] = pb;
         out[i + ldo] = Tb;
 #pragma unroll

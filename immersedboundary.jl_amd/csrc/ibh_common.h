@@ -174,6 +174,9 @@ struct ibh_bc {
     // stencils with the donor CELLS resolved (image_domain[idx])
     std::vector<int32_t> h_ghost, h_off, h_donor;
     std::vector<float> h_eta, h_w;
+    // ibh_bc_flow: 1 = no ghost cell is a donor of the boundary's stencils (written in the launch that interpolates), 0 = some
+    // are (staged and scattered), -1 = not looked at yet
+    mutable int flow_direct = -1;
 };
 
 // An ordered list of ghost-cell boundary conditions with closures the library knows (mode 0: a constant value, mode 1:

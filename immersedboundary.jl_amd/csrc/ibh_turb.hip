@@ -6,40 +6,20 @@
 // At the end: the closures on an all-block 3-D partition with the gradients made where they are consumed (block kernels).
 #include "ibh_common.h"
 #include "ibh_fused_int.h"
+#include "ibh_wall_dev.h"
 
 namespace {
 
 constexpr int TB = 256;
-constexpr float EPS32 = 1.1920929e-07f;
+constexpr float EPS32 = wall_dev::EPS32;
 
 struct GradPtrs {
     const float* g[9];
 };
 
-__device__ __forceinline__ float von_karman(float yp, float kappa, float C) {
-    return ibh_min(logf(ibh_max(yp, 1.0f)) / kappa + C, yp);  // :11-16
-}
-
-struct WallParams {
-    float kappa, C, A, beta, betastar, D, Aplus, omega;
-    int n_iter;
-};
-
-__device__ __forceinline__ void wall_point(float Rey, const WallParams& w, float& yp, float& up, float& mup, float& kp,
-                                           float& dudy) {
-    Rey = ibh_clamp(fabsf(Rey), EPS32, INFINITY);  // clamp(abs(Rey), eps, Inf32)
-    yp = sqrtf(Rey);
-    up = 0.0f;
-    for (int it = 0; it < w.n_iter; ++it) {
-        up = von_karman(yp, w.kappa, w.C);
-        yp = w.omega * (Rey / up) + (1.0f - w.omega) * yp;
-    }
-    up = Rey / yp;
-    const float e = 1.0f - expf(-yp / w.A);
-    mup = w.kappa * yp * (e * e);
-    dudy = 1.0f / (1.0f + mup);
-    kp = ibh_min(yp * yp / (6.0f * w.betastar / w.beta - 2.0f), w.D * expf(-yp / w.Aplus));
-}
+using wall_dev::wall_point;
+using wall_dev::WallParams;
+using wall_dev::wall_params;
 
 __global__ void k_wall_rey(int64_t n, const float* __restrict__ Rey, WallParams w, float* __restrict__ yp,
                            float* __restrict__ up, float* __restrict__ mup, float* __restrict__ kp,
@@ -55,18 +35,13 @@ __global__ void k_wall(int64_t n, const float* __restrict__ y, const float* __re
                        WallParams w, float* __restrict__ utau, float* __restrict__ nut, float* __restrict__ k,
                        float* __restrict__ omega, float* __restrict__ eps, float* __restrict__ dudn) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        float yp, up, mup, kp, dudy;
-        wall_point(u[i] * y[i] / nu[i], w, yp, up, mup, kp, dudy);
-        const float ut = u[i] / up;
-        const float nt = mup * nu[i];
-        const float kk = kp * (ut * ut);
-        const float om = kk / nt;
-        utau[i] = ut;
-        nut[i] = nt;
-        k[i] = kk;
-        omega[i] = om;
-        eps[i] = w.betastar * om * kk;
-        dudn[i] = dudy * (ut * ut) / nu[i];
+        const wall_dev::WallOut o = wall_dev::wall_eval(y[i], u[i], nu[i], w);
+        utau[i] = o.utau;
+        nut[i] = o.nut;
+        k[i] = o.k;
+        omega[i] = o.omega;
+        eps[i] = o.eps;
+        dudn[i] = o.dudn;
     }
 }
 
@@ -448,10 +423,6 @@ inline int tgrid(int64_t n) {
     int g = ibh_grid(n, TB);
     return g > 4096 ? 4096 : g;
 }
-inline WallParams wall_params(const float* p, int n_iter) {
-    return WallParams{p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], n_iter};
-}
-
 }  // namespace
 
 extern "C" {

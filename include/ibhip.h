@@ -525,6 +525,45 @@ int ibh_wray_agarwal_of(ibh_part*, const float* R, const float* S, float sigmaR,
 int ibh_turb_ducros(int nd, int64_t n, const float* const* g, float* out);
 int ibh_turb_wale(int64_t n, const float* Delta, const float* const* g, float Cw, float* out);
 
+/* ---- impose_bc! with a FlowBC closure in ONE launch (ImmersedBoundary.jl:1197-1247 over cfd.jl:243-300 and, on a wall,
+ * turbulence.jl:72-98): what a solver script writes as
+ *   impose_bc!(dom, bname, P, s...) do b, Pi, si...
+ *       wf = wall_function(b.image_distances, |u_tangential|, mu(T) / rho)                 (wall_function != 0)
+ *       bc(Pi, b.normals; du!dn = wf.du!dn, image_distances = b.image_distances, transpiration), values of s...
+ *   end
+ * for one Boundary: interpolation at the image points, the closure and the blend, per ghost cell, in the arithmetic of
+ * ibh_bc_interp, ibh_cfd_dynamic_viscosity, ibh_turb_wall_function, ibh_cfd_flow_bc and ibh_bc_blend (bit-identical to
+ * their composition with the glue evaluated left to right in Float32:
+ *   rho = p / (R T), nu = mu(T) / rho, un = sum_j u_j n_j, t_j = u_j - un n_j, ut = sqrt(sum_j t_j^2)). */
+typedef struct ibh_flow_bc_spec {
+    int32_t normal_flow;     /* 0: Dirichlet state [p_inf T_inf u_inf[0..nd-1]]; 1: u_inf[0] is the normal velocity (slip wall) */
+    float p_inf;
+    float T_inf;
+    float u_inf[3];
+    float transpiration;     /* added to the normal velocity (normal_flow only), a constant */
+    int32_t wall_function;   /* 0 or 1: du!dn (and the wall-function scalar modes) from wall_function(y, ut, nu) */
+    float wall_params[8];    /* {kappa, C, A, beta, betastar, D, Aplus, omega_fixed_point} as for ibh_turb_wall_function */
+    int32_t n_iter;
+} ibh_flow_bc_spec;
+/* boundary value of scalar field i: scalar_mode[i] = */
+#define IBH_BC_SCALAR_CONST 0    /* scalar_value[i]                                   */
+#define IBH_BC_SCALAR_COPY 1     /* the interpolated value (zero gradient)            */
+#define IBH_BC_SCALAR_NUT 2      /* wall_function's nu_t  (needs wall_function != 0)  */
+#define IBH_BC_SCALAR_K 3        /* ... k                                             */
+#define IBH_BC_SCALAR_OMEGA 4    /* ... omega                                         */
+#define IBH_BC_SCALAR_EPSILON 5  /* ... epsilon                                       */
+/* P: (n, nd + 2) rows [p T u v (w)] of the global array, leading dimension ldp, ghost rows updated in place; normals
+ * (n_ghost, nd) with leading dimension ldn and image_distances (n_ghost): device copies of the Boundary's; scalars: HOST
+ * table of ns <= 4 DEVICE vectors (global rows, updated in place), scalar_mode / scalar_value: host arrays of ns.
+ * *direct (ibh_bc_flow_info) = 1: no ghost cell of the boundary is a donor of its stencils, the launch writes the ghost cells
+ * themselves and `staging` may be NULL; 0: every ghost cell is interpolated from the arrays as they were before any is
+ * written, through `staging` (device, n_ghost * (nd + 2 + ns) floats) and a second launch that scatters it.
+ * Every misuse is reported before anything is launched. */
+int ibh_bc_flow_info(const ibh_bc*, int32_t* direct);
+int ibh_bc_flow(const ibh_bc*, const ibh_fluid*, int nd, const float* normals, int64_t ldn, const float* image_distances,
+                float* P, int64_t ldp, const ibh_flow_bc_spec* spec, int ns, float* const* scalars,
+                const int32_t* scalar_mode, const float* scalar_value, float* staging);
+
 /* ---- point-implicit smoother (reference: the orphan file src/point_implicit.jl) ------------------------------
  * Arrays are dense column-major (n points, nv variables) with leading dimension n, i.e. n*nv contiguous floats;
  * the block diagonal D is (n, nv, nv) column-major: D[p + n*(k + nv*i)] = d f_k / d x_i at point p (:56-91). */

@@ -1022,6 +1022,63 @@ function Turbulence.wall_function(Rey::HipArray{Float32, 1};
         length(Rey), Rey.ptr, par, n_iter, o[1].ptr, o[2].ptr, o[3].ptr, o[4].ptr, o[5].ptr))
     (y⁺ = o[1], u⁺ = o[2], μ⁺ = o[3], k⁺ = o[4], du⁺!dy⁺ = o[5])
 end
+
+# layout of `ibh_flow_bc_spec` (include/ibhip.h)
+struct IbhFlowBCSpec
+    normal_flow::Int32
+    p∞::Float32
+    T∞::Float32
+    u∞::NTuple{3, Float32}
+    transpiration::Float32
+    wall_function::Int32
+    wall_params::NTuple{8, Float32}
+    n_iter::Int32
+end
+const _flow_bc_scalar_modes = Dict(:copy => Int32(1), :νₜ => Int32(2), :k => Int32(3), :ω => Int32(4), :ϵ => Int32(5))
+"""
+`impose_flow_bc!(dom, bname, bc, P, scalars...; wall_function = nothing, transpiration = 0)`: `impose_bc!` with the `FlowBC`
+`bc` as its closure in one launch per boundary chunk (`ibh_bc_flow`) -- bit-identical to `impose_bc!` over `bc(Pi, b.normals;
+du!dn, image_distances, transpiration)` with `du!dn` from `wall_function(b.image_distances, uₜ, μ(T) / ρ; wall_function...)` at
+the image points where `wall_function` is a NamedTuple of its keywords (`(;)` for the defaults).  `scalars`: up to four pairs
+`field => value` with a number, `:copy`, or -- with `wall_function` -- `:νₜ`, `:k`, `:ω`, `:ϵ`.
+"""
+function impose_flow_bc!(dom::Domain, bname::String, bc::CFD.FlowBC, P::HipArray{Float32, 2},
+                         scalars::Pair{<:HipArray{Float32, 1}}...; wall_function::Union{Nothing, NamedTuple} = nothing,
+                         transpiration::Real = 0f0)
+    nd = _ndP(P)
+    ns = length(scalars)
+    ns <= 4 || throw(ArgumentError("impose_flow_bc!: at most 4 scalar fields"))
+    u∞ = Float32.(collect(bc.u∞))
+    bc.normal_flow && length(u∞) != 1 &&
+        throw(ArgumentError("Only 3 parcels in P (p, T and normal flow) allowed for normal_flow = true BC"))
+    wf = isnothing(wall_function) ? (;) : wall_function
+    kw = merge((κ = 0.41f0, C = 4.9f0, A = 19.0f0, β = 0.075f0, βstar = 0.09f0, D = 4.2f0, A⁺ = 360.0f0,
+                ω_fixed_point = 0.5f0, n_iter = 20), wf)
+    par = _wall_params(kw.κ, kw.C, kw.A, kw.β, kw.βstar, kw.D, kw.A⁺, kw.ω_fixed_point)
+    spec = Ref(IbhFlowBCSpec(bc.normal_flow ? 1 : 0, Float32(bc.p∞), Float32(bc.T∞),
+                             ntuple(i -> i <= length(u∞) ? u∞[i] : 0f0, 3), Float32(transpiration),
+                             isnothing(wall_function) ? 0 : 1, ntuple(i -> par[i], 8), Int32(kw.n_iter)))
+    modes = Int32[v isa Symbol ? _flow_bc_scalar_modes[v] : Int32(0) for (_, v) in scalars]
+    values = Float32[v isa Symbol ? 0f0 : Float32(v) for (_, v) in scalars]
+    any(m >= 2 for m in modes) && isnothing(wall_function) &&
+        throw(ArgumentError("impose_flow_bc!: :νₜ, :k, :ω and :ϵ need wall_function"))
+    fields = Ptr{Cvoid}[a.ptr for (a, _) in scalars]
+    f = Ref(IbhFluid(bc.fluid))
+    for (_, b) in dom.boundaries[bname]
+        bdry = to_backend(b, hip)
+        direct = Ref{Int32}(0)
+        check(ccall((:ibh_bc_flow_info, lib), Cint, (Ptr{Cvoid}, Ptr{Int32}), bdry.handle, direct))
+        staging = direct[] != 0 ? nothing : HipArray{Float32, 1}(undef, (bdry.ng * (nd + 2 + ns),))
+        GC.@preserve fields scalars staging begin
+            check(ccall((:ibh_bc_flow, lib), Cint,
+                (Ptr{Cvoid}, Ptr{IbhFluid}, Cint, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{IbhFlowBCSpec}, Cint,
+                 Ptr{Ptr{Cvoid}}, Ptr{Int32}, Ptr{Float32}, Ptr{Cvoid}),
+                bdry.handle, f, nd, bdry.normals.ptr, ld(bdry.normals), bdry.image_distances.ptr, P.ptr, ld(P), spec, ns,
+                fields, modes, values, isnothing(staging) ? C_NULL : staging.ptr))
+        end
+    end
+    nothing
+end
 function Turbulence.shear_rate(velocity_gradient::AbstractMatrix{<:HipArray})                       # :110-124
     nd, tab = _grad_table(velocity_gradient)
     S = _vec_like(velocity_gradient[1, 1])
