@@ -431,6 +431,7 @@ int ibh_step_advection_xgmi(ibh_part* p, float* u, const float* C, int64_t ldc, 
             A.dst[1][q] = dst1[q];
             A.sflag[q] = send_flags[q];
             A.sseg[q] = send_seg[q];
+            IBH_REQUIRE(send_seg[q + 1] >= send_seg[q], "ibh_step_advection_xgmi: segments must ascend");
         }
         A.sseg[n_send_peers] = send_seg[n_send_peers];
     }
@@ -439,6 +440,7 @@ int ibh_step_advection_xgmi(ibh_part* p, float* u, const float* C, int64_t ldc, 
         for (int q = 0; q < n_recv_peers; ++q) {
             A.rflag[q] = recv_flags[q];
             A.rseg[q] = recv_seg[q];
+            IBH_REQUIRE(recv_seg[q + 1] >= recv_seg[q], "ibh_step_advection_xgmi: segments must ascend");
         }
         A.rseg[n_recv_peers] = recv_seg[n_recv_peers];
     }
