@@ -108,3 +108,31 @@ def navier_stokes_wray_agarwal_residual(part, Q, nu=1.5e-5, fluid=None, out=None
                                 mu_t=B.at_faces(part, mut.contiguous(), d))
         r[:, :nvp] += B.green_gauss(part, Fv, d)
     return r
+
+
+def navier_stokes_les_residual(part, P, Delta, fluid=None, model="wale", out=None):
+    """``P = [p T u v (w)]`` -> residual of the compressible Navier-Stokes equations with an LES eddy viscosity, the script a
+    user of the reference would write:
+
+    * the Euler sweep with the sensor-scaled central + Rusanov flux and the pressure sensor (``residual_euler_sensor``,
+      cfd.jl:516-554),
+    * ``nu_sgs`` of ``model`` (``"wale"``, 3-D, turbulence.jl:292-337, or ``"smagorinsky"``, :134-137) from the velocity
+      gradients, which are kept for the viscous terms (``les_closure_of``: one launch where the fused closures apply),
+    * ``mu_t = rho nu_sgs`` in one broadcast launch,
+    * ``sum_d green_gauss(viscous_fluxes(fluid, at_faces(P), face_gradient(P, grad P, d), d; mu_t = at_faces(mu_t)), d)`` in
+      one launch (``ibh_viscous_residual``, cfd.jl:664-736).
+
+    ``Delta``: the filter width per cell, ``(nc,)``."""
+    from . import cfd
+    from .hiparray import HipArray
+    fluid = fluid or cfd.Fluid()
+    nd = part.nd
+    nvp = nd + 2
+    if P.shape[1] != nvp:
+        raise ValueError(f"P must be (nc, {nvp}) = [p T u v (w)]")
+    r = out if out is not None else B.colmajor_empty(P.shape[0], nvp)
+    B.residual_euler_sensor(part, P, out=r, fluid=fluid)
+    les = T.les_closure_of(part, P[:, 2:2 + nd], Delta, model=model, gradients=True)
+    mut = (HipArray(P[:, 0]) / (HipArray(P[:, 1]) * fluid.R) * HipArray(les["nusgs"])).t   # mu_t = rho nu_sgs, one launch
+    cfd.viscous_residual(part, fluid, P, les["gradients"], mut, r, velocity_gradients_only=True)
+    return r

@@ -5,6 +5,7 @@
 #include "ibh_common.h"
 #include "ibh_flux.h"
 #include "ibh_flowbc_dev.h"
+#include "ibh_les_dev.h"
 
 #define CFD_BLOCK 256
 
@@ -486,16 +487,9 @@ struct ShockGradPtrs {
 template <int ND>
 __global__ __launch_bounds__(CFD_BLOCK) void k_shock(int64_t n, ShockGradPtrs G, float* __restrict__ out) {
     for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x) {
-        float divu = 0.0f, vort2 = 0.0f;
-#pragma unroll
-        for (int i = 0; i < ND; ++i) {   // in 2-D both trips visit the one vorticity component: 2 w^2, as the reference
-            const int in = (i + 1) % ND, inn = (in + 1) % ND;
-            divu = divu + G.g[i * ND + i][p];
-            const float w = G.g[inn * ND + in][p] - G.g[in * ND + inn][p];
-            vort2 = vort2 + w * w;
-        }
-        divu = divu * divu;
-        out[p] = (divu + 1e-14f) / (divu + vort2 + 1e-14f);
+        float g[ND][ND];
+        les_dev::load_table<ND>(G.g, p, g);   // (in 2-D the formula visits the one vorticity component twice, as the reference)
+        out[p] = les_dev::shock<ND>(g);
     }
 }
 }  // namespace

@@ -198,6 +198,8 @@ extern "C" int ibh_shear_rate_of_velocity_cells(const ibh_part* p, const float* 
                                                 int64_t ldg);
 extern "C" int ibh_wray_agarwal_of_cells(const ibh_part* p, const float* R, const float* S, float sigmaR, float C1,
                                          float kappa, float* nut, float* nuR, float* Sout);
+extern "C" int ibh_les_of_cells(const ibh_part* p, const float* vel, int64_t ldv, const float* Delta, int model, float Cmodel,
+                                float* nusgs, float* ducros, float* shock, float* S, float* G, int64_t ldg);
 
 // internal: the boundary-condition set with the next step's time step beside it (ibh_ops.hip), called from ibh_fused.hip
 extern "C" int ibh_bcset_apply_with_dt(const ibh_bcset* s, float* a, ibh_part* p, const float* C, int64_t ldc, float scale,

@@ -8,6 +8,7 @@
 // with -ffp-contract=off, IEEE divide/sqrt) so results are bit-comparable with the oracle.
 #include "ibh_bcset_dev.h"
 #include "ibh_common.h"
+#include "ibh_les_dev.h"
 
 #define OPS_BLOCK 256
 #include "ibh_dt_dev.h"
@@ -244,6 +245,36 @@ __global__ void k_shear_of_velocity_cells(int32_t nc, GradDims G, const float* _
             for (int i = 0; i < ND; ++i)
 #pragma unroll
                 for (int j = 0; j < ND; ++j) Gout[(int64_t)(ND * j + i) * ldg + c] = g[i][j];
+        }
+    }
+}
+// the LES closure of a velocity field (ibh_les_of), face-list partitions: the gradients as in k_shear_of_velocity_cells, the
+// requested outputs from registers with the pointwise formulas of ibh_les_dev.h (bit-identical to the composition)
+template <int ND>
+__global__ void k_les_of_cells(int32_t nc, GradDims G, const float* __restrict__ vel, int64_t ldv,
+                               const float* __restrict__ Delta, int model, float Cmodel, les_dev::Outputs O) {
+    for (int64_t c = IBH_WG_X() * (int64_t)blockDim.x + threadIdx.x; c < nc; c += (int64_t)gridDim.x * blockDim.x) {
+        int32_t sd[2 * ND];
+#pragma unroll
+        for (int s = 0; s < 2 * ND; ++s) sd[s] = G.side[(int64_t)s * nc + c];
+        float g[ND][ND];
+#pragma unroll
+        for (int i = 0; i < ND; ++i) cell_gradient_at<ND>(G, sd, nc, (int32_t)c, vel + (int64_t)i * ldv, g[i]);
+        if (O.S || model == les_dev::MODEL_SMAGORINSKY) {  // (uniform, as every branch below)
+            const float s = les_dev::shear_rate<ND>(g);
+            if (O.S) O.S[c] = s;
+            if (model == les_dev::MODEL_SMAGORINSKY) O.nusgs[c] = les_dev::smagorinsky(Delta[c], s, Cmodel);
+        }
+        if constexpr (ND == 3) {
+            if (model == les_dev::MODEL_WALE) O.nusgs[c] = les_dev::wale(g, Delta[c], Cmodel);
+        }
+        if (O.ducros) O.ducros[c] = les_dev::ducros<ND>(g);
+        if (O.shock) O.shock[c] = les_dev::shock<ND>(g);
+        if (O.G) {  // d u_i / d x_j in column ND j + i (the tuple cell_gradient's layout)
+#pragma unroll
+            for (int i = 0; i < ND; ++i)
+#pragma unroll
+                for (int j = 0; j < ND; ++j) O.G[(int64_t)(ND * j + i) * O.ldg + c] = g[i][j];
         }
     }
 }
@@ -693,6 +724,19 @@ int ibh_wray_agarwal_of_cells(const ibh_part* p, const float* R, const float* S,
     else
         hipLaunchKernelGGL(k_wray_agarwal_of_cells<3>, grid2(p->nc, 1), dim3(OPS_BLOCK), 0, ibh_stream, p->nc, G, R, S, sigmaR,
                            C1, kappa, nut, nuR, Sout);
+    IBH_LAUNCH_CHECK();
+    return 0;
+}
+int ibh_les_of_cells(const ibh_part* p, const float* vel, int64_t ldv, const float* Delta, int model, float Cmodel,
+                     float* nusgs, float* ducros, float* shock, float* S, float* Gout, int64_t ldg) {
+    const GradDims G = grad_dims(p);
+    const les_dev::Outputs O{nusgs, ducros, shock, S, Gout, ldg};
+    if (p->nd == 2)
+        hipLaunchKernelGGL(k_les_of_cells<2>, grid2(p->nc, 1), dim3(OPS_BLOCK), 0, ibh_stream, p->nc, G, vel, ldv, Delta, model,
+                           Cmodel, O);
+    else
+        hipLaunchKernelGGL(k_les_of_cells<3>, grid2(p->nc, 1), dim3(OPS_BLOCK), 0, ibh_stream, p->nc, G, vel, ldv, Delta, model,
+                           Cmodel, O);
     IBH_LAUNCH_CHECK();
     return 0;
 }

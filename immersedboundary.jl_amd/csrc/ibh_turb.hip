@@ -7,6 +7,7 @@
 #include "ibh_common.h"
 #include "ibh_fused_int.h"
 #include "ibh_wall_dev.h"
+#include "ibh_les_dev.h"
 
 namespace {
 
@@ -48,24 +49,16 @@ __global__ void k_wall(int64_t n, const float* __restrict__ y, const float* __re
 template <int ND>
 __global__ void k_shear(int64_t n, GradPtrs G, float* __restrict__ S) {
     for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < n; c += (int64_t)gridDim.x * blockDim.x) {
-        float s = 0.0f;
-#pragma unroll
-        for (int i = 0; i < ND; ++i)
-#pragma unroll
-            for (int j = 0; j < ND; ++j) {
-                const float t = (G.g[i * ND + j][c] + G.g[j * ND + i][c]) / 2.0f;
-                s = s + t * t;
-            }
-        S[c] = sqrtf(2.0f * s);
+        float g[ND][ND];
+        les_dev::load_table<ND>(G.g, c, g);
+        S[c] = les_dev::shear_rate<ND>(g);
     }
 }
 
 __global__ void k_smagorinsky(int64_t n, const float* __restrict__ D, const float* __restrict__ S, float Cs,
                               float* __restrict__ out) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float t = Cs * D[i];
-        out[i] = t * t * S[i];
-    }
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        out[i] = les_dev::smagorinsky(D[i], S[i], Cs);
 }
 
 __global__ void k_keps(int64_t n, const float* __restrict__ k, const float* __restrict__ e, const float* __restrict__ S,
@@ -104,53 +97,17 @@ __global__ void k_wray_agarwal(int64_t n, const float* __restrict__ R, const flo
 template <int ND>
 __global__ void k_ducros(int64_t n, GradPtrs G, float* __restrict__ out) {
     for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < n; c += (int64_t)gridDim.x * blockDim.x) {
-        float div = 0.0f;
-#pragma unroll
-        for (int i = 0; i < ND; ++i) div = div + G.g[i * ND + i][c];
-        const float div2 = div * div;
-        float curl2;
-        if (ND == 2) {
-            const float w = G.g[1 * ND + 0][c] - G.g[0 * ND + 1][c];
-            curl2 = w * w;
-        } else {
-            const float a = G.g[2 * ND + 1][c] - G.g[1 * ND + 2][c];
-            const float b = G.g[0 * ND + 2][c] - G.g[2 * ND + 0][c];
-            const float d = G.g[1 * ND + 0][c] - G.g[0 * ND + 1][c];
-            curl2 = a * a + b * b + d * d;
-        }
-        out[c] = (div2 + EPS32) / (div2 + curl2 + EPS32);
+        float g[ND][ND];
+        les_dev::load_table<ND>(G.g, c, g);
+        out[c] = les_dev::ducros<ND>(g);
     }
 }
 
 __global__ void k_wale(int64_t n, const float* __restrict__ Delta, GradPtrs G, float Cw, float* __restrict__ out) {
     for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < n; c += (int64_t)gridDim.x * blockDim.x) {
-        float g[3][3], g2[3][3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) g[i][j] = G.g[i * 3 + j][c];
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                float s = 0.0f;
-#pragma unroll
-                for (int k = 0; k < 3; ++k) s = s + g[i][k] * g[k][j];
-                g2[i][j] = s;
-            }
-        float SS = 0.0f, SdSd = 0.0f;
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                const float t = (g[i][j] + g[j][i]) / 2.0f;
-                SS = SS + t * t;
-                const float dlt = (i == j) ? (1.0f / 3.0f) : 0.0f;
-                const float q = (g2[i][j] + g2[j][i]) / 2.0f - g2[i][j] * dlt;
-                SdSd = SdSd + q * q;
-            }
-        const float D = Delta[c];
-        out[c] = Cw * (D * D) * powf(SdSd, 1.5f) / (powf(SS, 2.5f) + powf(SdSd, 1.25f) + EPS32);
+        float g[3][3];
+        les_dev::load_table<3>(G.g, c, g);
+        out[c] = les_dev::wale(g, Delta[c], Cw);
     }
 }
 
@@ -290,6 +247,70 @@ __global__ __launch_bounds__(256) void k_wray_agarwal_of3(const BlockDesc3* __re
         nut[c] = r;
         nuR[c] = r * sigmaR;
         Sout[c] = ibh_min(src, 10.0f * r);
+    }
+}
+
+// ---- the LES closure of a velocity field on an all-block 3-D partition, gradients consumed where they are made:
+//   nusgs  = Smagorinsky_νSGS(Delta, shear_rate(g)) or WALE_νSGS(Delta, g)      (turbulence.jl:134-137, :292-337)
+//   ducros = Ducros_sensor(g), shock = CFD.shock_sensor(g), S = shear_rate(g)    (:253-283, cfd.jl:589-617, :110-124)
+// with g = the nine gradients of blk3::wave_gradients (the tuple cell_gradient's arithmetic) and the pointwise formulas of
+// ibh_les_dev.h (those of k_shear / k_smagorinsky / k_ducros / k_wale / k_shock): bit-identical to the composition.  Which
+// outputs are written is uniform over the launch: the model is a template parameter, the others branch on their pointers.
+// 12 B in + 4 B per requested output (+ 4 B of Delta with a model, + 36 B with G) per cell, one launch; the composition
+// writes the nine gradients (3 x (4 in + 12 out)) and reads them back once per closure (36 in + 4 out each).
+// WALE: three powf per cell.  Unrolled over the lane's eight cells they are 24 copies of the expansion, so the invariants
+// SS, SdSd of the eight cells go through the wave's LDS tile (free once the gradients are made) and ONE copy of the
+// expansion runs in a loop over them -- g itself is never indexed dynamically.
+template <int MODEL>
+__global__ __launch_bounds__(256) void k_les_of3(const BlockDesc3* __restrict__ blocks, const int32_t* __restrict__ htab,
+                                                 const int32_t* __restrict__ ftab, int32_t nblk, int32_t nwg,
+                                                 FieldPtrs<3> V, const float* __restrict__ Delta, float Cmodel,
+                                                 les_dev::Outputs O) {
+    __shared__ float lds[4 * BLK3W_PASSA_LDS];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int32_t blk = __builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x, nwg) * 4 + wave);
+    if (blk >= nblk) return;
+    const BlockDesc3 bb = blocks[blk];
+    float* wl = lds + wave * BLK3W_PASSA_LDS;
+    float g[3][8][3];
+    blk3::wave_gradients<3>(bb, htab, ftab, blk, V.f, wl, lane, g);
+    if (MODEL == les_dev::MODEL_WALE) blk2::wave_lds_sync();   // the gradients' LDS reads are done: the tile takes the invariants
+    const uint32_t ldg = (uint32_t)O.ldg;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const uint32_t c = (uint32_t)bb.base + lane + 64 * k;
+        float t[3][3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) t[i][j] = g[i][k][j];
+        if (O.S || MODEL == les_dev::MODEL_SMAGORINSKY) {  // (uniform, as every branch on O below)
+            const float s = les_dev::shear_rate<3>(t);
+            if (O.S) O.S[c] = s;
+            if (MODEL == les_dev::MODEL_SMAGORINSKY) O.nusgs[c] = les_dev::smagorinsky(Delta[c], s, Cmodel);
+        }
+        if (O.ducros) O.ducros[c] = les_dev::ducros<3>(t);
+        if (O.shock) O.shock[c] = les_dev::shock<3>(t);
+        if (MODEL == les_dev::MODEL_WALE) {
+            float SS, SdSd;
+            les_dev::wale_invariants(t, SS, SdSd);
+            wl[k * 64 + lane] = SS;
+            wl[512 + k * 64 + lane] = SdSd;
+        }
+        if (O.G) {  // d u_i / d x_j in column 3 j + i (the tuple cell_gradient's layout)
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = 0; j < 3; ++j) __builtin_nontemporal_store(t[i][j], O.G + (size_t)(3 * j + i) * ldg + c);
+        }
+    }
+    if (MODEL == les_dev::MODEL_WALE) {
+        blk2::wave_lds_sync();
+#pragma unroll 1
+        for (int k = 0; k < 8; ++k) {
+            const uint32_t c = (uint32_t)bb.base + lane + 64 * k;
+            O.nusgs[c] = les_dev::wale_of_invariants(Delta[c], wl[k * 64 + lane], wl[512 + k * 64 + lane], Cmodel);
+        }
     }
 }
 
@@ -581,6 +602,36 @@ int ibh_wray_agarwal_of(ibh_part* p, const float* R, const float* S, float sigma
     const int32_t nwg = (p->nblk + 3) / 4;
     hipLaunchKernelGGL(k_wray_agarwal_of3, dim3(nwg), dim3(256), 0, ibh_stream, p->blocks3, p->htab3, p->ftab3, p->nblk, nwg,
                        RS, sigmaR, C1, kappa, nut, nuR, Sout);
+    IBH_LAUNCH_CHECK();
+    return 0;
+}
+
+// The LES closure of a velocity field in one launch (dispatch as ibh_shear_rate_of_velocity_grad)
+int ibh_les_of(ibh_part* p, const float* vel, int64_t ldv, const float* Delta, int model, float Cmodel, float* nusgs,
+               float* ducros, float* shock, float* S, float* G, int64_t ldg) {
+    IBH_REQUIRE(p && vel, "ibh_les_of: null partition or velocity");
+    IBH_REQUIRE(nusgs || ducros || shock || S || G, "ibh_les_of: no output requested");
+    IBH_REQUIRE(model >= 0 && model <= 2, "ibh_les_of: model must be 0 (none), 1 (Smagorinsky) or 2 (WALE)");
+    IBH_REQUIRE(model == 0 || Delta, "ibh_les_of: a model needs Delta");
+    IBH_REQUIRE(model == 0 || nusgs, "ibh_les_of: a model needs nusgs to write to");
+    IBH_REQUIRE(model != 0 || !nusgs, "ibh_les_of: nusgs requested without a model");
+    IBH_REQUIRE(ldv >= p->nc, "ibh_les_of: ldv < nc");
+    IBH_REQUIRE(!G || ldg >= p->nc, "ibh_les_of: ldg < nc");
+    IBH_REQUIRE(model != 2 || p->nd == 3, "ibh_les_of: WALE model only implemented for 3D");
+    if (p->nc == 0) return 0;
+    if (!fused::has_blocks(p)) return ibh_les_of_cells(p, vel, ldv, Delta, model, Cmodel, nusgs, ducros, shock, S, G, ldg);
+    IBH_REQUIRE(fused::all_blocks3(p), "ibh_les_of: needs a 3-D partition made of complete blocks or one without block "
+                                "structure (compose cell_gradient and the pointwise closures otherwise)");
+    FieldPtrs<3> V{{vel, vel + ldv, vel + 2 * ldv}};
+    const les_dev::Outputs O{nusgs, ducros, shock, S, G, ldg};
+    const int32_t nwg = (p->nblk + 3) / 4;
+#define LES3_LAUNCH(M_)                                                                                                  \
+    hipLaunchKernelGGL(k_les_of3<M_>, dim3(nwg), dim3(256), 0, ibh_stream, p->blocks3, p->htab3, p->ftab3, p->nblk, nwg, V, \
+                       Delta, Cmodel, O)
+    if (model == 0) LES3_LAUNCH(0);
+    else if (model == 1) LES3_LAUNCH(1);
+    else LES3_LAUNCH(2);
+#undef LES3_LAUNCH
     IBH_LAUNCH_CHECK();
     return 0;
 }

@@ -142,6 +142,85 @@ def shear_rate_of_velocity(part, vel, gradients=False):
     return (S, B.cell_gradient(part, vel)) if gradients else S
 
 
+_LES_MODELS = {None: 0, "none": 0, "smagorinsky": 1, "wale": 2}
+
+
+def les_closure_of(part, vel, Delta=None, model=None, Cs=0.17, Cw=0.325, ducros=False, shock=False, shear=False,
+                   gradients=False):
+    """The LES closure of a velocity field from ``g[i][j] = cell_gradient(part, vel[:, i])[j]`` -- a dict with the requested
+    keys among
+
+    * ``nusgs``: ``Smagorinsky_nuSGS(Delta, shear_rate(g), Cs)`` (``model="smagorinsky"``, :134-137) or
+      ``WALE_nuSGS(Delta, g, Cw)`` (``model="wale"``, 3-D only, :292-337),
+    * ``ducros``: ``Ducros_sensor(g)`` (:253-283), ``shock``: ``CFD.shock_sensor(g)`` (cfd.jl:589-617),
+    * ``S``: ``shear_rate(g)`` (``shear=True``, :110-124),
+    * ``gradients``: ``cell_gradient(part, vel)``, the tuple over the dimensions of ``(nc, nd)`` views of one
+      ``(nc, nd * nd)`` buffer, as ``shear_rate_of_velocity(..., gradients=True)`` returns it --
+
+    in ONE launch where ``fused_closures_apply(part)`` (``ibh_les_of``: the gradients are consumed where they are made),
+    the composition of ``cell_gradient`` and the pointwise kernels elsewhere -- bit-identical.  ``vel`` may be a column view
+    of a state array (``P[:, 2:]``): it is read in place."""
+    from . import cfd
+    part = B._part(part)
+    if isinstance(model, str):
+        model = model.lower()
+    if model not in _LES_MODELS:
+        raise ValueError('model must be None, "smagorinsky" or "wale"')
+    m = _LES_MODELS[model]
+    if not (m or ducros or shock or shear or gradients):
+        raise ValueError("les_closure_of: nothing requested")
+    try:
+        v, nd, ldv = B._field(vel, part.nc)
+    except TypeError as e:
+        raise ValueError(str(e)) from None
+    if nd != part.nd:
+        raise ValueError("vel must be (nc, nd)")
+    if m == 2 and nd != 3:
+        raise ValueError("WALE model only implemented for 3D")
+    if m:
+        if Delta is None:
+            raise ValueError("les_closure_of: a model needs Delta")
+        try:
+            Delta = _vec(Delta, part.nc)
+        except TypeError as e:
+            raise ValueError(str(e)) from None
+    nc = part.nc
+    if fused_closures_apply(part):
+        out = {}
+        if m:
+            out["nusgs"] = B.colmajor_empty(nc)
+        if ducros:
+            out["ducros"] = B.colmajor_empty(nc)
+        if shock:
+            out["shock"] = B.colmajor_empty(nc)
+        if shear:
+            out["S"] = B.colmajor_empty(nc)
+        G = B.colmajor_empty(nc, nd * nd) if gradients else None
+        B._stream()
+        B.call("ibh_les_of", part.handle, B._ptr(v), ldv, B._ptr(Delta if m else None), m, _f(Cs if m == 1 else Cw),
+               B._ptr(out.get("nusgs")), B._ptr(out.get("ducros")), B._ptr(out.get("shock")), B._ptr(out.get("S")),
+               B._ptr(G), nc)
+        if gradients:
+            out["gradients"] = tuple(G[:, j * nd:(j + 1) * nd] for j in range(nd))
+        return out
+    g = [list(B.cell_gradient(part, v[:, i].contiguous())) for i in range(nd)]
+    out = {}
+    S = shear_rate(g) if (shear or m == 1) else None
+    if m == 1:
+        out["nusgs"] = Smagorinsky_nuSGS(Delta, S, Cs=Cs)
+    elif m == 2:
+        out["nusgs"] = WALE_nuSGS(Delta, g, Cw=Cw)
+    if ducros:
+        out["ducros"] = Ducros_sensor(g)
+    if shock:
+        out["shock"] = cfd.shock_sensor(g)
+    if shear:
+        out["S"] = S
+    if gradients:
+        out["gradients"] = B.cell_gradient(part, v)
+    return out
+
+
 def Wray_Agarwal_of(part, R, S, sigmaR=0.72, C1=0.0829, kappa=0.41):
     """``Wray_Agarwal(R, S, cell_gradient(part, R), cell_gradient(part, S))`` (:222-241): ONE launch on an all-block 3-D
     partition (``ibh_wray_agarwal_of``), the composition elsewhere -- bit-identical."""

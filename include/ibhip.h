@@ -522,6 +522,19 @@ int ibh_shear_rate_of_velocity(ibh_part*, const float* vel, int64_t ldv, float* 
 int ibh_shear_rate_of_velocity_grad(ibh_part*, const float* vel, int64_t ldv, float* S, float* G, int64_t ldg);
 int ibh_wray_agarwal_of(ibh_part*, const float* R, const float* S, float sigmaR, float C1, float kappa, float* nut,
                         float* nuR, float* Sout);
+/* The LES closure of a velocity field with the gradients consumed where they are made, one launch on the partitions of
+ * ibh_shear_rate_of_velocity_grad (an error otherwise: compose cell_gradient and the pointwise closures then).  With
+ * g[i][j] = cell_gradient(part, u_i)[j]:
+ *   nusgs  = Smagorinsky_nuSGS(Delta, shear_rate(g); Cs = Cmodel)   (model 1)            turbulence.jl:134-137
+ *          = WALE_nuSGS(Delta, g; Cw = Cmodel)                      (model 2, 3-D only)  turbulence.jl:292-337
+ *   ducros = Ducros_sensor(g)                                                            turbulence.jl:253-283
+ *   shock  = CFD.shock_sensor(g)                                                         cfd.jl:589-617
+ *   S      = shear_rate(g)                                                               turbulence.jl:110-124
+ *   G      = the gradients, (nc, nd * nd) with leading dimension ldg, d u_i / d x_j in column nd * j + i
+ * in the arithmetic of ibh_cell_gradient_nd and of the pointwise kernels (bit-identical to their composition).  model 0: no
+ * eddy viscosity (nusgs must be NULL); every output may be NULL, at least one is not; Delta (nc) is read with a model only. */
+int ibh_les_of(ibh_part*, const float* vel, int64_t ldv, const float* Delta, int model, float Cmodel, float* nusgs,
+               float* ducros, float* shock, float* S, float* G, int64_t ldg);
 int ibh_turb_ducros(int nd, int64_t n, const float* const* g, float* out);
 int ibh_turb_wale(int64_t n, const float* Delta, const float* const* g, float Cw, float* out);
 

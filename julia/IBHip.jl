@@ -838,6 +838,23 @@ function shear_rate_of_velocity!(S::HipArray{Float32}, G::HipArray{Float32, 2}, 
     S, G
 end
 
+"The LES closure of a velocity field in one launch, the gradients `g[i][j] = cell_gradient(part, vel[:, i])[j]` consumed where
+they are made (same partitions as `shear_rate_of_velocity!`): any of `νSGS` (`model = :smagorinsky`:
+`Smagorinsky_νSGS(Δ, shear_rate(g); Cs)`, src/turbulence.jl:134-137; `model = :wale`: `WALE_νSGS(Δ, g; Cw)`, :292-337, 3-D
+only), `ducros = Ducros_sensor(g)` (:253-283), `shock = CFD.shock_sensor(g)` (src/cfd.jl:589-617), `S = shear_rate(g)`
+(:110-124) and `G`, the gradients in the layout of `shear_rate_of_velocity!`.  Outputs left `nothing` are not written."
+function les_closure_of!(part::HipPartition, vel::HipArray{Float32}; Δ = nothing, model = nothing, Cs = 0.17f0,
+                         Cw = 0.325f0, νSGS = nothing, ducros = nothing, shock = nothing, S = nothing, G = nothing)
+    m = isnothing(model) ? 0 : model == :smagorinsky ? 1 : model == :wale ? 2 :
+        error("les_closure_of!: model must be nothing, :smagorinsky or :wale")
+    p(a) = isnothing(a) ? C_NULL : a.ptr
+    check(ccall((:ibh_les_of, lib), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Cint, Cfloat, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64),
+        part.handle, vel.ptr, ld(vel), p(Δ), Cint(m), Float32(m == 1 ? Cs : Cw), p(νSGS), p(ducros), p(shock), p(S), p(G),
+        isnothing(G) ? Int64(0) : ld(G)))
+    (νSGS = νSGS, ducros = ducros, shock = shock, S = S, gradients = G)
+end
+
 "`Wray_Agarwal(R, S, cell_gradient(part, R), cell_gradient(part, S))` (src/turbulence.jl:222-241) in one launch; returns
 `(νt = nut, νR = nuR, S = Sout)` written into the three arrays."
 function wray_agarwal_of!(nut::HipArray{Float32}, nuR::HipArray{Float32}, Sout::HipArray{Float32}, part::HipPartition,
