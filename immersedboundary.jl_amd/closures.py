@@ -110,6 +110,89 @@ def navier_stokes_wray_agarwal_residual(part, Q, nu=1.5e-5, fluid=None, out=None
     return r
 
 
+def k_epsilon_boundary_conditions(dom, Q, far, wall_name="sphere", far_name="farfield", fluid=None, Tu=0.10, Cmu=0.09,
+                                  k_inf=None, eps_inf=None, fused=False):
+    """The boundary conditions of a level of a k-epsilon RANS run, ``impose_bc!`` on that level's own ``Boundary`` structs in
+    the order a solver script would write them (``config5_boundary_conditions`` with two turbulence scalars):
+
+    * far field: ``FlowBC(fluid, [p, T, u, v, (w)])`` on the primitives (cfd.jl:243-300); ``k`` and ``eps`` take the free-stream
+      values of ``standard_kϵ``'s docstring (turbulence.jl:166-172), ``k_inf = 3 (U_inf Tu)^2 / 2`` and
+      ``eps_inf = Cmu k_inf^2 / (3 nu_inf)`` with ``Tu = 0.10``, ``nu_inf = mu(T_inf) / rho_inf``;
+    * immersed wall: slip wall ``FlowBC(fluid, [p, T, 0]; normal_flow = true)`` with ``du!dn`` from
+      ``wall_function(y, u, nu)`` (turbulence.jl:72-98) at the image points, and the wall function's ``k`` and ``epsilon`` as
+      the values of the two scalars.
+
+    ``Q = [p T u v (w) k eps]`` (global device array of the level, updated in place).  ``fused``: each of the two calls as one
+    launch per boundary partition (``impose_flow_bc``), bit-identical to the composition."""
+    import numpy as np
+    from . import cfd
+    fluid = fluid or cfd.Fluid()
+    nd = dom.ndims
+    if Q.shape[1] != nd + 4:
+        raise ValueError(f"Q must be (n, {nd + 4}) = [p T u v (w) k eps]")
+    P, k, eps = Q[:, :nd + 2], Q[:, nd + 2], Q[:, nd + 3]
+    free = cfd.FlowBC(fluid, far)
+    wall = cfd.FlowBC(fluid, [far[0], far[1], 0.0], normal_flow=True)
+    if k_inf is None:
+        U = float(np.sqrt(sum(float(x) ** 2 for x in far[2:2 + nd])))
+        k_inf = 1.5 * (U * float(Tu)) ** 2
+    if eps_inf is None:
+        import torch
+        T_inf = torch.full((1,), float(far[1]), dtype=torch.float32, device=Q.device)
+        nu_inf = float(cfd.dynamic_viscosity(fluid, T_inf)[0]) / (float(far[0]) / (fluid.R * float(far[1])))
+        eps_inf = float(Cmu) * float(k_inf) ** 2 / (3.0 * nu_inf)
+    k_inf, eps_inf = float(k_inf), float(eps_inf)
+    if fused:
+        B.impose_flow_bc(dom, far_name, free, P, scalars=[(k, k_inf), (eps, eps_inf)])
+        B.impose_flow_bc(dom, wall_name, wall, P, scalars=[(k, "k"), (eps, "epsilon")], wall_function={})
+        return
+    B.impose_bc(lambda b, Pi, ki, ei: (free(Pi, b.normals), k_inf, eps_inf), dom, far_name, P, k, eps)
+
+    def wall_bc(b, Pi, ki, ei):
+        # the glue lines column by column, left to right in Float32 (HipArray broadcasts: the IEEE elementwise kernels), as
+        # the fused launch evaluates them: the two forms agree bit for bit
+        from .hiparray import HipArray as H
+        u = [H(Pi[:, 2 + j]) for j in range(nd)]
+        nn = [H(b.normals[:, j]) for j in range(nd)]
+        rho = H((H(Pi[:, 0]) / (fluid.R * H(Pi[:, 1]))).t)
+        nu = H((H(cfd.dynamic_viscosity(fluid, Pi[:, 1].contiguous())) / rho).t)
+        un = u[0] * nn[0]
+        for j in range(1, nd):
+            un = un + u[j] * nn[j]
+        un = H(un.t)
+        t2 = None
+        for j in range(nd):
+            t = H((u[j] - un * nn[j]).t)
+            t2 = t * t if t2 is None else t2 + t * t
+        ut = H(t2.t).sqrt().t
+        wf = T.wall_function(b.image_distances, ut, nu.t)
+        return wall(Pi, b.normals, du_dn=wf["du_dn"], image_distances=b.image_distances), wf["k"], wf["epsilon"]
+    B.impose_bc(wall_bc, dom, wall_name, P, k, eps)
+
+
+def navier_stokes_k_epsilon_residual(part, Q, nu=1.5e-5, fluid=None, out=None):
+    """``Q = [p T u v (w) k eps]`` -> residual of the same shape: Euler HLL sweep (``ibh_residual_euler_hll``) + the viscous
+    fluxes with the eddy viscosity (cfd.jl:664-736, one launch: ``ibh_viscous_residual``) + the two transport equations of the
+    standard k-epsilon model (turbulence.jl:175-194), written straight into the last two columns by ``k_epsilon_rhs`` -- one
+    launch where the fused closures apply, which also leaves the velocity gradients for the viscous sum.  Four launches on
+    an all-block partition: the Euler sweep, ``ibh_k_epsilon_rhs``, one broadcast for ``mu_t = rho nu_t``, the viscous sum."""
+    from . import cfd
+    from .hiparray import HipArray
+    fluid = fluid or cfd.Fluid()
+    nd = part.nd
+    nvp = nd + 2
+    if Q.shape[1] != nvp + 2:
+        raise ValueError(f"Q must be (nc, {nvp + 2}) = [p T u v (w) k eps]")
+    r = out if out is not None else B.colmajor_empty(Q.shape[0], nvp + 2)
+    P = Q[:, :nvp]
+    B.residual_euler_hll(part, P, out=r[:, :nvp])
+    ke = T.k_epsilon_rhs(part, Q[:, 2:2 + nd], Q[:, nvp], Q[:, nvp + 1], float(nu), out_k=r[:, nvp], out_eps=r[:, nvp + 1],
+                         gradients=True)
+    mut = (HipArray(Q[:, 0]) / (HipArray(Q[:, 1]) * fluid.R) * HipArray(ke["nut"])).t   # mu_t = rho nu_t, one launch
+    cfd.viscous_residual(part, fluid, P, ke["gradients"], mut, r[:, :nvp], velocity_gradients_only=True)
+    return r
+
+
 def navier_stokes_les_residual(part, P, Delta, fluid=None, model="wale", out=None):
     """``P = [p T u v (w)]`` -> residual of the compressible Navier-Stokes equations with an LES eddy viscosity, the script a
     user of the reference would write:

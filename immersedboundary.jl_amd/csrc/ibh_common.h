@@ -200,6 +200,9 @@ extern "C" int ibh_wray_agarwal_of_cells(const ibh_part* p, const float* R, cons
                                          float kappa, float* nut, float* nuR, float* Sout);
 extern "C" int ibh_les_of_cells(const ibh_part* p, const float* vel, int64_t ldv, const float* Delta, int model, float Cmodel,
                                 float* nusgs, float* ducros, float* shock, float* S, float* G, int64_t ldg);
+extern "C" int ibh_k_epsilon_rhs_cells(const ibh_part* p, const float* vel, int64_t ldv, const float* k, const float* eps,
+                                       float nu, const float* params5, float* rk, float* reps, float* nut, float* S, float* G,
+                                       int64_t ldg);
 
 // internal: the boundary-condition set with the next step's time step beside it (ibh_ops.hip), called from ibh_fused.hip
 extern "C" int ibh_bcset_apply_with_dt(const ibh_bcset* s, float* a, ibh_part* p, const float* C, int64_t ldc, float scale,

@@ -9,6 +9,7 @@
 #include "ibh_bcset_dev.h"
 #include "ibh_common.h"
 #include "ibh_les_dev.h"
+#include "ibh_transport_dev.h"
 
 #define OPS_BLOCK 256
 #include "ibh_dt_dev.h"
@@ -276,6 +277,47 @@ __global__ void k_les_of_cells(int32_t nc, GradDims G, const float* __restrict__
 #pragma unroll
                 for (int j = 0; j < ND; ++j) O.G[(int64_t)(ND * j + i) * O.ldg + c] = g[i][j];
         }
+    }
+}
+// the right-hand sides of the standard k-epsilon model (ibh_k_epsilon_rhs), face-list partitions: the gradients as in
+// k_shear_of_velocity_cells, standard_kϵ with the expressions of ibh_turb.hip's k_keps, then both transport sums in one walk
+// over the cell's faces (tr_dev::cell_sum: the walk and the flux of k_scalar_transport).  The diffusivity nu + nut / sigma of
+// the cell across a face is made from that cell's own k and eps -- the bits the composition reads back from nuk / nue.
+template <int ND>
+__global__ void k_k_epsilon_rhs_cells(int32_t nc, GradDims G, const float* __restrict__ vel, int64_t ldv,
+                                      const float* __restrict__ kf, const float* __restrict__ ef, float nu, tr_dev::KEps P,
+                                      float* __restrict__ rk, float* __restrict__ reps, float* __restrict__ nut,
+                                      float* __restrict__ Sout, float* __restrict__ Gout, int64_t ldg) {
+    for (int64_t c = IBH_WG_X() * (int64_t)blockDim.x + threadIdx.x; c < nc; c += (int64_t)gridDim.x * blockDim.x) {
+        int32_t sd[2 * ND];
+#pragma unroll
+        for (int s = 0; s < 2 * ND; ++s) sd[s] = G.side[(int64_t)s * nc + c];
+        float g[ND][ND];
+#pragma unroll
+        for (int i = 0; i < ND; ++i) cell_gradient_at<ND>(G, sd, nc, (int32_t)c, vel + (int64_t)i * ldv, g[i]);
+        const float S = les_dev::shear_rate<ND>(g);
+        if (Sout) Sout[c] = S;   // (uniform, as every branch on an output pointer)
+        if (Gout) {              // d u_i / d x_j in column ND j + i (the tuple cell_gradient's layout)
+#pragma unroll
+            for (int i = 0; i < ND; ++i)
+#pragma unroll
+                for (int j = 0; j < ND; ++j) Gout[(int64_t)(ND * j + i) * ldg + c] = g[i][j];
+        }
+        const float kk = kf[c], ee = ef[c];
+        const float nt = tr_dev::keps_nut(P, kk, ee);
+        const float Pk = nt * (S * S);
+        if (nut) nut[c] = nt;
+        float rt[2] = {tr_dev::keps_Sk(Pk, ee), tr_dev::keps_Se(P, Pk, kk, ee)};
+        tr_dev::cell_sum<ND, 2>(G.d, G.h, sd, (int32_t)c, [&](int d, int32_t o, int32_t n, float (&f)[2]) {
+            const float ho = G.h[d][o], hn = G.h[d][n];
+            const float ko = kf[o], kn = kf[n], eo = ef[o], en = ef[n];
+            const float vo = vel[(int64_t)d * ldv + o], vn = vel[(int64_t)d * ldv + n];
+            const float nto = tr_dev::keps_nut(P, ko, eo), ntn = tr_dev::keps_nut(P, kn, en);
+            f[0] = tr_dev::flux(ko, kn, nu + nto / P.sk, nu + ntn / P.sk, vo * ko, vn * kn, ho, hn);
+            f[1] = tr_dev::flux(eo, en, nu + nto / P.se, nu + ntn / P.se, vo * eo, vn * en, ho, hn);
+        }, rt);
+        rk[c] = rt[0];
+        reps[c] = rt[1];
     }
 }
 template <int ND>
@@ -737,6 +779,20 @@ int ibh_les_of_cells(const ibh_part* p, const float* vel, int64_t ldv, const flo
     else
         hipLaunchKernelGGL(k_les_of_cells<3>, grid2(p->nc, 1), dim3(OPS_BLOCK), 0, ibh_stream, p->nc, G, vel, ldv, Delta, model,
                            Cmodel, O);
+    IBH_LAUNCH_CHECK();
+    return 0;
+}
+
+int ibh_k_epsilon_rhs_cells(const ibh_part* p, const float* vel, int64_t ldv, const float* k, const float* eps, float nu,
+                            const float* params5, float* rk, float* reps, float* nut, float* S, float* Gout, int64_t ldg) {
+    const GradDims G = grad_dims(p);
+    const tr_dev::KEps P{params5[0], params5[1], params5[2], params5[3], params5[4]};
+    if (p->nd == 2)
+        hipLaunchKernelGGL(k_k_epsilon_rhs_cells<2>, grid2(p->nc, 1), dim3(OPS_BLOCK), 0, ibh_stream, p->nc, G, vel, ldv, k, eps,
+                           nu, P, rk, reps, nut, S, Gout, ldg);
+    else
+        hipLaunchKernelGGL(k_k_epsilon_rhs_cells<3>, grid2(p->nc, 1), dim3(OPS_BLOCK), 0, ibh_stream, p->nc, G, vel, ldv, k, eps,
+                           nu, P, rk, reps, nut, S, Gout, ldg);
     IBH_LAUNCH_CHECK();
     return 0;
 }

@@ -8,6 +8,7 @@
 #include "ibh_fused_int.h"
 #include "ibh_wall_dev.h"
 #include "ibh_les_dev.h"
+#include "ibh_transport_dev.h"
 
 namespace {
 
@@ -122,52 +123,23 @@ struct TransportDims {
     const float* vel[IBH_MAXD];
     const int32_t* side;      // side table of the partition: sides with one face are evaluated from the cell across
 };
-__device__ __forceinline__ float tr_face_avg(float uo, float un, float ho, float hn) { return (uo * hn + un * ho) / (hn + ho); }
 __device__ __forceinline__ float tr_flux_on(int32_t o, int32_t n, const float* __restrict__ h, const float* __restrict__ R,
                                             const float* __restrict__ nuR, const float* __restrict__ vel, float nu) {
-    const float ho = h[o], hn = h[n];
     const float Ro = R[o], Rn = R[n];
-    const float conv = tr_face_avg(vel[o] * Ro, vel[n] * Rn, ho, hn);       // at_faces(vel_d .* R)
-    const float nuf = tr_face_avg(nu + nuR[o], nu + nuR[n], ho, hn);        // at_faces(nu .+ nuR)
-    const float fd = (ho + hn) / 2.0f;                                      // face_distance
-    const float fg = (Rn - Ro) / fd;                                        // face_gradient(R)
-    return nuf * fg - conv;
-}
-__device__ __forceinline__ float tr_flux(const DimData& D, const float* __restrict__ h, const float* __restrict__ R,
-                                         const float* __restrict__ nuR, const float* __restrict__ vel, float nu, int32_t f) {
-    return tr_flux_on(D.owners[f], D.neighbors[f], h, R, nuR, vel, nu);
-}
-__device__ __forceinline__ float tr_mean(const int32_t* __restrict__ off, const int32_t* __restrict__ idx, int32_t c,
-                                         const DimData& D, const float* __restrict__ h, const float* __restrict__ R,
-                                         const float* __restrict__ nuR, const float* __restrict__ vel, float nu) {
-    const int32_t b = off[c], e = off[c + 1];
-    if (e == b) return 0.0f;
-    const float w = 1.0f / (float)(e - b);
-    float s = tr_flux(D, h, R, nuR, vel, nu, idx[b]) * w;
-    for (int32_t k = b + 1; k < e; ++k) s = s + tr_flux(D, h, R, nuR, vel, nu, idx[k]) * w;
-    return s;
+    return tr_dev::flux(Ro, Rn, nu + nuR[o], nu + nuR[n], vel[o] * Ro, vel[n] * Rn, h[o], h[n]);
 }
 template <int ND>
 __global__ void k_scalar_transport(int32_t nc, TransportDims T, const float* __restrict__ R, const float* __restrict__ nuR,
                                    float nu, const float* __restrict__ S, float* __restrict__ out) {
     for (int64_t c = IBH_WG_X() * (int64_t)blockDim.x + threadIdx.x; c < nc; c += (int64_t)gridDim.x * blockDim.x) {
-        float rt = S[c];
+        float rt[1] = {S[c]};
         int32_t sd[2 * ND];
 #pragma unroll
         for (int s = 0; s < 2 * ND; ++s) sd[s] = T.side[(int64_t)s * nc + c];
-#pragma unroll
-        for (int d = 0; d < ND; ++d) {
-            const int32_t l = sd[2 * d], r = sd[2 * d + 1];
-            float ar, al;
-            if (r >= 0) ar = tr_flux_on((int32_t)c, r, T.h[d], R, nuR, T.vel[d], nu) * 1.0f;
-            else if (r == -2) ar = 0.0f;
-            else ar = tr_mean(T.d[d].roff, T.d[d].ridx, (int32_t)c, T.d[d], T.h[d], R, nuR, T.vel[d], nu);
-            if (l >= 0) al = tr_flux_on(l, (int32_t)c, T.h[d], R, nuR, T.vel[d], nu) * 1.0f;
-            else if (l == -2) al = 0.0f;
-            else al = tr_mean(T.d[d].loff, T.d[d].lidx, (int32_t)c, T.d[d], T.h[d], R, nuR, T.vel[d], nu);
-            rt = rt + (ar - al) / T.h[d][c];
-        }
-        out[c] = rt;
+        tr_dev::cell_sum<ND, 1>(T.d, T.h, sd, (int32_t)c, [&](int d, int32_t o, int32_t n, float (&f)[1]) {
+            f[0] = tr_flux_on(o, n, T.h[d], R, nuR, T.vel[d], nu);
+        }, rt);
+        out[c] = rt[0];
     }
 }
 
@@ -321,56 +293,28 @@ __global__ __launch_bounds__(256) void k_les_of3(const BlockDesc3* __restrict__ 
 // -- one, or the mean of four behind a FINE side -- and leaves it for the boundary cell.  The expressions and their order
 // are those of the face-list kernel (no contraction): equal bit for bit wherever a side has one face.
 #define TR3_LDS (4 * 512 + 384)
-__device__ __forceinline__ float tr3_avg(float uo, float un, float ho, float hn) { return (uo * hn + un * ho) / (hn + ho); }
-__device__ __forceinline__ float tr3_flux(float Ro, float Rn, float To, float Tn, float Ao, float An, float ho, float hn) {
-    const float conv = tr3_avg(Ao, An, ho, hn);   // at_faces(u_d .* R)
-    const float nuf = tr3_avg(To, Tn, ho, hn);    // at_faces(nu .+ nuR)
-    const float fd = (ho + hn) / 2.0f;            // face_distance
-    const float fg = (Rn - Ro) / fd;              // face_gradient(R)
-    return nuf * fg - conv;
-}
-__global__ __launch_bounds__(256) void k_scalar_transport_blocks3(const BlockDesc3* __restrict__ blocks,
-                                                                  const int32_t* __restrict__ htab,
-                                                                  const int32_t* __restrict__ ftab, int32_t nblk,
-                                                                  int32_t nwg, uint32_t nc, const float* __restrict__ hsp,
-                                                                  const float* __restrict__ R, const float* __restrict__ nuR,
-                                                                  float nu, const float* __restrict__ vel, uint32_t ldv,
-                                                                  const float* __restrict__ S, float* __restrict__ out) {
+// The transport sum of ONE scalar over one block, by one wavefront (the body of k_scalar_transport_blocks3; also run twice,
+// for k and for eps, by k_k_epsilon_rhs3).  The caller holds what every scalar over the block shares -- the block's
+// spacing h, the halo cells' spacing hh, the velocities of the own cells Vk and of the halo cells hV -- and the scalar's
+// own values: R and T = nu + nuR at the lane's eight cells (Rk, Tk) and at its six halo slots (hR, hT).  t_at(x) gives T
+// at any cell x (the three extra cells behind a FINE slot), src(k, c) the source term of cell c = plane k of this lane.
+template <class TAt, class Src>
+__device__ __forceinline__ void tr3_wave(const BlockDesc3& bb, const int32_t* __restrict__ ftab, uint32_t nc,
+                                         const float* __restrict__ hsp, float* lds, int lane, const float (&h)[3],
+                                         const float (&hh)[6], const float (&Vk)[3][8], const float (&hV)[6],
+                                         const float (&Rk)[8], const float (&Tk)[8], const float (&hR)[6],
+                                         const float (&hT)[6], const float* __restrict__ R, const float* __restrict__ vel,
+                                         uint32_t ldv, TAt t_at, Src src, float* __restrict__ out) {
     using blk2::ldg;
-    __shared__ float lds_all[4 * TR3_LDS];
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int32_t blk = __builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x, nwg) * 4 + wave);
-    if (blk >= nblk) return;
-    float* lds = lds_all + wave * TR3_LDS;
     float *tR = lds, *tT = lds + 512, *tAx = lds + 1024, *tAy = lds + 1536, *Hf = lds + 2048;
-    const BlockDesc3 bb = blocks[blk];
     const uint32_t base = (uint32_t)bb.base;
-    const float h[3] = {hsp[base], hsp[nc + base], hsp[2 * (size_t)nc + base]};   // the block's spacing as the cells hold it
-    float Rk[8], Tk[8], Ak[3][8];
+    float Ak[3][8], hA[6];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const uint32_t c = base + lane + 64 * k;
-        Rk[k] = ldg(R, c);
-        Tk[k] = nu + ldg(nuR, c);
+    for (int k = 0; k < 8; ++k)
 #pragma unroll
-        for (int d = 0; d < 3; ++d) Ak[d][k] = ldg(vel + (size_t)d * ldv, c) * Rk[k];
-    }
-    uint32_t hid[6];
-    hid[0] = blk3::halo_cell3s<0>(bb, htab, blk, lane);
-    hid[1] = blk3::halo_cell3s<1>(bb, htab, blk, lane);
-    hid[2] = blk3::halo_cell3s<2>(bb, htab, blk, lane);
-    hid[3] = blk3::halo_cell3s<3>(bb, htab, blk, lane);
-    hid[4] = blk3::halo_cell3s<4>(bb, htab, blk, lane);
-    hid[5] = blk3::halo_cell3s<5>(bb, htab, blk, lane);
-    float hR[6], hT[6], hA[6], hh[6];
+        for (int d = 0; d < 3; ++d) Ak[d][k] = Vk[d][k] * Rk[k];
 #pragma unroll
-    for (int s = 0; s < 6; ++s) {
-        const int d = s >> 1;
-        hR[s] = ldg(R, hid[s]);
-        hT[s] = nu + ldg(nuR, hid[s]);
-        hA[s] = ldg(vel + (size_t)d * ldv, hid[s]) * hR[s];
-        hh[s] = ldg(hsp + (size_t)d * nc, hid[s]);
-    }
+    for (int s = 0; s < 6; ++s) hA[s] = hV[s] * hR[s];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
         tR[k * 64 + lane] = Rk[k];
@@ -390,16 +334,16 @@ __global__ __launch_bounds__(256) void k_scalar_transport_blocks3(const BlockDes
         const float Ab = d == 0 ? tAx[pos] : d == 1 ? tAy[pos] : (low ? Ak[2][0] : Ak[2][7]);
         const float hb = h[d];
         // the halo cell is the owner on a low side, the neighbour on a high side
-        float F = low ? tr3_flux(hR[s], Rb, hT[s], Tb, hA[s], Ab, hh[s], hb) : tr3_flux(Rb, hR[s], Tb, hT[s], Ab, hA[s], hb, hh[s]);
+        float F = low ? tr_dev::flux(hR[s], Rb, hT[s], Tb, hA[s], Ab, hh[s], hb) : tr_dev::flux(Rb, hR[s], Tb, hT[s], Ab, hA[s], hb, hh[s]);
         if (bb.type[s] == SIDE_FINE) {  // wave-uniform: three more faces behind this slot, mean of the four fluxes
             const int32_t* ft = ftab + (((size_t)bb.fine * 6 + s) * 64 + lane) * 3;
             F = F * 0.25f;
 #pragma unroll
             for (int q = 0; q < 3; ++q) {
                 const uint32_t x = (uint32_t)ft[q];
-                const float Rx = ldg(R, x), Tx = nu + ldg(nuR, x), Ax = ldg(vel + (size_t)d * ldv, x) * Rx;
+                const float Rx = ldg(R, x), Tx = t_at(x), Ax = ldg(vel + (size_t)d * ldv, x) * Rx;
                 const float hx = ldg(hsp + (size_t)d * nc, x);
-                const float Fq = low ? tr3_flux(Rx, Rb, Tx, Tb, Ax, Ab, hx, hb) : tr3_flux(Rb, Rx, Tb, Tx, Ab, Ax, hb, hx);
+                const float Fq = low ? tr_dev::flux(Rx, Rb, Tx, Tb, Ax, Ab, hx, hb) : tr_dev::flux(Rb, Rx, Tb, Tx, Ab, Ax, hb, hx);
                 F = F + Fq * 0.25f;
             }
         } else {
@@ -419,24 +363,176 @@ __global__ __launch_bounds__(256) void k_scalar_transport_blocks3(const BlockDes
         float fl[3], fr[3];
         // x and y: inside the plane or the side's flux (x sides: slot j + 8 k, y sides: slot i + 8 k)
         const int xl = e0 ? lane : lane - 1, xr = e1 ? lane : lane + 1, yl = e2 ? lane : lane - 8, yr = e3 ? lane : lane + 8;
-        const float fxl = tr3_flux(r[xl], Rc, t[xl], Tc, ax[xl], Ak[0][k], h[0], h[0]) * 1.0f;
-        const float fxr = tr3_flux(Rc, r[xr], Tc, t[xr], Ak[0][k], ax[xr], h[0], h[0]) * 1.0f;
-        const float fyl = tr3_flux(r[yl], Rc, t[yl], Tc, ay[yl], Ak[1][k], h[1], h[1]) * 1.0f;
-        const float fyr = tr3_flux(Rc, r[yr], Tc, t[yr], Ak[1][k], ay[yr], h[1], h[1]) * 1.0f;
+        const float fxl = tr_dev::flux(r[xl], Rc, t[xl], Tc, ax[xl], Ak[0][k], h[0], h[0]) * 1.0f;
+        const float fxr = tr_dev::flux(Rc, r[xr], Tc, t[xr], Ak[0][k], ax[xr], h[0], h[0]) * 1.0f;
+        const float fyl = tr_dev::flux(r[yl], Rc, t[yl], Tc, ay[yl], Ak[1][k], h[1], h[1]) * 1.0f;
+        const float fyr = tr_dev::flux(Rc, r[yr], Tc, t[yr], Ak[1][k], ay[yr], h[1], h[1]) * 1.0f;
         fl[0] = e0 ? Hf[0 * 64 + j + 8 * k] : fxl;
         fr[0] = e1 ? Hf[1 * 64 + j + 8 * k] : fxr;
         fl[1] = e2 ? Hf[2 * 64 + i + 8 * k] : fyl;
         fr[1] = e3 ? Hf[3 * 64 + i + 8 * k] : fyr;
         // z: registers
         const int kl = k > 0 ? k - 1 : 0, kh = k < 7 ? k + 1 : 7;
-        const float fzl_in = tr3_flux(Rk[kl], Rc, Tk[kl], Tc, Ak[2][kl], Ak[2][k], h[2], h[2]) * 1.0f;
-        const float fzr_in = tr3_flux(Rc, Rk[kh], Tc, Tk[kh], Ak[2][k], Ak[2][kh], h[2], h[2]) * 1.0f;
+        const float fzl_in = tr_dev::flux(Rk[kl], Rc, Tk[kl], Tc, Ak[2][kl], Ak[2][k], h[2], h[2]) * 1.0f;
+        const float fzr_in = tr_dev::flux(Rc, Rk[kh], Tc, Tk[kh], Ak[2][k], Ak[2][kh], h[2], h[2]) * 1.0f;
         fl[2] = k == 0 ? fzl : fzl_in;
         fr[2] = k == 7 ? fzh : fzr_in;
-        float rt = ldg(S, c);
+        float rt = src(k, c);
 #pragma unroll
         for (int d = 0; d < 3; ++d) rt = rt + (fr[d] - fl[d]) / h[d];
         out[c] = rt;
+    }
+}
+// what every scalar transported over a block shares: halo ids, spacings, velocities -- loaded once
+struct Tr3Shared {
+    uint32_t hid[6];
+    float h[3], hh[6], Vk[3][8], hV[6];
+};
+__device__ __forceinline__ void tr3_shared(const BlockDesc3& bb, const int32_t* __restrict__ htab, int32_t blk, int lane,
+                                           uint32_t nc, const float* __restrict__ hsp, const float* __restrict__ vel,
+                                           uint32_t ldv, Tr3Shared& W) {
+    using blk2::ldg;
+    const uint32_t base = (uint32_t)bb.base;
+    W.h[0] = hsp[base];                      // the block's spacing as the cells hold it
+    W.h[1] = hsp[nc + base];
+    W.h[2] = hsp[2 * (size_t)nc + base];
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+#pragma unroll
+        for (int d = 0; d < 3; ++d) W.Vk[d][k] = ldg(vel + (size_t)d * ldv, base + lane + 64 * k);
+    W.hid[0] = blk3::halo_cell3s<0>(bb, htab, blk, lane);
+    W.hid[1] = blk3::halo_cell3s<1>(bb, htab, blk, lane);
+    W.hid[2] = blk3::halo_cell3s<2>(bb, htab, blk, lane);
+    W.hid[3] = blk3::halo_cell3s<3>(bb, htab, blk, lane);
+    W.hid[4] = blk3::halo_cell3s<4>(bb, htab, blk, lane);
+    W.hid[5] = blk3::halo_cell3s<5>(bb, htab, blk, lane);
+#pragma unroll
+    for (int s = 0; s < 6; ++s) {
+        const int d = s >> 1;
+        W.hV[s] = ldg(vel + (size_t)d * ldv, W.hid[s]);
+        W.hh[s] = ldg(hsp + (size_t)d * nc, W.hid[s]);
+    }
+}
+__global__ __launch_bounds__(256) void k_scalar_transport_blocks3(const BlockDesc3* __restrict__ blocks,
+                                                                  const int32_t* __restrict__ htab,
+                                                                  const int32_t* __restrict__ ftab, int32_t nblk,
+                                                                  int32_t nwg, uint32_t nc, const float* __restrict__ hsp,
+                                                                  const float* __restrict__ R, const float* __restrict__ nuR,
+                                                                  float nu, const float* __restrict__ vel, uint32_t ldv,
+                                                                  const float* __restrict__ S, float* __restrict__ out) {
+    using blk2::ldg;
+    __shared__ float lds_all[4 * TR3_LDS];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int32_t blk = __builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x, nwg) * 4 + wave);
+    if (blk >= nblk) return;
+    const BlockDesc3 bb = blocks[blk];
+    Tr3Shared W;
+    tr3_shared(bb, htab, blk, lane, nc, hsp, vel, ldv, W);
+    float Rk[8], Tk[8], hR[6], hT[6];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const uint32_t c = (uint32_t)bb.base + lane + 64 * k;
+        Rk[k] = ldg(R, c);
+        Tk[k] = nu + ldg(nuR, c);
+    }
+#pragma unroll
+    for (int s = 0; s < 6; ++s) {
+        hR[s] = ldg(R, W.hid[s]);
+        hT[s] = nu + ldg(nuR, W.hid[s]);
+    }
+    tr3_wave(bb, ftab, nc, hsp, lds_all + wave * TR3_LDS, lane, W.h, W.hh, W.Vk, W.hV, Rk, Tk, hR, hT, R, vel, ldv,
+             [=](uint32_t x) { return nu + ldg(nuR, x); }, [=](int, uint32_t c) { return ldg(S, c); }, out);
+}
+
+// ---- the right-hand sides of the standard k-epsilon model on an all-block 3-D partition in one launch (ibh_k_epsilon_rhs):
+//   S = shear_rate(g), (nuk, nue, Sk, Se, nut) = standard_kϵ(k, eps, S)                       (turbulence.jl:110-124, :175-194)
+//   rk = Sk + transport(k; nu + nuk),  reps = Se + transport(eps; nu + nue)                   (tr3_wave above)
+// One wavefront per 8^3 block.  Stage 1: blk3::wave_gradients on the velocities -> S of the lane's eight cells (G stored on
+// the way when asked); only the production nut S^2 stays live.  Stage 2: tr3_wave for k, then for eps, in a loop that is
+// not unrolled (one copy of the body, one scalar's registers).  nut = Cmu k^2 / eps is pointwise, so the diffusivity of a
+// neighbour cell is made from that cell's own k and eps with the expressions of k_keps -- the bits the composition reads
+// back from the nuk / nue arrays -- and nuk, nue, Sk, Se never exist in memory: 20 B in + 8 B (+ 4 B nut) out per cell.
+// The LDS tile of the wave is reused between the stages (max(BLK3W_PASSA_LDS, TR3_LDS) floats).
+#define KE3_LDS (TR3_LDS > BLK3W_PASSA_LDS ? TR3_LDS : BLK3W_PASSA_LDS)
+__global__ __launch_bounds__(256) void k_k_epsilon_rhs3(const BlockDesc3* __restrict__ blocks, const int32_t* __restrict__ htab,
+                                                        const int32_t* __restrict__ ftab, int32_t nblk, int32_t nwg,
+                                                        uint32_t nc, const float* __restrict__ hsp,
+                                                        const float* __restrict__ vel, uint32_t ldv,
+                                                        const float* __restrict__ kf, const float* __restrict__ ef, float nu,
+                                                        tr_dev::KEps P, float* __restrict__ rk, float* __restrict__ reps,
+                                                        float* __restrict__ nut, float* __restrict__ Sout,
+                                                        float* __restrict__ Gout, uint32_t ldg_) {
+    using blk2::ldg;
+    __shared__ float lds_all[4 * KE3_LDS];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int32_t blk = __builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x, nwg) * 4 + wave);
+    if (blk >= nblk) return;
+    const BlockDesc3 bb = blocks[blk];
+    float* wl = lds_all + wave * KE3_LDS;
+    const uint32_t base = (uint32_t)bb.base;
+    float Pk[8];   // S, then the production nut S^2
+    {
+        const FieldPtrs<3> V{{vel, vel + ldv, vel + 2 * (size_t)ldv}};
+        float g[3][8][3];
+        blk3::wave_gradients<3>(bb, htab, ftab, blk, V.f, wl, lane, g);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const uint32_t c = base + lane + 64 * k;
+            float t[3][3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = 0; j < 3; ++j) t[i][j] = g[i][k][j];
+            Pk[k] = les_dev::shear_rate<3>(t);
+            if (Sout) Sout[c] = Pk[k];   // (uniform, as every branch on an output pointer)
+            if (Gout) {                  // d u_i / d x_j in column 3 j + i (the tuple cell_gradient's layout)
+#pragma unroll
+                for (int i = 0; i < 3; ++i)
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) __builtin_nontemporal_store(t[i][j], Gout + (size_t)(3 * j + i) * ldg_ + c);
+            }
+        }
+    }
+    Tr3Shared W;
+    tr3_shared(bb, htab, blk, lane, nc, hsp, vel, ldv, W);
+    float kk[8], ee[8], nt[8], hk[6], he[6], hnt[6];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const uint32_t c = base + lane + 64 * k;
+        kk[k] = ldg(kf, c);
+        ee[k] = ldg(ef, c);
+        nt[k] = tr_dev::keps_nut(P, kk[k], ee[k]);
+        Pk[k] = nt[k] * (Pk[k] * Pk[k]);
+        if (nut) nut[c] = nt[k];
+    }
+#pragma unroll
+    for (int s = 0; s < 6; ++s) {
+        hk[s] = ldg(kf, W.hid[s]);
+        he[s] = ldg(ef, W.hid[s]);
+        hnt[s] = tr_dev::keps_nut(P, hk[s], he[s]);
+    }
+#pragma unroll 1
+    for (int q = 0; q < 2; ++q) {
+        blk2::wave_lds_sync();   // the LDS reads of the stage before are done: the tile takes this scalar
+        const bool second = q != 0;   // (uniform)
+        const float* __restrict__ R = second ? ef : kf;
+        float* __restrict__ out = second ? reps : rk;
+        const float sg = second ? P.se : P.sk;
+        float Rk[8], Tk[8], hR[6], hT[6];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            Rk[k] = second ? ee[k] : kk[k];
+            Tk[k] = nu + nt[k] / sg;
+        }
+#pragma unroll
+        for (int s = 0; s < 6; ++s) {
+            hR[s] = second ? he[s] : hk[s];
+            hT[s] = nu + hnt[s] / sg;
+        }
+        tr3_wave(bb, ftab, nc, hsp, wl, lane, W.h, W.hh, W.Vk, W.hV, Rk, Tk, hR, hT, R, vel, ldv,
+                 [=](uint32_t x) { return nu + tr_dev::keps_nut(P, ldg(kf, x), ldg(ef, x)) / sg; },
+                 [&](int k, uint32_t) { return second ? tr_dev::keps_Se(P, Pk[k], kk[k], ee[k]) : tr_dev::keps_Sk(Pk[k], ee[k]); },
+                 out);
     }
 }
 
@@ -632,6 +728,25 @@ int ibh_les_of(ibh_part* p, const float* vel, int64_t ldv, const float* Delta, i
     else if (model == 1) LES3_LAUNCH(1);
     else LES3_LAUNCH(2);
 #undef LES3_LAUNCH
+    IBH_LAUNCH_CHECK();
+    return 0;
+}
+
+// The right-hand sides of the standard k-epsilon model in one launch (dispatch as ibh_les_of)
+int ibh_k_epsilon_rhs(ibh_part* p, const float* vel, int64_t ldv, const float* k, const float* eps, float nu,
+                      const float* params5, float* rk, float* reps, float* nut, float* S, float* G, int64_t ldg) {
+    IBH_REQUIRE(p && vel && k && eps && params5 && rk && reps, "ibh_k_epsilon_rhs: null argument");
+    IBH_REQUIRE(ldv >= p->nc, "ibh_k_epsilon_rhs: ldv < nc");
+    IBH_REQUIRE(!G || ldg >= p->nc, "ibh_k_epsilon_rhs: ldg < nc");
+    if (p->nc == 0) return 0;
+    IBH_REQUIRE(p->nd == 2 || p->nd == 3, "ibh_k_epsilon_rhs: the partition is neither 2-D nor 3-D");
+    if (!fused::has_blocks(p)) return ibh_k_epsilon_rhs_cells(p, vel, ldv, k, eps, nu, params5, rk, reps, nut, S, G, ldg);
+    IBH_REQUIRE(fused::all_blocks3(p), "ibh_k_epsilon_rhs: needs a 3-D partition made of complete blocks or one without block "
+                                "structure (compose shear_rate_of_velocity, standard_k_epsilon and scalar_transport otherwise)");
+    const tr_dev::KEps P{params5[0], params5[1], params5[2], params5[3], params5[4]};
+    const int32_t nwg = (p->nblk + 3) / 4;
+    hipLaunchKernelGGL(k_k_epsilon_rhs3, dim3(nwg), dim3(256), 0, ibh_stream, p->blocks3, p->htab3, p->ftab3, p->nblk, nwg,
+                       (uint32_t)p->nc, p->spacing, vel, (uint32_t)ldv, k, eps, nu, P, rk, reps, nut, S, G, (uint32_t)ldg);
     IBH_LAUNCH_CHECK();
     return 0;
 }

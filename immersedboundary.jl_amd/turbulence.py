@@ -259,6 +259,75 @@ def scalar_transport(part, R, nuR, vel, nu, S, out=None):
     return out
 
 
+def k_epsilon_rhs(part, vel, k, eps, nu, Cmu=0.09, sigma_k=1.0, sigma_eps=1.3, C1eps=1.44, C2eps=1.92, out_k=None,
+                  out_eps=None, shear=False, gradients=False):
+    """The right-hand sides of the standard k-epsilon model (:175-194),
+
+        k_t   = -div(u k)   + div[(nu + nu_k)   grad k]   + S_k
+        eps_t = -div(u eps) + div[(nu + nu_eps) grad eps] + S_eps,
+
+    from ``g[i][j] = cell_gradient(part, vel[:, i])[j]``: with ``ke = standard_k_epsilon(k, eps, shear_rate(g), ...)``,
+
+    * ``rk = scalar_transport(part, k, ke["nuk"], vel, nu, ke["Sk"])``,
+    * ``reps = scalar_transport(part, eps, ke["nueps"], vel, nu, ke["Seps"])``,
+    * ``nut = ke["nut"]``, and when asked ``S = shear_rate(g)`` (``shear=True``) and ``gradients``: ``cell_gradient(part, vel)``,
+      the tuple over the dimensions of ``(nc, nd)`` views, as ``les_closure_of`` returns it --
+
+    in ONE launch where ``fused_closures_apply(part)`` (``ibh_k_epsilon_rhs``: ``nut = Cmu k^2 / eps`` is pointwise, so a
+    neighbour's diffusivity is made from the neighbour's own ``k`` and ``eps`` and ``nuk, nueps, Sk, Seps`` are never
+    written), that four-call composition elsewhere -- bit-identical.  ``vel``, ``k`` and ``eps`` may be column views of a state
+    array (``Q[:, 2:2 + nd]``, ``Q[:, nd + 2]``): they are read in place; ``out_k`` / ``out_eps`` may be columns of a residual."""
+    part = B._part(part)
+    nc = part.nc
+    try:
+        v, nd, ldv = B._field(vel, nc)
+        k, eps = _vec(k, nc), _vec(eps, nc)
+    except TypeError as e:
+        raise ValueError(str(e)) from None
+    if nd != part.nd:
+        raise ValueError("vel must be (nc, nd)")
+    outs = []
+    for o, what in ((out_k, "out_k"), (out_eps, "out_eps")):
+        if o is None:
+            o = B.colmajor_empty(nc)
+        else:
+            try:
+                o, nvo, _ = B._field_inplace(o, nc, what)
+            except TypeError as e:
+                raise ValueError(str(e)) from None
+            if nvo != 1 or o.ndim != 1:
+                raise ValueError(f"{what} must be a vector")
+        outs.append(o)
+    rk, reps = outs
+    if fused_closures_apply(part):
+        nut = B.colmajor_empty(nc)
+        S = B.colmajor_empty(nc) if shear else None
+        G = B.colmajor_empty(nc, nd * nd) if gradients else None
+        par = _params(Cmu, sigma_k, sigma_eps, C1eps, C2eps)
+        B._stream()
+        B.call("ibh_k_epsilon_rhs", part.handle, B._ptr(v), ldv, B._ptr(k), B._ptr(eps), _f(nu), C.cast(par, B.c_vp),
+               B._ptr(rk), B._ptr(reps), B._ptr(nut), B._ptr(S), B._ptr(G), nc)
+        out = dict(rk=rk, reps=reps, nut=nut)
+        if shear:
+            out["S"] = S
+        if gradients:
+            out["gradients"] = tuple(G[:, j * nd:(j + 1) * nd] for j in range(nd))
+        return out
+    if gradients:
+        S, gV = shear_rate_of_velocity(part, v, gradients=True)
+    else:
+        S = shear_rate_of_velocity(part, v)
+    ke = standard_k_epsilon(k, eps, S, Cmu=Cmu, sigma_k=sigma_k, sigma_eps=sigma_eps, C1eps=C1eps, C2eps=C2eps)
+    scalar_transport(part, k, ke["nuk"], v, float(nu), ke["Sk"], out=rk)
+    scalar_transport(part, eps, ke["nueps"], v, float(nu), ke["Seps"], out=reps)
+    out = dict(rk=rk, reps=reps, nut=ke["nut"])
+    if shear:
+        out["S"] = S
+    if gradients:
+        out["gradients"] = gV
+    return out
+
+
 def Ducros_sensor(velocity_gradient):
     """:252-282"""
     nd, n, keep, tab = _grad_table(velocity_gradient)

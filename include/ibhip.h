@@ -535,6 +535,20 @@ int ibh_wray_agarwal_of(ibh_part*, const float* R, const float* S, float sigmaR,
  * eddy viscosity (nusgs must be NULL); every output may be NULL, at least one is not; Delta (nc) is read with a model only. */
 int ibh_les_of(ibh_part*, const float* vel, int64_t ldv, const float* Delta, int model, float Cmodel, float* nusgs,
                float* ducros, float* shock, float* S, float* G, int64_t ldg);
+/* The right-hand sides of the standard k-epsilon model (turbulence.jl:175-194) in ONE launch (dispatch as ibh_les_of):
+ *   k_t   = -div(u k)   + div[(nu + nu_k)   grad k]   + S_k
+ *   eps_t = -div(u eps) + div[(nu + nu_eps) grad eps] + S_eps
+ * with g[i][j] = cell_gradient(part, vel_i)[j]:
+ *   S    = shear_rate(g)                                                                       turbulence.jl:110-124
+ *   (nuk, nue, Sk, Se, nut) = standard_kϵ(k, eps, S; params5...)                               turbulence.jl:175-194
+ *   rk   = Sk + sum_d green_gauss(at_faces(nu + nuk, d) .* face_gradient(k, d)   .- at_faces(vel_d .* k, d),   d)
+ *   reps = Se + sum_d green_gauss(at_faces(nu + nue, d) .* face_gradient(eps, d) .- at_faces(vel_d .* eps, d), d)
+ *   G    = the gradients, (nc, nd * nd) with leading dimension ldg, d u_i / d x_j in column nd * j + i
+ * bit-identical to ibh_shear_rate_of_velocity_grad, ibh_turb_k_epsilon and two ibh_scalar_transport; nuk, nue, Sk and Se are
+ * never written (nut = Cmu k^2 / eps is pointwise: a neighbour's diffusivity is made from the neighbour's own k and eps).
+ * params5 (host) = {Cmu, sigma_k, sigma_eps, C1eps, C2eps} as for ibh_turb_k_epsilon; nut, S and G may be NULL. */
+int ibh_k_epsilon_rhs(ibh_part*, const float* vel, int64_t ldv, const float* k, const float* eps, float nu,
+                      const float* params5, float* rk, float* reps, float* nut, float* S, float* G, int64_t ldg);
 int ibh_turb_ducros(int nd, int64_t n, const float* const* g, float* out);
 int ibh_turb_wale(int64_t n, const float* Delta, const float* const* g, float Cw, float* out);
 

@@ -855,6 +855,22 @@ function les_closure_of!(part::HipPartition, vel::HipArray{Float32}; Δ = nothin
     (νSGS = νSGS, ducros = ducros, shock = shock, S = S, gradients = G)
 end
 
+"The right-hand sides of the standard k-ϵ model (src/turbulence.jl:175-194) in one launch (same partitions as
+`shear_rate_of_velocity!`): `rk = Sk + transport(k; ν + νk)` and `rϵ = Sϵ + transport(ϵ; ν + νϵ)` with
+`(νk, νϵ, Sk, Sϵ, νₜ) = standard_kϵ(k, ϵ, shear_rate(g))`, `g[i][j] = cell_gradient(part, vel[:, i])[j]`; `νₜ`, `S` and the
+gradients `G` (layout of `shear_rate_of_velocity!`) are written when given."
+function k_epsilon_rhs!(rk::HipArray{Float32}, rϵ::HipArray{Float32}, part::HipPartition, vel::HipArray{Float32},
+                        k::HipArray{Float32}, ϵ::HipArray{Float32}, ν::Real; Cμ::Real = 0.09f0, σk::Real = 1.0f0,
+                        σϵ::Real = 1.3f0, C1ϵ::Real = 1.44f0, C2ϵ::Real = 1.92f0, νₜ = nothing, S = nothing, G = nothing)
+    p(a) = isnothing(a) ? C_NULL : a.ptr
+    par = Float32[Cμ, σk, σϵ, C1ϵ, C2ϵ]
+    check(ccall((:ibh_k_epsilon_rhs, lib), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Cfloat, Ptr{Float32}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64),
+        part.handle, vel.ptr, ld(vel), k.ptr, ϵ.ptr, Float32(ν), par, rk.ptr, rϵ.ptr, p(νₜ), p(S), p(G),
+        isnothing(G) ? Int64(0) : ld(G)))
+    (rk = rk, rϵ = rϵ, νₜ = νₜ, S = S, gradients = G)
+end
+
 "`Wray_Agarwal(R, S, cell_gradient(part, R), cell_gradient(part, S))` (src/turbulence.jl:222-241) in one launch; returns
 `(νt = nut, νR = nuR, S = Sout)` written into the three arrays."
 function wray_agarwal_of!(nut::HipArray{Float32}, nuR::HipArray{Float32}, Sout::HipArray{Float32}, part::HipPartition,
