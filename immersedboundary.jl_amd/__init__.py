@@ -23,6 +23,6 @@ def __getattr__(name):
         return getattr(backend, name)
     if name == "HipArray":
         return getattr(importlib.import_module(__name__ + ".hiparray"), name)
-    if name == "FAS":
-        return importlib.import_module(__name__ + ".solver").FAS
+    if name in ("FAS", "EulerMarch"):
+        return getattr(importlib.import_module(__name__ + ".solver"), name)
     raise AttributeError(name)

@@ -95,6 +95,9 @@ _SIGS = {
     "ibh_update_dev": [c_i64, c_vp, c_vp, c_vp, c_vp],
     "ibh_step_advection": [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp],
     "ibh_step_advection_dt": [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, C.c_float, c_vp],
+    "ibh_timestep_euler": [c_vp, C.POINTER(ibh_fluid), c_vp, c_i64, C.c_float, c_vp, c_vp],
+    "ibh_update_euler": [C.POINTER(ibh_fluid), c_int, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_vp, c_i64],
+    "ibh_step_euler": [c_vp, C.POINTER(ibh_fluid), c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_vp, c_i64, c_int],
     "ibh_ew_binary": [c_int, c_i64, c_int, c_vp, c_int, C.c_float, c_vp, c_int, C.c_float, c_vp],
     "ibh_ew_unary": [c_int, c_i64, c_vp, c_vp],
     "ibh_ew_fill": [c_i64, C.c_float, c_vp],

@@ -772,6 +772,114 @@ def residual_euler_sensor(part, P, nu=None, out=None, flags=0, fluid=None):
 
 
 # ---------------------------------------------------------------------------
+# an explicit Euler step, device resident (rows of P: [p T u v (w)])
+# ---------------------------------------------------------------------------
+IBH_EULER_HLL, IBH_EULER_SENSOR = 0, 1
+_EULER_SCHEMES = {"hll": IBH_EULER_HLL, "sensor": IBH_EULER_SENSOR}
+
+
+def _cfluid(fluid):
+    """``ibh_fluid`` of a ``cfd.Fluid`` (None: air, the defaults of cfd.jl:14-53)."""
+    if fluid is None:
+        from .cfd import Fluid
+        fluid = Fluid()
+    return fluid._c()
+
+
+def _primitives(P, n, nd=None):
+    P, nv, ldp = _field(P, n)
+    if (nd is not None and nv != nd + 2) or nv not in (4, 5):
+        raise ValueError("P must be (n, nd+2) = [p T u v (w)]")
+    return P, nv, ldp
+
+
+def _device_dt(dt, n, what):
+    """(tensor, per_cell) of a time step: a one-element Float32 device tensor, or ``(n,)`` for a per-cell time step."""
+    if not isinstance(dt, torch.Tensor) or not dt.is_cuda or dt.dtype != torch.float32:
+        raise TypeError(f"{what}: dt must be a Float32 device tensor (timestep_euler gives one): the step never reads it back")
+    if dt.numel() == 1:
+        return dt.reshape(1), 0
+    if dt.ndim == 1 and dt.shape[0] == n and dt.stride(0) == 1:
+        return dt, 1
+    raise ValueError(f"{what}: dt has shape {tuple(dt.shape)}; expected one element or ({n},) for a per-cell time step")
+
+
+@_hipaware
+def timestep_euler(part, P, fluid=None, scale=1.0, out=None, cells=None):
+    """The CFL time step of an explicit Euler step, ``scale * 0.5 / maximum(max.(unsigned_green_gauss(part, at_faces(part,
+    C_d, d), d) ...))`` with ``C_d = abs.(u_d) .+ speed_of_sound(fluid, T)`` (test/advection.jl:52-59, :65), evaluated from
+    ``P`` on the fly: bit for bit ``timestep_advection`` on the materialised ``C``, without the array and without a host
+    read-back.  Returns the one-element device tensor (``out`` if given).  ``cells``: an ``(nc,)`` device array that
+    receives the local time step ``scale * 0.5 / max_d(...)[c]`` of every cell; with ``cells`` and ``out=False`` only that
+    is computed (one launch) and ``cells`` is returned."""
+    part = _part(part)
+    P, _, ldp = _primitives(P, part.nc, part.nd)
+    if cells is not None:
+        cells, nvc, _ = _field_inplace(cells, part.nc, "cells")
+        if nvc != 1 or cells.ndim != 1:
+            raise ValueError("cells must be (nc,)")
+    if out is False:
+        if cells is None:
+            raise ValueError("timestep_euler: out=False needs cells")
+        dt = None
+    else:
+        dt = out if out is not None else torch.empty(1, dtype=torch.float32, device=P.device)
+        if not isinstance(dt, torch.Tensor) or not dt.is_cuda or dt.dtype != torch.float32 or dt.numel() != 1:
+            raise TypeError("out must be a one-element Float32 device tensor")
+    f = _cfluid(fluid)
+    _stream()
+    call("ibh_timestep_euler", part.handle, C.byref(f), _ptr(P), ldp, C.c_float(scale), _ptr(dt), _ptr(cells))
+    return dt if dt is not None else cells
+
+
+@_hipaware
+def update_euler(P, R, dt, fluid=None, out=None):
+    """``state2primitive(fluid, primitive2state(fluid, P) .+ dt .* R)`` in one launch (bit for bit the three).  ``dt``: a
+    one-element device tensor, or ``(n,)`` for a per-cell time step.  ``out`` may be ``P`` itself (in place)."""
+    P, nv, ldp = _primitives(P, None)
+    n = P.shape[0]
+    R, nvr, ldr = _field(R, n)
+    if nvr != nv:
+        raise ValueError(f"R must be (n, {nv})")
+    dt, per_cell = _device_dt(dt, n, "update_euler")
+    if out is None:
+        out = colmajor_empty(n, nv)
+    o, nvo, ldo = _field_inplace(out, n, "out")
+    if nvo != nv:
+        raise ValueError(f"out must be (n, {nv})")
+    f = _cfluid(fluid)
+    _stream()
+    call("ibh_update_euler", C.byref(f), nv - 2, n, _ptr(P), ldp, _ptr(R), ldr, _ptr(dt), per_cell, _ptr(o), ldo)
+    return out
+
+
+@_hipaware
+def step_euler(part, P, dt, out, fluid=None, scheme="hll", work=None, flags=0):
+    """One explicit Euler step ``out = update_euler(P, residual_euler_hll | residual_euler_sensor(part, P, flags), dt)``
+    (``scheme``: "hll" or "sensor").  One launch where the 2-D single-kernel sweep takes the whole partition, ``dt`` is one
+    element and ``out`` is not ``P``; elsewhere the sweep goes into ``work`` -- ``(nc, nd+2)``, required there: the step
+    allocates nothing -- and the update follows (``out`` may be ``P`` then).  Same bits either way."""
+    part = _part(part)
+    P, nv, ldp = _primitives(P, part.nc, part.nd)
+    dt, per_cell = _device_dt(dt, part.nc, "step_euler")
+    o, nvo, ldo = _field_inplace(out, part.nc, "out")
+    if nvo != nv:
+        raise ValueError(f"out must be (nc, {nv})")
+    w, ldw = None, 0
+    if work is not None:
+        w, nvw, ldw = _field_inplace(work, part.nc, "work")
+        if nvw != nv:
+            raise ValueError(f"work must be (nc, {nv})")
+    if scheme not in _EULER_SCHEMES:
+        raise ValueError('scheme must be "hll" or "sensor"')
+    f = _cfluid(fluid)
+    _stream()
+    call("ibh_step_euler", part.handle, C.byref(f), _EULER_SCHEMES[scheme], _ptr(P), ldp, _ptr(o), ldo, _ptr(dt), per_cell,
+         _ptr(w), ldw, int(flags))
+    return out
+
+
+# ---------------------------------------------------------------------------
 # partition runtime and ghost-cell BC
 # ---------------------------------------------------------------------------
 def domain_call(dom, f, args, conv_to_backend, conv_from_backend, kwargs):

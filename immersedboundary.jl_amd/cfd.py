@@ -119,6 +119,13 @@ def state2primitive(fluid, Q):
     return P
 
 
+# the explicit Euler step around the fused sweeps (ibh_timestep_euler / ibh_update_euler / ibh_step_euler): defined with the
+# other fused entries in backend.py, reachable from here beside the pointwise functions they compose
+timestep_euler = B.timestep_euler
+update_euler = B.update_euler
+step_euler = B.step_euler
+
+
 def inviscid_fluxes(fluid, PL, PR, *args):
     """``inviscid_fluxes(fluid, PL, PR, dim)`` (HLL, cfd.jl:459-508) or
     ``inviscid_fluxes(fluid, PL, PR, nuL, nuR, dim)`` (sensor/Rusanov, cfd.jl:516-554)."""

@@ -1,4 +1,4 @@
-// libibhip: device bodies of the time-step evaluation of an explicit advection step (ibh_timestep_advection, ibh_ops.hip), with
+// libibhip: device bodies of the time-step evaluation of an explicit step (ibh_timestep_advection, ibh_timestep_euler: ibh_ops.hip), with
 // the workgroup's index and count as arguments: the same code runs as its own launches and beside the BC-set workgroups of a
 // march step (ibh_ops.hip: k_bcinterp_dt / k_bcscatter_dt).
 #pragma once
@@ -11,10 +11,11 @@ namespace dt_dev {
 
 // at_faces (:907-909): (u_o*h_n + u_n*h_o)/(h_n + h_o)
 __device__ __forceinline__ float dt_face_avg(float uo, float un, float ho, float hn) { return (uo * hn + un * ho) / (hn + ho); }
+template <class Load>
 __device__ __forceinline__ float dt_csr_mean_face_avg(const int32_t* __restrict__ off, const int32_t* __restrict__ idx,
                                                       int32_t c, const int32_t* __restrict__ own,
                                                       const int32_t* __restrict__ nei, const float* __restrict__ h,
-                                                      const float* __restrict__ u) {
+                                                      const Load& load, int d) {
     int32_t b = off[c], e = off[c + 1];
     if (e == b) return 0.0f;
     float w = 1.0f / (float)(e - b);
@@ -22,7 +23,7 @@ __device__ __forceinline__ float dt_csr_mean_face_avg(const int32_t* __restrict_
     for (int32_t k = b; k < e; ++k) {
         int32_t f = idx[k];
         int32_t o = own[f], n = nei[f];
-        float t = dt_face_avg(u[o], u[n], h[o], h[n]) * w;
+        float t = dt_face_avg(load(d, o), load(d, n), h[o], h[n]) * w;
         s = (k == b) ? t : s + t;
     }
     return s;
@@ -44,11 +45,31 @@ inline GradDims grad_dims(const ibh_part* p) {
     return G;
 }
 
+// Loaders: load(d, c) = the field value of cell c in dimension d.  ArrayLoad reads an (nc, nd) array (the advection script's
+// C); AcousticLoad computes |u_d| + a from the primitives P = [p T u v (w)] on the fly -- abs(u_d) + sqrt(gamma R max(T, 10)),
+// the arithmetic of k_pointwise mode 0 (ibh_cfd.hip) and of the IEEE broadcasts abs and + --, so that no (nc, nd) array of
+// wave speeds is ever written (ibh_timestep_euler).
+struct ArrayLoad {
+    const float* __restrict__ C;
+    int64_t ldc;
+    __device__ __forceinline__ float operator()(int d, int64_t c) const { return (C + (int64_t)d * ldc)[c]; }
+};
+struct AcousticLoad {
+    const float* __restrict__ P;
+    int64_t ldp;
+    float Rgas, gamma;
+    __device__ __forceinline__ float operator()(int d, int64_t c) const {
+        return fabsf(P[(int64_t)(2 + d) * ldp + c]) + sqrtf(gamma * Rgas * ibh_max(P[ldp + c], 10.0f));
+    }
+};
+
 // (device bodies with the workgroup's index and count as arguments: the same code runs as its own launch and beside the
 // BC-set workgroups of a march step, k_bcinterp_dt / k_bcscatter_dt below)
-template <int ND, bool TILED>
-__device__ __forceinline__ void dt_partial_wg(int wg, int nwg, int32_t nc, const GradDims& G, const float* __restrict__ C,
-                                              int64_t ldc, float* __restrict__ partial) {
+// CELLS: the local time step of every cell, (0.5 / max_d(...)[c]) * scale, goes to dt_cells as well
+template <int ND, bool TILED, class Load, bool CELLS = false>
+__device__ __forceinline__ void dt_partial_wg(int wg, int nwg, int32_t nc, const GradDims& G, const Load& load,
+                                              float* __restrict__ partial, float scale = 1.0f,
+                                              float* __restrict__ dt_cells = nullptr) {
     // Julia's maximum has no floor at zero: the maximum starts below every value (an all-negative C gives a negative dt).
     // fmaxf stays -- it drops a NaN where Julia's max keeps it; ibh_max here cost the march 6.5 %
     float m = -INFINITY;
@@ -67,20 +88,23 @@ __device__ __forceinline__ void dt_partial_wg(int wg, int nwg, int32_t nc, const
                 sd[s] = inb ? (int32_t)c + ((s & 1) ? st : -st) : G.side[(int64_t)s * nc + c];
             } else sd[s] = G.side[(int64_t)s * nc + c];
         }
+        float mc = -INFINITY;
 #pragma unroll
         for (int d = 0; d < ND; ++d) {
-            const float* Cd = C + (int64_t)d * ldc;
-            const float hc = G.h[d][c], uc = Cd[c];
+            const float hc = G.h[d][c], uc = load(d, c);
             const int32_t l = sd[2 * d], r = sd[2 * d + 1];
             float ar, al;
-            if (r >= 0) ar = dt_face_avg(uc, Cd[r], hc, G.h[d][r]) * 1.0f;
+            if (r >= 0) ar = dt_face_avg(uc, load(d, r), hc, G.h[d][r]) * 1.0f;
             else if (r == -2) ar = 0.0f;
-            else ar = dt_csr_mean_face_avg(G.d[d].roff, G.d[d].ridx, (int32_t)c, G.d[d].owners, G.d[d].neighbors, G.h[d], Cd);
-            if (l >= 0) al = dt_face_avg(Cd[l], uc, G.h[d][l], hc) * 1.0f;
+            else ar = dt_csr_mean_face_avg(G.d[d].roff, G.d[d].ridx, (int32_t)c, G.d[d].owners, G.d[d].neighbors, G.h[d], load, d);
+            if (l >= 0) al = dt_face_avg(load(d, l), uc, G.h[d][l], hc) * 1.0f;
             else if (l == -2) al = 0.0f;
-            else al = dt_csr_mean_face_avg(G.d[d].loff, G.d[d].lidx, (int32_t)c, G.d[d].owners, G.d[d].neighbors, G.h[d], Cd);
-            m = fmaxf(m, (ar + al) / hc);
+            else al = dt_csr_mean_face_avg(G.d[d].loff, G.d[d].lidx, (int32_t)c, G.d[d].owners, G.d[d].neighbors, G.h[d], load, d);
+            const float g = (ar + al) / hc;
+            m = fmaxf(m, g);
+            if constexpr (CELLS) mc = fmaxf(mc, g);
         }
+        if constexpr (CELLS) dt_cells[c] = (0.5f / mc) * scale;  // (the expression of dt_final_wg, per cell)
     }
     m = ibh_red::wg_reduce<DT_BLOCK, ibh_red::FMax>(m);
     if (threadIdx.x == 0) partial[wg] = m;

@@ -146,6 +146,42 @@ int ibh_residual_euler_sensor(ibh_part* p, const float* P, int64_t ldp, const fl
                           "eligible for the single-kernel sweep; run the sweep unphased after the exchange");
 }
 
+// One explicit Euler step, P_out = state2primitive(primitive2state(P) + dt * R(P)).  Where the 2-D single-kernel sweep takes
+// the whole partition (EUL2_SINGLE without image / phase flags), with a global dt and P_out != P, the sweep's STEP form
+// stores the update itself: one launch.  Everywhere else -- 3-D, face-list or mixed partitions, a per-cell dt, IBH_FORCE_GENERAL,
+// IBH_NO_FUSE, P_out == P -- the sweep goes into `work` (nc x (nd + 2), leading dimension ldw) and ibh_update_euler runs:
+// two launches.  Either way the result is bit for bit ibh_update_euler(P, ibh_residual_euler_{hll,sensor}(P, flags), dt).
+int ibh_step_euler(ibh_part* p, const ibh_fluid* fluid, int scheme, const float* P, int64_t ldp, float* P_out, int64_t ldo,
+                   const float* dt, int dt_per_cell, float* work, int64_t ldw, int flags) {
+    IBH_REQUIRE(p && fluid && P && P_out && dt, "ibh_step_euler: null argument");
+    IBH_REQUIRE(scheme == EULER_HLL || scheme == EULER_SENSOR, "ibh_step_euler: scheme must be 0 (HLL) or 1 (sensor)");
+    IBH_REQUIRE(!(flags & IBH_IMAGE_ONLY),
+                "ibh_step_euler: IBH_IMAGE_ONLY is not taken: the update would read skirt rows that the sweep never wrote "
+                "(the multi-GPU step is out of scope)");
+    IBH_REQUIRE(!(flags & F_PHASES),
+                "ibh_step_euler: the overlap phases IBH_PHASE_INTERIOR / IBH_PHASE_BOUNDARY are not taken: the update would "
+                "read rows that the phase never wrote");
+    IBH_REQUIRE(!(flags & (IBH_PASS_A_ONLY | IBH_PASS_B_ONLY)), "ibh_step_euler: a single pass of the sweep is no step");
+    IBH_REQUIRE(p->nd == 2 || p->nd == 3, "ibh_step_euler: nd must be 2 or 3");
+    IBH_REQUIRE(ldp >= p->nc && ldo >= p->nc, "ibh_step_euler: a leading dimension is smaller than the number of cells");
+    if (p->nc == 0) return 0;
+    EulerArgs e{P, ldp, P_out, ldo, fluid, scheme == EULER_SENSOR ? EULER_SENSOR : EULER_HLL};
+    if (euler_path(p, flags, e) == EUL2_SINGLE && p->fuse_all && !dt_per_cell && P_out != P) {
+        e.dt = dt;
+        euler2_single(p, e, flags, Phase(0));
+        IBH_LAUNCH_CHECK();
+        return 0;
+    }
+    IBH_REQUIRE(work, "ibh_step_euler: this partition / these arguments take the two-launch form (sweep into `work`, then "
+                      "ibh_update_euler): work must be nc x (nd + 2) floats");
+    IBH_REQUIRE(ldw >= p->nc, "ibh_step_euler: ldw is smaller than the number of cells");
+    IBH_REQUIRE(work != P && work != P_out, "ibh_step_euler: work may not alias P or P_out");
+    const int rc = scheme == EULER_SENSOR ? ibh_residual_euler_sensor(p, P, ldp, nullptr, work, ldw, fluid, flags)
+                                          : ibh_residual_euler_hll(p, P, ldp, work, ldw, fluid, flags);
+    if (rc) return rc;
+    return ibh_update_euler(fluid, p->nd, p->nc, P, ldp, work, ldw, dt, dt_per_cell, P_out, ldo);
+}
+
 // One step, u_out = u + dt * residual: in one launch where the quad sweep covers the whole partition (it stores the update,
 // its cells of u are in registers), the sweep and the update one after the other elsewhere.
 int ibh_step_advection(ibh_part* p, const float* u, float* u_out, const float* C, int64_t ldc, const float* dt_dev,

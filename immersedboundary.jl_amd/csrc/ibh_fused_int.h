@@ -80,6 +80,7 @@ struct AdvArgs { const float *u, *C; int64_t ldc; float* ud; };
 struct EulerArgs {  // (the entries' fields)
     const float* P; int64_t ldp; float* R; int64_t ldr; const ibh_fluid* fluid;
     EulerScheme scheme = EULER_HLL; const float* nu = nullptr;
+    const float* dt = nullptr;  // ibh_step_euler on a single-kernel path: R is P_out, the sweep stores the updated primitives
 };
 
 // ---- advection: paths

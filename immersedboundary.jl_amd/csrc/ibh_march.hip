@@ -7,6 +7,8 @@
 //   * ibh_timestep_advection (ibh_ops.hip): dt = scale * 0.5 / max over cells and dimensions of
 //     unsigned_green_gauss(at_faces(C_d, d), d) (advection.jl:52-59) left in device memory -- no host read-back in the loop.
 // The step itself (sweep + u += dt ud in one launch) is ibh_step_advection in ibh_fused.hip.
+//   * ibh_update_euler: P_out = state2primitive(primitive2state(P) + dt R) in one launch (euler_step::update_row); the Euler
+//     step around it is ibh_step_euler in ibh_fused.hip, its time step ibh_timestep_euler in ibh_ops.hip.
 // Arithmetic: the operator kernels' (ibh_ops.hip): -ffp-contract=off, the reference's evaluation order.
 #include <algorithm>
 #include <cstdlib>
@@ -14,6 +16,7 @@
 
 #include "ibh_bcset_dev.h"
 #include "ibh_common.h"
+#include "ibh_euler_step_dev.h"
 
 #define MARCH_BLOCK 256
 
@@ -104,6 +107,29 @@ __global__ void k_update_dev(int64_t n, const float* __restrict__ dt, const floa
     const float h = *dt;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
         out[i] = u[i] + r[i] * h;
+}
+
+// P_out = state2primitive(primitive2state(P) + dt R), one thread per row: the row is read whole before it is written, so
+// P_out may be P (no __restrict__ on the two).  dt: one value, or one per row (PER_CELL)
+template <int ND, bool PER_CELL>
+__global__ __launch_bounds__(MARCH_BLOCK) void k_update_euler(float Rgas, float gamma, int64_t n, const float* P, int64_t ldp,
+                                                              const float* __restrict__ R, int64_t ldr,
+                                                              const float* __restrict__ dt, float* P_out, int64_t ldo) {
+    constexpr int NV = ND + 2;
+    float h = 0.0f;
+    if constexpr (!PER_CELL) h = *dt;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        float Pr[NV], r[NV], o[NV];
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+            Pr[v] = P[i + v * ldp];
+            r[v] = R[i + v * ldr];
+        }
+        if constexpr (PER_CELL) h = dt[i];
+        euler_step::update_row<ND>(Rgas, gamma, Pr, r, h, o);
+#pragma unroll
+        for (int v = 0; v < NV; ++v) P_out[i + v * ldo] = o[v];
+    }
 }
 
 }  // namespace
@@ -255,6 +281,30 @@ int ibh_update_dev(int64_t n, const float* dt_dev, const float* u, const float* 
     if (n <= 0) return 0;
     hipLaunchKernelGGL(k_update_dev, dim3(std::min(ibh_grid(n, MARCH_BLOCK), 2048)), dim3(MARCH_BLOCK), 0, ibh_stream, n,
                        dt_dev, u, r, out);
+    IBH_LAUNCH_CHECK();
+    return 0;
+}
+
+// P_out = state2primitive(primitive2state(P) + dt * R): the three launches and three passes over nd + 2 columns of the
+// composition in one.  dt: one device value, or n of them (dt_per_cell: the local time step of a pseudo-time march)
+int ibh_update_euler(const ibh_fluid* f, int nd, int64_t n, const float* P, int64_t ldp, const float* R, int64_t ldr,
+                     const float* dt, int dt_per_cell, float* P_out, int64_t ldo) {
+    IBH_REQUIRE(f && P && R && dt && P_out, "ibh_update_euler: null argument");
+    IBH_REQUIRE(nd == 2 || nd == 3, "ibh_update_euler: nd must be 2 or 3");
+    IBH_REQUIRE(n >= 0 && ldp >= n && ldr >= n && ldo >= n, "ibh_update_euler: a leading dimension is smaller than n");
+    IBH_REQUIRE(P_out != R && P != R, "ibh_update_euler: R may not alias P or P_out (P_out may be P)");
+    if (n == 0) return 0;
+    const dim3 grid(ibh_grid_cap(n, MARCH_BLOCK, 2048)), block(MARCH_BLOCK);
+#define UPD_LAUNCH(ND_, PC_) \
+    hipLaunchKernelGGL((k_update_euler<ND_, PC_>), grid, block, 0, ibh_stream, f->R, f->gamma, n, P, ldp, R, ldr, dt, P_out, ldo)
+    if (nd == 2) {
+        if (dt_per_cell) UPD_LAUNCH(2, true);
+        else UPD_LAUNCH(2, false);
+    } else {
+        if (dt_per_cell) UPD_LAUNCH(3, true);
+        else UPD_LAUNCH(3, false);
+    }
+#undef UPD_LAUNCH
     IBH_LAUNCH_CHECK();
     return 0;
 }

@@ -160,7 +160,16 @@ __global__ void k_cell_gradient_all(int32_t nc, GradDims G, const float* __restr
 template <int ND, bool TILED>
 __global__ __launch_bounds__(OPS_BLOCK) void k_timestep_advection(int32_t nc, GradDims G, const float* __restrict__ C,
                                                                   int64_t ldc, float* __restrict__ partial) {
-    dt_partial_wg<ND, TILED>(blockIdx.x, gridDim.x, nc, G, C, ldc, partial);
+    dt_partial_wg<ND, TILED>(blockIdx.x, gridDim.x, nc, G, dt_dev::ArrayLoad{C, ldc}, partial);
+}
+// the same for the acoustic wave speeds |u_d| + a of P = [p T u v (w)], computed on the fly (ibh_timestep_euler); CELLS: the
+// local time step of every cell as well
+template <int ND, bool TILED, bool CELLS>
+__global__ __launch_bounds__(OPS_BLOCK) void k_timestep_euler(int32_t nc, GradDims G, const float* __restrict__ P, int64_t ldp,
+                                                              float Rgas, float gamma, float* __restrict__ partial,
+                                                              float scale, float* __restrict__ dt_cells) {
+    dt_partial_wg<ND, TILED, dt_dev::AcousticLoad, CELLS>(blockIdx.x, gridDim.x, nc, G,
+                                                          dt_dev::AcousticLoad{P, ldp, Rgas, gamma}, partial, scale, dt_cells);
 }
 __global__ __launch_bounds__(OPS_BLOCK) void k_dt_from_partials(int n, const float* __restrict__ partial, float scale,
                                                                 float* __restrict__ dt) {
@@ -182,7 +191,7 @@ __global__ __launch_bounds__(OPS_BLOCK) void k_bcinterp_dt(int nwg_bc, BcLaunch 
     if ((int)blockIdx.x < nwg_bc)
         bcset_dev::interp_wg(blockIdx.x, nwg_bc, B.g0, B.g1, B.eta, B.off, B.donor, B.w, B.bidx, B.mode, B.value, a, B.gval,
                              B.ghost_direct, a);
-    else dt_partial_wg<ND, TILED>(blockIdx.x - nwg_bc, gridDim.x - nwg_bc, nc, G, C, ldc, partial);
+    else dt_partial_wg<ND, TILED>(blockIdx.x - nwg_bc, gridDim.x - nwg_bc, nc, G, dt_dev::ArrayLoad{C, ldc}, partial);
 }
 __global__ __launch_bounds__(OPS_BLOCK) void k_bcscatter_dt(int nwg_bc, BcLaunch B, float* a, int npart,
                                                             const float* __restrict__ partial, float scale,
@@ -825,6 +834,44 @@ int ibh_timestep_advection(ibh_part* p, const float* C, int64_t ldc, float scale
     }
 #undef DT_LAUNCH
     hipLaunchKernelGGL(k_dt_from_partials, dim3(1), dim3(OPS_BLOCK), 0, ibh_stream, nwg, p->march_tmp, scale, dt_dev);
+    IBH_LAUNCH_CHECK();
+    return 0;
+}
+
+// The CFL time step of an explicit Euler step: the advection script's formula above with the acoustic speed C_d = |u_d| + a in
+// place of C, evaluated from P by the loader (no wave-speed array); bit for bit ibh_timestep_advection on the materialised
+// C.  dt_device: the global time step; dt_cells: (0.5 / max_d(...)[c]) * scale per cell; either may be null, not both.  Two
+// launches like ibh_timestep_advection, one when only dt_cells is asked for.
+int ibh_timestep_euler(ibh_part* p, const ibh_fluid* f, const float* P, int64_t ldp, float scale, float* dt_device,
+                       float* dt_cells) {
+    IBH_REQUIRE(p && f && P, "ibh_timestep_euler: null argument");
+    IBH_REQUIRE(dt_device || dt_cells, "ibh_timestep_euler: null dt_device and dt_cells (one of them must be given)");
+    IBH_REQUIRE(p->nd == 2 || p->nd == 3, "ibh_timestep_euler: nd must be 2 or 3");
+    IBH_REQUIRE(p->nc > 0, "ibh_timestep_euler: empty partition");
+    IBH_REQUIRE(ldp >= p->nc, "ibh_timestep_euler: ldp is smaller than the number of cells");
+    IBH_HIP(ensure_march_tmp(p));
+    const GradDims G = grad_dims(p);
+    const int nwg = ibh_grid_cap(p->nc, OPS_BLOCK, 8192);
+    const bool tiled = p->info[20] != 0;
+#define DT_LAUNCH(ND_, T_, C_)                                                                                           \
+    hipLaunchKernelGGL((k_timestep_euler<ND_, T_, C_>), dim3(nwg), dim3(OPS_BLOCK), 0, ibh_stream, p->nc, G, P, ldp, f->R, \
+                       f->gamma, p->march_tmp, scale, dt_cells)
+#define DT_LAUNCH_C(ND_, T_)            \
+    do {                                \
+        if (dt_cells) DT_LAUNCH(ND_, T_, true); \
+        else DT_LAUNCH(ND_, T_, false); \
+    } while (0)
+    if (p->nd == 2) {
+        if (tiled) DT_LAUNCH_C(2, true);
+        else DT_LAUNCH_C(2, false);
+    } else {
+        if (tiled) DT_LAUNCH_C(3, true);
+        else DT_LAUNCH_C(3, false);
+    }
+#undef DT_LAUNCH_C
+#undef DT_LAUNCH
+    if (dt_device)
+        hipLaunchKernelGGL(k_dt_from_partials, dim3(1), dim3(OPS_BLOCK), 0, ibh_stream, nwg, p->march_tmp, scale, dt_device);
     IBH_LAUNCH_CHECK();
     return 0;
 }

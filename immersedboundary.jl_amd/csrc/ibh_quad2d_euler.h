@@ -9,8 +9,12 @@
 //   * LDS holds only the two boundary ROWS of the tile (the bottom / top edge lanes read them); left / right edge lanes
 //     take their boundary cells from their own registers, the COARSE pair mate by a quad_perm DPP.
 // Arithmetic: blk2::euler_flux_w / euler_side (ibh_sweep2d.h, ibh_block2d.h), Float32 HLL combine like every tuned path.
+// STEP (ibh_step_euler): the store epilogue passes every cell's own state (U, in registers) and its four residual values
+// through euler_step::update_row (ibh_euler_step_dev.h, contraction off) and stores P_out = state2primitive(
+// primitive2state(P) + dt R) to `Rr` with ordinary stores -- the next step reads it.
 #pragma once
 #include "ibh_quad2d.h"
+#include "ibh_euler_step_dev.h"
 
 namespace quad2 {
 
@@ -131,11 +135,11 @@ __device__ __forceinline__ void euler_flux_w2(const v2f* Pa, const v2f* Pb, cons
     F[1] += mL * uL - mR * uR;
 }
 
-template <int SCH = EULER_HLL>
+template <int SCH = EULER_HLL, bool STEP = false>
 __device__ __forceinline__ void sweep_quad_euler(const QuadDesc2* __restrict__ qd, const int32_t* __restrict__ qtab,
                                                  int32_t q, const float* __restrict__ P, uint32_t ldp,
                                                  float* __restrict__ Rr, uint32_t ldr, blk2::Gas gas, float* lds,
-                                                 int lane) {
+                                                 int lane, float dt = 0.0f) {
     using blk2::ldg;
     using blk2::wave_lds_sync;
     typedef float v2f_g __attribute__((ext_vector_type(2), aligned(4)));
@@ -403,6 +407,10 @@ __device__ __forceinline__ void sweep_quad_euler(const QuadDesc2* __restrict__ q
                 FTf[c] = t15 ? ex[c] : FT[v][c];
             }
             const v4f r = res[v] - ((FTf - FB) * rhy);
+            if constexpr (STEP) {
+                res[v] = r;   // (all four residuals of a cell are needed before its row can be updated)
+                continue;
+            }
             // the residual is not read again by this sweep: stores that do not allocate in L2 -- 14.13 -> 12.78 us per sweep at
             // 0.87 M cells (same box, alternating builds, three times)
 #ifdef Q2E_NO_NT_STORE   // (A/B)
@@ -410,6 +418,20 @@ __device__ __forceinline__ void sweep_quad_euler(const QuadDesc2* __restrict__ q
 #else
             __builtin_nontemporal_store(r, (v4f_g*)((char*)(Rr + (size_t)v * ldr) + ((size_t)a0 << 2)));
 #endif
+        }
+        if constexpr (STEP) {
+            v4f O[QE_NV];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const float Pc[QE_NV] = {U[0][c], U[1][c], U[2][c], U[3][c]};
+                const float rc[QE_NV] = {res[0][c], res[1][c], res[2][c], res[3][c]};
+                float o[QE_NV];
+                euler_step::update_row<2>(gas.R, gas.gamma, Pc, rc, dt, o);
+#pragma unroll
+                for (int v = 0; v < QE_NV; ++v) O[v][c] = o[v];
+            }
+#pragma unroll
+            for (int v = 0; v < QE_NV; ++v) *(v4f_g*)((char*)(Rr + (size_t)v * ldr) + ((size_t)a0 << 2)) = O[v];
         }
     }
 }

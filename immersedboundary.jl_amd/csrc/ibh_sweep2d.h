@@ -21,6 +21,7 @@
 // LDS per wave: the six [tile | halo] fields U, D, SX, SY, CX, CY + extra[64] + ext[80].
 #pragma once
 #include "ibh_block2d.h"
+#include "ibh_euler_step_dev.h"
 
 namespace blk2 {
 
@@ -426,12 +427,14 @@ __device__ __forceinline__ SweepPreE sweep_prefetch_e(const BlockDesc2* __restri
     return T;
 }
 
-template <int SCH = EULER_HLL>
+// STEP (ibh_step_euler): the cell's own state T.Pc and its four residual values go through euler_step::update_row
+// (ibh_euler_step_dev.h, contraction off) and P_out = state2primitive(primitive2state(P) + dt R) is stored to `Rr`
+template <int SCH = EULER_HLL, bool STEP = false>
 __device__ __forceinline__ void sweep_euler(const BlockDesc2* __restrict__ blocks, const int32_t* __restrict__ htab,
                                             const int32_t* __restrict__ etab, const int32_t* __restrict__ dtab,
                                             const int32_t* __restrict__ blist, int32_t blk0, int32_t stride, int32_t nb,
                                             const float* __restrict__ P, uint32_t ldp, float* __restrict__ Rr,
-                                            uint32_t ldr, Gas gas, float* lds, int lane) {
+                                            uint32_t ldr, Gas gas, float* lds, int lane, float dt = 0.0f) {
     float* fP = lds;           // [4][128]
     float* fD = lds + 512;     // [128]
     float* fSX = lds + 640;    // [4][128]
@@ -611,6 +614,7 @@ __device__ __forceinline__ void sweep_euler(const BlockDesc2* __restrict__ block
             FBs[v] = __shfl_up(FT[v], 8, 64);
         }
         wave_lds_sync();
+        float rv[4];
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
             const float* e = ex + v * 64;
@@ -619,7 +623,15 @@ __device__ __forceinline__ void sweep_euler(const BlockDesc2* __restrict__ block
             const float fb = e2 ? eB : FBs[v];
             const float fr = e1 ? 0.5f * (FR[v] + FR1[v]) : FR[v];
             const float ft = e3 ? 0.5f * (FT[v] + FT1[v]) : FT[v];
-            stg(Rr + (size_t)v * ldr, (uint32_t)bb.base + lane, -((fr - fl) * bb.rh[0]) - ((ft - fb) * bb.rh[1]));
+            const float r = -((fr - fl) * bb.rh[0]) - ((ft - fb) * bb.rh[1]);
+            if constexpr (STEP) rv[v] = r;
+            else stg(Rr + (size_t)v * ldr, (uint32_t)bb.base + lane, r);
+        }
+        if constexpr (STEP) {
+            float o[4];
+            euler_step::update_row<2>(gas.R, gas.gamma, T.Pc, rv, dt, o);
+#pragma unroll
+            for (int v = 0; v < 4; ++v) stg(Rr + (size_t)v * ldr, (uint32_t)bb.base + lane, o[v]);
         }
     }
 }

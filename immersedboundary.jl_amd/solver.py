@@ -1,4 +1,5 @@
-"""Device-resident ``FAS!`` (mirror of /root/reference/src/solver.jl:39-91).
+"""Device-resident ``FAS!`` (mirror of /root/reference/src/solver.jl:39-91) and ``EulerMarch``, the explicit time march
+of the compressible equations (the ``march!`` loop of test/advection.jl:61-89 around the fused Euler sweeps).
 
 Same signature and semantics as the reference (including its quirks: the recursion guard is
 ``length(coarseners) > 1`` so the last supplied level is never visited, and the coarse problem is solved
@@ -152,3 +153,64 @@ def FAS(f, Q, coarseners=(), prolongators=(), perscribed_f=None, multigrid_level
             if nr < nr0 * rtol + atol:
                 break
     return nr / (nr0 + _eps32)
+
+
+class EulerMarch:
+    """The explicit time march of an unsteady Euler / LES run on one partition, without the host in the loop: per step
+
+    1. ``timestep_euler`` (the CFL time step from ``P``, left on the device) on every ``dt_every``-th step,
+    2. ``step_euler`` (sweep + conservative update: one launch where the 2-D single-kernel sweep applies),
+    3. ``bcs(P_new)``: any callable on the new array, e.g. the two ``impose_flow_bc`` calls of
+       ``closures.config5_boundary_conditions(fused=True)``,
+    4. ``average.push(P_new, dt)`` with the device ``dt`` (``cfd.TimeAverage``, cfd.jl:738-802).
+
+    The march owns the ping-pong arrays, the one-element device ``dt`` (``local_dt``: an ``(nc,)`` array of per-cell time
+    steps, the pseudo-time march to a steady state) and the sweep's ``work`` array; ``step(P)`` returns the new array -- one
+    of the two ping-pong arrays, valid until the step after the next -- and makes no host read-back and no allocation after
+    construction, so ``n`` steps can be captured in ``torch.cuda.graph`` and replayed (a ``TimeAverage`` registers its
+    arrays on its first push: push once, or run one step, before capturing).
+
+    ``residual``: a callable ``f(part, P, out)`` that writes the residual of ``[rho E rho*u rho*v (rho*w)]`` into ``out``,
+    e.g. ``lambda part, P, out: closures.navier_stokes_les_residual(part, P, Delta, out=out)``; the step is then ``f``
+    followed by ``update_euler``.  ``scheme``: "hll" or "sensor" (``residual_euler_hll`` / ``residual_euler_sensor``)."""
+
+    def __init__(self, part, fluid=None, scheme="hll", scale=0.75, bcs=None, average=None, local_dt=False, dt_every=1,
+                 residual=None, flags=0):
+        from . import cfd
+        self.part = B._part(part)
+        self.fluid = fluid if fluid is not None else cfd.Fluid()
+        if scheme not in B._EULER_SCHEMES:
+            raise ValueError('scheme must be "hll" or "sensor"')
+        if int(dt_every) < 1:
+            raise ValueError("dt_every must be >= 1")
+        if local_dt and average is not None:
+            raise ValueError("a time average needs one time step for all cells: local_dt marches in pseudo-time")
+        self.scheme, self.scale, self.bcs, self.average = scheme, float(scale), bcs, average
+        self.local_dt, self.dt_every, self.residual, self.flags = bool(local_dt), int(dt_every), residual, int(flags)
+        nc, nv = self.part.nc, self.part.nd + 2
+        self._buf = (B.colmajor_empty(nc, nv), B.colmajor_empty(nc, nv))
+        self.work = B.colmajor_empty(nc, nv)
+        self.dt = B.colmajor_empty(nc) if self.local_dt else torch.empty(1, dtype=torch.float32, device=self.work.device)
+        self.nsteps = 0
+
+    def step(self, P):
+        """One step from ``P`` (any ``(nc, nd+2)`` device array, e.g. the previous return value); returns the new array."""
+        if not isinstance(P, torch.Tensor):
+            P = P.t                                    # a HipArray: its pending broadcasts are evaluated here
+        if self.nsteps % self.dt_every == 0:
+            if self.local_dt:
+                B.timestep_euler(self.part, P, self.fluid, self.scale, out=False, cells=self.dt)
+            else:
+                B.timestep_euler(self.part, P, self.fluid, self.scale, out=self.dt)
+        out = self._buf[0] if P.data_ptr() != self._buf[0].data_ptr() else self._buf[1]
+        if self.residual is not None:
+            self.residual(self.part, P, self.work)
+            B.update_euler(P, self.work, self.dt, self.fluid, out=out)
+        else:
+            B.step_euler(self.part, P, self.dt, out, self.fluid, self.scheme, work=self.work, flags=self.flags)
+        if self.bcs is not None:
+            self.bcs(out)
+        if self.average is not None:
+            self.average.push(out, self.dt)
+        self.nsteps += 1
+        return out

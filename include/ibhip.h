@@ -416,6 +416,35 @@ int ibh_step_advection(ibh_part*, const float* u, float* u_out, const float* C, 
  * calls; dt_next may alias dt_dev. */
 int ibh_step_advection_dt(ibh_part* p, const float* u, float* u_out, const float* C, int64_t ldc, const float* dt_dev,
                           const ibh_bcset* bcs, float scale, float* dt_next);
+/* ---- an explicit Euler step, device resident: what connects the fused Euler sweeps, impose_flow_bc and TimeAverage.push
+ * into a time march without the host.  Rows of P are [p T u v (w)], rows of R [rho E rho*u rho*v (rho*w)] as the sweeps write.
+ * ibh_timestep_euler: the advection script's CFL formula (advection.jl:52-59, :65) with the acoustic speed in place of C,
+ *     C_d = abs(u_d) + sqrt(gamma R max(T, 10))   (ibh_cfd_speed_of_sound, then the IEEE broadcasts abs and +)
+ *     dt = (0.5 / max_cells max_d unsigned_green_gauss(at_faces(C_d, d), d)) * scale        -> dt_device (1 float, or NULL)
+ *     dt_cells[c] = (0.5 / max_d(...)[c]) * scale, the local time step of a pseudo-time march  -> dt_cells (nc, or NULL)
+ *   bit for bit ibh_timestep_advection on the materialised C; no (nc, nd) array of wave speeds is written.  Two launches,
+ *   one when only dt_cells is asked for; one of the two outputs must be given.
+ * ibh_update_euler: P_out = state2primitive(primitive2state(P) + dt * R) in one launch, bit for bit ibh_cfd_primitive2state,
+ *   ibh_update_dev per column and ibh_cfd_state2primitive.  dt: one device value, or n of them (dt_per_cell != 0).  P_out may
+ *   be P (a row is read whole before it is written); R may alias neither.
+ * ibh_step_euler: P_out = that update with R = ibh_residual_euler_hll / _sensor(P, flags) (scheme IBH_EULER_HLL /
+ *   IBH_EULER_SENSOR, the pressure sensor).  ONE launch where the 2-D single-kernel sweep takes the whole partition (every
+ *   block eligible, no face-list cells; by quads or, with IBH_NO_QUAD, per block), dt is global and P_out != P: the
+ *   sweep stores the updated primitives itself.  Two launches everywhere else (3-D, face-list or mixed partitions, dt_per_cell,
+ *   IBH_FORCE_GENERAL, IBH_NO_FUSE, IBH_EXACT, P_out == P): the sweep into `work`, nc x (nd + 2) floats with leading dimension
+ *   ldw -- an argument check there, never an allocation -- then ibh_update_euler.  Same bits either way.  IBH_IMAGE_ONLY and
+ *   the overlap phases are rejected: the update would read rows the sweep never wrote (the multi-GPU step is out of scope).
+ * Every misuse (null pointer, nd other than 2 or 3, a leading dimension below n, the aliasing above) is an error before any
+ * launch. */
+#define IBH_EULER_HLL 0
+#define IBH_EULER_SENSOR 1
+int ibh_timestep_euler(ibh_part*, const ibh_fluid*, const float* P, int64_t ldp, float scale,
+                       float* dt_device /* 1 float, may be NULL */, float* dt_cells /* nc floats, may be NULL */);
+int ibh_update_euler(const ibh_fluid*, int nd, int64_t n, const float* P, int64_t ldp, const float* R, int64_t ldr,
+                     const float* dt, int dt_per_cell, float* P_out, int64_t ldo);
+int ibh_step_euler(ibh_part*, const ibh_fluid*, int scheme /* IBH_EULER_HLL | IBH_EULER_SENSOR */, const float* P, int64_t ldp,
+                   float* P_out, int64_t ldo, const float* dt, int dt_per_cell, float* work /* nc x (nd+2) or NULL */,
+                   int64_t ldw, int flags);
 int ibh_axpy_clamped(int64_t n, float omega, const float* r, float* q);
 /* y = a*x + y */
 int ibh_axpy(int64_t n, float a, const float* x, float* y);

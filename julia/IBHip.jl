@@ -811,6 +811,42 @@ function step_advection!(u_out::HipArray{Float32}, part::HipPartition, u::HipArr
     u_out
 end
 
+# ---- an explicit Euler step, device resident (rows of P: [p T u v (w)])
+"The CFL time step of an explicit Euler step: the formula of `timestep_advection!` with `C_d = abs.(u_d) .+ speed_of_sound`
+evaluated from `P` on the fly.  `dt` (length 1) and / or `dt_cells` (length `nc`, the local time step) are written; returns
+`dt` (or `dt_cells` when `dt === nothing`)."
+function timestep_euler(part::HipPartition, P::HipArray{Float32}, fluid; scale = 1f0,
+                        dt::Union{HipArray{Float32}, Nothing} = nothing, dt_cells::Union{HipArray{Float32}, Nothing} = nothing)
+    isnothing(dt) && isnothing(dt_cells) && (dt = HipArray{Float32}(undef, 1))
+    f = Ref(IbhFluid(fluid))
+    check(ccall((:ibh_timestep_euler, lib), Cint, (Ptr{Cvoid}, Ptr{IbhFluid}, Ptr{Cvoid}, Int64, Cfloat, Ptr{Cvoid}, Ptr{Cvoid}),
+        part.handle, f, P.ptr, ld(P), Float32(scale), isnothing(dt) ? C_NULL : dt.ptr, isnothing(dt_cells) ? C_NULL : dt_cells.ptr))
+    isnothing(dt) ? dt_cells : dt
+end
+
+"`P_out = state2primitive(fluid, primitive2state(fluid, P) .+ dt .* R)` in one launch; `dt` of length 1, or one per row.
+`P_out` may be `P`."
+function update_euler!(P_out::HipArray{Float32}, fluid, P::HipArray{Float32}, R::HipArray{Float32}, dt::HipArray{Float32})
+    f = Ref(IbhFluid(fluid))
+    check(ccall((:ibh_update_euler, lib), Cint,
+        (Ptr{IbhFluid}, Cint, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64),
+        f, size(P, 2) - 2, size(P, 1), P.ptr, ld(P), R.ptr, ld(R), dt.ptr, length(dt) == 1 ? 0 : 1, P_out.ptr, ld(P_out)))
+    P_out
+end
+
+"One explicit Euler step, `update_euler!(P_out, fluid, P, residual_euler_hll!/sensor!(work, part, P, fluid; flags), dt)`: one
+launch where the 2-D single-kernel sweep takes the whole partition (global `dt`, `P_out !== P`), the sweep into `work` and the
+update elsewhere (`work` is `nc × (nd + 2)` and must be given there).  `scheme`: `:hll` or `:sensor`."
+function step_euler!(P_out::HipArray{Float32}, part::HipPartition, P::HipArray{Float32}, dt::HipArray{Float32}, fluid;
+                     scheme::Symbol = :hll, work::Union{HipArray{Float32}, Nothing} = nothing, flags::Integer = 0)
+    f = Ref(IbhFluid(fluid))
+    check(ccall((:ibh_step_euler, lib), Cint,
+        (Ptr{Cvoid}, Ptr{IbhFluid}, Cint, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Cint),
+        part.handle, f, scheme === :sensor ? 1 : 0, P.ptr, ld(P), P_out.ptr, ld(P_out), dt.ptr, length(dt) == 1 ? 0 : 1,
+        isnothing(work) ? C_NULL : work.ptr, isnothing(work) ? 0 : ld(work), flags))
+    P_out
+end
+
 "`S .+ Σ_d green_gauss(at_faces(ν .+ νR, d) .* face_gradient(R, d) .- at_faces(vel[:, d] .* R, d), d)` in one launch
 (the transport residual closed by `Wray_Agarwal`, src/turbulence.jl:222-241), bit-identical to the composition."
 function scalar_transport!(out::HipArray{Float32}, part::HipPartition, R::HipArray{Float32}, νR::HipArray{Float32},
