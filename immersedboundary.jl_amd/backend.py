@@ -879,6 +879,57 @@ def step_euler(part, P, dt, out, fluid=None, scheme="hll", work=None, flags=0):
     return out
 
 
+@_hipaware
+def update_euler_stage(P0, R, dt, alpha, fluid=None, out=None):
+    """A Runge-Kutta stage of the low-storage family, ``state2primitive(fluid, primitive2state(fluid, P0) .+ (alpha .* dt)
+    .* R)`` in one launch: bit for bit ``update_euler(P0, R, dt .* Float32(alpha))``.  ``dt``: a one-element device tensor,
+    or ``(n,)`` for a per-cell time step.  ``out`` may be ``P0`` itself."""
+    P0, nv, ld0 = _primitives(P0, None)
+    n = P0.shape[0]
+    R, nvr, ldr = _field(R, n)
+    if nvr != nv:
+        raise ValueError(f"R must be (n, {nv})")
+    dt, per_cell = _device_dt(dt, n, "update_euler_stage")
+    if out is None:
+        out = colmajor_empty(n, nv)
+    o, nvo, ldo = _field_inplace(out, n, "out")
+    if nvo != nv:
+        raise ValueError(f"out must be (n, {nv})")
+    f = _cfluid(fluid)
+    _stream()
+    call("ibh_update_euler_stage", C.byref(f), nv - 2, n, _ptr(P0), ld0, _ptr(R), ldr, _ptr(dt), per_cell,
+         C.c_float(alpha), _ptr(o), ldo)
+    return out
+
+
+@_hipaware
+def stage_euler(part, P, P0, dt, alpha, out, fluid=None, scheme="hll", work=None, flags=0):
+    """One stage of a multi-stage step, ``out = update_euler_stage(P0, residual_euler_hll | residual_euler_sensor(part, P,
+    flags), dt, alpha)``: ``P`` is the previous stage, ``P0`` the state the step started from (they may be the same array).
+    One launch where the 2-D single-kernel sweep takes the whole partition and ``out`` is not ``P`` -- with a one-element
+    and with a per-cell ``dt``; elsewhere the sweep goes into ``work`` -- ``(nc, nd+2)``, required there: the stage
+    allocates nothing -- and the update follows.  ``out`` may be ``P0`` when ``P0`` is not ``P``.  Same bits either way."""
+    part = _part(part)
+    P, nv, ldp = _primitives(P, part.nc, part.nd)
+    P0, _, ld0 = _primitives(P0, part.nc, part.nd)
+    dt, per_cell = _device_dt(dt, part.nc, "stage_euler")
+    o, nvo, ldo = _field_inplace(out, part.nc, "out")
+    if nvo != nv:
+        raise ValueError(f"out must be (nc, {nv})")
+    w, ldw = None, 0
+    if work is not None:
+        w, nvw, ldw = _field_inplace(work, part.nc, "work")
+        if nvw != nv:
+            raise ValueError(f"work must be (nc, {nv})")
+    if scheme not in _EULER_SCHEMES:
+        raise ValueError('scheme must be "hll" or "sensor"')
+    f = _cfluid(fluid)
+    _stream()
+    call("ibh_stage_euler", part.handle, C.byref(f), _EULER_SCHEMES[scheme], _ptr(P), ldp, _ptr(P0), ld0, _ptr(o), ldo,
+         _ptr(dt), per_cell, C.c_float(alpha), _ptr(w), ldw, int(flags))
+    return out
+
+
 # ---------------------------------------------------------------------------
 # partition runtime and ghost-cell BC
 # ---------------------------------------------------------------------------

@@ -124,6 +124,8 @@ def state2primitive(fluid, Q):
 timestep_euler = B.timestep_euler
 update_euler = B.update_euler
 step_euler = B.step_euler
+update_euler_stage = B.update_euler_stage          # (ibh_update_euler_stage / ibh_stage_euler: a Runge-Kutta stage)
+stage_euler = B.stage_euler
 
 
 def inviscid_fluxes(fluid, PL, PR, *args):

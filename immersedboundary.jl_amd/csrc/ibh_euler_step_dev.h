@@ -5,6 +5,9 @@
 // are those of k_p2s, k_update_dev and k_s2p (ibh_cfd.hip, ibh_march.hip) -- both max(T, 10) clamps, k / 2 -- so the result
 // is bit for bit the three launches'.  The tuned sweep bodies are compiled with contraction on; this function must not be:
 // its expressions carry contract(off) wherever they are inlined.
+// A Runge-Kutta stage of the low-storage family (ibh_update_euler_stage, ibh_stage_euler; the STAGE form of the sweeps) is
+// the same row function on a base state P0 that need not be the state the residual was swept from, with the time step
+// stage_dt(alpha, dt): P_out = state2primitive(primitive2state(P0) + (alpha * dt) R).
 #pragma once
 #include "ibh_common.h"
 
@@ -45,6 +48,18 @@ __device__ __forceinline__ void update_row(float Rgas, float gamma, const float 
     out[1] = ibh_max(p / (rho * Rgas), 10.0f);
 #pragma unroll
     for (int j = 0; j < ND; ++j) out[2 + j] = u[j];
+}
+
+// what the STAGE form of a sweep takes beside dt: the base state (it may be the output), the stage coefficient and, for a
+// per-cell time step, the nc values (dt is then unused)
+struct StageArgs {
+    const float* P0 = nullptr; uint32_t ld0 = 0; float alpha = 1.0f; const float* dtc = nullptr;
+};
+
+// the time step of a stage: one IEEE multiply, the broadcast dt .* alpha
+__device__ __forceinline__ float stage_dt(float alpha, float dt) {
+#pragma clang fp contract(off)
+    return alpha * dt;
 }
 
 }  // namespace euler_step

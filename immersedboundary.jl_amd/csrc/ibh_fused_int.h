@@ -81,6 +81,9 @@ struct EulerArgs {  // (the entries' fields)
     const float* P; int64_t ldp; float* R; int64_t ldr; const ibh_fluid* fluid;
     EulerScheme scheme = EULER_HLL; const float* nu = nullptr;
     const float* dt = nullptr;  // ibh_step_euler on a single-kernel path: R is P_out, the sweep stores the updated primitives
+    // ibh_stage_euler on a single-kernel path (with dt): the row that is updated is P0's (P0 may be R), the time step is
+    // alpha * dt, and dt holds one value per cell where dt_cells is set
+    const float* P0 = nullptr; int64_t ld0 = 0; float alpha = 1.0f; bool dt_cells = false;
 };
 
 // ---- advection: paths

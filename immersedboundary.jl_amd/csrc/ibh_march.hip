@@ -9,6 +9,8 @@
 // The step itself (sweep + u += dt ud in one launch) is ibh_step_advection in ibh_fused.hip.
 //   * ibh_update_euler: P_out = state2primitive(primitive2state(P) + dt R) in one launch (euler_step::update_row); the Euler
 //     step around it is ibh_step_euler in ibh_fused.hip, its time step ibh_timestep_euler in ibh_ops.hip.
+//   * ibh_update_euler_stage: the same row function on a base state P0 with the time step alpha * dt, a Runge-Kutta stage of
+//     the low-storage family; the stage around it is ibh_stage_euler in ibh_fused.hip.
 // Arithmetic: the operator kernels' (ibh_ops.hip): -ffp-contract=off, the reference's evaluation order.
 #include <algorithm>
 #include <cstdlib>
@@ -126,6 +128,30 @@ __global__ __launch_bounds__(MARCH_BLOCK) void k_update_euler(float Rgas, float 
             r[v] = R[i + v * ldr];
         }
         if constexpr (PER_CELL) h = dt[i];
+        euler_step::update_row<ND>(Rgas, gamma, Pr, r, h, o);
+#pragma unroll
+        for (int v = 0; v < NV; ++v) P_out[i + v * ldo] = o[v];
+    }
+}
+
+// A stage: P_out = state2primitive(primitive2state(P0) + (alpha dt) R).  k_update_euler with one more IEEE multiply
+// (euler_step::stage_dt); P_out may be P0
+template <int ND, bool PER_CELL>
+__global__ __launch_bounds__(MARCH_BLOCK) void k_update_euler_stage(float Rgas, float gamma, int64_t n, const float* P0,
+                                                                    int64_t ld0, const float* __restrict__ R, int64_t ldr,
+                                                                    const float* __restrict__ dt, float alpha, float* P_out,
+                                                                    int64_t ldo) {
+    constexpr int NV = ND + 2;
+    float h = 0.0f;
+    if constexpr (!PER_CELL) h = euler_step::stage_dt(alpha, *dt);
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        float Pr[NV], r[NV], o[NV];
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+            Pr[v] = P0[i + v * ld0];
+            r[v] = R[i + v * ldr];
+        }
+        if constexpr (PER_CELL) h = euler_step::stage_dt(alpha, dt[i]);
         euler_step::update_row<ND>(Rgas, gamma, Pr, r, h, o);
 #pragma unroll
         for (int v = 0; v < NV; ++v) P_out[i + v * ldo] = o[v];
@@ -297,6 +323,31 @@ int ibh_update_euler(const ibh_fluid* f, int nd, int64_t n, const float* P, int6
     const dim3 grid(ibh_grid_cap(n, MARCH_BLOCK, 2048)), block(MARCH_BLOCK);
 #define UPD_LAUNCH(ND_, PC_) \
     hipLaunchKernelGGL((k_update_euler<ND_, PC_>), grid, block, 0, ibh_stream, f->R, f->gamma, n, P, ldp, R, ldr, dt, P_out, ldo)
+    if (nd == 2) {
+        if (dt_per_cell) UPD_LAUNCH(2, true);
+        else UPD_LAUNCH(2, false);
+    } else {
+        if (dt_per_cell) UPD_LAUNCH(3, true);
+        else UPD_LAUNCH(3, false);
+    }
+#undef UPD_LAUNCH
+    IBH_LAUNCH_CHECK();
+    return 0;
+}
+
+// A Runge-Kutta stage of the low-storage family, P_out = state2primitive(primitive2state(P0) + (alpha * dt) * R) in one
+// launch: bit for bit ibh_update_euler(P0, R, dt .* alpha) with the product taken by the broadcast layer
+int ibh_update_euler_stage(const ibh_fluid* f, int nd, int64_t n, const float* P0, int64_t ld0, const float* R, int64_t ldr,
+                           const float* dt, int dt_per_cell, float alpha, float* P_out, int64_t ldo) {
+    IBH_REQUIRE(f && P0 && R && dt && P_out, "ibh_update_euler_stage: null argument");
+    IBH_REQUIRE(nd == 2 || nd == 3, "ibh_update_euler_stage: nd must be 2 or 3");
+    IBH_REQUIRE(n >= 0 && ld0 >= n && ldr >= n && ldo >= n, "ibh_update_euler_stage: a leading dimension is smaller than n");
+    IBH_REQUIRE(P_out != R && P0 != R, "ibh_update_euler_stage: R may not alias P0 or P_out (P_out may be P0)");
+    if (n == 0) return 0;
+    const dim3 grid(ibh_grid_cap(n, MARCH_BLOCK, 2048)), block(MARCH_BLOCK);
+#define UPD_LAUNCH(ND_, PC_)                                                                                               \
+    hipLaunchKernelGGL((k_update_euler_stage<ND_, PC_>), grid, block, 0, ibh_stream, f->R, f->gamma, n, P0, ld0, R, ldr, dt, \
+                       alpha, P_out, ldo)
     if (nd == 2) {
         if (dt_per_cell) UPD_LAUNCH(2, true);
         else UPD_LAUNCH(2, false);

@@ -12,6 +12,9 @@
 // STEP (ibh_step_euler): the store epilogue passes every cell's own state (U, in registers) and its four residual values
 // through euler_step::update_row (ibh_euler_step_dev.h, contraction off) and stores P_out = state2primitive(
 // primitive2state(P) + dt R) to `Rr` with ordinary stores -- the next step reads it.
+// STAGE (ibh_stage_euler, with STEP): the row that is updated is the cell's row of the base state P0, four v4f loads at the
+// offsets of the stores, issued after the last flux pass (the cell's own U is dead by then); the time step is alpha * dt,
+// dt per wave or (DTC) one v4f of per-cell values.  P_out may be P0: a lane reads its rows of P0 before it stores.
 #pragma once
 #include "ibh_quad2d.h"
 #include "ibh_euler_step_dev.h"
@@ -135,11 +138,14 @@ __device__ __forceinline__ void euler_flux_w2(const v2f* Pa, const v2f* Pb, cons
     F[1] += mL * uL - mR * uR;
 }
 
-template <int SCH = EULER_HLL, bool STEP = false>
+template <int SCH = EULER_HLL, bool STEP = false, bool STAGE = false, bool DTC = false>
 __device__ __forceinline__ void sweep_quad_euler(const QuadDesc2* __restrict__ qd, const int32_t* __restrict__ qtab,
                                                  int32_t q, const float* __restrict__ P, uint32_t ldp,
                                                  float* __restrict__ Rr, uint32_t ldr, blk2::Gas gas, float* lds,
-                                                 int lane, float dt = 0.0f) {
+                                                 int lane, float dt = 0.0f,
+                                                 euler_step::StageArgs sa = euler_step::StageArgs()) {
+    static_assert(STEP || !STAGE, "the STAGE form is a STEP form");
+    static_assert(STAGE || !DTC, "per-cell time steps come with the STAGE form");
     using blk2::ldg;
     using blk2::wave_lds_sync;
     typedef float v2f_g __attribute__((ext_vector_type(2), aligned(4)));
@@ -419,7 +425,7 @@ __device__ __forceinline__ void sweep_quad_euler(const QuadDesc2* __restrict__ q
             __builtin_nontemporal_store(r, (v4f_g*)((char*)(Rr + (size_t)v * ldr) + ((size_t)a0 << 2)));
 #endif
         }
-        if constexpr (STEP) {
+        if constexpr (STEP && !STAGE) {
             v4f O[QE_NV];
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
@@ -427,6 +433,25 @@ __device__ __forceinline__ void sweep_quad_euler(const QuadDesc2* __restrict__ q
                 const float rc[QE_NV] = {res[0][c], res[1][c], res[2][c], res[3][c]};
                 float o[QE_NV];
                 euler_step::update_row<2>(gas.R, gas.gamma, Pc, rc, dt, o);
+#pragma unroll
+                for (int v = 0; v < QE_NV; ++v) O[v][c] = o[v];
+            }
+#pragma unroll
+            for (int v = 0; v < QE_NV; ++v) *(v4f_g*)((char*)(Rr + (size_t)v * ldr) + ((size_t)a0 << 2)) = O[v];
+        }
+        if constexpr (STAGE) {
+            // (no __restrict__ on P0: it may be the output; all of this lane's rows are loaded before its first store)
+            v4f B[QE_NV], O[QE_NV];
+#pragma unroll
+            for (int v = 0; v < QE_NV; ++v) B[v] = *(const v4f_g*)((const char*)(sa.P0 + (size_t)v * sa.ld0) + ((size_t)a0 << 2));
+            v4f h = v4f{dt, dt, dt, dt};
+            if constexpr (DTC) h = *(const v4f_g*)((const char*)sa.dtc + ((size_t)a0 << 2));
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const float Pc[QE_NV] = {B[0][c], B[1][c], B[2][c], B[3][c]};
+                const float rc[QE_NV] = {res[0][c], res[1][c], res[2][c], res[3][c]};
+                float o[QE_NV];
+                euler_step::update_row<2>(gas.R, gas.gamma, Pc, rc, euler_step::stage_dt(sa.alpha, h[c]), o);
 #pragma unroll
                 for (int v = 0; v < QE_NV; ++v) O[v][c] = o[v];
             }

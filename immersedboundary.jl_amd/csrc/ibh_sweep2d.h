@@ -429,12 +429,17 @@ __device__ __forceinline__ SweepPreE sweep_prefetch_e(const BlockDesc2* __restri
 
 // STEP (ibh_step_euler): the cell's own state T.Pc and its four residual values go through euler_step::update_row
 // (ibh_euler_step_dev.h, contraction off) and P_out = state2primitive(primitive2state(P) + dt R) is stored to `Rr`
-template <int SCH = EULER_HLL, bool STEP = false>
+// STAGE (ibh_stage_euler, with STEP): the row that is updated is the cell's row of the base state P0, loaded here (P0 may be
+// the output: a lane reads its row before it stores), and the time step is alpha * dt -- dt per wave or (DTC) one per lane
+template <int SCH = EULER_HLL, bool STEP = false, bool STAGE = false, bool DTC = false>
 __device__ __forceinline__ void sweep_euler(const BlockDesc2* __restrict__ blocks, const int32_t* __restrict__ htab,
                                             const int32_t* __restrict__ etab, const int32_t* __restrict__ dtab,
                                             const int32_t* __restrict__ blist, int32_t blk0, int32_t stride, int32_t nb,
                                             const float* __restrict__ P, uint32_t ldp, float* __restrict__ Rr,
-                                            uint32_t ldr, Gas gas, float* lds, int lane, float dt = 0.0f) {
+                                            uint32_t ldr, Gas gas, float* lds, int lane, float dt = 0.0f,
+                                            euler_step::StageArgs sa = euler_step::StageArgs()) {
+    static_assert(STEP || !STAGE, "the STAGE form is a STEP form");
+    static_assert(STAGE || !DTC, "per-cell time steps come with the STAGE form");
     float* fP = lds;           // [4][128]
     float* fD = lds + 512;     // [128]
     float* fSX = lds + 640;    // [4][128]
@@ -627,11 +632,22 @@ __device__ __forceinline__ void sweep_euler(const BlockDesc2* __restrict__ block
             if constexpr (STEP) rv[v] = r;
             else stg(Rr + (size_t)v * ldr, (uint32_t)bb.base + lane, r);
         }
-        if constexpr (STEP) {
+        if constexpr (STEP && !STAGE) {
             float o[4];
             euler_step::update_row<2>(gas.R, gas.gamma, T.Pc, rv, dt, o);
 #pragma unroll
             for (int v = 0; v < 4; ++v) stg(Rr + (size_t)v * ldr, (uint32_t)bb.base + lane, o[v]);
+        }
+        if constexpr (STAGE) {
+            const uint32_t c = (uint32_t)bb.base + lane;
+            float b[4], o[4];
+#pragma unroll
+            for (int v = 0; v < 4; ++v) b[v] = *(const float*)((const char*)(sa.P0 + (size_t)v * sa.ld0) + (size_t)(c << 2));
+            float h = dt;
+            if constexpr (DTC) h = *(const float*)((const char*)sa.dtc + (size_t)(c << 2));
+            euler_step::update_row<2>(gas.R, gas.gamma, b, rv, euler_step::stage_dt(sa.alpha, h), o);
+#pragma unroll
+            for (int v = 0; v < 4; ++v) stg(Rr + (size_t)v * ldr, c, o[v]);
         }
     }
 }

@@ -155,6 +155,16 @@ def FAS(f, Q, coarseners=(), prolongators=(), perscribed_f=None, multigrid_level
     return nr / (nr0 + _eps32)
 
 
+def rk_stages(m):
+    """The stage coefficients ``alpha_k = 1/(m-k+1)``, ``k = 1..m``, of the ``m``-stage low-storage (Jameson) Runge-Kutta step
+    ``P_k = state2primitive(primitive2state(P_0) + (alpha_k dt) R(P_{k-1}))``: its linear amplification factor is the
+    degree-``m`` Taylor polynomial of ``exp``.  ``rk_stages(1) == (1.0,)`` is forward Euler."""
+    if isinstance(m, bool) or int(m) != m or int(m) < 1:
+        raise ValueError("the number of stages must be an integer >= 1")
+    m = int(m)
+    return tuple(1.0 / (m - k + 1) for k in range(1, m + 1))
+
+
 class EulerMarch:
     """The explicit time march of an unsteady Euler / LES run on one partition, without the host in the loop: per step
 
@@ -172,10 +182,18 @@ class EulerMarch:
 
     ``residual``: a callable ``f(part, P, out)`` that writes the residual of ``[rho E rho*u rho*v (rho*w)]`` into ``out``,
     e.g. ``lambda part, P, out: closures.navier_stokes_les_residual(part, P, Delta, out=out)``; the step is then ``f``
-    followed by ``update_euler``.  ``scheme``: "hll" or "sensor" (``residual_euler_hll`` / ``residual_euler_sensor``)."""
+    followed by ``update_euler``.  ``scheme``: "hll" or "sensor" (``residual_euler_hll`` / ``residual_euler_sensor``).
+
+    ``stages``: the number ``m`` of Runge-Kutta stages (``rk_stages(m)``), or the tuple of stage coefficients itself.  With
+    ``stages=1`` a step is exactly the calls above.  With more, the time step is computed once from the step's input
+    ``P_0`` and step 2 becomes ``m`` calls ``stage_euler(P_{k-1}, P_0, dt, alpha_k) -> P_k`` (with ``residual``: the callable
+    into ``work``, then ``update_euler_stage``), ``bcs`` after every one of them -- the next sweep reads the ghost cells --
+    and ``average.push(P_m, dt)`` once with the full ``dt``.  The march then owns three arrays: the stages alternate between
+    the two that do not hold ``P_0``, so ``P_0`` -- the caller's array or the previous return value -- is never written.
+    Either way a returned array stays valid during the next ``step`` and is overwritten by the one after it."""
 
     def __init__(self, part, fluid=None, scheme="hll", scale=0.75, bcs=None, average=None, local_dt=False, dt_every=1,
-                 residual=None, flags=0):
+                 residual=None, flags=0, stages=1):
         from . import cfd
         self.part = B._part(part)
         self.fluid = fluid if fluid is not None else cfd.Fluid()
@@ -187,8 +205,12 @@ class EulerMarch:
             raise ValueError("a time average needs one time step for all cells: local_dt marches in pseudo-time")
         self.scheme, self.scale, self.bcs, self.average = scheme, float(scale), bcs, average
         self.local_dt, self.dt_every, self.residual, self.flags = bool(local_dt), int(dt_every), residual, int(flags)
+        self.stages = tuple(float(a) for a in stages) if isinstance(stages, (tuple, list)) else rk_stages(stages)
+        if not self.stages:
+            raise ValueError("stages must name at least one stage coefficient")
+        self._staged = self.stages != (1.0,)
         nc, nv = self.part.nc, self.part.nd + 2
-        self._buf = (B.colmajor_empty(nc, nv), B.colmajor_empty(nc, nv))
+        self._buf = tuple(B.colmajor_empty(nc, nv) for _ in range(3 if self._staged else 2))
         self.work = B.colmajor_empty(nc, nv)
         self.dt = B.colmajor_empty(nc) if self.local_dt else torch.empty(1, dtype=torch.float32, device=self.work.device)
         self.nsteps = 0
@@ -202,6 +224,8 @@ class EulerMarch:
                 B.timestep_euler(self.part, P, self.fluid, self.scale, out=False, cells=self.dt)
             else:
                 B.timestep_euler(self.part, P, self.fluid, self.scale, out=self.dt)
+        if self._staged:
+            return self._stages(P)
         out = self._buf[0] if P.data_ptr() != self._buf[0].data_ptr() else self._buf[1]
         if self.residual is not None:
             self.residual(self.part, P, self.work)
@@ -214,3 +238,24 @@ class EulerMarch:
             self.average.push(out, self.dt)
         self.nsteps += 1
         return out
+
+    def _stages(self, P0):
+        """The stages of one step from ``P0`` (the time step is in ``self.dt``): stage ``k`` sweeps the previous stage and
+        updates ``P0`` into one of the two arrays that are neither ``P0`` nor its own input."""
+        free = [b for b in self._buf if b.data_ptr() != P0.data_ptr()][:2]
+        src = P0
+        for k, alpha in enumerate(self.stages):
+            out = free[k % 2]
+            if self.residual is not None:
+                self.residual(self.part, src, self.work)
+                B.update_euler_stage(P0, self.work, self.dt, alpha, self.fluid, out=out)
+            else:
+                B.stage_euler(self.part, src, P0, self.dt, alpha, out, self.fluid, self.scheme, work=self.work,
+                              flags=self.flags)
+            if self.bcs is not None:
+                self.bcs(out)
+            src = out
+        if self.average is not None:
+            self.average.push(src, self.dt)
+        self.nsteps += 1
+        return src

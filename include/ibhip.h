@@ -445,6 +445,25 @@ int ibh_update_euler(const ibh_fluid*, int nd, int64_t n, const float* P, int64_
 int ibh_step_euler(ibh_part*, const ibh_fluid*, int scheme /* IBH_EULER_HLL | IBH_EULER_SENSOR */, const float* P, int64_t ldp,
                    float* P_out, int64_t ldo, const float* dt, int dt_per_cell, float* work /* nc x (nd+2) or NULL */,
                    int64_t ldw, int flags);
+/* ---- multi-stage (Runge-Kutta) steps of the low-storage family: stage k of m is
+ *     P_k = state2primitive(primitive2state(P_0) + (alpha_k * dt) * R(P_{k-1})),   P_0 the step's input, P_m the new state;
+ *   alpha_k = 1/(m-k+1) has the degree-m Taylor polynomial as its linear amplification factor, m = 1 is ibh_step_euler.
+ * ibh_update_euler_stage: P_out = state2primitive(primitive2state(P0) + (alpha * dt) * R) in one launch, bit for bit
+ *   ibh_update_euler(P0, R, dt .* alpha) with the Float32 product taken by the broadcast layer.  dt: one device value, or n of
+ *   them (dt_per_cell != 0).  P_out may be P0; R may alias neither.
+ * ibh_stage_euler: P_out = that update with R = ibh_residual_euler_hll / _sensor(P, flags); P is the previous stage, P0 the
+ *   base state (they may be the same array).  ONE launch where the 2-D single-kernel sweep takes the whole partition and
+ *   P_out != P -- with a global and with a per-cell dt, with P0 == P or not: the sweep loads the cell's row of P0 and its time
+ *   step in its store epilogue.  Two launches everywhere else (3-D, face-list or mixed partitions, IBH_FORCE_GENERAL,
+ *   IBH_NO_FUSE, IBH_EXACT, P_out == P): the sweep into `work` -- an argument check there, never an allocation -- then
+ *   ibh_update_euler_stage.  Same bits either way.  P_out may be P0 when P0 is not P (a cell reads only its own row of P0,
+ *   before it writes); work may alias none of P, P0, P_out.  IBH_IMAGE_ONLY, the overlap phases and the single-pass flags are
+ *   rejected as by ibh_step_euler; every misuse is an error before any launch. */
+int ibh_update_euler_stage(const ibh_fluid*, int nd, int64_t n, const float* P0, int64_t ld0, const float* R, int64_t ldr,
+                           const float* dt, int dt_per_cell, float alpha, float* P_out, int64_t ldo);
+int ibh_stage_euler(ibh_part*, const ibh_fluid*, int scheme /* IBH_EULER_HLL | IBH_EULER_SENSOR */, const float* P, int64_t ldp,
+                    const float* P0, int64_t ld0, float* P_out, int64_t ldo, const float* dt, int dt_per_cell, float alpha,
+                    float* work /* nc x (nd+2) or NULL */, int64_t ldw, int flags);
 int ibh_axpy_clamped(int64_t n, float omega, const float* r, float* q);
 /* y = a*x + y */
 int ibh_axpy(int64_t n, float a, const float* x, float* y);

@@ -847,6 +847,36 @@ function step_euler!(P_out::HipArray{Float32}, part::HipPartition, P::HipArray{F
     P_out
 end
 
+"A Runge-Kutta stage of the low-storage family, `P_out = state2primitive(fluid, primitive2state(fluid, P0) .+ (alpha .* dt) .* R)`
+in one launch, bit for bit `update_euler!(P_out, fluid, P0, R, dt .* Float32(alpha))`; `dt` of length 1, or one per row.
+`P_out` may be `P0`."
+function update_euler_stage!(P_out::HipArray{Float32}, fluid, P0::HipArray{Float32}, R::HipArray{Float32}, dt::HipArray{Float32},
+                             alpha::Real)
+    f = Ref(IbhFluid(fluid))
+    check(ccall((:ibh_update_euler_stage, lib), Cint,
+        (Ptr{IbhFluid}, Cint, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Cint, Cfloat, Ptr{Cvoid}, Int64),
+        f, size(P0, 2) - 2, size(P0, 1), P0.ptr, ld(P0), R.ptr, ld(R), dt.ptr, length(dt) == 1 ? 0 : 1, Float32(alpha), P_out.ptr,
+        ld(P_out)))
+    P_out
+end
+
+"One stage of a multi-stage step, `update_euler_stage!(P_out, fluid, P0, residual_euler_hll!/sensor!(work, part, P, fluid; flags),
+dt, alpha)`: `P` is the previous stage, `P0` the state the step started from.  One launch where the 2-D single-kernel sweep
+takes the whole partition and `P_out !== P` (with `dt` of length 1 or one per cell), the sweep into `work` and the update
+elsewhere (`work` is `nc × (nd + 2)` and must be given there).  `P_out` may be `P0` when `P0 !== P`.  An `m`-stage step runs
+this with `alpha = 1 / (m - k + 1)`, `k = 1:m`."
+function stage_euler!(P_out::HipArray{Float32}, part::HipPartition, P::HipArray{Float32}, P0::HipArray{Float32},
+                      dt::HipArray{Float32}, alpha::Real, fluid; scheme::Symbol = :hll,
+                      work::Union{HipArray{Float32}, Nothing} = nothing, flags::Integer = 0)
+    f = Ref(IbhFluid(fluid))
+    check(ccall((:ibh_stage_euler, lib), Cint,
+        (Ptr{Cvoid}, Ptr{IbhFluid}, Cint, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Cint, Cfloat,
+         Ptr{Cvoid}, Int64, Cint),
+        part.handle, f, scheme === :sensor ? 1 : 0, P.ptr, ld(P), P0.ptr, ld(P0), P_out.ptr, ld(P_out), dt.ptr,
+        length(dt) == 1 ? 0 : 1, Float32(alpha), isnothing(work) ? C_NULL : work.ptr, isnothing(work) ? 0 : ld(work), flags))
+    P_out
+end
+
 "`S .+ Σ_d green_gauss(at_faces(ν .+ νR, d) .* face_gradient(R, d) .- at_faces(vel[:, d] .* R, d), d)` in one launch
 (the transport residual closed by `Wray_Agarwal`, src/turbulence.jl:222-241), bit-identical to the composition."
 function scalar_transport!(out::HipArray{Float32}, part::HipPartition, R::HipArray{Float32}, νR::HipArray{Float32},
