@@ -930,6 +930,59 @@ def stage_euler(part, P, P0, dt, alpha, out, fluid=None, scheme="hll", work=None
     return out
 
 
+@_hipaware
+def update_euler_ssp(P0, P, R, dt, a, b, c, fluid=None, out=None):
+    """A Shu-Osher stage of a strong-stability-preserving Runge-Kutta scheme, ``state2primitive(fluid, (primitive2state(fluid,
+    P0) .* a .+ primitive2state(fluid, P) .* b) .+ R .* (dt .* c))`` in one launch, every product and sum rounded on its own:
+    bit for bit that composition of launches.  ``dt``: a one-element device tensor, or ``(n,)`` for a per-cell time step.
+    ``out`` may be ``P0`` or ``P``; ``P0`` may be ``P``."""
+    P0, nv, ld0 = _primitives(P0, None)
+    n = P0.shape[0]
+    P, _, ldp = _primitives(P, n, nv - 2)
+    R, nvr, ldr = _field(R, n)
+    if nvr != nv:
+        raise ValueError(f"R must be (n, {nv})")
+    dt, per_cell = _device_dt(dt, n, "update_euler_ssp")
+    if out is None:
+        out = colmajor_empty(n, nv)
+    o, nvo, ldo = _field_inplace(out, n, "out")
+    if nvo != nv:
+        raise ValueError(f"out must be (n, {nv})")
+    f = _cfluid(fluid)
+    _stream()
+    call("ibh_update_euler_ssp", C.byref(f), nv - 2, n, _ptr(P0), ld0, _ptr(P), ldp, _ptr(R), ldr, _ptr(dt), per_cell,
+         C.c_float(a), C.c_float(b), C.c_float(c), _ptr(o), ldo)
+    return out
+
+
+@_hipaware
+def stage_euler_ssp(part, P, P0, dt, a, b, c, out, fluid=None, scheme="hll", work=None, flags=0):
+    """One Shu-Osher stage, ``out = update_euler_ssp(P0, P, residual_euler_hll | residual_euler_sensor(part, P, flags), dt, a, b,
+    c)``: ``P`` is the previous stage -- swept, and blended with weight ``b`` -- and ``P0`` the state the step started from
+    (weight ``a``).  One launch where the 2-D single-kernel sweep takes the whole partition and ``out`` is not ``P``, with a
+    one-element and with a per-cell ``dt``; elsewhere the sweep goes into ``work`` -- ``(nc, nd+2)``, required there: the stage
+    allocates nothing -- and the update follows.  ``out`` may be ``P0`` when ``P0`` is not ``P``.  Same bits either way."""
+    part = _part(part)
+    P, nv, ldp = _primitives(P, part.nc, part.nd)
+    P0, _, ld0 = _primitives(P0, part.nc, part.nd)
+    dt, per_cell = _device_dt(dt, part.nc, "stage_euler_ssp")
+    o, nvo, ldo = _field_inplace(out, part.nc, "out")
+    if nvo != nv:
+        raise ValueError(f"out must be (nc, {nv})")
+    w, ldw = None, 0
+    if work is not None:
+        w, nvw, ldw = _field_inplace(work, part.nc, "work")
+        if nvw != nv:
+            raise ValueError(f"work must be (nc, {nv})")
+    if scheme not in _EULER_SCHEMES:
+        raise ValueError('scheme must be "hll" or "sensor"')
+    f = _cfluid(fluid)
+    _stream()
+    call("ibh_stage_euler_ssp", part.handle, C.byref(f), _EULER_SCHEMES[scheme], _ptr(P), ldp, _ptr(P0), ld0, _ptr(o), ldo,
+         _ptr(dt), per_cell, C.c_float(a), C.c_float(b), C.c_float(c), _ptr(w), ldw, int(flags))
+    return out
+
+
 # ---------------------------------------------------------------------------
 # partition runtime and ghost-cell BC
 # ---------------------------------------------------------------------------

@@ -126,6 +126,8 @@ update_euler = B.update_euler
 step_euler = B.step_euler
 update_euler_stage = B.update_euler_stage          # (ibh_update_euler_stage / ibh_stage_euler: a Runge-Kutta stage)
 stage_euler = B.stage_euler
+update_euler_ssp = B.update_euler_ssp              # (ibh_update_euler_ssp / ibh_stage_euler_ssp: a Shu-Osher stage)
+stage_euler_ssp = B.stage_euler_ssp
 
 
 def inviscid_fluxes(fluid, PL, PR, *args):

@@ -220,6 +220,46 @@ int ibh_stage_euler(ibh_part* p, const ibh_fluid* fluid, int scheme, const float
     return ibh_update_euler_stage(fluid, p->nd, p->nc, P0, ld0, work, ldw, dt, dt_per_cell, alpha, P_out, ldo);
 }
 
+// One Shu-Osher stage of a strong-stability-preserving scheme, P_out = state2primitive((primitive2state(P0) * a +
+// primitive2state(P) * b) + (c * dt) * R(P)): the sweep runs on the previous stage P, whose state also enters the blend.
+// ibh_stage_euler's dispatch: one launch where the 2-D single-kernel sweep takes the whole partition and P_out != P (the
+// sweep's SSP form keeps the cell's own state, loads the row of P0 and the cell's time step), two launches elsewhere.  Same
+// bits as ibh_update_euler_ssp(P0, P, R(P), dt, a, b, c) either way.
+int ibh_stage_euler_ssp(ibh_part* p, const ibh_fluid* fluid, int scheme, const float* P, int64_t ldp, const float* P0,
+                        int64_t ld0, float* P_out, int64_t ldo, const float* dt, int dt_per_cell, float a, float b, float c,
+                        float* work, int64_t ldw, int flags) {
+    IBH_REQUIRE(p && fluid && P && P0 && P_out && dt, "ibh_stage_euler_ssp: null argument");
+    IBH_REQUIRE(scheme == EULER_HLL || scheme == EULER_SENSOR, "ibh_stage_euler_ssp: scheme must be 0 (HLL) or 1 (sensor)");
+    IBH_REQUIRE(!(flags & IBH_IMAGE_ONLY),
+                "ibh_stage_euler_ssp: IBH_IMAGE_ONLY is not taken: the update would read skirt rows that the sweep never "
+                "wrote (the multi-GPU step is out of scope)");
+    IBH_REQUIRE(!(flags & F_PHASES),
+                "ibh_stage_euler_ssp: the overlap phases IBH_PHASE_INTERIOR / IBH_PHASE_BOUNDARY are not taken: the update "
+                "would read rows that the phase never wrote");
+    IBH_REQUIRE(!(flags & (IBH_PASS_A_ONLY | IBH_PASS_B_ONLY)), "ibh_stage_euler_ssp: a single pass of the sweep is no stage");
+    IBH_REQUIRE(p->nd == 2 || p->nd == 3, "ibh_stage_euler_ssp: nd must be 2 or 3");
+    IBH_REQUIRE(ldp >= p->nc && ld0 >= p->nc && ldo >= p->nc,
+                "ibh_stage_euler_ssp: a leading dimension is smaller than the number of cells");
+    IBH_REQUIRE(work != P && work != P0 && work != P_out, "ibh_stage_euler_ssp: work may not alias P, P0 or P_out");
+    if (p->nc == 0) return 0;
+    EulerArgs e{P, ldp, P_out, ldo, fluid, scheme == EULER_SENSOR ? EULER_SENSOR : EULER_HLL};
+    if (euler_path(p, flags, e) == EUL2_SINGLE && p->fuse_all && P_out != P) {
+        e.dt = dt;
+        e.P0 = P0, e.ld0 = ld0, e.alpha = c, e.dt_cells = dt_per_cell != 0;
+        e.ssp = true, e.a = a, e.b = b;
+        euler2_single(p, e, flags, Phase(0));
+        IBH_LAUNCH_CHECK();
+        return 0;
+    }
+    IBH_REQUIRE(work, "ibh_stage_euler_ssp: this partition / these arguments take the two-launch form (sweep into `work`, "
+                      "then ibh_update_euler_ssp): work must be nc x (nd + 2) floats");
+    IBH_REQUIRE(ldw >= p->nc, "ibh_stage_euler_ssp: ldw is smaller than the number of cells");
+    const int rc = scheme == EULER_SENSOR ? ibh_residual_euler_sensor(p, P, ldp, nullptr, work, ldw, fluid, flags)
+                                          : ibh_residual_euler_hll(p, P, ldp, work, ldw, fluid, flags);
+    if (rc) return rc;
+    return ibh_update_euler_ssp(fluid, p->nd, p->nc, P0, ld0, P, ldp, work, ldw, dt, dt_per_cell, a, b, c, P_out, ldo);
+}
+
 // One step, u_out = u + dt * residual: in one launch where the quad sweep covers the whole partition (it stores the update,
 // its cells of u are in registers), the sweep and the update one after the other elsewhere.
 int ibh_step_advection(ibh_part* p, const float* u, float* u_out, const float* C, int64_t ldc, const float* dt_dev,

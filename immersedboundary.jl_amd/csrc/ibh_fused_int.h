@@ -84,6 +84,8 @@ struct EulerArgs {  // (the entries' fields)
     // ibh_stage_euler on a single-kernel path (with dt): the row that is updated is P0's (P0 may be R), the time step is
     // alpha * dt, and dt holds one value per cell where dt_cells is set
     const float* P0 = nullptr; int64_t ld0 = 0; float alpha = 1.0f; bool dt_cells = false;
+    // ibh_stage_euler_ssp on a single-kernel path (with P0): the update of the blend a p2s(P0) + b p2s(P), alpha is the stage's c
+    bool ssp = false; float a = 0.0f, b = 1.0f;
 };
 
 // ---- advection: paths

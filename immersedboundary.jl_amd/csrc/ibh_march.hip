@@ -11,6 +11,8 @@
 //     step around it is ibh_step_euler in ibh_fused.hip, its time step ibh_timestep_euler in ibh_ops.hip.
 //   * ibh_update_euler_stage: the same row function on a base state P0 with the time step alpha * dt, a Runge-Kutta stage of
 //     the low-storage family; the stage around it is ibh_stage_euler in ibh_fused.hip.
+//   * ibh_update_euler_ssp: a Shu-Osher stage, the update of the blend a primitive2state(P0) + b primitive2state(P) with the
+//     time step c * dt (euler_step::blend_row); the stage around it is ibh_stage_euler_ssp in ibh_fused.hip.
 // Arithmetic: the operator kernels' (ibh_ops.hip): -ffp-contract=off, the reference's evaluation order.
 #include <algorithm>
 #include <cstdlib>
@@ -153,6 +155,32 @@ __global__ __launch_bounds__(MARCH_BLOCK) void k_update_euler_stage(float Rgas, 
         }
         if constexpr (PER_CELL) h = euler_step::stage_dt(alpha, dt[i]);
         euler_step::update_row<ND>(Rgas, gamma, Pr, r, h, o);
+#pragma unroll
+        for (int v = 0; v < NV; ++v) P_out[i + v * ldo] = o[v];
+    }
+}
+
+// A Shu-Osher stage: P_out = state2primitive((primitive2state(P0) a + primitive2state(P) b) + (c dt) R)
+// (euler_step::blend_row).  The rows of P0 and of P are read whole before the row of P_out is written: P_out may be either
+template <int ND, bool PER_CELL>
+__global__ __launch_bounds__(MARCH_BLOCK) void k_update_euler_ssp(float Rgas, float gamma, int64_t n, const float* P0,
+                                                                  int64_t ld0, const float* P, int64_t ldp,
+                                                                  const float* __restrict__ R, int64_t ldr,
+                                                                  const float* __restrict__ dt, float a, float b, float c,
+                                                                  float* P_out, int64_t ldo) {
+    constexpr int NV = ND + 2;
+    float h = 0.0f;
+    if constexpr (!PER_CELL) h = euler_step::stage_dt(c, *dt);
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        float Br[NV], Pr[NV], r[NV], o[NV];
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+            Br[v] = P0[i + v * ld0];
+            Pr[v] = P[i + v * ldp];
+            r[v] = R[i + v * ldr];
+        }
+        if constexpr (PER_CELL) h = euler_step::stage_dt(c, dt[i]);
+        euler_step::blend_row<ND>(Rgas, gamma, Br, Pr, r, a, b, h, o);
 #pragma unroll
         for (int v = 0; v < NV; ++v) P_out[i + v * ldo] = o[v];
     }
@@ -348,6 +376,35 @@ int ibh_update_euler_stage(const ibh_fluid* f, int nd, int64_t n, const float* P
 #define UPD_LAUNCH(ND_, PC_)                                                                                               \
     hipLaunchKernelGGL((k_update_euler_stage<ND_, PC_>), grid, block, 0, ibh_stream, f->R, f->gamma, n, P0, ld0, R, ldr, dt, \
                        alpha, P_out, ldo)
+    if (nd == 2) {
+        if (dt_per_cell) UPD_LAUNCH(2, true);
+        else UPD_LAUNCH(2, false);
+    } else {
+        if (dt_per_cell) UPD_LAUNCH(3, true);
+        else UPD_LAUNCH(3, false);
+    }
+#undef UPD_LAUNCH
+    IBH_LAUNCH_CHECK();
+    return 0;
+}
+
+// A Shu-Osher stage of a strong-stability-preserving Runge-Kutta scheme in one launch,
+//     P_out = state2primitive((primitive2state(P0) * a + primitive2state(P) * b) + (c * dt) * R):
+// bit for bit primitive2state twice, the broadcasts dt .* c and Q0 .* a .+ Q .* b, the column updates and state2primitive
+int ibh_update_euler_ssp(const ibh_fluid* f, int nd, int64_t n, const float* P0, int64_t ld0, const float* P, int64_t ldp,
+                         const float* R, int64_t ldr, const float* dt, int dt_per_cell, float a, float b, float c,
+                         float* P_out, int64_t ldo) {
+    IBH_REQUIRE(f && P0 && P && R && dt && P_out, "ibh_update_euler_ssp: null argument");
+    IBH_REQUIRE(nd == 2 || nd == 3, "ibh_update_euler_ssp: nd must be 2 or 3");
+    IBH_REQUIRE(n >= 0 && ld0 >= n && ldp >= n && ldr >= n && ldo >= n,
+                "ibh_update_euler_ssp: a leading dimension is smaller than n");
+    IBH_REQUIRE(P_out != R && P0 != R && P != R,
+                "ibh_update_euler_ssp: R may not alias P0, P or P_out (P_out may be P0 or P, P0 may be P)");
+    if (n == 0) return 0;
+    const dim3 grid(ibh_grid_cap(n, MARCH_BLOCK, 2048)), block(MARCH_BLOCK);
+#define UPD_LAUNCH(ND_, PC_)                                                                                                  \
+    hipLaunchKernelGGL((k_update_euler_ssp<ND_, PC_>), grid, block, 0, ibh_stream, f->R, f->gamma, n, P0, ld0, P, ldp, R, ldr, \
+                       dt, a, b, c, P_out, ldo)
     if (nd == 2) {
         if (dt_per_cell) UPD_LAUNCH(2, true);
         else UPD_LAUNCH(2, false);

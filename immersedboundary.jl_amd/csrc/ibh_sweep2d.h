@@ -431,7 +431,9 @@ __device__ __forceinline__ SweepPreE sweep_prefetch_e(const BlockDesc2* __restri
 // (ibh_euler_step_dev.h, contraction off) and P_out = state2primitive(primitive2state(P) + dt R) is stored to `Rr`
 // STAGE (ibh_stage_euler, with STEP): the row that is updated is the cell's row of the base state P0, loaded here (P0 may be
 // the output: a lane reads its row before it stores), and the time step is alpha * dt -- dt per wave or (DTC) one per lane
-template <int SCH = EULER_HLL, bool STEP = false, bool STAGE = false, bool DTC = false>
+// SSP (ibh_stage_euler_ssp, with STEP and STAGE): a Shu-Osher stage -- T.Pc as in the STEP form, the row of P0 and the time step as
+// in the STAGE form, through euler_step::blend_row with the weights sa.a, sa.b and the time step sa.alpha * dt
+template <int SCH = EULER_HLL, bool STEP = false, bool STAGE = false, bool DTC = false, bool SSP = false>
 __device__ __forceinline__ void sweep_euler(const BlockDesc2* __restrict__ blocks, const int32_t* __restrict__ htab,
                                             const int32_t* __restrict__ etab, const int32_t* __restrict__ dtab,
                                             const int32_t* __restrict__ blist, int32_t blk0, int32_t stride, int32_t nb,
@@ -440,6 +442,7 @@ __device__ __forceinline__ void sweep_euler(const BlockDesc2* __restrict__ block
                                             euler_step::StageArgs sa = euler_step::StageArgs()) {
     static_assert(STEP || !STAGE, "the STAGE form is a STEP form");
     static_assert(STAGE || !DTC, "per-cell time steps come with the STAGE form");
+    static_assert((STEP && STAGE) || !SSP, "the SSP form is a STEP and a STAGE form");
     float* fP = lds;           // [4][128]
     float* fD = lds + 512;     // [128]
     float* fSX = lds + 640;    // [4][128]
@@ -638,7 +641,7 @@ __device__ __forceinline__ void sweep_euler(const BlockDesc2* __restrict__ block
 #pragma unroll
             for (int v = 0; v < 4; ++v) stg(Rr + (size_t)v * ldr, (uint32_t)bb.base + lane, o[v]);
         }
-        if constexpr (STAGE) {
+        if constexpr (STAGE && !SSP) {
             const uint32_t c = (uint32_t)bb.base + lane;
             float b[4], o[4];
 #pragma unroll
@@ -646,6 +649,17 @@ __device__ __forceinline__ void sweep_euler(const BlockDesc2* __restrict__ block
             float h = dt;
             if constexpr (DTC) h = *(const float*)((const char*)sa.dtc + (size_t)(c << 2));
             euler_step::update_row<2>(gas.R, gas.gamma, b, rv, euler_step::stage_dt(sa.alpha, h), o);
+#pragma unroll
+            for (int v = 0; v < 4; ++v) stg(Rr + (size_t)v * ldr, c, o[v]);
+        }
+        if constexpr (SSP) {
+            const uint32_t c = (uint32_t)bb.base + lane;
+            float b[4], o[4];
+#pragma unroll
+            for (int v = 0; v < 4; ++v) b[v] = *(const float*)((const char*)(sa.P0 + (size_t)v * sa.ld0) + (size_t)(c << 2));
+            float h = dt;
+            if constexpr (DTC) h = *(const float*)((const char*)sa.dtc + (size_t)(c << 2));
+            euler_step::blend_row<2>(gas.R, gas.gamma, b, T.Pc, rv, sa.a, sa.b, euler_step::stage_dt(sa.alpha, h), o);
 #pragma unroll
             for (int v = 0; v < 4; ++v) stg(Rr + (size_t)v * ldr, c, o[v]);
         }

@@ -165,6 +165,19 @@ def rk_stages(m):
     return tuple(1.0 / (m - k + 1) for k in range(1, m + 1))
 
 
+def ssp_stages(order):
+    """The Shu-Osher form of the strong-stability-preserving Runge-Kutta scheme of ``order`` 2 or 3 (SSPRK2: Heun's method,
+    SSPRK3: Shu and Osher's third-order scheme) as a tuple of ``(a, b, c)`` triples, one per stage:
+    ``Q_k = a Q_0 + b Q_{k-1} + c dt R(P_{k-1})`` in conserved variables.  Every stage is a convex combination (``a, b >= 0``,
+    ``a + b = 1``, ``c = b``) of the step's input and a forward-Euler step of the previous stage, so the scheme keeps every
+    bound forward Euler keeps under the same time step."""
+    if isinstance(order, bool) or order not in (2, 3):
+        raise ValueError("ssp_stages: order must be 2 or 3")
+    if int(order) == 2:
+        return ((0.0, 1.0, 1.0), (1.0 / 2, 1.0 / 2, 1.0 / 2))
+    return ((0.0, 1.0, 1.0), (3.0 / 4, 1.0 / 4, 1.0 / 4), (1.0 / 3, 2.0 / 3, 2.0 / 3))
+
+
 class EulerMarch:
     """The explicit time march of an unsteady Euler / LES run on one partition, without the host in the loop: per step
 
@@ -190,7 +203,13 @@ class EulerMarch:
     into ``work``, then ``update_euler_stage``), ``bcs`` after every one of them -- the next sweep reads the ghost cells --
     and ``average.push(P_m, dt)`` once with the full ``dt``.  The march then owns three arrays: the stages alternate between
     the two that do not hold ``P_0``, so ``P_0`` -- the caller's array or the previous return value -- is never written.
-    Either way a returned array stays valid during the next ``step`` and is overwritten by the one after it."""
+    Either way a returned array stays valid during the next ``step`` and is overwritten by the one after it.
+
+    ``stages`` as a tuple of ``(a, b, c)`` triples (``ssp_stages(order)``) marches in the Shu-Osher form
+    ``Q_k = a Q_0 + b Q_{k-1} + c dt R(P_{k-1})``: a stage with ``(a, b) == (0, 1)`` is ``stage_euler(P_{k-1}, P_{k-1}, dt, c)``
+    -- no blend -- and every other one ``stage_euler_ssp(P_{k-1}, P_0, dt, a, b, c)`` (with ``residual``: the callable into
+    ``work``, then ``update_euler_stage`` / ``update_euler_ssp``); time step, ``bcs``, ``average`` and the three arrays as
+    above."""
 
     def __init__(self, part, fluid=None, scheme="hll", scale=0.75, bcs=None, average=None, local_dt=False, dt_every=1,
                  residual=None, flags=0, stages=1):
@@ -205,7 +224,13 @@ class EulerMarch:
             raise ValueError("a time average needs one time step for all cells: local_dt marches in pseudo-time")
         self.scheme, self.scale, self.bcs, self.average = scheme, float(scale), bcs, average
         self.local_dt, self.dt_every, self.residual, self.flags = bool(local_dt), int(dt_every), residual, int(flags)
-        self.stages = tuple(float(a) for a in stages) if isinstance(stages, (tuple, list)) else rk_stages(stages)
+        self._ssp = isinstance(stages, (tuple, list)) and any(isinstance(a, (tuple, list)) for a in stages)
+        if self._ssp:
+            if not all(isinstance(a, (tuple, list)) and len(a) == 3 for a in stages):
+                raise ValueError("stages in the Shu-Osher form must be (a, b, c) triples, every one of them")
+            self.stages = tuple(tuple(float(x) for x in a) for a in stages)
+        else:
+            self.stages = tuple(float(a) for a in stages) if isinstance(stages, (tuple, list)) else rk_stages(stages)
         if not self.stages:
             raise ValueError("stages must name at least one stage coefficient")
         self._staged = self.stages != (1.0,)
@@ -224,6 +249,8 @@ class EulerMarch:
                 B.timestep_euler(self.part, P, self.fluid, self.scale, out=False, cells=self.dt)
             else:
                 B.timestep_euler(self.part, P, self.fluid, self.scale, out=self.dt)
+        if self._ssp:
+            return self._ssp_stages(P)
         if self._staged:
             return self._stages(P)
         out = self._buf[0] if P.data_ptr() != self._buf[0].data_ptr() else self._buf[1]
@@ -252,6 +279,33 @@ class EulerMarch:
             else:
                 B.stage_euler(self.part, src, P0, self.dt, alpha, out, self.fluid, self.scheme, work=self.work,
                               flags=self.flags)
+            if self.bcs is not None:
+                self.bcs(out)
+            src = out
+        if self.average is not None:
+            self.average.push(src, self.dt)
+        self.nsteps += 1
+        return src
+
+    def _ssp_stages(self, P0):
+        """The Shu-Osher stages of one step from ``P0``: stage ``k`` sweeps the previous stage and writes the update of its
+        blend with ``P0`` into one of the two arrays that are neither ``P0`` nor its own input."""
+        free = [b for b in self._buf if b.data_ptr() != P0.data_ptr()][:2]
+        src = P0
+        for k, (a, b, c) in enumerate(self.stages):
+            out = free[k % 2]
+            plain = a == 0.0 and b == 1.0                  # no blend: the low-storage stage on the previous stage itself
+            if self.residual is not None:
+                self.residual(self.part, src, self.work)
+                if plain:
+                    B.update_euler_stage(src, self.work, self.dt, c, self.fluid, out=out)
+                else:
+                    B.update_euler_ssp(P0, src, self.work, self.dt, a, b, c, self.fluid, out=out)
+            elif plain:
+                B.stage_euler(self.part, src, src, self.dt, c, out, self.fluid, self.scheme, work=self.work, flags=self.flags)
+            else:
+                B.stage_euler_ssp(self.part, src, P0, self.dt, a, b, c, out, self.fluid, self.scheme, work=self.work,
+                                  flags=self.flags)
             if self.bcs is not None:
                 self.bcs(out)
             src = out

@@ -464,6 +464,28 @@ int ibh_update_euler_stage(const ibh_fluid*, int nd, int64_t n, const float* P0,
 int ibh_stage_euler(ibh_part*, const ibh_fluid*, int scheme /* IBH_EULER_HLL | IBH_EULER_SENSOR */, const float* P, int64_t ldp,
                     const float* P0, int64_t ld0, float* P_out, int64_t ldo, const float* dt, int dt_per_cell, float alpha,
                     float* work /* nc x (nd+2) or NULL */, int64_t ldw, int flags);
+/* ---- Shu-Osher stages of the strong-stability-preserving Runge-Kutta schemes: a stage is a convex combination of the step's
+ *   input P_0 and a forward-Euler step of the previous stage P,
+ *     P_out = state2primitive((primitive2state(P0) * a + primitive2state(P) * b) + (c * dt) * R(P)),
+ *   every product and sum rounded on its own, in this order; nothing is dropped for a == 0 or b == 0.
+ *   SSPRK2: (a, b, c) = (0, 1, 1), (1/2, 1/2, 1/2); SSPRK3: (0, 1, 1), (3/4, 1/4, 1/4), (1/3, 2/3, 2/3).
+ * ibh_update_euler_ssp: that update in one launch for a given R, bit for bit the composition primitive2state(P0),
+ *   primitive2state(P), the broadcasts dt .* c and Q0 .* a .+ Q .* b, ibh_update_dev per column (per-cell dt: the broadcasts
+ *   R .* dts and +), state2primitive.  dt: one device value, or n of them (dt_per_cell != 0).  P_out may be P0 or P, P0 may be
+ *   P; R may alias none of them.  n == 0 launches nothing.
+ * ibh_stage_euler_ssp: the update with R = ibh_residual_euler_hll / _sensor(P, flags).  ibh_stage_euler's dispatch: ONE launch
+ *   where the 2-D single-kernel sweep takes the whole partition and P_out != P, with a global and with a per-cell dt (the
+ *   sweep keeps the cell's own state and loads its row of P0 and its time step in its store epilogue); two launches
+ *   everywhere else (3-D, face-list or mixed partitions, IBH_FORCE_GENERAL, IBH_NO_FUSE, IBH_EXACT, P_out == P): the sweep
+ *   into `work` -- an argument check there, never an allocation -- then ibh_update_euler_ssp.  Same bits either way.  P_out
+ *   may be P0 when P0 is not P; work may alias none of P, P0, P_out.  IBH_IMAGE_ONLY, the overlap phases and the single-pass
+ *   flags are rejected as by ibh_stage_euler; every misuse is an error before any launch. */
+int ibh_update_euler_ssp(const ibh_fluid*, int nd, int64_t n, const float* P0, int64_t ld0, const float* P, int64_t ldp,
+                         const float* R, int64_t ldr, const float* dt, int dt_per_cell, float a, float b, float c,
+                         float* P_out, int64_t ldo);
+int ibh_stage_euler_ssp(ibh_part*, const ibh_fluid*, int scheme /* IBH_EULER_HLL | IBH_EULER_SENSOR */, const float* P,
+                        int64_t ldp, const float* P0, int64_t ld0, float* P_out, int64_t ldo, const float* dt, int dt_per_cell,
+                        float a, float b, float c, float* work /* nc x (nd+2) or NULL */, int64_t ldw, int flags);
 int ibh_axpy_clamped(int64_t n, float omega, const float* r, float* q);
 /* y = a*x + y */
 int ibh_axpy(int64_t n, float a, const float* x, float* y);

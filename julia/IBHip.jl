@@ -877,6 +877,38 @@ function stage_euler!(P_out::HipArray{Float32}, part::HipPartition, P::HipArray{
     P_out
 end
 
+"A Shu-Osher stage of a strong-stability-preserving Runge-Kutta scheme, `P_out = state2primitive(fluid, (primitive2state(fluid,
+P0) .* a .+ primitive2state(fluid, P) .* b) .+ R .* (dt .* c))` in one launch, every product and sum rounded on its own; `dt` of
+length 1, or one per row.  `P_out` may be `P0` or `P`."
+function update_euler_ssp!(P_out::HipArray{Float32}, fluid, P0::HipArray{Float32}, P::HipArray{Float32}, R::HipArray{Float32},
+                           dt::HipArray{Float32}, a::Real, b::Real, c::Real)
+    f = Ref(IbhFluid(fluid))
+    check(ccall((:ibh_update_euler_ssp, lib), Cint,
+        (Ptr{IbhFluid}, Cint, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Cint, Cfloat, Cfloat,
+         Cfloat, Ptr{Cvoid}, Int64),
+        f, size(P0, 2) - 2, size(P0, 1), P0.ptr, ld(P0), P.ptr, ld(P), R.ptr, ld(R), dt.ptr, length(dt) == 1 ? 0 : 1, Float32(a),
+        Float32(b), Float32(c), P_out.ptr, ld(P_out)))
+    P_out
+end
+
+"One Shu-Osher stage, `update_euler_ssp!(P_out, fluid, P0, P, residual_euler_hll!/sensor!(work, part, P, fluid; flags), dt, a, b,
+c)`: `P` is the previous stage, `P0` the state the step started from.  One launch where the 2-D single-kernel sweep takes the
+whole partition and `P_out !== P` (with `dt` of length 1 or one per cell), the sweep into `work` and the update elsewhere
+(`work` is `nc × (nd + 2)` and must be given there).  `P_out` may be `P0` when `P0 !== P`.  SSPRK3 runs `stage_euler!` with
+`alpha = 1` on `P0`, then this with `(3/4, 1/4, 1/4)` and `(1/3, 2/3, 2/3)`."
+function stage_euler_ssp!(P_out::HipArray{Float32}, part::HipPartition, P::HipArray{Float32}, P0::HipArray{Float32},
+                          dt::HipArray{Float32}, a::Real, b::Real, c::Real, fluid; scheme::Symbol = :hll,
+                          work::Union{HipArray{Float32}, Nothing} = nothing, flags::Integer = 0)
+    f = Ref(IbhFluid(fluid))
+    check(ccall((:ibh_stage_euler_ssp, lib), Cint,
+        (Ptr{Cvoid}, Ptr{IbhFluid}, Cint, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Cint, Cfloat,
+         Cfloat, Cfloat, Ptr{Cvoid}, Int64, Cint),
+        part.handle, f, scheme === :sensor ? 1 : 0, P.ptr, ld(P), P0.ptr, ld(P0), P_out.ptr, ld(P_out), dt.ptr,
+        length(dt) == 1 ? 0 : 1, Float32(a), Float32(b), Float32(c), isnothing(work) ? C_NULL : work.ptr,
+        isnothing(work) ? 0 : ld(work), flags))
+    P_out
+end
+
 "`S .+ Σ_d green_gauss(at_faces(ν .+ νR, d) .* face_gradient(R, d) .- at_faces(vel[:, d] .* R, d), d)` in one launch
 (the transport residual closed by `Wray_Agarwal`, src/turbulence.jl:222-241), bit-identical to the composition."
 function scalar_transport!(out::HipArray{Float32}, part::HipPartition, R::HipArray{Float32}, νR::HipArray{Float32},
