@@ -832,24 +832,57 @@ def timestep_euler(part, P, fluid=None, scale=1.0, out=None, cells=None):
     return dt if dt is not None else cells
 
 
-@_hipaware
-def update_euler(P, R, dt, fluid=None, out=None):
-    """``state2primitive(fluid, primitive2state(fluid, P) .+ dt .* R)`` in one launch (bit for bit the three).  ``dt``: a
-    one-element device tensor, or ``(n,)`` for a per-cell time step.  ``out`` may be ``P`` itself (in place)."""
-    P, nv, ldp = _primitives(P, None)
-    n = P.shape[0]
-    R, nvr, ldr = _field(R, n)
-    if nvr != nv:
-        raise ValueError(f"R must be (n, {nv})")
-    dt, per_cell = _device_dt(dt, n, "update_euler")
+def _update_args(what, states, dt, out, R=None, n=None, nd=None):
+    """The arguments of an Euler update ``what``, checked: the primitive ``states`` in the order of the C call (the first one
+    gives ``n`` and ``nd`` where the partition does not), the residual ``R`` (None for a step, which sweeps it itself), ``dt``
+    and ``out`` (None: a new array).  Returns ``(n, nv, S, R, D, O, out, keep)``: ``S``, ``R``, ``D``, ``O`` are the C arguments
+    of the states (pointer, leading dimension, ...), of ``R``, of ``dt`` (pointer, per_cell) and of ``out``; ``keep`` holds
+    the tensors they point into and stays with the caller until the call has returned."""
+    rows, nv, S, keep = "n" if n is None else "nc", None, [], []
+    for P in states:
+        P, nv, ld = _primitives(P, n, nd if nv is None else nv - 2)
+        n = P.shape[0]
+        S += [_ptr(P), ld]
+        keep.append(P)
+    Ra = []
+    if R is not None:
+        R, nvr, ldr = _field(R, n)
+        if nvr != nv:
+            raise ValueError(f"R must be (n, {nv})")
+        Ra = [_ptr(R), ldr]
+        keep.append(R)
+    dt, per_cell = _device_dt(dt, n, what)
     if out is None:
         out = colmajor_empty(n, nv)
     o, nvo, ldo = _field_inplace(out, n, "out")
     if nvo != nv:
-        raise ValueError(f"out must be (n, {nv})")
+        raise ValueError(f"out must be ({rows}, {nv})")
+    return n, nv, S, Ra, [_ptr(dt), per_cell], [_ptr(o), ldo], out, keep + [dt, o]
+
+
+def _step_args(what, part, states, dt, out, work, scheme):
+    """The arguments of a sweep plus update ``what`` on a partition: ``_update_args`` of the states at the partition's size,
+    then ``work`` (None, or ``(nc, nd+2)``) and the scheme's number.  Returns ``(part, sch, S, D, O, W, out, keep)``."""
+    part = _part(part)
+    _, nv, S, _, D, O, out, keep = _update_args(what, states, dt, out, n=part.nc, nd=part.nd)
+    w, ldw = None, 0
+    if work is not None:
+        w, nvw, ldw = _field_inplace(work, part.nc, "work")
+        if nvw != nv:
+            raise ValueError(f"work must be (nc, {nv})")
+    if scheme not in _EULER_SCHEMES:
+        raise ValueError('scheme must be "hll" or "sensor"')
+    return part, _EULER_SCHEMES[scheme], S, D, O, [_ptr(w), ldw], out, keep + [w]
+
+
+@_hipaware
+def update_euler(P, R, dt, fluid=None, out=None):
+    """``state2primitive(fluid, primitive2state(fluid, P) .+ dt .* R)`` in one launch (bit for bit the three).  ``dt``: a
+    one-element device tensor, or ``(n,)`` for a per-cell time step.  ``out`` may be ``P`` itself (in place)."""
+    n, nv, S, Ra, D, O, out, keep = _update_args("update_euler", (P,), dt, out, R)
     f = _cfluid(fluid)
     _stream()
-    call("ibh_update_euler", C.byref(f), nv - 2, n, _ptr(P), ldp, _ptr(R), ldr, _ptr(dt), per_cell, _ptr(o), ldo)
+    call("ibh_update_euler", C.byref(f), nv - 2, n, *S, *Ra, *D, *O)
     return out
 
 
@@ -859,23 +892,10 @@ def step_euler(part, P, dt, out, fluid=None, scheme="hll", work=None, flags=0):
     (``scheme``: "hll" or "sensor").  One launch where the 2-D single-kernel sweep takes the whole partition, ``dt`` is one
     element and ``out`` is not ``P``; elsewhere the sweep goes into ``work`` -- ``(nc, nd+2)``, required there: the step
     allocates nothing -- and the update follows (``out`` may be ``P`` then).  Same bits either way."""
-    part = _part(part)
-    P, nv, ldp = _primitives(P, part.nc, part.nd)
-    dt, per_cell = _device_dt(dt, part.nc, "step_euler")
-    o, nvo, ldo = _field_inplace(out, part.nc, "out")
-    if nvo != nv:
-        raise ValueError(f"out must be (nc, {nv})")
-    w, ldw = None, 0
-    if work is not None:
-        w, nvw, ldw = _field_inplace(work, part.nc, "work")
-        if nvw != nv:
-            raise ValueError(f"work must be (nc, {nv})")
-    if scheme not in _EULER_SCHEMES:
-        raise ValueError('scheme must be "hll" or "sensor"')
+    part, sch, S, D, O, W, out, keep = _step_args("step_euler", part, (P,), dt, out, work, scheme)
     f = _cfluid(fluid)
     _stream()
-    call("ibh_step_euler", part.handle, C.byref(f), _EULER_SCHEMES[scheme], _ptr(P), ldp, _ptr(o), ldo, _ptr(dt), per_cell,
-         _ptr(w), ldw, int(flags))
+    call("ibh_step_euler", part.handle, C.byref(f), sch, *S, *O, *D, *W, int(flags))
     return out
 
 
@@ -884,21 +904,10 @@ def update_euler_stage(P0, R, dt, alpha, fluid=None, out=None):
     """A Runge-Kutta stage of the low-storage family, ``state2primitive(fluid, primitive2state(fluid, P0) .+ (alpha .* dt)
     .* R)`` in one launch: bit for bit ``update_euler(P0, R, dt .* Float32(alpha))``.  ``dt``: a one-element device tensor,
     or ``(n,)`` for a per-cell time step.  ``out`` may be ``P0`` itself."""
-    P0, nv, ld0 = _primitives(P0, None)
-    n = P0.shape[0]
-    R, nvr, ldr = _field(R, n)
-    if nvr != nv:
-        raise ValueError(f"R must be (n, {nv})")
-    dt, per_cell = _device_dt(dt, n, "update_euler_stage")
-    if out is None:
-        out = colmajor_empty(n, nv)
-    o, nvo, ldo = _field_inplace(out, n, "out")
-    if nvo != nv:
-        raise ValueError(f"out must be (n, {nv})")
+    n, nv, S, Ra, D, O, out, keep = _update_args("update_euler_stage", (P0,), dt, out, R)
     f = _cfluid(fluid)
     _stream()
-    call("ibh_update_euler_stage", C.byref(f), nv - 2, n, _ptr(P0), ld0, _ptr(R), ldr, _ptr(dt), per_cell,
-         C.c_float(alpha), _ptr(o), ldo)
+    call("ibh_update_euler_stage", C.byref(f), nv - 2, n, *S, *Ra, *D, C.c_float(alpha), *O)
     return out
 
 
@@ -909,24 +918,10 @@ def stage_euler(part, P, P0, dt, alpha, out, fluid=None, scheme="hll", work=None
     One launch where the 2-D single-kernel sweep takes the whole partition and ``out`` is not ``P`` -- with a one-element
     and with a per-cell ``dt``; elsewhere the sweep goes into ``work`` -- ``(nc, nd+2)``, required there: the stage
     allocates nothing -- and the update follows.  ``out`` may be ``P0`` when ``P0`` is not ``P``.  Same bits either way."""
-    part = _part(part)
-    P, nv, ldp = _primitives(P, part.nc, part.nd)
-    P0, _, ld0 = _primitives(P0, part.nc, part.nd)
-    dt, per_cell = _device_dt(dt, part.nc, "stage_euler")
-    o, nvo, ldo = _field_inplace(out, part.nc, "out")
-    if nvo != nv:
-        raise ValueError(f"out must be (nc, {nv})")
-    w, ldw = None, 0
-    if work is not None:
-        w, nvw, ldw = _field_inplace(work, part.nc, "work")
-        if nvw != nv:
-            raise ValueError(f"work must be (nc, {nv})")
-    if scheme not in _EULER_SCHEMES:
-        raise ValueError('scheme must be "hll" or "sensor"')
+    part, sch, S, D, O, W, out, keep = _step_args("stage_euler", part, (P, P0), dt, out, work, scheme)
     f = _cfluid(fluid)
     _stream()
-    call("ibh_stage_euler", part.handle, C.byref(f), _EULER_SCHEMES[scheme], _ptr(P), ldp, _ptr(P0), ld0, _ptr(o), ldo,
-         _ptr(dt), per_cell, C.c_float(alpha), _ptr(w), ldw, int(flags))
+    call("ibh_stage_euler", part.handle, C.byref(f), sch, *S, *O, *D, C.c_float(alpha), *W, int(flags))
     return out
 
 
@@ -936,22 +931,10 @@ def update_euler_ssp(P0, P, R, dt, a, b, c, fluid=None, out=None):
     P0) .* a .+ primitive2state(fluid, P) .* b) .+ R .* (dt .* c))`` in one launch, every product and sum rounded on its own:
     bit for bit that composition of launches.  ``dt``: a one-element device tensor, or ``(n,)`` for a per-cell time step.
     ``out`` may be ``P0`` or ``P``; ``P0`` may be ``P``."""
-    P0, nv, ld0 = _primitives(P0, None)
-    n = P0.shape[0]
-    P, _, ldp = _primitives(P, n, nv - 2)
-    R, nvr, ldr = _field(R, n)
-    if nvr != nv:
-        raise ValueError(f"R must be (n, {nv})")
-    dt, per_cell = _device_dt(dt, n, "update_euler_ssp")
-    if out is None:
-        out = colmajor_empty(n, nv)
-    o, nvo, ldo = _field_inplace(out, n, "out")
-    if nvo != nv:
-        raise ValueError(f"out must be (n, {nv})")
+    n, nv, S, Ra, D, O, out, keep = _update_args("update_euler_ssp", (P0, P), dt, out, R)
     f = _cfluid(fluid)
     _stream()
-    call("ibh_update_euler_ssp", C.byref(f), nv - 2, n, _ptr(P0), ld0, _ptr(P), ldp, _ptr(R), ldr, _ptr(dt), per_cell,
-         C.c_float(a), C.c_float(b), C.c_float(c), _ptr(o), ldo)
+    call("ibh_update_euler_ssp", C.byref(f), nv - 2, n, *S, *Ra, *D, C.c_float(a), C.c_float(b), C.c_float(c), *O)
     return out
 
 
@@ -962,24 +945,11 @@ def stage_euler_ssp(part, P, P0, dt, a, b, c, out, fluid=None, scheme="hll", wor
     (weight ``a``).  One launch where the 2-D single-kernel sweep takes the whole partition and ``out`` is not ``P``, with a
     one-element and with a per-cell ``dt``; elsewhere the sweep goes into ``work`` -- ``(nc, nd+2)``, required there: the stage
     allocates nothing -- and the update follows.  ``out`` may be ``P0`` when ``P0`` is not ``P``.  Same bits either way."""
-    part = _part(part)
-    P, nv, ldp = _primitives(P, part.nc, part.nd)
-    P0, _, ld0 = _primitives(P0, part.nc, part.nd)
-    dt, per_cell = _device_dt(dt, part.nc, "stage_euler_ssp")
-    o, nvo, ldo = _field_inplace(out, part.nc, "out")
-    if nvo != nv:
-        raise ValueError(f"out must be (nc, {nv})")
-    w, ldw = None, 0
-    if work is not None:
-        w, nvw, ldw = _field_inplace(work, part.nc, "work")
-        if nvw != nv:
-            raise ValueError(f"work must be (nc, {nv})")
-    if scheme not in _EULER_SCHEMES:
-        raise ValueError('scheme must be "hll" or "sensor"')
+    part, sch, S, D, O, W, out, keep = _step_args("stage_euler_ssp", part, (P, P0), dt, out, work, scheme)
     f = _cfluid(fluid)
     _stream()
-    call("ibh_stage_euler_ssp", part.handle, C.byref(f), _EULER_SCHEMES[scheme], _ptr(P), ldp, _ptr(P0), ld0, _ptr(o), ldo,
-         _ptr(dt), per_cell, C.c_float(a), C.c_float(b), C.c_float(c), _ptr(w), ldw, int(flags))
+    call("ibh_stage_euler_ssp", part.handle, C.byref(f), sch, *S, *O, *D, C.c_float(a), C.c_float(b), C.c_float(c),
+         *W, int(flags))
     return out
 
 

@@ -146,118 +146,86 @@ int ibh_residual_euler_sensor(ibh_part* p, const float* P, int64_t ldp, const fl
                           "eligible for the single-kernel sweep; run the sweep unphased after the exchange");
 }
 
-// One explicit Euler step, P_out = state2primitive(primitive2state(P) + dt * R(P)).  Where the 2-D single-kernel sweep takes
-// the whole partition (EUL2_SINGLE without image / phase flags), with a global dt and P_out != P, the sweep's STEP form
-// stores the update itself: one launch.  Everywhere else -- 3-D, face-list or mixed partitions, a per-cell dt, IBH_FORCE_GENERAL,
-// IBH_NO_FUSE, P_out == P -- the sweep goes into `work` (nc x (nd + 2), leading dimension ldw) and ibh_update_euler runs:
-// two launches.  Either way the result is bit for bit ibh_update_euler(P, ibh_residual_euler_{hll,sensor}(P, flags), dt).
-int ibh_step_euler(ibh_part* p, const ibh_fluid* fluid, int scheme, const float* P, int64_t ldp, float* P_out, int64_t ldo,
-                   const float* dt, int dt_per_cell, float* work, int64_t ldw, int flags) {
-    IBH_REQUIRE(p && fluid && P && P_out && dt, "ibh_step_euler: null argument");
-    IBH_REQUIRE(scheme == EULER_HLL || scheme == EULER_SENSOR, "ibh_step_euler: scheme must be 0 (HLL) or 1 (sensor)");
-    IBH_REQUIRE(!(flags & IBH_IMAGE_ONLY),
-                "ibh_step_euler: IBH_IMAGE_ONLY is not taken: the update would read skirt rows that the sweep never wrote "
-                "(the multi-GPU step is out of scope)");
-    IBH_REQUIRE(!(flags & F_PHASES),
-                "ibh_step_euler: the overlap phases IBH_PHASE_INTERIOR / IBH_PHASE_BOUNDARY are not taken: the update would "
-                "read rows that the phase never wrote");
-    IBH_REQUIRE(!(flags & (IBH_PASS_A_ONLY | IBH_PASS_B_ONLY)), "ibh_step_euler: a single pass of the sweep is no step");
-    IBH_REQUIRE(p->nd == 2 || p->nd == 3, "ibh_step_euler: nd must be 2 or 3");
-    IBH_REQUIRE(ldp >= p->nc && ldo >= p->nc, "ibh_step_euler: a leading dimension is smaller than the number of cells");
+// The Euler step in its three forms (EulerForm), P_out = the form's update with R = R(P): what ibh_step_euler,
+// ibh_stage_euler and ibh_stage_euler_ssp share -- the checks, the one-launch condition and the two-launch tail.  `e` holds the
+// entry's arguments (e.R is P_out; the step form's base state is P itself), `name` the entry for its messages.
+// One launch where the 2-D single-kernel sweep takes the whole partition (EUL2_SINGLE without image / phase flags) and P_out
+// != P: the sweep's store epilogue writes the form itself.  The step form also needs a global dt there; the stage forms load
+// the cell's row of P0 anyway and its time step with it.  Everywhere else -- 3-D, face-list or mixed partitions,
+// IBH_FORCE_GENERAL, IBH_NO_FUSE, P_out == P -- the sweep goes into `work` (nc x (nd + 2), leading dimension ldw) and the form's
+// ibh_update_euler* runs: two launches.  Same bits either way.
+static int euler_form(const char* name, ibh_part* p, int scheme, EulerArgs e, int dt_per_cell, float* work, int64_t ldw,
+                      int flags) {
+    const bool step = e.form == FORM_STEP;
+    const char* const update = step ? "ibh_update_euler" : e.form == FORM_STAGE ? "ibh_update_euler_stage" : "ibh_update_euler_ssp";
+#define FORM_REQUIRE(cond, ...) IBH_REQUIRE(cond, (std::string(name) + __VA_ARGS__).c_str())  // (the text is built on failure only)
+    FORM_REQUIRE(p && e.fluid && e.P && e.P0 && e.R && e.dt, ": null argument");
+    FORM_REQUIRE(scheme == EULER_HLL || scheme == EULER_SENSOR, ": scheme must be 0 (HLL) or 1 (sensor)");
+    FORM_REQUIRE(!(flags & IBH_IMAGE_ONLY), ": IBH_IMAGE_ONLY is not taken: the update would read skirt rows that the sweep never "
+                                            "wrote (the multi-GPU step is out of scope)");
+    FORM_REQUIRE(!(flags & F_PHASES), ": the overlap phases IBH_PHASE_INTERIOR / IBH_PHASE_BOUNDARY are not taken: the update "
+                                      "would read rows that the phase never wrote");
+    FORM_REQUIRE(!(flags & (IBH_PASS_A_ONLY | IBH_PASS_B_ONLY)), ": a single pass of the sweep is no " + (step ? "step" : "stage"));
+    FORM_REQUIRE(p->nd == 2 || p->nd == 3, ": nd must be 2 or 3");
+    FORM_REQUIRE(e.ldp >= p->nc && e.ld0 >= p->nc && e.ldr >= p->nc, ": a leading dimension is smaller than the number of cells");
+    FORM_REQUIRE(!work || (work != e.P && work != e.P0 && work != e.R),
+                 ": work may not alias " + (step ? "P or P_out" : "P, P0 or P_out"));
     if (p->nc == 0) return 0;
-    EulerArgs e{P, ldp, P_out, ldo, fluid, scheme == EULER_SENSOR ? EULER_SENSOR : EULER_HLL};
-    if (euler_path(p, flags, e) == EUL2_SINGLE && p->fuse_all && !dt_per_cell && P_out != P) {
-        e.dt = dt;
+    e.scheme = scheme == EULER_SENSOR ? EULER_SENSOR : EULER_HLL;
+    e.dt_cells = dt_per_cell != 0;
+    if (euler_path(p, flags, e) == EUL2_SINGLE && p->fuse_all && !(step && e.dt_cells) && e.R != e.P) {
         euler2_single(p, e, flags, Phase(0));
         IBH_LAUNCH_CHECK();
         return 0;
     }
-    IBH_REQUIRE(work, "ibh_step_euler: this partition / these arguments take the two-launch form (sweep into `work`, then "
-                      "ibh_update_euler): work must be nc x (nd + 2) floats");
-    IBH_REQUIRE(ldw >= p->nc, "ibh_step_euler: ldw is smaller than the number of cells");
-    IBH_REQUIRE(work != P && work != P_out, "ibh_step_euler: work may not alias P or P_out");
-    const int rc = scheme == EULER_SENSOR ? ibh_residual_euler_sensor(p, P, ldp, nullptr, work, ldw, fluid, flags)
-                                          : ibh_residual_euler_hll(p, P, ldp, work, ldw, fluid, flags);
+    FORM_REQUIRE(work, ": this partition / these arguments take the two-launch form (sweep into `work`, then " + update +
+                           "): work must be nc x (nd + 2) floats");
+    FORM_REQUIRE(ldw >= p->nc, ": ldw is smaller than the number of cells");
+#undef FORM_REQUIRE
+    const int rc = scheme == EULER_SENSOR ? ibh_residual_euler_sensor(p, e.P, e.ldp, nullptr, work, ldw, e.fluid, flags)
+                                          : ibh_residual_euler_hll(p, e.P, e.ldp, work, ldw, e.fluid, flags);
     if (rc) return rc;
-    return ibh_update_euler(fluid, p->nd, p->nc, P, ldp, work, ldw, dt, dt_per_cell, P_out, ldo);
+    if (step) return ibh_update_euler(e.fluid, p->nd, p->nc, e.P, e.ldp, work, ldw, e.dt, dt_per_cell, e.R, e.ldr);
+    if (e.form == FORM_STAGE)
+        return ibh_update_euler_stage(e.fluid, p->nd, p->nc, e.P0, e.ld0, work, ldw, e.dt, dt_per_cell, e.c, e.R, e.ldr);
+    return ibh_update_euler_ssp(e.fluid, p->nd, p->nc, e.P0, e.ld0, e.P, e.ldp, work, ldw, e.dt, dt_per_cell, e.a, e.b, e.c, e.R,
+                                e.ldr);
+}
+
+// One explicit Euler step, P_out = state2primitive(primitive2state(P) + dt * R(P)): bit for bit ibh_update_euler(P,
+// ibh_residual_euler_{hll,sensor}(P, flags), dt), in one launch or two (euler_form; a per-cell dt takes two).  A `work` that is
+// given may alias neither P nor P_out on either path -- also on a one-launch partition, where `work` is not used: the shared
+// body checks it before it knows the path.
+int ibh_step_euler(ibh_part* p, const ibh_fluid* fluid, int scheme, const float* P, int64_t ldp, float* P_out, int64_t ldo,
+                   const float* dt, int dt_per_cell, float* work, int64_t ldw, int flags) {
+    EulerArgs e{P, ldp, P_out, ldo, fluid};
+    e.form = FORM_STEP, e.dt = dt;
+    e.P0 = P, e.ld0 = ldp;
+    return euler_form("ibh_step_euler", p, scheme, e, dt_per_cell, work, ldw, flags);
 }
 
 // One Runge-Kutta stage of the low-storage family, P_out = state2primitive(primitive2state(P0) + (alpha * dt) * R(P)): the
-// update works on the base state P0 of the step, the sweep on the previous stage P.  ibh_step_euler's dispatch with two
-// differences: a per-cell dt and P0 != P keep the one-launch form (the sweep's STAGE form loads the row of P0 and the cell's
-// time step itself), and P_out may be P0 where P0 is not P.  Same bits as ibh_update_euler_stage(P0, R(P), dt, alpha) either way.
+// update works on the base state P0 of the step, the sweep on the previous stage P.  P_out may be P0 where P0 is not P.  Same
+// bits as ibh_update_euler_stage(P0, R(P), dt, alpha) in one launch or two.
 int ibh_stage_euler(ibh_part* p, const ibh_fluid* fluid, int scheme, const float* P, int64_t ldp, const float* P0, int64_t ld0,
                     float* P_out, int64_t ldo, const float* dt, int dt_per_cell, float alpha, float* work, int64_t ldw,
                     int flags) {
-    IBH_REQUIRE(p && fluid && P && P0 && P_out && dt, "ibh_stage_euler: null argument");
-    IBH_REQUIRE(scheme == EULER_HLL || scheme == EULER_SENSOR, "ibh_stage_euler: scheme must be 0 (HLL) or 1 (sensor)");
-    IBH_REQUIRE(!(flags & IBH_IMAGE_ONLY),
-                "ibh_stage_euler: IBH_IMAGE_ONLY is not taken: the update would read skirt rows that the sweep never wrote "
-                "(the multi-GPU step is out of scope)");
-    IBH_REQUIRE(!(flags & F_PHASES),
-                "ibh_stage_euler: the overlap phases IBH_PHASE_INTERIOR / IBH_PHASE_BOUNDARY are not taken: the update would "
-                "read rows that the phase never wrote");
-    IBH_REQUIRE(!(flags & (IBH_PASS_A_ONLY | IBH_PASS_B_ONLY)), "ibh_stage_euler: a single pass of the sweep is no stage");
-    IBH_REQUIRE(p->nd == 2 || p->nd == 3, "ibh_stage_euler: nd must be 2 or 3");
-    IBH_REQUIRE(ldp >= p->nc && ld0 >= p->nc && ldo >= p->nc,
-                "ibh_stage_euler: a leading dimension is smaller than the number of cells");
-    IBH_REQUIRE(work != P && work != P0 && work != P_out, "ibh_stage_euler: work may not alias P, P0 or P_out");
-    if (p->nc == 0) return 0;
-    EulerArgs e{P, ldp, P_out, ldo, fluid, scheme == EULER_SENSOR ? EULER_SENSOR : EULER_HLL};
-    if (euler_path(p, flags, e) == EUL2_SINGLE && p->fuse_all && P_out != P) {
-        e.dt = dt;
-        e.P0 = P0, e.ld0 = ld0, e.alpha = alpha, e.dt_cells = dt_per_cell != 0;
-        euler2_single(p, e, flags, Phase(0));
-        IBH_LAUNCH_CHECK();
-        return 0;
-    }
-    IBH_REQUIRE(work, "ibh_stage_euler: this partition / these arguments take the two-launch form (sweep into `work`, then "
-                      "ibh_update_euler_stage): work must be nc x (nd + 2) floats");
-    IBH_REQUIRE(ldw >= p->nc, "ibh_stage_euler: ldw is smaller than the number of cells");
-    const int rc = scheme == EULER_SENSOR ? ibh_residual_euler_sensor(p, P, ldp, nullptr, work, ldw, fluid, flags)
-                                          : ibh_residual_euler_hll(p, P, ldp, work, ldw, fluid, flags);
-    if (rc) return rc;
-    return ibh_update_euler_stage(fluid, p->nd, p->nc, P0, ld0, work, ldw, dt, dt_per_cell, alpha, P_out, ldo);
+    EulerArgs e{P, ldp, P_out, ldo, fluid};
+    e.form = FORM_STAGE, e.dt = dt;
+    e.P0 = P0, e.ld0 = ld0, e.c = alpha;
+    return euler_form("ibh_stage_euler", p, scheme, e, dt_per_cell, work, ldw, flags);
 }
 
 // One Shu-Osher stage of a strong-stability-preserving scheme, P_out = state2primitive((primitive2state(P0) * a +
-// primitive2state(P) * b) + (c * dt) * R(P)): the sweep runs on the previous stage P, whose state also enters the blend.
-// ibh_stage_euler's dispatch: one launch where the 2-D single-kernel sweep takes the whole partition and P_out != P (the
-// sweep's SSP form keeps the cell's own state, loads the row of P0 and the cell's time step), two launches elsewhere.  Same
-// bits as ibh_update_euler_ssp(P0, P, R(P), dt, a, b, c) either way.
+// primitive2state(P) * b) + (c * dt) * R(P)): the sweep runs on the previous stage P, whose state also enters the blend (in one
+// launch the sweep keeps the cell's own state).  Same bits as ibh_update_euler_ssp(P0, P, R(P), dt, a, b, c) in one launch or two.
 int ibh_stage_euler_ssp(ibh_part* p, const ibh_fluid* fluid, int scheme, const float* P, int64_t ldp, const float* P0,
                         int64_t ld0, float* P_out, int64_t ldo, const float* dt, int dt_per_cell, float a, float b, float c,
                         float* work, int64_t ldw, int flags) {
-    IBH_REQUIRE(p && fluid && P && P0 && P_out && dt, "ibh_stage_euler_ssp: null argument");
-    IBH_REQUIRE(scheme == EULER_HLL || scheme == EULER_SENSOR, "ibh_stage_euler_ssp: scheme must be 0 (HLL) or 1 (sensor)");
-    IBH_REQUIRE(!(flags & IBH_IMAGE_ONLY),
-                "ibh_stage_euler_ssp: IBH_IMAGE_ONLY is not taken: the update would read skirt rows that the sweep never "
-                "wrote (the multi-GPU step is out of scope)");
-    IBH_REQUIRE(!(flags & F_PHASES),
-                "ibh_stage_euler_ssp: the overlap phases IBH_PHASE_INTERIOR / IBH_PHASE_BOUNDARY are not taken: the update "
-                "would read rows that the phase never wrote");
-    IBH_REQUIRE(!(flags & (IBH_PASS_A_ONLY | IBH_PASS_B_ONLY)), "ibh_stage_euler_ssp: a single pass of the sweep is no stage");
-    IBH_REQUIRE(p->nd == 2 || p->nd == 3, "ibh_stage_euler_ssp: nd must be 2 or 3");
-    IBH_REQUIRE(ldp >= p->nc && ld0 >= p->nc && ldo >= p->nc,
-                "ibh_stage_euler_ssp: a leading dimension is smaller than the number of cells");
-    IBH_REQUIRE(work != P && work != P0 && work != P_out, "ibh_stage_euler_ssp: work may not alias P, P0 or P_out");
-    if (p->nc == 0) return 0;
-    EulerArgs e{P, ldp, P_out, ldo, fluid, scheme == EULER_SENSOR ? EULER_SENSOR : EULER_HLL};
-    if (euler_path(p, flags, e) == EUL2_SINGLE && p->fuse_all && P_out != P) {
-        e.dt = dt;
-        e.P0 = P0, e.ld0 = ld0, e.alpha = c, e.dt_cells = dt_per_cell != 0;
-        e.ssp = true, e.a = a, e.b = b;
-        euler2_single(p, e, flags, Phase(0));
-        IBH_LAUNCH_CHECK();
-        return 0;
-    }
-    IBH_REQUIRE(work, "ibh_stage_euler_ssp: this partition / these arguments take the two-launch form (sweep into `work`, "
-                      "then ibh_update_euler_ssp): work must be nc x (nd + 2) floats");
-    IBH_REQUIRE(ldw >= p->nc, "ibh_stage_euler_ssp: ldw is smaller than the number of cells");
-    const int rc = scheme == EULER_SENSOR ? ibh_residual_euler_sensor(p, P, ldp, nullptr, work, ldw, fluid, flags)
-                                          : ibh_residual_euler_hll(p, P, ldp, work, ldw, fluid, flags);
-    if (rc) return rc;
-    return ibh_update_euler_ssp(fluid, p->nd, p->nc, P0, ld0, P, ldp, work, ldw, dt, dt_per_cell, a, b, c, P_out, ldo);
+    EulerArgs e{P, ldp, P_out, ldo, fluid};
+    e.form = FORM_SSP, e.dt = dt;
+    e.P0 = P0, e.ld0 = ld0, e.c = c, e.a = a, e.b = b;
+    return euler_form("ibh_stage_euler_ssp", p, scheme, e, dt_per_cell, work, ldw, flags);
 }
 
 // One step, u_out = u + dt * residual: in one launch where the quad sweep covers the whole partition (it stores the update,

@@ -210,13 +210,10 @@ __global__ __launch_bounds__(64 * WPB) void k_step_quad(float* __restrict__ u, c
 #ifndef WPBE
 #define WPBE 4
 #endif
-// STEP (ibh_step_euler): `R` is P_out and receives state2primitive(primitive2state(P) + dt R); dt = *dtp, one scalar load
-// per wave as in k_sweep_quad<..., STEP>
-// STAGE (ibh_stage_euler, with STEP): P_out = state2primitive(primitive2state(P0) + (alpha dt) R); DTC: dtp holds one time step
-// per cell and is read where the cell is
-// SSP (ibh_stage_euler_ssp, with STEP and STAGE): P_out = state2primitive((primitive2state(P0) sa + primitive2state(P) sb) +
-// (alpha dt) R), alpha the coefficient c of the Shu-Osher stage
-template <int SCH = EULER_HLL, bool STEP = false, bool STAGE = false, bool DTC = false, bool SSP = false>
+// FORM (EulerForm, ibh_euler_step_dev.h): beyond FORM_RESIDUAL `R` is P_out and receives the updated primitives; dt = *dtp,
+// one scalar load per wave as in k_sweep_quad<..., STEP>, or (DTC, the stage forms) dtp holds one time step per cell and is
+// read where the cell is.  P0, ld0, c, sa, sb: euler_step::FormArgs
+template <int SCH = EULER_HLL, int FORM = FORM_RESIDUAL, bool DTC = false>
 __global__ __launch_bounds__(64 * WPBE) void k_sweep_euler(const float* __restrict__ P, uint32_t ldp,
                                                            float* __restrict__ R, uint32_t ldr, float Rgas, float gamma,
                                                            const BlockDesc2* __restrict__ blocks,
@@ -225,17 +222,17 @@ __global__ __launch_bounds__(64 * WPBE) void k_sweep_euler(const float* __restri
                                                            const int32_t* __restrict__ dtab, int32_t nblk, int32_t nwg,
                                                            int32_t iters, const int32_t* __restrict__ blist,
                                                            const float* __restrict__ dtp = nullptr,
-                                                           const float* P0 = nullptr, uint32_t ld0 = 0, float alpha = 1.0f,
+                                                           const float* P0 = nullptr, uint32_t ld0 = 0, float c = 1.0f,
                                                            float sa = 0.0f, float sb = 1.0f) {
     __shared__ float lds[WPBE * BLK2_SWEEP_EULER_LDS];
     float dt = 0.0f;
-    if constexpr (STEP && !DTC) dt = *dtp;
+    if constexpr (FORM != FORM_RESIDUAL && !DTC) dt = *dtp;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int32_t first = __builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x, nwg) * (WPBE * iters) + wave);
     if (first >= nblk) return;
     const int32_t nb = __builtin_amdgcn_readfirstlane(min(iters, (nblk - first + WPBE - 1) / WPBE));
-    blk2::sweep_euler<SCH, STEP, STAGE, DTC, SSP>(blocks, htab, etab, dtab, blist, first, WPBE, nb, P, ldp, R, ldr, blk2::Gas{Rgas, gamma},
-                      lds + wave * BLK2_SWEEP_EULER_LDS, lane, dt, euler_step::StageArgs{P0, ld0, alpha, dtp, sa, sb});
+    blk2::sweep_euler<SCH, FORM, DTC>(blocks, htab, etab, dtab, blist, first, WPBE, nb, P, ldp, R, ldr, blk2::Gas{Rgas, gamma},
+                                      lds + wave * BLK2_SWEEP_EULER_LDS, lane, dt, euler_step::FormArgs{P0, ld0, c, dtp, sa, sb});
 }
 
 // Quad form of the Euler sweep (quad2::sweep_quad_euler): grid = [quad workgroups | single-block workgroups], like
@@ -249,7 +246,7 @@ __global__ __launch_bounds__(64 * WPBE) void k_sweep_euler(const float* __restri
 #ifndef QE_WAVES
 #define QE_WAVES 3
 #endif
-template <int SCH = EULER_HLL, bool STEP = false, bool STAGE = false, bool DTC = false, bool SSP = false>
+template <int SCH = EULER_HLL, int FORM = FORM_RESIDUAL, bool DTC = false>
 __global__ __launch_bounds__(64 * WPBE) __attribute__((amdgpu_waves_per_eu(QE_WAVES, QE_WAVES))) void k_sweep_quad_euler(const float* __restrict__ P, uint32_t ldp,
                                                                 float* __restrict__ R, uint32_t ldr, float Rgas,
                                                                 float gamma, const QuadDesc2* __restrict__ qd,
@@ -262,26 +259,26 @@ __global__ __launch_bounds__(64 * WPBE) __attribute__((amdgpu_waves_per_eu(QE_WA
                                                                 int32_t nwgs, int32_t singles_first,
                                                                 const float* __restrict__ dtp = nullptr,
                                                                 const float* P0 = nullptr, uint32_t ld0 = 0,
-                                                                float alpha = 1.0f, float ssa = 0.0f,
-                                                                float ssb = 1.0f) {
+                                                                float c = 1.0f, float sa = 0.0f,
+                                                                float sb = 1.0f) {
     __shared__ __attribute__((aligned(16))) float lds[QUADE_WG_LDS];
     float dt = 0.0f;
-    if constexpr (STEP && !DTC) dt = *dtp;  // (scalar load: the time step lives on the device, ibh_timestep_euler)
-    const euler_step::StageArgs sa{P0, ld0, alpha, dtp, ssa, ssb};
+    if constexpr (FORM != FORM_RESIDUAL && !DTC) dt = *dtp;  // (scalar load: the time step lives on the device, ibh_timestep_euler)
+    const euler_step::FormArgs fa{P0, ld0, c, dtp, sa, sb};
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int32_t wg = singles_first ? ((int32_t)blockIdx.x < nwgs ? (int32_t)blockIdx.x + nwgq : (int32_t)blockIdx.x - nwgs)
                                      : (int32_t)blockIdx.x;
     if (wg < nwgq) {
         const int32_t q = __builtin_amdgcn_readfirstlane(xcd_remap(wg, nwgq) * WPBE + wave);
         if (q < nq)
-            quad2::sweep_quad_euler<SCH, STEP, STAGE, DTC, SSP>(qd, qtab, q, P, ldp, R, ldr, blk2::Gas{Rgas, gamma}, lds + wave * QE_LDS,
-                                                           lane, dt, sa);
+            quad2::sweep_quad_euler<SCH, FORM, DTC>(qd, qtab, q, P, ldp, R, ldr, blk2::Gas{Rgas, gamma}, lds + wave * QE_LDS, lane,
+                                                    dt, fa);
     } else {
         const int32_t first = __builtin_amdgcn_readfirstlane(xcd_remap(wg - nwgq, nwgs) * WPBE + wave);
 #ifndef IBH_QE_NO_SINGLES  // (instruction counts of the quad path alone: scripts/isa_count.py)
         if (first < ns)
-            blk2::sweep_euler<SCH, STEP, STAGE, DTC, SSP>(blocks, htab, etab, dtab, singles, first, WPBE, 1, P, ldp, R, ldr, blk2::Gas{Rgas, gamma},
-                              lds + wave * BLK2_SWEEP_EULER_LDS, lane, dt, sa);
+            blk2::sweep_euler<SCH, FORM, DTC>(blocks, htab, etab, dtab, singles, first, WPBE, 1, P, ldp, R, ldr, blk2::Gas{Rgas, gamma},
+                                              lds + wave * BLK2_SWEEP_EULER_LDS, lane, dt, fa);
 #endif
     }
 }
@@ -313,6 +310,15 @@ BlockList block_list(const ibh_part* p, const int32_t* list, Range r, int wpb, i
             list ? p->etab : p->etab + (size_t)r.first * 16, list ? list + r.first : nullptr, count, iters,
             (count + wpb * iters - 1) / (wpb * iters)};
 }
+
+// The map (scheme, form, per-cell dt) -> instantiation of an Euler sweep kernel template K, written once for k_sweep_euler and
+// k_sweep_quad_euler: twelve of each.  FORM_STEP with a per-cell dt is none of them (ibh_step_euler sends it to two launches)
+#define EULER_FORM_OF(K, S, e)                                                            \
+    ((e).form == FORM_SSP     ? ((e).dt_cells ? K<S, FORM_SSP, true> : K<S, FORM_SSP>)     \
+     : (e).form == FORM_STAGE ? ((e).dt_cells ? K<S, FORM_STAGE, true> : K<S, FORM_STAGE>) \
+     : (e).form == FORM_STEP  ? K<S, FORM_STEP>                                            \
+                              : K<S>)
+#define EULER_KERNEL(K, e) ((e).scheme == EULER_SENSOR ? EULER_FORM_OF(K, EULER_SENSOR, e) : EULER_FORM_OF(K, EULER_HLL, e))
 }  // namespace
 
 namespace fused {
@@ -385,44 +391,27 @@ void adv2_single(const ibh_part* p, const AdvArgs& a, int flags, Phase ph, int k
 }
 
 // every block eligible, or only the image blocks wanted and all of them eligible: one launch per phase, no workspace
-// e.dt (ibh_step_euler): the STEP form of the same kernels -- e.R is P_out and receives the updated primitives
-// e.P0 (ibh_stage_euler, with e.dt): their STAGE form -- the row updated is P0's, the time step e.alpha * dt, per cell with e.dt_cells
-// e.ssp (ibh_stage_euler_ssp, with e.P0): their SSP form -- the update of the blend e.a p2s(P0) + e.b p2s(P), e.alpha the stage's c
+// e.form beyond FORM_RESIDUAL (ibh_step_euler, ibh_stage_euler, ibh_stage_euler_ssp): that form of the same kernels -- e.R is
+// P_out and receives the updated primitives
 void euler2_single(const ibh_part* p, const EulerArgs& e, int flags, Phase ph) {
     const int k = p->fuse_all ? 0 : 1;  // quad set; block list: all blocks / the image blocks
-    const bool sensor = e.scheme == EULER_SENSOR;
     if (quads_usable(p, k, flags)) {
         const QuadRange r = quad_range(p, k, ph);
         const int32_t nwgq = (r.q.count() + WPBE - 1) / WPBE, nwgs = (r.s.count() + WPBE - 1) / WPBE;
-        auto kq = sensor ? k_sweep_quad_euler<EULER_SENSOR> : k_sweep_quad_euler<EULER_HLL>;
-        if (e.dt) kq = sensor ? k_sweep_quad_euler<EULER_SENSOR, true> : k_sweep_quad_euler<EULER_HLL, true>;
-        if (e.P0 && !e.dt_cells) kq = sensor ? k_sweep_quad_euler<EULER_SENSOR, true, true> : k_sweep_quad_euler<EULER_HLL, true, true>;
-        if (e.P0 && e.dt_cells)
-            kq = sensor ? k_sweep_quad_euler<EULER_SENSOR, true, true, true> : k_sweep_quad_euler<EULER_HLL, true, true, true>;
-        if (e.ssp && !e.dt_cells)
-            kq = sensor ? k_sweep_quad_euler<EULER_SENSOR, true, true, false, true> : k_sweep_quad_euler<EULER_HLL, true, true, false, true>;
-        if (e.ssp && e.dt_cells)
-            kq = sensor ? k_sweep_quad_euler<EULER_SENSOR, true, true, true, true> : k_sweep_quad_euler<EULER_HLL, true, true, true, true>;
         if (nwgq + nwgs > 0)
-            hipLaunchKernelGGL(kq, dim3(nwgq + nwgs), dim3(64 * WPBE), 0, ibh_stream, e.P, (uint32_t)e.ldp,
-                               e.R, (uint32_t)e.ldr, e.fluid->R, e.fluid->gamma, p->qd[k] + r.q.first,
+            hipLaunchKernelGGL(EULER_KERNEL(k_sweep_quad_euler, e), dim3(nwgq + nwgs), dim3(64 * WPBE), 0, ibh_stream, e.P,
+                               (uint32_t)e.ldp, e.R, (uint32_t)e.ldr, e.fluid->R, e.fluid->gamma, p->qd[k] + r.q.first,
                                p->qtab[k] + (size_t)r.q.first * IBH_QROW, r.q.count(), nwgq, p->blocks2, p->htab, p->etab,
                                p->dtab, p->qsingles[k] + r.s.first, r.s.count(), nwgs, T.quad_singles_first, e.dt, e.P0,
-                               (uint32_t)e.ld0, e.alpha, e.a, e.b);
+                               (uint32_t)e.ld0, e.c, e.a, e.b);
         return;
     }
     const Range b = p->fuse_all ? ph.of(p->nB1, p->nblk) : ph.of(p->n_img_int, p->n_img);
     if (b.count() <= 0) return;
     const BlockList L = block_list(p, p->fuse_all ? nullptr : p->img_list, b, WPBE, 4);
-    auto kb = sensor ? k_sweep_euler<EULER_SENSOR> : k_sweep_euler<EULER_HLL>;
-    if (e.dt) kb = sensor ? k_sweep_euler<EULER_SENSOR, true> : k_sweep_euler<EULER_HLL, true>;
-    if (e.P0 && !e.dt_cells) kb = sensor ? k_sweep_euler<EULER_SENSOR, true, true> : k_sweep_euler<EULER_HLL, true, true>;
-    if (e.P0 && e.dt_cells) kb = sensor ? k_sweep_euler<EULER_SENSOR, true, true, true> : k_sweep_euler<EULER_HLL, true, true, true>;
-    if (e.ssp && !e.dt_cells) kb = sensor ? k_sweep_euler<EULER_SENSOR, true, true, false, true> : k_sweep_euler<EULER_HLL, true, true, false, true>;
-    if (e.ssp && e.dt_cells) kb = sensor ? k_sweep_euler<EULER_SENSOR, true, true, true, true> : k_sweep_euler<EULER_HLL, true, true, true, true>;
-    hipLaunchKernelGGL(kb, dim3(L.nwg), dim3(64 * WPBE), 0, ibh_stream, e.P, (uint32_t)e.ldp, e.R, (uint32_t)e.ldr, e.fluid->R,
-                       e.fluid->gamma, L.bl, L.ht, L.et, p->dtab, L.count, L.nwg, L.iters, L.ls, e.dt, e.P0, (uint32_t)e.ld0,
-                       e.alpha, e.a, e.b);
+    hipLaunchKernelGGL(EULER_KERNEL(k_sweep_euler, e), dim3(L.nwg), dim3(64 * WPBE), 0, ibh_stream, e.P, (uint32_t)e.ldp, e.R,
+                       (uint32_t)e.ldr, e.fluid->R, e.fluid->gamma, L.bl, L.ht, L.et, p->dtab, L.count, L.nwg, L.iters, L.ls, e.dt,
+                       e.P0, (uint32_t)e.ld0, e.c, e.a, e.b);
 }
 
 // sweep and update in one launch: the quad sweep stores u + dt * residual (its cells of u are in registers)

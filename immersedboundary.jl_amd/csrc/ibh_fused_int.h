@@ -1,12 +1,13 @@
 // libibhip: what the units of the fused sweeps share on the host -- the tuning state, the partition predicates, the path
 // names and one launcher per path.  ibh_fused.hip decides the path and switches over it; the launchers live beside their
 // kernels in ibh_fused2d.hip, ibh_fused3d.hip and ibh_fused_general.hip; ibh_turb.hip reads the predicates and the tuning
-// state for its block closures.  Host code only: no kernel header is included here.  Internal to the library: the namespace
-// is hidden, nothing of it is exported.
+// state for its block closures.  Host code only: no kernel header is included here but the one that names the forms of an
+// Euler step (EulerForm).  Internal to the library: the namespace is hidden, nothing of it is exported.
 #pragma once
 #include <stdlib.h>
 
 #include "ibh_common.h"
+#include "ibh_euler_step_dev.h"
 
 namespace fused __attribute__((visibility("hidden"))) {
 
@@ -80,12 +81,13 @@ struct AdvArgs { const float *u, *C; int64_t ldc; float* ud; };
 struct EulerArgs {  // (the entries' fields)
     const float* P; int64_t ldp; float* R; int64_t ldr; const ibh_fluid* fluid;
     EulerScheme scheme = EULER_HLL; const float* nu = nullptr;
-    const float* dt = nullptr;  // ibh_step_euler on a single-kernel path: R is P_out, the sweep stores the updated primitives
-    // ibh_stage_euler on a single-kernel path (with dt): the row that is updated is P0's (P0 may be R), the time step is
-    // alpha * dt, and dt holds one value per cell where dt_cells is set
-    const float* P0 = nullptr; int64_t ld0 = 0; float alpha = 1.0f; bool dt_cells = false;
-    // ibh_stage_euler_ssp on a single-kernel path (with P0): the update of the blend a p2s(P0) + b p2s(P), alpha is the stage's c
-    bool ssp = false; float a = 0.0f, b = 1.0f;
+    // ibh_step_euler, ibh_stage_euler, ibh_stage_euler_ssp on a single-kernel path: the form the sweep stores (R is then P_out)
+    // and what the form reads (euler_step::FormArgs) -- from FORM_STEP on dt, one value or (dt_cells, the stage forms only) one
+    // per cell; from FORM_STAGE on the base state P0 (it may be R) and the coefficient c of dt; FORM_SSP the weights a and b
+    EulerForm form = FORM_RESIDUAL;
+    const float* dt = nullptr; bool dt_cells = false;
+    const float* P0 = nullptr; int64_t ld0 = 0; float c = 1.0f;
+    float a = 0.0f, b = 1.0f;
 };
 
 // ---- advection: paths

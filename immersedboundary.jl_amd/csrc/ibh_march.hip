@@ -113,6 +113,10 @@ __global__ void k_update_dev(int64_t n, const float* __restrict__ dt, const floa
         out[i] = u[i] + r[i] * h;
 }
 
+// The update kernels of an Euler step, one per form (EulerForm, ibh_euler_step_dev.h) and each with its entry's own argument
+// list.  The three grid-stride loops are written out: moved into one device function template over the form, the same loop
+// compiles to other instruction orders in all twelve instantiations (scripts/kernel_bodies.py), and these kernels are held
+// instruction for instruction.  What differs between them is which rows are loaded and the one call of a row function.
 // P_out = state2primitive(primitive2state(P) + dt R), one thread per row: the row is read whole before it is written, so
 // P_out may be P (no __restrict__ on the two).  dt: one value, or one per row (PER_CELL)
 template <int ND, bool PER_CELL>
@@ -184,6 +188,17 @@ __global__ __launch_bounds__(MARCH_BLOCK) void k_update_euler_ssp(float Rgas, fl
 #pragma unroll
         for (int v = 0; v < NV; ++v) P_out[i + v * ldo] = o[v];
     }
+}
+
+// the four instantiations of an update kernel K as k[nd - 2][per-cell dt], and the launch of the one that (nd, dt_per_cell)
+// picks over n rows
+#define UPDATE_KERNELS(K) {{K<2, false>, K<2, true>}, {K<3, false>, K<3, true>}}
+template <class K, class... A>
+int launch_update(K const (&k)[2][2], int nd, int dt_per_cell, int64_t n, A... args) {
+    hipLaunchKernelGGL(k[nd - 2][dt_per_cell != 0], dim3(ibh_grid_cap(n, MARCH_BLOCK, 2048)), dim3(MARCH_BLOCK), 0, ibh_stream,
+                       args...);
+    IBH_LAUNCH_CHECK();
+    return 0;
 }
 
 }  // namespace
@@ -348,19 +363,8 @@ int ibh_update_euler(const ibh_fluid* f, int nd, int64_t n, const float* P, int6
     IBH_REQUIRE(n >= 0 && ldp >= n && ldr >= n && ldo >= n, "ibh_update_euler: a leading dimension is smaller than n");
     IBH_REQUIRE(P_out != R && P != R, "ibh_update_euler: R may not alias P or P_out (P_out may be P)");
     if (n == 0) return 0;
-    const dim3 grid(ibh_grid_cap(n, MARCH_BLOCK, 2048)), block(MARCH_BLOCK);
-#define UPD_LAUNCH(ND_, PC_) \
-    hipLaunchKernelGGL((k_update_euler<ND_, PC_>), grid, block, 0, ibh_stream, f->R, f->gamma, n, P, ldp, R, ldr, dt, P_out, ldo)
-    if (nd == 2) {
-        if (dt_per_cell) UPD_LAUNCH(2, true);
-        else UPD_LAUNCH(2, false);
-    } else {
-        if (dt_per_cell) UPD_LAUNCH(3, true);
-        else UPD_LAUNCH(3, false);
-    }
-#undef UPD_LAUNCH
-    IBH_LAUNCH_CHECK();
-    return 0;
+    static constexpr decltype(&k_update_euler<2, false>) k[2][2] = UPDATE_KERNELS(k_update_euler);
+    return launch_update(k, nd, dt_per_cell, n, f->R, f->gamma, n, P, ldp, R, ldr, dt, P_out, ldo);
 }
 
 // A Runge-Kutta stage of the low-storage family, P_out = state2primitive(primitive2state(P0) + (alpha * dt) * R) in one
@@ -372,20 +376,8 @@ int ibh_update_euler_stage(const ibh_fluid* f, int nd, int64_t n, const float* P
     IBH_REQUIRE(n >= 0 && ld0 >= n && ldr >= n && ldo >= n, "ibh_update_euler_stage: a leading dimension is smaller than n");
     IBH_REQUIRE(P_out != R && P0 != R, "ibh_update_euler_stage: R may not alias P0 or P_out (P_out may be P0)");
     if (n == 0) return 0;
-    const dim3 grid(ibh_grid_cap(n, MARCH_BLOCK, 2048)), block(MARCH_BLOCK);
-#define UPD_LAUNCH(ND_, PC_)                                                                                               \
-    hipLaunchKernelGGL((k_update_euler_stage<ND_, PC_>), grid, block, 0, ibh_stream, f->R, f->gamma, n, P0, ld0, R, ldr, dt, \
-                       alpha, P_out, ldo)
-    if (nd == 2) {
-        if (dt_per_cell) UPD_LAUNCH(2, true);
-        else UPD_LAUNCH(2, false);
-    } else {
-        if (dt_per_cell) UPD_LAUNCH(3, true);
-        else UPD_LAUNCH(3, false);
-    }
-#undef UPD_LAUNCH
-    IBH_LAUNCH_CHECK();
-    return 0;
+    static constexpr decltype(&k_update_euler_stage<2, false>) k[2][2] = UPDATE_KERNELS(k_update_euler_stage);
+    return launch_update(k, nd, dt_per_cell, n, f->R, f->gamma, n, P0, ld0, R, ldr, dt, alpha, P_out, ldo);
 }
 
 // A Shu-Osher stage of a strong-stability-preserving Runge-Kutta scheme in one launch,
@@ -401,20 +393,8 @@ int ibh_update_euler_ssp(const ibh_fluid* f, int nd, int64_t n, const float* P0,
     IBH_REQUIRE(P_out != R && P0 != R && P != R,
                 "ibh_update_euler_ssp: R may not alias P0, P or P_out (P_out may be P0 or P, P0 may be P)");
     if (n == 0) return 0;
-    const dim3 grid(ibh_grid_cap(n, MARCH_BLOCK, 2048)), block(MARCH_BLOCK);
-#define UPD_LAUNCH(ND_, PC_)                                                                                                  \
-    hipLaunchKernelGGL((k_update_euler_ssp<ND_, PC_>), grid, block, 0, ibh_stream, f->R, f->gamma, n, P0, ld0, P, ldp, R, ldr, \
-                       dt, a, b, c, P_out, ldo)
-    if (nd == 2) {
-        if (dt_per_cell) UPD_LAUNCH(2, true);
-        else UPD_LAUNCH(2, false);
-    } else {
-        if (dt_per_cell) UPD_LAUNCH(3, true);
-        else UPD_LAUNCH(3, false);
-    }
-#undef UPD_LAUNCH
-    IBH_LAUNCH_CHECK();
-    return 0;
+    static constexpr decltype(&k_update_euler_ssp<2, false>) k[2][2] = UPDATE_KERNELS(k_update_euler_ssp);
+    return launch_update(k, nd, dt_per_cell, n, f->R, f->gamma, n, P0, ld0, P, ldp, R, ldr, dt, a, b, c, P_out, ldo);
 }
 
 }  // extern "C"

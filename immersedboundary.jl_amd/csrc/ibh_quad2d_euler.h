@@ -9,15 +9,16 @@
 //   * LDS holds only the two boundary ROWS of the tile (the bottom / top edge lanes read them); left / right edge lanes
 //     take their boundary cells from their own registers, the COARSE pair mate by a quad_perm DPP.
 // Arithmetic: blk2::euler_flux_w / euler_side (ibh_sweep2d.h, ibh_block2d.h), Float32 HLL combine like every tuned path.
-// STEP (ibh_step_euler): the store epilogue passes every cell's own state (U, in registers) and its four residual values
-// through euler_step::update_row (ibh_euler_step_dev.h, contraction off) and stores P_out = state2primitive(
-// primitive2state(P) + dt R) to `Rr` with ordinary stores -- the next step reads it.
-// STAGE (ibh_stage_euler, with STEP): the row that is updated is the cell's row of the base state P0, four v4f loads at the
-// offsets of the stores, issued after the last flux pass (the cell's own U is dead by then); the time step is alpha * dt,
-// dt per wave or (DTC) one v4f of per-cell values.  P_out may be P0: a lane reads its rows of P0 before it stores.
-// SSP (ibh_stage_euler_ssp, with STEP and STAGE): a Shu-Osher stage -- the cell's own state U stays in registers as in the STEP
-// form, the row of P0 and the time step are loaded as in the STAGE form, and euler_step::blend_row updates the blend
-// a primitive2state(P0) + b primitive2state(U) with the time step c * dt (c travels as StageArgs::alpha).
+// FORM (EulerForm, ibh_euler_step_dev.h; contraction off there): what the one store epilogue writes to `Rr`
+// FORM_STEP (ibh_step_euler): every cell's own state (U, in registers) and its four residual values go through
+// euler_step::update_row, and P_out = state2primitive(primitive2state(P) + dt R) is stored with ordinary stores -- the next
+// step reads it.
+// FORM_STAGE (ibh_stage_euler): the row that is updated is the cell's row of the base state P0, four v4f loads at the offsets
+// of the stores, issued after the last flux pass (the cell's own U is dead by then); the time step is fa.c * dt, dt per wave
+// or (DTC) one v4f of per-cell values.  P_out may be P0: a lane reads its rows of P0 before it stores.
+// FORM_SSP (ibh_stage_euler_ssp): a Shu-Osher stage -- the cell's own state U stays in registers as in the step form, the row
+// of P0 and the time step are loaded as in the stage form, and euler_step::blend_row updates the blend
+// fa.a primitive2state(P0) + fa.b primitive2state(U).
 #pragma once
 #include "ibh_quad2d.h"
 #include "ibh_euler_step_dev.h"
@@ -141,15 +142,13 @@ __device__ __forceinline__ void euler_flux_w2(const v2f* Pa, const v2f* Pb, cons
     F[1] += mL * uL - mR * uR;
 }
 
-template <int SCH = EULER_HLL, bool STEP = false, bool STAGE = false, bool DTC = false, bool SSP = false>
+template <int SCH = EULER_HLL, int FORM = FORM_RESIDUAL, bool DTC = false>
 __device__ __forceinline__ void sweep_quad_euler(const QuadDesc2* __restrict__ qd, const int32_t* __restrict__ qtab,
                                                  int32_t q, const float* __restrict__ P, uint32_t ldp,
                                                  float* __restrict__ Rr, uint32_t ldr, blk2::Gas gas, float* lds,
                                                  int lane, float dt = 0.0f,
-                                                 euler_step::StageArgs sa = euler_step::StageArgs()) {
-    static_assert(STEP || !STAGE, "the STAGE form is a STEP form");
-    static_assert(STAGE || !DTC, "per-cell time steps come with the STAGE form");
-    static_assert((STEP && STAGE) || !SSP, "the SSP form is a STEP and a STAGE form");
+                                                 euler_step::FormArgs fa = euler_step::FormArgs()) {
+    static_assert(FORM >= FORM_STAGE || !DTC, "per-cell time steps come with the stage forms");
     using blk2::ldg;
     using blk2::wave_lds_sync;
     typedef float v2f_g __attribute__((ext_vector_type(2), aligned(4)));
@@ -417,7 +416,7 @@ __device__ __forceinline__ void sweep_quad_euler(const QuadDesc2* __restrict__ q
                 FTf[c] = t15 ? ex[c] : FT[v][c];
             }
             const v4f r = res[v] - ((FTf - FB) * rhy);
-            if constexpr (STEP) {
+            if constexpr (FORM != FORM_RESIDUAL) {
                 res[v] = r;   // (all four residuals of a cell are needed before its row can be updated)
                 continue;
             }
@@ -429,53 +428,26 @@ __device__ __forceinline__ void sweep_quad_euler(const QuadDesc2* __restrict__ q
             __builtin_nontemporal_store(r, (v4f_g*)((char*)(Rr + (size_t)v * ldr) + ((size_t)a0 << 2)));
 #endif
         }
-        if constexpr (STEP && !STAGE) {
-            v4f O[QE_NV];
+        if constexpr (FORM != FORM_RESIDUAL) {
+            // (no __restrict__ on P0: it may be the output; all of this lane's rows of P0 are loaded before its first store)
+            v4f B[QE_NV], O[QE_NV];
+            v4f h = v4f{dt, dt, dt, dt};
+            if constexpr (FORM >= FORM_STAGE) {
+#pragma unroll
+                for (int v = 0; v < QE_NV; ++v) B[v] = *(const v4f_g*)((const char*)(fa.P0 + (size_t)v * fa.ld0) + ((size_t)a0 << 2));
+                if constexpr (DTC) h = *(const v4f_g*)((const char*)fa.dtc + ((size_t)a0 << 2));
+            }
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 const float Pc[QE_NV] = {U[0][c], U[1][c], U[2][c], U[3][c]};
                 const float rc[QE_NV] = {res[0][c], res[1][c], res[2][c], res[3][c]};
                 float o[QE_NV];
-                euler_step::update_row<2>(gas.R, gas.gamma, Pc, rc, dt, o);
-#pragma unroll
-                for (int v = 0; v < QE_NV; ++v) O[v][c] = o[v];
-            }
-#pragma unroll
-            for (int v = 0; v < QE_NV; ++v) *(v4f_g*)((char*)(Rr + (size_t)v * ldr) + ((size_t)a0 << 2)) = O[v];
-        }
-        if constexpr (STAGE && !SSP) {
-            // (no __restrict__ on P0: it may be the output; all of this lane's rows are loaded before its first store)
-            v4f B[QE_NV], O[QE_NV];
-#pragma unroll
-            for (int v = 0; v < QE_NV; ++v) B[v] = *(const v4f_g*)((const char*)(sa.P0 + (size_t)v * sa.ld0) + ((size_t)a0 << 2));
-            v4f h = v4f{dt, dt, dt, dt};
-            if constexpr (DTC) h = *(const v4f_g*)((const char*)sa.dtc + ((size_t)a0 << 2));
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const float Pc[QE_NV] = {B[0][c], B[1][c], B[2][c], B[3][c]};
-                const float rc[QE_NV] = {res[0][c], res[1][c], res[2][c], res[3][c]};
-                float o[QE_NV];
-                euler_step::update_row<2>(gas.R, gas.gamma, Pc, rc, euler_step::stage_dt(sa.alpha, h[c]), o);
-#pragma unroll
-                for (int v = 0; v < QE_NV; ++v) O[v][c] = o[v];
-            }
-#pragma unroll
-            for (int v = 0; v < QE_NV; ++v) *(v4f_g*)((char*)(Rr + (size_t)v * ldr) + ((size_t)a0 << 2)) = O[v];
-        }
-        if constexpr (SSP) {
-            // (P0 may be the output: all of this lane's rows of P0 are loaded before its first store; its rows of P are U)
-            v4f B[QE_NV], O[QE_NV];
-#pragma unroll
-            for (int v = 0; v < QE_NV; ++v) B[v] = *(const v4f_g*)((const char*)(sa.P0 + (size_t)v * sa.ld0) + ((size_t)a0 << 2));
-            v4f h = v4f{dt, dt, dt, dt};
-            if constexpr (DTC) h = *(const v4f_g*)((const char*)sa.dtc + ((size_t)a0 << 2));
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const float Bc[QE_NV] = {B[0][c], B[1][c], B[2][c], B[3][c]};
-                const float Pc[QE_NV] = {U[0][c], U[1][c], U[2][c], U[3][c]};
-                const float rc[QE_NV] = {res[0][c], res[1][c], res[2][c], res[3][c]};
-                float o[QE_NV];
-                euler_step::blend_row<2>(gas.R, gas.gamma, Bc, Pc, rc, sa.a, sa.b, euler_step::stage_dt(sa.alpha, h[c]), o);
+                if constexpr (FORM >= FORM_STAGE) {
+                    const float Bc[QE_NV] = {B[0][c], B[1][c], B[2][c], B[3][c]};
+                    const float hc = euler_step::stage_dt(fa.c, h[c]);
+                    if constexpr (FORM == FORM_SSP) euler_step::blend_row<2>(gas.R, gas.gamma, Bc, Pc, rc, fa.a, fa.b, hc, o);
+                    else euler_step::update_row<2>(gas.R, gas.gamma, Bc, rc, hc, o);
+                } else euler_step::update_row<2>(gas.R, gas.gamma, Pc, rc, dt, o);
 #pragma unroll
                 for (int v = 0; v < QE_NV; ++v) O[v][c] = o[v];
             }

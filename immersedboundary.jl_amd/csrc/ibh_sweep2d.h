@@ -427,22 +427,21 @@ __device__ __forceinline__ SweepPreE sweep_prefetch_e(const BlockDesc2* __restri
     return T;
 }
 
-// STEP (ibh_step_euler): the cell's own state T.Pc and its four residual values go through euler_step::update_row
-// (ibh_euler_step_dev.h, contraction off) and P_out = state2primitive(primitive2state(P) + dt R) is stored to `Rr`
-// STAGE (ibh_stage_euler, with STEP): the row that is updated is the cell's row of the base state P0, loaded here (P0 may be
-// the output: a lane reads its row before it stores), and the time step is alpha * dt -- dt per wave or (DTC) one per lane
-// SSP (ibh_stage_euler_ssp, with STEP and STAGE): a Shu-Osher stage -- T.Pc as in the STEP form, the row of P0 and the time step as
-// in the STAGE form, through euler_step::blend_row with the weights sa.a, sa.b and the time step sa.alpha * dt
-template <int SCH = EULER_HLL, bool STEP = false, bool STAGE = false, bool DTC = false, bool SSP = false>
+// FORM (EulerForm, ibh_euler_step_dev.h; contraction off there): what is stored to `Rr`
+// FORM_STEP (ibh_step_euler): the cell's own state T.Pc and its four residual values go through euler_step::update_row:
+// P_out = state2primitive(primitive2state(P) + dt R)
+// FORM_STAGE (ibh_stage_euler): the row that is updated is the cell's row of the base state P0, loaded here (P0 may be the
+// output: a lane reads its row before it stores), and the time step is fa.c * dt -- dt per wave or (DTC) one per lane
+// FORM_SSP (ibh_stage_euler_ssp): a Shu-Osher stage -- T.Pc as in the step form, the row of P0 and the time step as in the
+// stage form, through euler_step::blend_row with the weights fa.a, fa.b
+template <int SCH = EULER_HLL, int FORM = FORM_RESIDUAL, bool DTC = false>
 __device__ __forceinline__ void sweep_euler(const BlockDesc2* __restrict__ blocks, const int32_t* __restrict__ htab,
                                             const int32_t* __restrict__ etab, const int32_t* __restrict__ dtab,
                                             const int32_t* __restrict__ blist, int32_t blk0, int32_t stride, int32_t nb,
                                             const float* __restrict__ P, uint32_t ldp, float* __restrict__ Rr,
                                             uint32_t ldr, Gas gas, float* lds, int lane, float dt = 0.0f,
-                                            euler_step::StageArgs sa = euler_step::StageArgs()) {
-    static_assert(STEP || !STAGE, "the STAGE form is a STEP form");
-    static_assert(STAGE || !DTC, "per-cell time steps come with the STAGE form");
-    static_assert((STEP && STAGE) || !SSP, "the SSP form is a STEP and a STAGE form");
+                                            euler_step::FormArgs fa = euler_step::FormArgs()) {
+    static_assert(FORM >= FORM_STAGE || !DTC, "per-cell time steps come with the stage forms");
     float* fP = lds;           // [4][128]
     float* fD = lds + 512;     // [128]
     float* fSX = lds + 640;    // [4][128]
@@ -632,34 +631,23 @@ __device__ __forceinline__ void sweep_euler(const BlockDesc2* __restrict__ block
             const float fr = e1 ? 0.5f * (FR[v] + FR1[v]) : FR[v];
             const float ft = e3 ? 0.5f * (FT[v] + FT1[v]) : FT[v];
             const float r = -((fr - fl) * bb.rh[0]) - ((ft - fb) * bb.rh[1]);
-            if constexpr (STEP) rv[v] = r;
+            if constexpr (FORM != FORM_RESIDUAL) rv[v] = r;
             else stg(Rr + (size_t)v * ldr, (uint32_t)bb.base + lane, r);
         }
-        if constexpr (STEP && !STAGE) {
-            float o[4];
-            euler_step::update_row<2>(gas.R, gas.gamma, T.Pc, rv, dt, o);
-#pragma unroll
-            for (int v = 0; v < 4; ++v) stg(Rr + (size_t)v * ldr, (uint32_t)bb.base + lane, o[v]);
-        }
-        if constexpr (STAGE && !SSP) {
+        if constexpr (FORM != FORM_RESIDUAL) {
+            // (no __restrict__ on P0: it may be the output; this lane's row is loaded before its first store)
             const uint32_t c = (uint32_t)bb.base + lane;
             float b[4], o[4];
-#pragma unroll
-            for (int v = 0; v < 4; ++v) b[v] = *(const float*)((const char*)(sa.P0 + (size_t)v * sa.ld0) + (size_t)(c << 2));
             float h = dt;
-            if constexpr (DTC) h = *(const float*)((const char*)sa.dtc + (size_t)(c << 2));
-            euler_step::update_row<2>(gas.R, gas.gamma, b, rv, euler_step::stage_dt(sa.alpha, h), o);
+            if constexpr (FORM >= FORM_STAGE) {
 #pragma unroll
-            for (int v = 0; v < 4; ++v) stg(Rr + (size_t)v * ldr, c, o[v]);
-        }
-        if constexpr (SSP) {
-            const uint32_t c = (uint32_t)bb.base + lane;
-            float b[4], o[4];
-#pragma unroll
-            for (int v = 0; v < 4; ++v) b[v] = *(const float*)((const char*)(sa.P0 + (size_t)v * sa.ld0) + (size_t)(c << 2));
-            float h = dt;
-            if constexpr (DTC) h = *(const float*)((const char*)sa.dtc + (size_t)(c << 2));
-            euler_step::blend_row<2>(gas.R, gas.gamma, b, T.Pc, rv, sa.a, sa.b, euler_step::stage_dt(sa.alpha, h), o);
+                for (int v = 0; v < 4; ++v) b[v] = *(const float*)((const char*)(fa.P0 + (size_t)v * fa.ld0) + (size_t)(c << 2));
+                if constexpr (DTC) h = *(const float*)((const char*)fa.dtc + (size_t)(c << 2));
+                h = euler_step::stage_dt(fa.c, h);
+            }
+            if constexpr (FORM == FORM_SSP) euler_step::blend_row<2>(gas.R, gas.gamma, b, T.Pc, rv, fa.a, fa.b, h, o);
+            else if constexpr (FORM == FORM_STAGE) euler_step::update_row<2>(gas.R, gas.gamma, b, rv, h, o);
+            else euler_step::update_row<2>(gas.R, gas.gamma, T.Pc, rv, h, o);
 #pragma unroll
             for (int v = 0; v < 4; ++v) stg(Rr + (size_t)v * ldr, c, o[v]);
         }

@@ -224,8 +224,8 @@ class EulerMarch:
             raise ValueError("a time average needs one time step for all cells: local_dt marches in pseudo-time")
         self.scheme, self.scale, self.bcs, self.average = scheme, float(scale), bcs, average
         self.local_dt, self.dt_every, self.residual, self.flags = bool(local_dt), int(dt_every), residual, int(flags)
-        self._ssp = isinstance(stages, (tuple, list)) and any(isinstance(a, (tuple, list)) for a in stages)
-        if self._ssp:
+        ssp = isinstance(stages, (tuple, list)) and any(isinstance(a, (tuple, list)) for a in stages)
+        if ssp:
             if not all(isinstance(a, (tuple, list)) and len(a) == 3 for a in stages):
                 raise ValueError("stages in the Shu-Osher form must be (a, b, c) triples, every one of them")
             self.stages = tuple(tuple(float(x) for x in a) for a in stages)
@@ -234,6 +234,14 @@ class EulerMarch:
         if not self.stages:
             raise ValueError("stages must name at least one stage coefficient")
         self._staged = self.stages != (1.0,)
+        # one record per stage, (form, base, coefficients): what `_stage` calls, which state it updates and with what
+        if not self._staged:
+            self._records = [("step", "src", ())]
+        elif ssp:   # (a, b) == (0, 1): no blend, the low-storage stage on the previous stage itself
+            self._records = [("stage", "src", (c,)) if (a, b) == (0.0, 1.0) else ("ssp", "P0", (a, b, c))
+                             for a, b, c in self.stages]
+        else:
+            self._records = [("stage", "P0", (alpha,)) for alpha in self.stages]
         nc, nv = self.part.nc, self.part.nd + 2
         self._buf = tuple(B.colmajor_empty(nc, nv) for _ in range(3 if self._staged else 2))
         self.work = B.colmajor_empty(nc, nv)
@@ -249,67 +257,38 @@ class EulerMarch:
                 B.timestep_euler(self.part, P, self.fluid, self.scale, out=False, cells=self.dt)
             else:
                 B.timestep_euler(self.part, P, self.fluid, self.scale, out=self.dt)
-        if self._ssp:
-            return self._ssp_stages(P)
-        if self._staged:
-            return self._stages(P)
-        out = self._buf[0] if P.data_ptr() != self._buf[0].data_ptr() else self._buf[1]
+        # stage k sweeps the previous stage into one of the two arrays that are neither the step's input nor its own input
+        free = [b for b in self._buf if b.data_ptr() != P.data_ptr()][:2]
+        src = P
+        for k, record in enumerate(self._records):
+            out = free[k % 2]
+            self._stage(record, src, P, out)
+            if self.bcs is not None:
+                self.bcs(out)
+            src = out
+        if self.average is not None:
+            self.average.push(src, self.dt)
+        self.nsteps += 1
+        return src
+
+    def _stage(self, record, src, P0, out):
+        """One stage of a step from ``P0`` (the time step is in ``self.dt``): the sweep of the previous stage ``src`` and the
+        update of the record's form into ``out``."""
+        form, base, coef = record
+        base = src if base == "src" else P0
         if self.residual is not None:
-            self.residual(self.part, P, self.work)
-            B.update_euler(P, self.work, self.dt, self.fluid, out=out)
+            self.residual(self.part, src, self.work)
+            if form == "step":
+                B.update_euler(src, self.work, self.dt, self.fluid, out=out)
+            elif form == "stage":
+                B.update_euler_stage(base, self.work, self.dt, *coef, self.fluid, out=out)
+            else:
+                B.update_euler_ssp(P0, src, self.work, self.dt, *coef, self.fluid, out=out)
+            return
+        tail = dict(fluid=self.fluid, scheme=self.scheme, work=self.work, flags=self.flags)
+        if form == "step":
+            B.step_euler(self.part, src, self.dt, out, **tail)
+        elif form == "stage":
+            B.stage_euler(self.part, src, base, self.dt, *coef, out, **tail)
         else:
-            B.step_euler(self.part, P, self.dt, out, self.fluid, self.scheme, work=self.work, flags=self.flags)
-        if self.bcs is not None:
-            self.bcs(out)
-        if self.average is not None:
-            self.average.push(out, self.dt)
-        self.nsteps += 1
-        return out
-
-    def _stages(self, P0):
-        """The stages of one step from ``P0`` (the time step is in ``self.dt``): stage ``k`` sweeps the previous stage and
-        updates ``P0`` into one of the two arrays that are neither ``P0`` nor its own input."""
-        free = [b for b in self._buf if b.data_ptr() != P0.data_ptr()][:2]
-        src = P0
-        for k, alpha in enumerate(self.stages):
-            out = free[k % 2]
-            if self.residual is not None:
-                self.residual(self.part, src, self.work)
-                B.update_euler_stage(P0, self.work, self.dt, alpha, self.fluid, out=out)
-            else:
-                B.stage_euler(self.part, src, P0, self.dt, alpha, out, self.fluid, self.scheme, work=self.work,
-                              flags=self.flags)
-            if self.bcs is not None:
-                self.bcs(out)
-            src = out
-        if self.average is not None:
-            self.average.push(src, self.dt)
-        self.nsteps += 1
-        return src
-
-    def _ssp_stages(self, P0):
-        """The Shu-Osher stages of one step from ``P0``: stage ``k`` sweeps the previous stage and writes the update of its
-        blend with ``P0`` into one of the two arrays that are neither ``P0`` nor its own input."""
-        free = [b for b in self._buf if b.data_ptr() != P0.data_ptr()][:2]
-        src = P0
-        for k, (a, b, c) in enumerate(self.stages):
-            out = free[k % 2]
-            plain = a == 0.0 and b == 1.0                  # no blend: the low-storage stage on the previous stage itself
-            if self.residual is not None:
-                self.residual(self.part, src, self.work)
-                if plain:
-                    B.update_euler_stage(src, self.work, self.dt, c, self.fluid, out=out)
-                else:
-                    B.update_euler_ssp(P0, src, self.work, self.dt, a, b, c, self.fluid, out=out)
-            elif plain:
-                B.stage_euler(self.part, src, src, self.dt, c, out, self.fluid, self.scheme, work=self.work, flags=self.flags)
-            else:
-                B.stage_euler_ssp(self.part, src, P0, self.dt, a, b, c, out, self.fluid, self.scheme, work=self.work,
-                                  flags=self.flags)
-            if self.bcs is not None:
-                self.bcs(out)
-            src = out
-        if self.average is not None:
-            self.average.push(src, self.dt)
-        self.nsteps += 1
-        return src
+            B.stage_euler_ssp(self.part, src, P0, self.dt, *coef, out, **tail)

@@ -432,7 +432,8 @@ int ibh_step_advection_dt(ibh_part* p, const float* u, float* u_out, const float
  *   block eligible, no face-list cells; by quads or, with IBH_NO_QUAD, per block), dt is global and P_out != P: the
  *   sweep stores the updated primitives itself.  Two launches everywhere else (3-D, face-list or mixed partitions, dt_per_cell,
  *   IBH_FORCE_GENERAL, IBH_NO_FUSE, IBH_EXACT, P_out == P): the sweep into `work`, nc x (nd + 2) floats with leading dimension
- *   ldw -- an argument check there, never an allocation -- then ibh_update_euler.  Same bits either way.  IBH_IMAGE_ONLY and
+ *   ldw -- an argument check there, never an allocation -- then ibh_update_euler.  Same bits either way.  A `work` that is
+ *   given may alias neither P nor P_out, whichever form runs.  IBH_IMAGE_ONLY and
  *   the overlap phases are rejected: the update would read rows the sweep never wrote (the multi-GPU step is out of scope).
  * Every misuse (null pointer, nd other than 2 or 3, a leading dimension below n, the aliasing above) is an error before any
  * launch. */

@@ -4,11 +4,14 @@ kernels from its code-object metadata.
 
     hipcc <the Makefile's CXXFLAGS> -S --cuda-device-only csrc/ibh_fused2d.hip -o head.s     (same at the parent: parent.s)
     scripts/kernel_bodies.py diff parent.s head.s k_sweep_quad_euler k_sweep_euler
+    scripts/kernel_bodies.py diff --rename '<(\d), true, true, false, true>=<\1, 3, false>' parent.s head.s k_sweep
     scripts/kernel_bodies.py meta head.s k_sweep_quad_euler k_update_euler
 
 `diff`: for every kernel of the FIRST listing whose demangled name contains one of the patterns, the instructions between
 its label and its end label must be the same lines in the second listing (labels are renumbered per function, so local
-labels are compared by their order of appearance).  Exit status 1 on any difference.  `meta`: .vgpr_count, .sgpr_count,
+labels are compared by their order of appearance).  Exit status 1 on any difference.  `--rename OLD=NEW` (repeatable): a
+regular expression substitution on the demangled names of the FIRST listing before they are looked up in the second, for a
+kernel whose template parameters were renumbered between the two.  `meta`: .vgpr_count, .sgpr_count,
 .private_segment_fixed_size (scratch bytes), .group_segment_fixed_size (LDS bytes) per matching kernel.
 """
 import re
@@ -66,7 +69,11 @@ def meta(path):
 
 
 def main():
-    mode, args = sys.argv[1], sys.argv[2:]
+    mode, args, renames = sys.argv[1], sys.argv[2:], []
+    while "--rename" in args:
+        i = args.index("--rename")
+        renames.append(args[i + 1].split("=", 1))
+        del args[i:i + 2]
     if mode == "diff":
         a, b, pats = bodies(args[0]), bodies(args[1]), args[2:]
         dm, dmb = demangle(list(a)), demangle(list(b))
@@ -74,12 +81,17 @@ def main():
         # same kernel: matched by its name without them
         key = lambda d: re.sub(r"(, false)+>$", ">", d.replace("(anonymous namespace)::", "").split("(")[0])
         byname = {key(dmb[k]): k for k in b}
+
+        def renamed(d):
+            for old, new in renames:
+                d = re.sub(old, new, d)
+            return d
         bad = n = 0
         for k in sorted(a, key=lambda x: dm[x]):
             if not any(p in dm[k] for p in pats) or not dm[k].startswith("void"):
                 continue
             n += 1
-            kb = byname.get(key(dm[k]))
+            kb = byname.get(key(renamed(dm[k])))
             same = kb is not None and canon(a[k]) == canon(b[kb])
             bad += not same
             print(("identical  " if same else "DIFFERENT  " if kb else "MISSING    ") + f"{len(a[k]):6d} lines  {dm[k]}")

@@ -210,6 +210,15 @@ def test_python_layer_rejects_misuse(meshes):
         ibamd.step_euler(c.dpart, Pd, dt, out, scheme="roe")
     with pytest.raises(TypeError):
         ibamd.step_euler(c.dpart, Pd, dt, torch.empty((Pd.shape[0], Pd.shape[1]), dtype=torch.float32, device="cuda"))
+    # a work that aliases P or out is rejected on the one-launch path too, where it would not be used: nothing is launched
+    a = meshes["adv"]
+    Pa = ibamd.hip(rg.euler_regime(a.part, "rest"))
+    oa = B.colmajor_empty(*Pa.shape)
+    oa.fill_(float("nan"))
+    for work in (Pa, oa):
+        with pytest.raises(_lib.IbhError, match="work may not alias"):
+            ibamd.step_euler(a.dpart, Pa, dt, oa, FLUID, "hll", work=work, flags=0)
+        assert torch.isnan(oa).all()
 
 
 # ---------------------------------------------------------------------------------------------------------------------
