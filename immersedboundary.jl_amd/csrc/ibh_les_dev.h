@@ -1,8 +1,11 @@
 // libibhip: device bodies of the pointwise LES closures and shock sensors over a register table g[ND][ND],
 // g[i][j] = d u_i / d x_j -- shear_rate (turbulence.jl:110-124), Smagorinsky_νSGS (:134-137), Ducros_sensor (:253-283),
-// WALE_νSGS (:292-337) and CFD.shock_sensor (cfd.jl:589-617) -- shared by the pointwise kernels of ibh_turb.hip / ibh_cfd.hip
-// and the fused closure ibh_les_of (k_les_of3 in ibh_turb.hip, k_les_of_cells in ibh_ops.hip).  Float32, the reference's
-// operation order (-ffp-contract=off).
+// WALE_νSGS (:292-337) and CFD.shock_sensor (cfd.jl:589-617) -- and of Wray_Agarwal (:222-241) at one cell, shared by the
+// pointwise kernels of ibh_turb.hip / ibh_cfd.hip and the fused closures that consume cell_gradient where it is made:
+// ibh_les_of (k_les_of3 in ibh_turb.hip, k_les_of_cells in ibh_ops.hip), ibh_shear_rate_of_velocity[_grad]
+// (k_shear_of_velocity3, k_shear_of_velocity_cells), ibh_k_epsilon_rhs (k_k_epsilon_rhs3, k_k_epsilon_rhs_cells: shear_rate)
+// and ibh_wray_agarwal_of (k_wray_agarwal_of3, k_wray_agarwal_of_cells).  Float32, the reference's operation order
+// (-ffp-contract=off).
 #pragma once
 #include "ibh_common.h"
 
@@ -108,6 +111,16 @@ __device__ __forceinline__ float shock(const float (&g)[ND][ND]) {
     }
     divu = divu * divu;
     return (divu + EPS_SHOCK) / (divu + vort2 + EPS_SHOCK);
+}
+
+// Wray_Agarwal (turbulence.jl:222-241) at one cell, dot = grad R . grad S and C2 = sigmaR + C1 / kappa^2:
+// nut = R, nuR = sigmaR R, S = min(C1 R S + C2 dot R / (S + eps), 10 R)
+struct WrayAgarwal {
+    float nut, nuR, S;
+};
+__device__ __forceinline__ WrayAgarwal wray_agarwal(float r, float s, float dot, float sigmaR, float C1, float C2) {
+    const float src = C1 * r * s + C2 * dot * (r / (s + EPS32));
+    return {r, r * sigmaR, ibh_min(src, 10.0f * r)};
 }
 
 // the register table of cell c from an nd x nd table of device pointers, G[i * ND + j] = d u_i / d x_j

@@ -2,7 +2,8 @@
 // operator (ImmersedBoundary.jl:873-1157), accumulators, ghost-cell BC, row gather/scatter
 // and the small vector ops of the FAS loop.  HBM-bound gathers: threads run over the
 // contiguous row index (cell or face) so loads/stores of the row-major side are coalesced;
-// the variable index is the slow grid dimension.
+// the variable index is the slow grid dimension.  Also here, beside cell_gradient_at: the thread-per-cell forms of the fused
+// closures of ibh_turb.hip (k_shear_of_velocity_cells, k_les_of_cells, k_k_epsilon_rhs_cells, k_wray_agarwal_of_cells).
 //
 // Arithmetic follows the reference's broadcast order operation by operation (compiled
 // with -ffp-contract=off, IEEE divide/sqrt) so results are bit-comparable with the oracle.
@@ -228,46 +229,47 @@ __device__ __forceinline__ void cell_gradient_at(const GradDims& G, const int32_
         g[d] = (ar - al) / hc;
     }
 }
-// shear_rate of the gradients of a velocity field / Wray_Agarwal of the gradients of (R, S), face-list partitions: thread per
-// cell, the gradients never leave the registers (same expressions as k_cell_gradient_all + ibh_turb.hip's k_shear /
-// k_wray_agarwal: bit-identical to the composition)
+// ---- the fused closures on face-list partitions (ibh_turb.hip dispatches here): thread per cell, the gradients never
+// leave the registers -- the expressions of k_cell_gradient_all and the pointwise formulas of ibh_les_dev.h /
+// ibh_transport_dev.h, bit-identical to the composition.  What the kernels share: the 2 ND entries of cell c in the side
+// table, and the way out of the table g[i][j] = d u_i / d x_j when the gradients are asked for (column ND j + i: the tuple
+// cell_gradient's layout).  The loop of cell_gradient_at over the velocity components stays written in the kernels: inside
+// a function it reorders a third of their instructions, and the 3-D kernels measured 1 % slower.
+template <int ND>
+__device__ __forceinline__ void cell_sides(const GradDims& G, int32_t nc, int64_t c, int32_t (&sd)[2 * ND]) {
+#pragma unroll
+    for (int s = 0; s < 2 * ND; ++s) sd[s] = G.side[(int64_t)s * nc + c];
+}
+template <int ND>
+__device__ __forceinline__ void store_gradients(const float (&g)[ND][ND], float* __restrict__ Gout, int64_t ldg, int64_t c) {
+#pragma unroll
+    for (int i = 0; i < ND; ++i)
+#pragma unroll
+        for (int j = 0; j < ND; ++j) Gout[(int64_t)(ND * j + i) * ldg + c] = g[i][j];
+}
+// ibh_shear_rate_of_velocity[_grad]: k_les_of_cells without a model, asked for S (and G) -- kept as a kernel of its own for
+// its registers (71 against 78 VGPRs in 3-D: seven waves per SIMD against six)
 template <int ND>
 __global__ void k_shear_of_velocity_cells(int32_t nc, GradDims G, const float* __restrict__ vel, int64_t ldv,
                                           float* __restrict__ S, float* __restrict__ Gout, int64_t ldg) {
     for (int64_t c = IBH_WG_X() * (int64_t)blockDim.x + threadIdx.x; c < nc; c += (int64_t)gridDim.x * blockDim.x) {
         int32_t sd[2 * ND];
-#pragma unroll
-        for (int s = 0; s < 2 * ND; ++s) sd[s] = G.side[(int64_t)s * nc + c];
-        float g[ND][ND];
+        cell_sides<ND>(G, nc, c, sd);
+        float g[ND][ND];   // g[i][j] = d u_i / d x_j
 #pragma unroll
         for (int i = 0; i < ND; ++i) cell_gradient_at<ND>(G, sd, nc, (int32_t)c, vel + (int64_t)i * ldv, g[i]);
-        float s = 0.0f;
-#pragma unroll
-        for (int i = 0; i < ND; ++i)
-#pragma unroll
-            for (int j = 0; j < ND; ++j) {
-                const float t = (g[i][j] + g[j][i]) / 2.0f;
-                s = s + t * t;
-            }
-        S[c] = sqrtf(2.0f * s);
-        if (Gout) {  // d u_i / d x_j in column ND j + i (the tuple cell_gradient's layout)
-#pragma unroll
-            for (int i = 0; i < ND; ++i)
-#pragma unroll
-                for (int j = 0; j < ND; ++j) Gout[(int64_t)(ND * j + i) * ldg + c] = g[i][j];
-        }
+        S[c] = les_dev::shear_rate<ND>(g);
+        if (Gout) store_gradients<ND>(g, Gout, ldg, c);
     }
 }
-// the LES closure of a velocity field (ibh_les_of), face-list partitions: the gradients as in k_shear_of_velocity_cells, the
-// requested outputs from registers with the pointwise formulas of ibh_les_dev.h (bit-identical to the composition)
+// the LES closure of a velocity field (ibh_les_of): the requested outputs from registers
 template <int ND>
 __global__ void k_les_of_cells(int32_t nc, GradDims G, const float* __restrict__ vel, int64_t ldv,
                                const float* __restrict__ Delta, int model, float Cmodel, les_dev::Outputs O) {
     for (int64_t c = IBH_WG_X() * (int64_t)blockDim.x + threadIdx.x; c < nc; c += (int64_t)gridDim.x * blockDim.x) {
         int32_t sd[2 * ND];
-#pragma unroll
-        for (int s = 0; s < 2 * ND; ++s) sd[s] = G.side[(int64_t)s * nc + c];
-        float g[ND][ND];
+        cell_sides<ND>(G, nc, c, sd);
+        float g[ND][ND];   // g[i][j] = d u_i / d x_j
 #pragma unroll
         for (int i = 0; i < ND; ++i) cell_gradient_at<ND>(G, sd, nc, (int32_t)c, vel + (int64_t)i * ldv, g[i]);
         if (O.S || model == les_dev::MODEL_SMAGORINSKY) {  // (uniform, as every branch below)
@@ -280,18 +282,13 @@ __global__ void k_les_of_cells(int32_t nc, GradDims G, const float* __restrict__
         }
         if (O.ducros) O.ducros[c] = les_dev::ducros<ND>(g);
         if (O.shock) O.shock[c] = les_dev::shock<ND>(g);
-        if (O.G) {  // d u_i / d x_j in column ND j + i (the tuple cell_gradient's layout)
-#pragma unroll
-            for (int i = 0; i < ND; ++i)
-#pragma unroll
-                for (int j = 0; j < ND; ++j) O.G[(int64_t)(ND * j + i) * O.ldg + c] = g[i][j];
-        }
+        if (O.G) store_gradients<ND>(g, O.G, O.ldg, c);
     }
 }
-// the right-hand sides of the standard k-epsilon model (ibh_k_epsilon_rhs), face-list partitions: the gradients as in
-// k_shear_of_velocity_cells, standard_kϵ with the expressions of ibh_turb.hip's k_keps, then both transport sums in one walk
-// over the cell's faces (tr_dev::cell_sum: the walk and the flux of k_scalar_transport).  The diffusivity nu + nut / sigma of
-// the cell across a face is made from that cell's own k and eps -- the bits the composition reads back from nuk / nue.
+// the right-hand sides of the standard k-epsilon model (ibh_k_epsilon_rhs): standard_kϵ with the expressions of
+// ibh_turb.hip's k_keps, then both transport sums in one walk over the cell's faces (tr_dev::cell_sum: the walk and the flux
+// of k_scalar_transport).  The diffusivity nu + nut / sigma of the cell across a face is made from that cell's own k and eps
+// -- the bits the composition reads back from nuk / nue.
 template <int ND>
 __global__ void k_k_epsilon_rhs_cells(int32_t nc, GradDims G, const float* __restrict__ vel, int64_t ldv,
                                       const float* __restrict__ kf, const float* __restrict__ ef, float nu, tr_dev::KEps P,
@@ -299,19 +296,13 @@ __global__ void k_k_epsilon_rhs_cells(int32_t nc, GradDims G, const float* __res
                                       float* __restrict__ Sout, float* __restrict__ Gout, int64_t ldg) {
     for (int64_t c = IBH_WG_X() * (int64_t)blockDim.x + threadIdx.x; c < nc; c += (int64_t)gridDim.x * blockDim.x) {
         int32_t sd[2 * ND];
-#pragma unroll
-        for (int s = 0; s < 2 * ND; ++s) sd[s] = G.side[(int64_t)s * nc + c];
-        float g[ND][ND];
+        cell_sides<ND>(G, nc, c, sd);
+        float g[ND][ND];   // g[i][j] = d u_i / d x_j
 #pragma unroll
         for (int i = 0; i < ND; ++i) cell_gradient_at<ND>(G, sd, nc, (int32_t)c, vel + (int64_t)i * ldv, g[i]);
         const float S = les_dev::shear_rate<ND>(g);
         if (Sout) Sout[c] = S;   // (uniform, as every branch on an output pointer)
-        if (Gout) {              // d u_i / d x_j in column ND j + i (the tuple cell_gradient's layout)
-#pragma unroll
-            for (int i = 0; i < ND; ++i)
-#pragma unroll
-                for (int j = 0; j < ND; ++j) Gout[(int64_t)(ND * j + i) * ldg + c] = g[i][j];
-        }
+        if (Gout) store_gradients<ND>(g, Gout, ldg, c);
         const float kk = kf[c], ee = ef[c];
         const float nt = tr_dev::keps_nut(P, kk, ee);
         const float Pk = nt * (S * S);
@@ -329,27 +320,25 @@ __global__ void k_k_epsilon_rhs_cells(int32_t nc, GradDims G, const float* __res
         reps[c] = rt[1];
     }
 }
+// Wray_Agarwal of the gradients of (R, S) (ibh_wray_agarwal_of)
 template <int ND>
 __global__ void k_wray_agarwal_of_cells(int32_t nc, GradDims G, const float* __restrict__ R, const float* __restrict__ S,
                                         float sigmaR, float C1, float kappa, float* __restrict__ nut,
                                         float* __restrict__ nuR, float* __restrict__ Sout) {
     const float C2 = sigmaR + C1 / (kappa * kappa);
-    constexpr float EPS32 = 1.1920929e-07f;
     for (int64_t c = IBH_WG_X() * (int64_t)blockDim.x + threadIdx.x; c < nc; c += (int64_t)gridDim.x * blockDim.x) {
         int32_t sd[2 * ND];
-#pragma unroll
-        for (int s = 0; s < 2 * ND; ++s) sd[s] = G.side[(int64_t)s * nc + c];
+        cell_sides<ND>(G, nc, c, sd);
         float gR[ND], gS[ND];
         cell_gradient_at<ND>(G, sd, nc, (int32_t)c, R, gR);
         cell_gradient_at<ND>(G, sd, nc, (int32_t)c, S, gS);
         float dot = gR[0] * gS[0];
 #pragma unroll
         for (int d = 1; d < ND; ++d) dot = dot + gR[d] * gS[d];
-        const float r = R[c], s = S[c];
-        const float src = C1 * r * s + C2 * dot * (r / (s + EPS32));
-        nut[c] = r;
-        nuR[c] = r * sigmaR;
-        Sout[c] = ibh_min(src, 10.0f * r);
+        const les_dev::WrayAgarwal w = les_dev::wray_agarwal(R[c], S[c], dot, sigmaR, C1, C2);
+        nut[c] = w.nut;
+        nuR[c] = w.nuR;
+        Sout[c] = w.S;
     }
 }
 
@@ -655,6 +644,12 @@ __global__ void k_fas_update(int64_t n, float omega, const float* __restrict__ r
 }
 
 inline dim3 grid2(int64_t n, int nv) { return dim3(ibh_grid_cap(n, OPS_BLOCK, 4096), nv); }
+// a thread-per-cell kernel template <int ND> over the cells of p (x nv fields): k2, k3 = its instantiations for nd = 2, 3
+template <class... P, class... A>
+void launch_cells(const ibh_part* p, int nv, void (*k2)(P...), void (*k3)(P...), A... args) {
+    const auto k = p->nd == 2 ? k2 : k3;
+    hipLaunchKernelGGL(k, grid2(p->nc, nv), dim3(OPS_BLOCK), 0, ibh_stream, args...);
+}
 
 // launch of the accumulation kernels: per (row, field) for one field, per row over blocks of up to 4 fields otherwise
 static inline void launch_accumulate(int32_t n_out, const int32_t* off, const int32_t* idx, const float* w,
@@ -741,67 +736,36 @@ int ibh_cell_gradient_all(const ibh_part* p, const float* u, int nv, int64_t ldu
     IBH_REQUIRE(p && u && out && (p->nd == 2 || p->nd == 3), "ibh_cell_gradient_all: bad argument");
     CHECK_NV(nv);
     if (p->nc == 0) return 0;
-    GradDims G;
-    for (int d = 0; d < p->nd; ++d) {
-        G.d[d] = p->dim[d];
-        G.h[d] = p->spacing + (int64_t)d * p->nc;
-    }
-    G.side = p->side;
-    if (p->nd == 2)
-        hipLaunchKernelGGL(k_cell_gradient_all<2>, grid2(p->nc, nv), dim3(OPS_BLOCK), 0, ibh_stream, p->nc, G, u, ldu, nv, out, ldo);
-    else
-        hipLaunchKernelGGL(k_cell_gradient_all<3>, grid2(p->nc, nv), dim3(OPS_BLOCK), 0, ibh_stream, p->nc, G, u, ldu, nv, out, ldo);
+    launch_cells(p, nv, k_cell_gradient_all<2>, k_cell_gradient_all<3>, p->nc, grad_dims(p), u, ldu, nv, out, ldo);
     IBH_LAUNCH_CHECK();
     return 0;
 }
 
-// face-list forms of ibh_shear_rate_of_velocity / ibh_wray_agarwal_of (ibh_turb.hip dispatches here on partitions
-// without block structure)
+// face-list forms of the fused closures (ibh_turb.hip dispatches here on partitions without block structure, arguments
+// checked)
 int ibh_shear_rate_of_velocity_cells(const ibh_part* p, const float* vel, int64_t ldv, float* S, float* Gout, int64_t ldg) {
-    const GradDims G = grad_dims(p);
-    if (p->nd == 2)
-        hipLaunchKernelGGL(k_shear_of_velocity_cells<2>, grid2(p->nc, 1), dim3(OPS_BLOCK), 0, ibh_stream, p->nc, G, vel, ldv, S, Gout, ldg);
-    else
-        hipLaunchKernelGGL(k_shear_of_velocity_cells<3>, grid2(p->nc, 1), dim3(OPS_BLOCK), 0, ibh_stream, p->nc, G, vel, ldv, S, Gout, ldg);
+    launch_cells(p, 1, k_shear_of_velocity_cells<2>, k_shear_of_velocity_cells<3>, p->nc, grad_dims(p), vel, ldv, S, Gout, ldg);
     IBH_LAUNCH_CHECK();
     return 0;
 }
 int ibh_wray_agarwal_of_cells(const ibh_part* p, const float* R, const float* S, float sigmaR, float C1, float kappa,
                               float* nut, float* nuR, float* Sout) {
-    const GradDims G = grad_dims(p);
-    if (p->nd == 2)
-        hipLaunchKernelGGL(k_wray_agarwal_of_cells<2>, grid2(p->nc, 1), dim3(OPS_BLOCK), 0, ibh_stream, p->nc, G, R, S, sigmaR,
-                           C1, kappa, nut, nuR, Sout);
-    else
-        hipLaunchKernelGGL(k_wray_agarwal_of_cells<3>, grid2(p->nc, 1), dim3(OPS_BLOCK), 0, ibh_stream, p->nc, G, R, S, sigmaR,
-                           C1, kappa, nut, nuR, Sout);
+    launch_cells(p, 1, k_wray_agarwal_of_cells<2>, k_wray_agarwal_of_cells<3>, p->nc, grad_dims(p), R, S, sigmaR, C1, kappa,
+                 nut, nuR, Sout);
     IBH_LAUNCH_CHECK();
     return 0;
 }
 int ibh_les_of_cells(const ibh_part* p, const float* vel, int64_t ldv, const float* Delta, int model, float Cmodel,
                      float* nusgs, float* ducros, float* shock, float* S, float* Gout, int64_t ldg) {
-    const GradDims G = grad_dims(p);
-    const les_dev::Outputs O{nusgs, ducros, shock, S, Gout, ldg};
-    if (p->nd == 2)
-        hipLaunchKernelGGL(k_les_of_cells<2>, grid2(p->nc, 1), dim3(OPS_BLOCK), 0, ibh_stream, p->nc, G, vel, ldv, Delta, model,
-                           Cmodel, O);
-    else
-        hipLaunchKernelGGL(k_les_of_cells<3>, grid2(p->nc, 1), dim3(OPS_BLOCK), 0, ibh_stream, p->nc, G, vel, ldv, Delta, model,
-                           Cmodel, O);
+    launch_cells(p, 1, k_les_of_cells<2>, k_les_of_cells<3>, p->nc, grad_dims(p), vel, ldv, Delta, model, Cmodel,
+                 les_dev::Outputs{nusgs, ducros, shock, S, Gout, ldg});
     IBH_LAUNCH_CHECK();
     return 0;
 }
-
 int ibh_k_epsilon_rhs_cells(const ibh_part* p, const float* vel, int64_t ldv, const float* k, const float* eps, float nu,
                             const float* params5, float* rk, float* reps, float* nut, float* S, float* Gout, int64_t ldg) {
-    const GradDims G = grad_dims(p);
-    const tr_dev::KEps P{params5[0], params5[1], params5[2], params5[3], params5[4]};
-    if (p->nd == 2)
-        hipLaunchKernelGGL(k_k_epsilon_rhs_cells<2>, grid2(p->nc, 1), dim3(OPS_BLOCK), 0, ibh_stream, p->nc, G, vel, ldv, k, eps,
-                           nu, P, rk, reps, nut, S, Gout, ldg);
-    else
-        hipLaunchKernelGGL(k_k_epsilon_rhs_cells<3>, grid2(p->nc, 1), dim3(OPS_BLOCK), 0, ibh_stream, p->nc, G, vel, ldv, k, eps,
-                           nu, P, rk, reps, nut, S, Gout, ldg);
+    launch_cells(p, 1, k_k_epsilon_rhs_cells<2>, k_k_epsilon_rhs_cells<3>, p->nc, grad_dims(p), vel, ldv, k, eps, nu,
+                 tr_dev::keps_params(params5), rk, reps, nut, S, Gout, ldg);
     IBH_LAUNCH_CHECK();
     return 0;
 }

@@ -22,6 +22,9 @@ __device__ __forceinline__ float flux(float Ro, float Rn, float To, float Tn, fl
 struct KEps {
     float Cmu, sk, se, C1, C2;
 };
+inline KEps keps_params(const float* params5) {   // (host) the C entries' (Cmu, sigma_k, sigma_eps, C1eps, C2eps)
+    return {params5[0], params5[1], params5[2], params5[3], params5[4]};
+}
 __device__ __forceinline__ float keps_nut(const KEps& P, float kk, float ee) { return P.Cmu * (kk * kk) / ee; }
 __device__ __forceinline__ float keps_Sk(float Pk, float ee) { return Pk - ee; }
 __device__ __forceinline__ float keps_Se(const KEps& P, float Pk, float kk, float ee) {

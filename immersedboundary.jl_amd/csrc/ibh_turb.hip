@@ -3,7 +3,9 @@
 // Wray_Agarwal :222-241, Ducros_sensor :252-282, WALE_νSGS :291-337.  Float32, the reference's operation order
 // (-ffp-contract=off); log/exp/pow come from the device math library (a few ulp from Julia's).
 // Velocity gradients: an nd x nd table of device pointers, g[i*nd + j] = d u_i / d x_j (the reference's Matrix of vectors).
-// At the end: the closures on an all-block 3-D partition with the gradients made where they are consumed (block kernels).
+// After them: the closures on an all-block 3-D partition with the gradients made where they are consumed (block kernels
+// k_shear_of_velocity3, k_wray_agarwal_of3, k_les_of3, k_scalar_transport_blocks3, k_k_epsilon_rhs3),
+// and the C entries, which send the same closures on a partition without block structure to ibh_ops.hip's *_cells kernels.
 #include "ibh_common.h"
 #include "ibh_fused_int.h"
 #include "ibh_wall_dev.h"
@@ -13,7 +15,6 @@
 namespace {
 
 constexpr int TB = 256;
-constexpr float EPS32 = wall_dev::EPS32;
 
 struct GradPtrs {
     const float* g[9];
@@ -87,8 +88,11 @@ __global__ void k_wray_agarwal(int64_t n, const float* __restrict__ R, const flo
         float dot = gR[i] * gS[i];
 #pragma unroll
         for (int d = 1; d < ND; ++d) dot = dot + gR[i + d * ldr] * gS[i + d * lds];
+        // (les_dev::wray_agarwal written out: this kernel is the composition the fused forms are tested against, so its body
+        // is held instruction for instruction, and through the function it comes out in another order:
+        // profiles/closure_forms/README.md)
         const float r = R[i], s = S[i];
-        const float src = C1 * r * s + C2 * dot * (r / (s + EPS32));
+        const float src = C1 * r * s + C2 * dot * (r / (s + les_dev::EPS32));
         nut[i] = r;
         nuR[i] = r * sigmaR;
         Sout[i] = ibh_min(src, 10.0f * r);
@@ -151,46 +155,59 @@ namespace {
 
 // ---- closures of a turbulence model on an all-block 3-D partition, gradients consumed where they are made (one wavefront
 // per 8^3 block, blk3::wave_gradients: the arithmetic of the tuple cell_gradient's block sweep; the pointwise formulas are
-// those of k_shear / k_wray_agarwal above, evaluated without contraction):
-//   k_shear_of_velocity3: S = shear_rate(cell_gradient(u), cell_gradient(v), cell_gradient(w))      (turbulence.jl:110-124)
-//   k_wray_agarwal_of3:   (nut, nuR, S) = Wray_Agarwal(R, S, cell_gradient(R), cell_gradient(S))    (turbulence.jl:222-241)
-// 12 B in + 4 B out per cell instead of 3 x (4 in + 16 out) + 36 in + 4 out; 8 in + 12 out instead of 2 x 20 + 44.
+// those of the kernels above, from ibh_les_dev.h, evaluated without contraction).  What the block kernels share:
 template <int NV>
 struct FieldPtrs {
     const float* f[NV];
 };
+// the wave's place in a launch of one wavefront per block, four per workgroup (launch_blocks3 below): blk >= nblk is idle
+struct Wave3 {
+    int wave, lane;
+    int32_t blk;
+};
+__device__ __forceinline__ Wave3 wave3(int32_t nwg) {
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    return {wave, (int)(threadIdx.x & 63), __builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x, nwg) * 4 + wave)};
+}
+// the 3 x 3 table t[i][j] = d u_i / d x_j of the lane's cell in plane k
+__device__ __forceinline__ void cell_table(const float (&g)[3][8][3], int k, float (&t)[3][3]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) t[i][j] = g[i][k][j];
+}
+// ... and its way out when the gradients are asked for: d u_i / d x_j in column 3 j + i (the tuple cell_gradient's layout)
+__device__ __forceinline__ void store_table_nt(const float (&t)[3][3], float* __restrict__ G, uint32_t ldg, uint32_t c) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) __builtin_nontemporal_store(t[i][j], G + (size_t)(3 * j + i) * ldg + c);
+}
+
+//   k_shear_of_velocity3: S = shear_rate(cell_gradient(u), cell_gradient(v), cell_gradient(w))      (turbulence.jl:110-124)
+//   k_wray_agarwal_of3:   (nut, nuR, S) = Wray_Agarwal(R, S, cell_gradient(R), cell_gradient(S))    (turbulence.jl:222-241)
+// 12 B in + 4 B out per cell instead of 3 x (4 in + 16 out) + 36 in + 4 out; 8 in + 12 out instead of 2 x 20 + 44.
+// k_shear_of_velocity3 is k_les_of3<MODEL_NONE> below asked for S (and G), the same arithmetic in the same order; it stays a
+// kernel of its own because S alone came out 4 % slower through the LES kernel (profiles/closure_forms/README.md).
+// Gout (or null): the nine gradients on the way -- a Navier-Stokes closure needs them again for its viscous fluxes.
 __global__ __launch_bounds__(256) void k_shear_of_velocity3(const BlockDesc3* __restrict__ blocks,
                                                             const int32_t* __restrict__ htab,
                                                             const int32_t* __restrict__ ftab, int32_t nblk, int32_t nwg,
                                                             FieldPtrs<3> V, float* __restrict__ S,
                                                             float* __restrict__ Gout, uint32_t ldg) {
-    // Gout (or null): the nine gradients on the way, d u_i / d x_j in column 3 j + i (the tuple cell_gradient's layout) --
-    // a Navier-Stokes closure needs them again for its viscous fluxes (three pass-A sweeps otherwise)
     __shared__ float lds[4 * BLK3W_PASSA_LDS];
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int32_t blk = __builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x, nwg) * 4 + wave);
+    const auto [wave, lane, blk] = wave3(nwg);
     if (blk >= nblk) return;
     const BlockDesc3 bb = blocks[blk];
     float g[3][8][3];
     blk3::wave_gradients<3>(bb, htab, ftab, blk, V.f, lds + wave * BLK3W_PASSA_LDS, lane, g);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-        float s = 0.0f;
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                const float t = (g[i][k][j] + g[j][k][i]) / 2.0f;
-                s = s + t * t;
-            }
-        S[(uint32_t)bb.base + lane + 64 * k] = sqrtf(2.0f * s);
-        if (Gout) {  // (uniform)
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int j = 0; j < 3; ++j)
-                    __builtin_nontemporal_store(g[i][k][j], Gout + (size_t)(3 * j + i) * ldg + (uint32_t)bb.base + lane + 64 * k);
-        }
+        const uint32_t c = (uint32_t)bb.base + lane + 64 * k;
+        float t[3][3];
+        cell_table(g, k, t);
+        S[c] = les_dev::shear_rate<3>(t);
+        if (Gout) store_table_nt(t, Gout, ldg, c);   // (uniform)
     }
 }
 __global__ __launch_bounds__(256) void k_wray_agarwal_of3(const BlockDesc3* __restrict__ blocks,
@@ -200,25 +217,22 @@ __global__ __launch_bounds__(256) void k_wray_agarwal_of3(const BlockDesc3* __re
                                                           float* __restrict__ nut, float* __restrict__ nuR,
                                                           float* __restrict__ Sout) {
     __shared__ float lds[4 * BLK3W_PASSA_LDS];
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int32_t blk = __builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x, nwg) * 4 + wave);
+    const auto [wave, lane, blk] = wave3(nwg);
     if (blk >= nblk) return;
     const BlockDesc3 bb = blocks[blk];
     float g[2][8][3];
     blk3::wave_gradients<2>(bb, htab, ftab, blk, RS.f, lds + wave * BLK3W_PASSA_LDS, lane, g);
     const float C2 = sigmaR + C1 / (kappa * kappa);
-    constexpr float EPS32 = 1.1920929e-07f;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
         const uint32_t c = (uint32_t)bb.base + lane + 64 * k;
         float dot = g[0][k][0] * g[1][k][0];
         dot = dot + g[0][k][1] * g[1][k][1];
         dot = dot + g[0][k][2] * g[1][k][2];
-        const float r = RS.f[0][c], s = RS.f[1][c];
-        const float src = C1 * r * s + C2 * dot * (r / (s + EPS32));
-        nut[c] = r;
-        nuR[c] = r * sigmaR;
-        Sout[c] = ibh_min(src, 10.0f * r);
+        const les_dev::WrayAgarwal w = les_dev::wray_agarwal(RS.f[0][c], RS.f[1][c], dot, sigmaR, C1, C2);
+        nut[c] = w.nut;
+        nuR[c] = w.nuR;
+        Sout[c] = w.S;
     }
 }
 
@@ -239,23 +253,18 @@ __global__ __launch_bounds__(256) void k_les_of3(const BlockDesc3* __restrict__ 
                                                  FieldPtrs<3> V, const float* __restrict__ Delta, float Cmodel,
                                                  les_dev::Outputs O) {
     __shared__ float lds[4 * BLK3W_PASSA_LDS];
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int32_t blk = __builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x, nwg) * 4 + wave);
+    const auto [wave, lane, blk] = wave3(nwg);
     if (blk >= nblk) return;
     const BlockDesc3 bb = blocks[blk];
     float* wl = lds + wave * BLK3W_PASSA_LDS;
     float g[3][8][3];
     blk3::wave_gradients<3>(bb, htab, ftab, blk, V.f, wl, lane, g);
     if (MODEL == les_dev::MODEL_WALE) blk2::wave_lds_sync();   // the gradients' LDS reads are done: the tile takes the invariants
-    const uint32_t ldg = (uint32_t)O.ldg;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
         const uint32_t c = (uint32_t)bb.base + lane + 64 * k;
         float t[3][3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) t[i][j] = g[i][k][j];
+        cell_table(g, k, t);
         if (O.S || MODEL == les_dev::MODEL_SMAGORINSKY) {  // (uniform, as every branch on O below)
             const float s = les_dev::shear_rate<3>(t);
             if (O.S) O.S[c] = s;
@@ -269,12 +278,7 @@ __global__ __launch_bounds__(256) void k_les_of3(const BlockDesc3* __restrict__ 
             wl[k * 64 + lane] = SS;
             wl[512 + k * 64 + lane] = SdSd;
         }
-        if (O.G) {  // d u_i / d x_j in column 3 j + i (the tuple cell_gradient's layout)
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int j = 0; j < 3; ++j) __builtin_nontemporal_store(t[i][j], O.G + (size_t)(3 * j + i) * ldg + c);
-        }
+        if (O.G) store_table_nt(t, O.G, (uint32_t)O.ldg, c);
     }
     if (MODEL == les_dev::MODEL_WALE) {
         blk2::wave_lds_sync();
@@ -422,8 +426,7 @@ __global__ __launch_bounds__(256) void k_scalar_transport_blocks3(const BlockDes
                                                                   const float* __restrict__ S, float* __restrict__ out) {
     using blk2::ldg;
     __shared__ float lds_all[4 * TR3_LDS];
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int32_t blk = __builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x, nwg) * 4 + wave);
+    const auto [wave, lane, blk] = wave3(nwg);
     if (blk >= nblk) return;
     const BlockDesc3 bb = blocks[blk];
     Tr3Shared W;
@@ -464,8 +467,7 @@ __global__ __launch_bounds__(256) void k_k_epsilon_rhs3(const BlockDesc3* __rest
                                                         float* __restrict__ Gout, uint32_t ldg_) {
     using blk2::ldg;
     __shared__ float lds_all[4 * KE3_LDS];
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int32_t blk = __builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x, nwg) * 4 + wave);
+    const auto [wave, lane, blk] = wave3(nwg);
     if (blk >= nblk) return;
     const BlockDesc3 bb = blocks[blk];
     float* wl = lds_all + wave * KE3_LDS;
@@ -479,18 +481,10 @@ __global__ __launch_bounds__(256) void k_k_epsilon_rhs3(const BlockDesc3* __rest
         for (int k = 0; k < 8; ++k) {
             const uint32_t c = base + lane + 64 * k;
             float t[3][3];
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int j = 0; j < 3; ++j) t[i][j] = g[i][k][j];
+            cell_table(g, k, t);
             Pk[k] = les_dev::shear_rate<3>(t);
             if (Sout) Sout[c] = Pk[k];   // (uniform, as every branch on an output pointer)
-            if (Gout) {                  // d u_i / d x_j in column 3 j + i (the tuple cell_gradient's layout)
-#pragma unroll
-                for (int i = 0; i < 3; ++i)
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) __builtin_nontemporal_store(t[i][j], Gout + (size_t)(3 * j + i) * ldg_ + c);
-            }
+            if (Gout) store_table_nt(t, Gout, ldg_, c);
         }
     }
     Tr3Shared W;
@@ -540,6 +534,32 @@ inline int tgrid(int64_t n) {
     int g = ibh_grid(n, TB);
     return g > 4096 ? 4096 : g;
 }
+// a pointwise kernel template <int ND> over n elements: k2, k3 = its instantiations for nd = 2, 3
+template <class... P, class... A>
+void launch_nd(int nd, int64_t n, void (*k2)(P...), void (*k3)(P...), A... args) {
+    const auto k = nd == 2 ? k2 : k3;
+    hipLaunchKernelGGL(k, dim3(tgrid(n)), dim3(TB), 0, ibh_stream, args...);
+}
+// a block kernel over an all-block 3-D partition: one wavefront per 8^3 block, four per workgroup (wave3), and the five
+// arguments every block kernel starts with
+template <class... P, class... A>
+void launch_blocks3(void (*k)(const BlockDesc3*, const int32_t*, const int32_t*, int32_t, int32_t, P...), const ibh_part* p,
+                    A... args) {
+    const int32_t nwg = (p->nblk + 3) / 4;
+    hipLaunchKernelGGL(k, dim3(nwg), dim3(256), 0, ibh_stream, p->blocks3, p->htab3, p->ftab3, p->nblk, nwg, args...);
+}
+// the dispatch of a fused closure: nothing on an empty partition, cells() on one without block structure (the face-list
+// kernels of ibh_ops.hip; the tuple cell_gradient is the face-list kernel there), blocks() on one made of complete 3-D
+// blocks, the caller's message anywhere else
+template <class Cells, class Blocks>
+int fused_closure(const ibh_part* p, const char* needs, Cells cells, Blocks blocks) {
+    if (p->nc == 0) return 0;
+    if (!fused::has_blocks(p)) return cells();
+    IBH_REQUIRE(fused::all_blocks3(p), needs);
+    blocks();
+    IBH_LAUNCH_CHECK();
+    return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -576,8 +596,7 @@ int ibh_turb_shear_rate(int nd, int64_t n, const float* const* g, float* S) {
     int rc = grad_ptrs(nd, g, &G);
     if (rc) return rc;
     IBH_REQUIRE(S, "ibh_turb_shear_rate: null argument");
-    if (nd == 2) hipLaunchKernelGGL(k_shear<2>, dim3(tgrid(n)), dim3(TB), 0, ibh_stream, n, G, S);
-    else hipLaunchKernelGGL(k_shear<3>, dim3(tgrid(n)), dim3(TB), 0, ibh_stream, n, G, S);
+    launch_nd(nd, n, k_shear<2>, k_shear<3>, n, G, S);
     IBH_LAUNCH_CHECK();
     return 0;
 }
@@ -602,12 +621,7 @@ int ibh_turb_wray_agarwal(int nd, int64_t n, const float* R, const float* S, con
                           float* Sout) {
     if (n <= 0) return 0;
     IBH_REQUIRE(R && S && gradR && gradS && nut && nuR && Sout && (nd == 2 || nd == 3), "ibh_turb_wray_agarwal: bad argument");
-    if (nd == 2)
-        hipLaunchKernelGGL(k_wray_agarwal<2>, dim3(tgrid(n)), dim3(TB), 0, ibh_stream, n, R, S, gradR, ldr, gradS, lds, sigmaR,
-                           C1, kappa, nut, nuR, Sout);
-    else
-        hipLaunchKernelGGL(k_wray_agarwal<3>, dim3(tgrid(n)), dim3(TB), 0, ibh_stream, n, R, S, gradR, ldr, gradS, lds, sigmaR,
-                           C1, kappa, nut, nuR, Sout);
+    launch_nd(nd, n, k_wray_agarwal<2>, k_wray_agarwal<3>, n, R, S, gradR, ldr, gradS, lds, sigmaR, C1, kappa, nut, nuR, Sout);
     IBH_LAUNCH_CHECK();
     return 0;
 }
@@ -616,9 +630,7 @@ int ibh_scalar_transport_blocks(const ibh_part* p, const float* R, const float* 
                                 const float* S, float* out, int* done) {
     *done = 0;
     if (!fused::all_blocks3(p) || !fused::T.transport_blocks) return 0;
-    const int32_t nwg = (p->nblk + 3) / 4;
-    hipLaunchKernelGGL(k_scalar_transport_blocks3, dim3(nwg), dim3(256), 0, ibh_stream, p->blocks3, p->htab3, p->ftab3,
-                       p->nblk, nwg, (uint32_t)p->nc, p->spacing, R, nuR, nu, vel, (uint32_t)ldv, S, out);
+    launch_blocks3(k_scalar_transport_blocks3, p, (uint32_t)p->nc, p->spacing, R, nuR, nu, vel, (uint32_t)ldv, S, out);
     IBH_LAUNCH_CHECK();
     *done = 1;
     return 0;
@@ -639,10 +651,7 @@ int ibh_scalar_transport(const ibh_part* p, const float* R, const float* nuR, fl
         T.vel[d] = vel + (int64_t)d * ldv;
     }
     T.side = p->side;
-    if (p->nd == 2)
-        hipLaunchKernelGGL(k_scalar_transport<2>, dim3(tgrid(p->nc)), dim3(TB), 0, ibh_stream, p->nc, T, R, nuR, nu, S, out);
-    else
-        hipLaunchKernelGGL(k_scalar_transport<3>, dim3(tgrid(p->nc)), dim3(TB), 0, ibh_stream, p->nc, T, R, nuR, nu, S, out);
+    launch_nd(p->nd, p->nc, k_scalar_transport<2>, k_scalar_transport<3>, p->nc, T, R, nuR, nu, S, out);
     IBH_LAUNCH_CHECK();
     return 0;
 }
@@ -652,8 +661,7 @@ int ibh_turb_ducros(int nd, int64_t n, const float* const* g, float* out) {
     int rc = grad_ptrs(nd, g, &G);
     if (rc) return rc;
     IBH_REQUIRE(out, "ibh_turb_ducros: null argument");
-    if (nd == 2) hipLaunchKernelGGL(k_ducros<2>, dim3(tgrid(n)), dim3(TB), 0, ibh_stream, n, G, out);
-    else hipLaunchKernelGGL(k_ducros<3>, dim3(tgrid(n)), dim3(TB), 0, ibh_stream, n, G, out);
+    launch_nd(nd, n, k_ducros<2>, k_ducros<3>, n, G, out);
     IBH_LAUNCH_CHECK();
     return 0;
 }
@@ -668,21 +676,16 @@ int ibh_turb_wale(int64_t n, const float* Delta, const float* const* g, float Cw
     return 0;
 }
 
-// The fused closures: face-list kernels on a partition without block structure (the tuple cell_gradient is the face-list
-// kernel there: ibh_cell_gradient_nd), block kernels on one made of complete blocks
+// The fused closures (fused_closure above): face-list kernels on a partition without block structure, block kernels on one
+// made of complete blocks
 int ibh_shear_rate_of_velocity_grad(ibh_part* p, const float* vel, int64_t ldv, float* S, float* G, int64_t ldg) {
     IBH_REQUIRE(p && vel && S, "ibh_shear_rate_of_velocity: null argument");
     IBH_REQUIRE(!G || ldg >= p->nc, "ibh_shear_rate_of_velocity_grad: ldg < nc");
-    if (p->nc == 0) return 0;
-    if (!fused::has_blocks(p)) return ibh_shear_rate_of_velocity_cells(p, vel, ldv, S, G, ldg);
-    IBH_REQUIRE(fused::all_blocks3(p), "ibh_shear_rate_of_velocity: needs a 3-D partition made of complete blocks or one without "
-                                "block structure (compose cell_gradient and shear_rate otherwise)");
-    FieldPtrs<3> V{{vel, vel + ldv, vel + 2 * ldv}};
-    const int32_t nwg = (p->nblk + 3) / 4;
-    hipLaunchKernelGGL(k_shear_of_velocity3, dim3(nwg), dim3(256), 0, ibh_stream, p->blocks3, p->htab3, p->ftab3, p->nblk, nwg,
-                       V, S, G, (uint32_t)ldg);
-    IBH_LAUNCH_CHECK();
-    return 0;
+    return fused_closure(
+        p, "ibh_shear_rate_of_velocity: needs a 3-D partition made of complete blocks or one without "
+           "block structure (compose cell_gradient and shear_rate otherwise)",
+        [&] { return ibh_shear_rate_of_velocity_cells(p, vel, ldv, S, G, ldg); },
+        [&] { launch_blocks3(k_shear_of_velocity3, p, FieldPtrs<3>{{vel, vel + ldv, vel + 2 * ldv}}, S, G, (uint32_t)ldg); });
 }
 int ibh_shear_rate_of_velocity(ibh_part* p, const float* vel, int64_t ldv, float* S) {
     return ibh_shear_rate_of_velocity_grad(p, vel, ldv, S, nullptr, 0);
@@ -690,19 +693,14 @@ int ibh_shear_rate_of_velocity(ibh_part* p, const float* vel, int64_t ldv, float
 int ibh_wray_agarwal_of(ibh_part* p, const float* R, const float* S, float sigmaR, float C1, float kappa, float* nut,
                         float* nuR, float* Sout) {
     IBH_REQUIRE(p && R && S && nut && nuR && Sout, "ibh_wray_agarwal_of: null argument");
-    if (p->nc == 0) return 0;
-    if (!fused::has_blocks(p)) return ibh_wray_agarwal_of_cells(p, R, S, sigmaR, C1, kappa, nut, nuR, Sout);
-    IBH_REQUIRE(fused::all_blocks3(p), "ibh_wray_agarwal_of: needs a 3-D partition made of complete blocks or one without block "
-                                "structure (compose cell_gradient and Wray_Agarwal otherwise)");
-    FieldPtrs<2> RS{{R, S}};
-    const int32_t nwg = (p->nblk + 3) / 4;
-    hipLaunchKernelGGL(k_wray_agarwal_of3, dim3(nwg), dim3(256), 0, ibh_stream, p->blocks3, p->htab3, p->ftab3, p->nblk, nwg,
-                       RS, sigmaR, C1, kappa, nut, nuR, Sout);
-    IBH_LAUNCH_CHECK();
-    return 0;
+    return fused_closure(
+        p, "ibh_wray_agarwal_of: needs a 3-D partition made of complete blocks or one without block "
+           "structure (compose cell_gradient and Wray_Agarwal otherwise)",
+        [&] { return ibh_wray_agarwal_of_cells(p, R, S, sigmaR, C1, kappa, nut, nuR, Sout); },
+        [&] { launch_blocks3(k_wray_agarwal_of3, p, FieldPtrs<2>{{R, S}}, sigmaR, C1, kappa, nut, nuR, Sout); });
 }
 
-// The LES closure of a velocity field in one launch (dispatch as ibh_shear_rate_of_velocity_grad)
+// The LES closure of a velocity field in one launch
 int ibh_les_of(ibh_part* p, const float* vel, int64_t ldv, const float* Delta, int model, float Cmodel, float* nusgs,
                float* ducros, float* shock, float* S, float* G, int64_t ldg) {
     IBH_REQUIRE(p && vel, "ibh_les_of: null partition or velocity");
@@ -714,41 +712,32 @@ int ibh_les_of(ibh_part* p, const float* vel, int64_t ldv, const float* Delta, i
     IBH_REQUIRE(ldv >= p->nc, "ibh_les_of: ldv < nc");
     IBH_REQUIRE(!G || ldg >= p->nc, "ibh_les_of: ldg < nc");
     IBH_REQUIRE(model != 2 || p->nd == 3, "ibh_les_of: WALE model only implemented for 3D");
-    if (p->nc == 0) return 0;
-    if (!fused::has_blocks(p)) return ibh_les_of_cells(p, vel, ldv, Delta, model, Cmodel, nusgs, ducros, shock, S, G, ldg);
-    IBH_REQUIRE(fused::all_blocks3(p), "ibh_les_of: needs a 3-D partition made of complete blocks or one without block "
-                                "structure (compose cell_gradient and the pointwise closures otherwise)");
-    FieldPtrs<3> V{{vel, vel + ldv, vel + 2 * ldv}};
-    const les_dev::Outputs O{nusgs, ducros, shock, S, G, ldg};
-    const int32_t nwg = (p->nblk + 3) / 4;
-#define LES3_LAUNCH(M_)                                                                                                  \
-    hipLaunchKernelGGL(k_les_of3<M_>, dim3(nwg), dim3(256), 0, ibh_stream, p->blocks3, p->htab3, p->ftab3, p->nblk, nwg, V, \
-                       Delta, Cmodel, O)
-    if (model == 0) LES3_LAUNCH(0);
-    else if (model == 1) LES3_LAUNCH(1);
-    else LES3_LAUNCH(2);
-#undef LES3_LAUNCH
-    IBH_LAUNCH_CHECK();
-    return 0;
+    return fused_closure(
+        p, "ibh_les_of: needs a 3-D partition made of complete blocks or one without block "
+           "structure (compose cell_gradient and the pointwise closures otherwise)",
+        [&] { return ibh_les_of_cells(p, vel, ldv, Delta, model, Cmodel, nusgs, ducros, shock, S, G, ldg); },
+        [&] {
+            launch_blocks3(model == 0 ? k_les_of3<0> : model == 1 ? k_les_of3<1> : k_les_of3<2>, p,
+                           FieldPtrs<3>{{vel, vel + ldv, vel + 2 * ldv}}, Delta, Cmodel,
+                           les_dev::Outputs{nusgs, ducros, shock, S, G, ldg});
+        });
 }
 
-// The right-hand sides of the standard k-epsilon model in one launch (dispatch as ibh_les_of)
+// The right-hand sides of the standard k-epsilon model in one launch
 int ibh_k_epsilon_rhs(ibh_part* p, const float* vel, int64_t ldv, const float* k, const float* eps, float nu,
                       const float* params5, float* rk, float* reps, float* nut, float* S, float* G, int64_t ldg) {
     IBH_REQUIRE(p && vel && k && eps && params5 && rk && reps, "ibh_k_epsilon_rhs: null argument");
     IBH_REQUIRE(ldv >= p->nc, "ibh_k_epsilon_rhs: ldv < nc");
     IBH_REQUIRE(!G || ldg >= p->nc, "ibh_k_epsilon_rhs: ldg < nc");
-    if (p->nc == 0) return 0;
-    IBH_REQUIRE(p->nd == 2 || p->nd == 3, "ibh_k_epsilon_rhs: the partition is neither 2-D nor 3-D");
-    if (!fused::has_blocks(p)) return ibh_k_epsilon_rhs_cells(p, vel, ldv, k, eps, nu, params5, rk, reps, nut, S, G, ldg);
-    IBH_REQUIRE(fused::all_blocks3(p), "ibh_k_epsilon_rhs: needs a 3-D partition made of complete blocks or one without block "
-                                "structure (compose shear_rate_of_velocity, standard_k_epsilon and scalar_transport otherwise)");
-    const tr_dev::KEps P{params5[0], params5[1], params5[2], params5[3], params5[4]};
-    const int32_t nwg = (p->nblk + 3) / 4;
-    hipLaunchKernelGGL(k_k_epsilon_rhs3, dim3(nwg), dim3(256), 0, ibh_stream, p->blocks3, p->htab3, p->ftab3, p->nblk, nwg,
-                       (uint32_t)p->nc, p->spacing, vel, (uint32_t)ldv, k, eps, nu, P, rk, reps, nut, S, G, (uint32_t)ldg);
-    IBH_LAUNCH_CHECK();
-    return 0;
+    IBH_REQUIRE(p->nc == 0 || p->nd == 2 || p->nd == 3, "ibh_k_epsilon_rhs: the partition is neither 2-D nor 3-D");
+    return fused_closure(
+        p, "ibh_k_epsilon_rhs: needs a 3-D partition made of complete blocks or one without block "
+           "structure (compose shear_rate_of_velocity, standard_k_epsilon and scalar_transport otherwise)",
+        [&] { return ibh_k_epsilon_rhs_cells(p, vel, ldv, k, eps, nu, params5, rk, reps, nut, S, G, ldg); },
+        [&] {
+            launch_blocks3(k_k_epsilon_rhs3, p, (uint32_t)p->nc, p->spacing, vel, (uint32_t)ldv, k, eps, nu,
+                           tr_dev::keps_params(params5), rk, reps, nut, S, G, (uint32_t)ldg);
+        });
 }
 
 }  // extern "C"

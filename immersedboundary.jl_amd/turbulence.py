@@ -21,6 +21,21 @@ def _vec(t, n=None):
     return t
 
 
+def _or_value_error(f, *args):
+    """``f(*args)`` -- ``B._field``, ``B._field_inplace`` or ``_vec`` -- with its ``TypeError`` as a ``ValueError``: the
+    fused closures answer every misuse with one exception type."""
+    try:
+        return f(*args)
+    except TypeError as e:
+        raise ValueError(str(e)) from None
+
+
+def _gradient_views(G, nd):
+    """``cell_gradient(part, vel)`` as the fused closures return it: the tuple over the dimensions of ``(nc, nd)`` views of
+    one ``(nc, nd * nd)`` buffer (``d u_i / d x_j`` in column ``nd j + i``)."""
+    return tuple(G[:, j * nd:(j + 1) * nd] for j in range(nd))
+
+
 def _params(*vals):
     return (C.c_float * len(vals))(*[float(v) for v in vals])
 
@@ -135,7 +150,7 @@ def shear_rate_of_velocity(part, vel, gradients=False):
         if gradients:
             G = B.colmajor_empty(part.nc, nd * nd)
             B.call("ibh_shear_rate_of_velocity_grad", part.handle, B._ptr(v), ldv, B._ptr(S), B._ptr(G), part.nc)
-            return S, tuple(G[:, j * nd:(j + 1) * nd] for j in range(nd))
+            return S, _gradient_views(G, nd)
         B.call("ibh_shear_rate_of_velocity", part.handle, B._ptr(v), ldv, B._ptr(S))
         return S
     S = shear_rate([list(B.cell_gradient(part, vel[:, i].contiguous())) for i in range(nd)])
@@ -169,10 +184,7 @@ def les_closure_of(part, vel, Delta=None, model=None, Cs=0.17, Cw=0.325, ducros=
     m = _LES_MODELS[model]
     if not (m or ducros or shock or shear or gradients):
         raise ValueError("les_closure_of: nothing requested")
-    try:
-        v, nd, ldv = B._field(vel, part.nc)
-    except TypeError as e:
-        raise ValueError(str(e)) from None
+    v, nd, ldv = _or_value_error(B._field, vel, part.nc)
     if nd != part.nd:
         raise ValueError("vel must be (nc, nd)")
     if m == 2 and nd != 3:
@@ -180,10 +192,7 @@ def les_closure_of(part, vel, Delta=None, model=None, Cs=0.17, Cw=0.325, ducros=
     if m:
         if Delta is None:
             raise ValueError("les_closure_of: a model needs Delta")
-        try:
-            Delta = _vec(Delta, part.nc)
-        except TypeError as e:
-            raise ValueError(str(e)) from None
+        Delta = _or_value_error(_vec, Delta, part.nc)
     nc = part.nc
     if fused_closures_apply(part):
         out = {}
@@ -201,7 +210,7 @@ def les_closure_of(part, vel, Delta=None, model=None, Cs=0.17, Cw=0.325, ducros=
                B._ptr(out.get("nusgs")), B._ptr(out.get("ducros")), B._ptr(out.get("shock")), B._ptr(out.get("S")),
                B._ptr(G), nc)
         if gradients:
-            out["gradients"] = tuple(G[:, j * nd:(j + 1) * nd] for j in range(nd))
+            out["gradients"] = _gradient_views(G, nd)
         return out
     g = [list(B.cell_gradient(part, v[:, i].contiguous())) for i in range(nd)]
     out = {}
@@ -279,11 +288,8 @@ def k_epsilon_rhs(part, vel, k, eps, nu, Cmu=0.09, sigma_k=1.0, sigma_eps=1.3, C
     array (``Q[:, 2:2 + nd]``, ``Q[:, nd + 2]``): they are read in place; ``out_k`` / ``out_eps`` may be columns of a residual."""
     part = B._part(part)
     nc = part.nc
-    try:
-        v, nd, ldv = B._field(vel, nc)
-        k, eps = _vec(k, nc), _vec(eps, nc)
-    except TypeError as e:
-        raise ValueError(str(e)) from None
+    v, nd, ldv = _or_value_error(B._field, vel, nc)
+    k, eps = _or_value_error(_vec, k, nc), _or_value_error(_vec, eps, nc)
     if nd != part.nd:
         raise ValueError("vel must be (nc, nd)")
     outs = []
@@ -291,10 +297,7 @@ def k_epsilon_rhs(part, vel, k, eps, nu, Cmu=0.09, sigma_k=1.0, sigma_eps=1.3, C
         if o is None:
             o = B.colmajor_empty(nc)
         else:
-            try:
-                o, nvo, _ = B._field_inplace(o, nc, what)
-            except TypeError as e:
-                raise ValueError(str(e)) from None
+            o, nvo, _ = _or_value_error(B._field_inplace, o, nc, what)
             if nvo != 1 or o.ndim != 1:
                 raise ValueError(f"{what} must be a vector")
         outs.append(o)
@@ -311,7 +314,7 @@ def k_epsilon_rhs(part, vel, k, eps, nu, Cmu=0.09, sigma_k=1.0, sigma_eps=1.3, C
         if shear:
             out["S"] = S
         if gradients:
-            out["gradients"] = tuple(G[:, j * nd:(j + 1) * nd] for j in range(nd))
+            out["gradients"] = _gradient_views(G, nd)
         return out
     if gradients:
         S, gV = shear_rate_of_velocity(part, v, gradients=True)

@@ -9,6 +9,9 @@ seeded velocity field, the closure that wants ``nusgs`` (WALE), ``ducros`` and t
   (c) ``composed_components``: ``cell_gradient`` per velocity component (what an LES script written against the reference
       does) and the two pointwise kernels, 3 + 2 launches -- the gradient arrays are the ones the viscous terms take.
 (b) and (c) are code the fused entry does not touch.  All three give the same bits (checked here before anything is timed).
+Three more legs time the other fused closures over ``cell_gradient`` alone, as the calls a V-cycle makes:
+  (d) ``shear``: ``shear_rate_of_velocity(part, vel)``;  (e) ``shear_gradients``: the same with ``gradients=True``;
+  (f) ``wray_agarwal``: ``Wray_Agarwal_of(part, R, S)`` on two seeded positive scalars.
 
 How a figure is taken: after ``--warmup`` eager calls a variant is captured into a HIP graph of ``--batch`` calls on a side
 stream; a timed block is that graph replayed back to back between two device events, as often as a first short block says
@@ -38,7 +41,9 @@ import ibamd  # noqa: E402
 from ibamd import turbulence as T  # noqa: E402
 
 LABELS = {"fused": "(a) fused: `les_closure_of`", "composed_tuple": "(b) composed: tuple `cell_gradient` + 2 pointwise",
-          "composed_components": "(c) composed: `cell_gradient` per component + 2 pointwise"}
+          "composed_components": "(c) composed: `cell_gradient` per component + 2 pointwise",
+          "shear": "(d) `shear_rate_of_velocity`", "shear_gradients": "(e) `shear_rate_of_velocity(gradients=True)`",
+          "wray_agarwal": "(f) `Wray_Agarwal_of`"}
 # per cell, counted from the code (field values only; side tables, spacings and block descriptors are left out on both sides):
 # fused = 12 in (velocity) + 4 (Delta) + 4 + 4 (nusgs, ducros) + 36 (gradients); the least any form moves is the same 60
 # (24 without the gradients).  The composition writes the nine gradients -- on a block partition cell_gradient's sensor
@@ -48,10 +53,11 @@ LABELS = {"fused": "(a) fused: `les_closure_of`", "composed_tuple": "(b) compose
 def bytes_per_cell(blocks):
     grad = 3 * (4 + (16 if blocks else 12))
     return {"fused": 12 + 4 + 8 + 36, "algorithmic_without_gradients": 12 + 4 + 8, "algorithmic_with_gradients": 12 + 4 + 8 + 36,
-            "composed_tuple": grad + (36 + 4 + 4) + (36 + 4), "composed_components": grad + (36 + 4 + 4) + (36 + 4)}
+            "composed_tuple": grad + (36 + 4 + 4) + (36 + 4), "composed_components": grad + (36 + 4 + 4) + (36 + 4),
+            "shear": 12 + 4, "shear_gradients": 12 + 4 + 36, "wray_agarwal": 8 + 12}
 
 
-def variants(dpart, vel, Delta):
+def variants(dpart, vel, Delta, R, S):
     nd = 3
 
     def fused():
@@ -67,7 +73,10 @@ def variants(dpart, vel, Delta):
         g = [list(ibamd.cell_gradient(dpart, vel[:, i])) for i in range(nd)]
         return T.WALE_nuSGS(Delta, g), T.Ducros_sensor(g), g
 
-    return {"fused": fused, "composed_tuple": composed_tuple, "composed_components": composed_components}
+    return {"fused": fused, "composed_tuple": composed_tuple, "composed_components": composed_components,
+            "shear": lambda: T.shear_rate_of_velocity(dpart, vel),
+            "shear_gradients": lambda: T.shear_rate_of_velocity(dpart, vel, gradients=True),
+            "wray_agarwal": lambda: T.Wray_Agarwal_of(dpart, R, S)}
 
 
 class Launcher:
@@ -111,7 +120,9 @@ def time_level(l, part, rounds, batch, warmup, block_seconds):
     vel = ibamd.hip(np.stack([100 * (1 + 0.1 * np.sin(X[:, 1])), 10 * np.cos(X[:, 0] + X[:, 2]), 5 * np.sin(X[:, 0] * X[:, 1])],
                              axis=1).astype(np.float32) + rng.uniform(-1, 1, (nc, 3)).astype(np.float32))
     Delta = ibamd.hip(np.cbrt(np.prod(np.asarray(part.spacing, np.float64), axis=1)).astype(np.float32))
-    fns = variants(dpart, vel, Delta)
+    R = ibamd.hip((1e-4 * (1.5 + np.sin(X[:, 0]) * np.cos(X[:, 2])) * (1 + 0.05 * rng.uniform(-1, 1, nc))).astype(np.float32))
+    S = ibamd.hip((20 * (1.5 + np.cos(X[:, 1] + X[:, 2])) * (1 + 0.05 * rng.uniform(-1, 1, nc))).astype(np.float32))
+    fns = variants(dpart, vel, Delta, R, S)
     ref = fns["fused"]()
     for k in ("composed_tuple", "composed_components"):
         nus, duc, g = fns[k]()

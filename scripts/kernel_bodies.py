@@ -7,9 +7,11 @@ kernels from its code-object metadata.
     scripts/kernel_bodies.py diff --rename '<(\d), true, true, false, true>=<\1, 3, false>' parent.s head.s k_sweep
     scripts/kernel_bodies.py meta head.s k_sweep_quad_euler k_update_euler
 
-`diff`: for every kernel of the FIRST listing whose demangled name contains one of the patterns, the instructions between
-its label and its end label must be the same lines in the second listing (labels are renumbered per function, so local
-labels are compared by their order of appearance).  Exit status 1 on any difference.  `--rename OLD=NEW` (repeatable): a
+`diff`: for every kernel of the FIRST listing -- every name in its amdhsa.kernels metadata, template instantiation or not --
+whose demangled name contains one of the patterns, the instructions between its label and its end label must be the same
+lines in the second listing (labels are renumbered per function, so local
+labels are compared by their order of appearance).  Exit status 1 on any difference, and when no kernel
+matches.  `--rename OLD=NEW` (repeatable): a
 regular expression substitution on the demangled names of the FIRST listing before they are looked up in the second, for a
 kernel whose template parameters were renumbered between the two.  `meta`: .vgpr_count, .sgpr_count,
 .private_segment_fixed_size (scratch bytes), .group_segment_fixed_size (LDS bytes) per matching kernel.
@@ -76,6 +78,7 @@ def main():
         del args[i:i + 2]
     if mode == "diff":
         a, b, pats = bodies(args[0]), bodies(args[1]), args[2:]
+        kernels = meta(args[0])   # (c++filt prints a return type for template instantiations only: no test on `void`)
         dm, dmb = demangle(list(a)), demangle(list(b))
         # a kernel that gained trailing template parameters with `false` defaults (and trailing arguments for them) is the
         # same kernel: matched by its name without them
@@ -88,7 +91,7 @@ def main():
             return d
         bad = n = 0
         for k in sorted(a, key=lambda x: dm[x]):
-            if not any(p in dm[k] for p in pats) or not dm[k].startswith("void"):
+            if k not in kernels or not any(p in dm[k] for p in pats):
                 continue
             n += 1
             kb = byname.get(key(renamed(dm[k])))

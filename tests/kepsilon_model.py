@@ -36,7 +36,7 @@ WAVY_OUTPUTS = ("rk", "reps", "nut")
 # fields: all positive, k in [0.5, 2], eps in [1, 4], smooth plus 5 % seeded noise
 # ---------------------------------------------------------------------------------------------------------------------
 def wavy_velocity(part, seed=21):
-    """``Case.wavy`` of tests/test_gpu_les.py, restated: every gradient component alive, plus noise."""
+    """A velocity field with every gradient component alive, plus noise (``closure_cases.Case.wavy``)."""
     X, nd = part.centers, part.ndims
     rng = np.random.default_rng(seed)
     v = np.stack([np.sin(2 * X[:, (i + 1) % nd]) * np.cos(X[:, i]) + 0.3 * X[:, i] for i in range(nd)], axis=1)

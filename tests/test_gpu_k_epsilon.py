@@ -20,6 +20,8 @@ import torch
 import ibamd
 import kepsilon_model as km
 import les_model as lm
+import closure_cases as cc
+from closure_cases import same
 from conftest import euler_field, oracle_view
 from ibamd import _lib, cfd, closures
 from ibamd import backend as B
@@ -40,17 +42,11 @@ def _print_measured():
             print(f"  {k[0]} | {k[1]} | {k[2]}: {MEASURED[k][0]:.3e} / {MEASURED[k][1]:.3e}")
 
 
-class Case:
-    def __init__(self, part):
-        self.part = part
-        self.dpart = ibamd.to_backend(part, ibamd.hip)
-        self.nd = part.ndims
-        self.nc = part.spacing.shape[0]
-
+class Case(cc.Case):
     def fields(self, seed=21):
         """(vel, k, eps) on the host: the wavy velocity, k in [0.5, 2], eps in [1, 4]."""
         k, eps = km.k_eps_fields(self.part, seed + 1)
-        return km.wavy_velocity(self.part, seed), k, eps
+        return self.wavy(seed), k, eps
 
     def device_fields(self, seed=21):
         return tuple(ibamd.hip(a) for a in self.fields(seed))
@@ -58,15 +54,7 @@ class Case:
 
 @pytest.fixture(scope="module")
 def cases():
-    out = {"octree": Case(lm.one_partition(lm.octree_mesh())), "single": Case(lm.one_partition(lm.single_block_mesh())),
-           "bs4 2d": Case(lm.one_partition(lm.bs4_mesh(2))), "bs4 3d": Case(lm.one_partition(lm.bs4_mesh(3)))}
-    for k in ("octree", "single"):
-        assert T.all_blocks(out[k].dpart), k
-    for k in ("bs4 2d", "bs4 3d"):
-        d = out[k].dpart
-        assert d.info["full_blocks"] == 0 and T.fused_closures_apply(d) and not T.all_blocks(d), k
-        assert 0 < d.info["direct_sides"] < 2 * d.nd * d.nc, k     # some sides take the CSR walk (2:1 interfaces)
-    return out
+    return cc.make_cases(Case)
 
 
 def composition(dpart, vel, k, eps, nu=NU):
@@ -76,12 +64,6 @@ def composition(dpart, vel, k, eps, nu=NU):
     rk = T.scalar_transport(dpart, k, ke["nuk"], vel, nu, ke["Sk"])
     reps = T.scalar_transport(dpart, eps, ke["nueps"], vel, nu, ke["Seps"])
     return dict(rk=rk, reps=reps, nut=ke["nut"], S=S, gradients=gV)
-
-
-def same(a, b):
-    """Bit for bit where neither is NaN, and the same NaN pattern."""
-    na, nb = torch.isnan(a), torch.isnan(b)
-    return torch.equal(na, nb) and torch.equal(torch.where(na, torch.zeros_like(a), a), torch.where(nb, torch.zeros_like(b), b))
 
 
 def check(c, got, comp, keys, what):
@@ -124,14 +106,7 @@ def test_all_block_partitions_are_the_composition(cases, mesh):
     """Wave per 8^3 block (``k_k_epsilon_rhs3``): the octree has SAME, MIRROR, COARSE and FINE sides and a block count that
     is no multiple of the four waves of a workgroup; the single block has six mirror sides."""
     c = cases[mesh]
-    i = c.dpart.info
-    nblk = i["full_blocks"]
-    assert nblk * 512 == c.nc
-    if mesh == "octree":
-        assert nblk % 4 != 0 and nblk > 4, nblk                  # the last workgroup has idle waves
-        assert i["sides_fine"] > 0 and i["sides_coarse"] > 0
-    else:
-        assert nblk == 1
+    cc.assert_block_case(c, mesh)
     assert_is_the_composition(c, *c.device_fields(), mesh)
 
 
@@ -161,13 +136,7 @@ def test_nan_has_the_compositions_pattern(cases, mesh, where):
 def test_past_the_grid_cap():
     """A face-list partition of just over 4096 * 256 cells (the mesh of tests/test_gpu_les.py): the launch is capped at 4096
     workgroups, so some threads take a second cell."""
-    from ibamd import Ball, Mesh
-    msh = Mesh(f32([0, 0]), f32([1, 1]), block_size=4,
-               refinement_regions=[(Ball(np.array([0.5, 0.5]), 2.0), f32(1 / 1024)),
-                                   (Ball(np.array([0.3, 0.3]), 0.004), f32(1 / 2048))])
-    c = Case(lm.one_partition(msh))
-    assert 4096 * 256 < c.nc < 4096 * 256 + 8192
-    assert c.dpart.info["full_blocks"] == 0 and T.fused_closures_apply(c.dpart)
+    c = cc.grid_cap_case(Case)
     vel, k, eps = c.device_fields(2)
     comp = composition(c.dpart, vel, k, eps)
     got = T.k_epsilon_rhs(c.dpart, vel, k, eps, NU, shear=True)
@@ -198,12 +167,7 @@ def test_graph_replay(cases, mesh):
 
 def test_partition_with_skirt_fragments_composes():
     """Two partitions of the octree: blocks and skirt fragments, not all-block.  The wrapper composes; the C entry says so."""
-    msh = lm.octree_mesh()
-    n = len(msh)
-    dom = ibamd.Domain(msh, max_partition_size=-(-(-(-n // 2)) // 512) * 512, boundaries=False)
-    assert len(dom.partitions) == 2
-    c = Case(dom.partitions[1])
-    assert not T.fused_closures_apply(c.dpart) and c.dpart.info["full_blocks"] > 0
+    c = cc.skirt_case(Case)
     vel, k, eps = c.device_fields()
     assert_is_the_composition(c, vel, k, eps, "two partitions")
     rk, reps = B.colmajor_empty(c.nc), B.colmajor_empty(c.nc)
@@ -362,12 +326,7 @@ def _operator_form(dpart, Q, nu, fluid):
 def test_navier_stokes_k_epsilon_residual(cases, adv_mesh, mesh):
     """Everything behind the Euler sweep is the operator-by-operator form bit for bit.  The 2-D mesh has 8^2 blocks: the
     composed path."""
-    if mesh == "octree":
-        c = cases[mesh]
-    else:
-        (p,) = ibamd.Domain(adv_mesh, hypercube_families=[], boundaries=False, max_partition_size=10 ** 9).partitions.values()
-        c = Case(p)
-        assert not T.fused_closures_apply(c.dpart)
+    c = cases[mesh] if mesh == "octree" else cc.adv2d_case(Case, adv_mesh)
     fluid = cfd.Fluid()
     vel_h, k_h, eps_h = c.fields(6)
     Ph = euler_field(c.part.centers)

@@ -16,9 +16,11 @@ import numpy as np
 import pytest
 import torch
 
+import closure_cases as cc
 import ibamd
 import les_model as lm
 import percell as pc
+from closure_cases import same
 from conftest import euler_field, oracle_view
 from ibamd import _lib, cfd, closures
 from ibamd import backend as B
@@ -38,34 +40,16 @@ def _print_measured():
             print(f"  {k[0]} | {k[1]}: {MEASURED[k][0]:.3e} / {MEASURED[k][1]:.3e}")
 
 
-class Case:
+class Case(cc.Case):
     def __init__(self, part):
-        self.part = part
-        self.dpart = ibamd.to_backend(part, ibamd.hip)
-        self.nd = part.ndims
-        self.nc = part.spacing.shape[0]
+        super().__init__(part)
         self.Delta_h = lm.filter_width(part)
         self.Delta = ibamd.hip(self.Delta_h)
-
-    def wavy(self, seed=21):
-        """A velocity field with every gradient component alive, plus noise."""
-        X, nd = self.part.centers, self.nd
-        rng = np.random.default_rng(seed)
-        v = np.stack([np.sin(2 * X[:, (i + 1) % nd]) * np.cos(X[:, i]) + 0.3 * X[:, i] for i in range(nd)], axis=1)
-        return (v + 0.05 * rng.standard_normal((self.nc, nd))).astype(f32)
 
 
 @pytest.fixture(scope="module")
 def cases():
-    out = {"octree": Case(lm.one_partition(lm.octree_mesh())), "single": Case(lm.one_partition(lm.single_block_mesh())),
-           "bs4 2d": Case(lm.one_partition(lm.bs4_mesh(2))), "bs4 3d": Case(lm.one_partition(lm.bs4_mesh(3)))}
-    for k in ("octree", "single"):
-        assert T.all_blocks(out[k].dpart), k
-    for k in ("bs4 2d", "bs4 3d"):
-        d = out[k].dpart
-        assert d.info["full_blocks"] == 0 and T.fused_closures_apply(d) and not T.all_blocks(d), k
-        assert 0 < d.info["direct_sides"] < 2 * d.nd * d.nc, k     # some sides take the CSR walk (2:1 interfaces)
-    return out
+    return cc.make_cases(Case)
 
 
 def composition(dpart, vel, Delta):
@@ -78,12 +62,6 @@ def composition(dpart, vel, Delta):
     if nd == 3:
         out["wale"] = T.WALE_nuSGS(Delta, g, Cw=0.325)
     return out
-
-
-def same(a, b):
-    """Bit for bit where neither is NaN, and the same NaN pattern."""
-    na, nb = torch.isnan(a), torch.isnan(b)
-    return torch.equal(na, nb) and torch.equal(torch.where(na, torch.zeros_like(a), a), torch.where(nb, torch.zeros_like(b), b))
 
 
 def assert_is_the_composition(c, vel, what=""):
@@ -127,14 +105,7 @@ def test_all_block_partitions_are_the_composition(cases, mesh):
     """Wave per 8^3 block (``k_les_of3``): the octree has SAME, MIRROR, COARSE and FINE sides and a block count that is no
     multiple of the four waves of a workgroup; the single block has six mirror sides."""
     c = cases[mesh]
-    i = c.dpart.info
-    nblk = i["full_blocks"]
-    assert nblk * 512 == c.nc
-    if mesh == "octree":
-        assert nblk % 4 != 0 and nblk > 4, nblk                  # the last workgroup has idle waves
-        assert i["sides_fine"] > 0 and i["sides_coarse"] > 0
-    else:
-        assert nblk == 1
+    cc.assert_block_case(c, mesh)
     assert_is_the_composition(c, ibamd.hip(c.wavy()), mesh)
 
 
@@ -162,12 +133,7 @@ def test_misuse_raises_value_error(cases):
 
 def test_partition_with_skirt_fragments_composes():
     """Two partitions of the octree: blocks and skirt fragments, not all-block.  The wrapper composes; the C entry says so."""
-    msh = lm.octree_mesh()
-    n = len(msh)
-    dom = ibamd.Domain(msh, max_partition_size=-(-(-(-n // 2)) // 512) * 512, boundaries=False)
-    assert len(dom.partitions) == 2
-    c = Case(dom.partitions[1])
-    assert not T.fused_closures_apply(c.dpart) and c.dpart.info["full_blocks"] > 0
+    c = cc.skirt_case(Case)
     vel = ibamd.hip(c.wavy())
     assert_is_the_composition(c, vel, "two partitions")
     S = B.colmajor_empty(c.nc)
@@ -175,6 +141,47 @@ def test_partition_with_skirt_fragments_composes():
     lib = _lib.load()
     rc = lib.ibh_les_of(c.dpart.handle, B._ptr(vel), c.nc, None, 0, 0.0, None, None, None, B._ptr(S), None, 0)
     assert rc != 0 and b"compose" in lib.ibh_last_error(), lib.ibh_last_error()
+
+
+@pytest.mark.parametrize("field", ["wavy", "nan", "view"])
+@pytest.mark.parametrize("mesh", ["octree", "single", "bs4 2d", "bs4 3d"])
+def test_shear_rate_of_velocity_is_the_closure_without_a_model(cases, mesh, field):
+    """``shear_rate_of_velocity(part, vel[, gradients=True])`` is ``les_closure_of(part, vel, shear=True[, gradients=True])``
+    bit for bit with the same NaN pattern -- a cross-check: the first has kernels of its own (``k_shear_of_velocity3``,
+    ``k_shear_of_velocity_cells``) over the helpers of ``k_les_of3<MODEL_NONE>`` / ``k_les_of_cells``.  ``"view"``: the
+    velocity is ``P[:, 2:2 + nd]`` of a wider state and both C entries write ``G`` into a buffer with ``ldg > nc``."""
+    c = cases[mesh]
+    nd, nc = c.nd, c.nc
+    v = c.wavy(12)
+    if field == "nan":
+        v[nc // 3, nd - 1] = np.nan
+    P = ibamd.hip(np.concatenate([np.full((nc, 2), 1.5, f32), v, np.full((nc, 1), -2.5, f32)], axis=1))
+    P0 = P.clone()
+    vel = P[:, 2:2 + nd] if field == "view" else ibamd.hip(v)
+    S = T.shear_rate_of_velocity(c.dpart, vel)
+    S2, G = T.shear_rate_of_velocity(c.dpart, vel, gradients=True)
+    les = T.les_closure_of(c.dpart, vel, shear=True, gradients=True)
+    assert same(S, les["S"]) and same(S2, les["S"]) and same(T.les_closure_of(c.dpart, vel, shear=True)["S"], S)
+    n_nan = int(torch.isnan(S).sum())
+    assert (0 < n_nan < nc) if field == "nan" else n_nan == 0
+    assert float(torch.nan_to_num(S).abs().max()) > 0 and len(G) == len(les["gradients"]) == nd
+    for j in range(nd):
+        assert G[j].shape == (nc, nd) and same(G[j], les["gradients"][j]), j
+    if field != "view":
+        return
+    vp, _, ldv = B._field(vel, nc)
+    assert vp.data_ptr() == P.data_ptr() + 8 * nc and ldv == nc     # no copy was made
+    ldg = nc + 19
+    pad = torch.full((2, nd * nd + 2, ldg), -7.25, dtype=torch.float32, device=P.device)    # row r = column r of a parent
+    out = [B.colmajor_empty(nc), B.colmajor_empty(nc)]
+    B._stream()
+    B.call("ibh_shear_rate_of_velocity_grad", c.dpart.handle, B._ptr(vp), ldv, B._ptr(out[0]), C.c_void_p(pad[0, 1].data_ptr()), ldg)
+    B.call("ibh_les_of", c.dpart.handle, B._ptr(vp), ldv, None, 0, C.c_float(0.0), None, None, None, B._ptr(out[1]),
+           C.c_void_p(pad[1, 1].data_ptr()), ldg)
+    assert torch.equal(P, P0) and same(out[0], S) and same(out[1], S) and torch.equal(pad[0], pad[1])
+    assert bool((pad[:, 0] == -7.25).all() and (pad[:, -1] == -7.25).all() and (pad[:, :, nc:] == -7.25).all())
+    for j in range(nd):
+        assert same(pad[0, 1 + nd * j:1 + nd * (j + 1), :nc].T, G[j]), j
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -255,13 +262,7 @@ def test_nan_velocity_has_the_compositions_pattern(cases, mesh):
 def test_past_the_grid_cap():
     """A face-list partition of just over 4096 * 256 cells: the launch is capped at 4096 workgroups, so some threads take a
     second cell (``k_jst3`` and ``k_shock`` once had no loop: their last elements were never written)."""
-    from ibamd import Ball, Mesh
-    msh = Mesh(f32([0, 0]), f32([1, 1]), block_size=4,
-               refinement_regions=[(Ball(np.array([0.5, 0.5]), 2.0), f32(1 / 1024)),
-                                   (Ball(np.array([0.3, 0.3]), 0.004), f32(1 / 2048))])
-    c = Case(lm.one_partition(msh))
-    assert 4096 * 256 < c.nc < 4096 * 256 + 8192
-    assert c.dpart.info["full_blocks"] == 0 and T.fused_closures_apply(c.dpart)
+    c = cc.grid_cap_case(Case)
     vel = ibamd.hip(c.wavy(2))
     comp = composition(c.dpart, vel, c.Delta)
     got = T.les_closure_of(c.dpart, vel, ducros=True, shear=True)
@@ -311,12 +312,7 @@ def test_navier_stokes_les_residual(cases, adv_mesh, mesh, model):
     """Everything behind the Euler sweep is the operator-by-operator form bit for bit; the tuned sweep's Euler rows are held
     to ``percell.BOUND_CLOSURE`` per cell against the literal form.  The 2-D mesh has 8^2 blocks: the composed path."""
     import euler_sensor_model as esm
-    if mesh == "octree":
-        c = cases[mesh]
-    else:
-        (p,) = ibamd.Domain(adv_mesh, hypercube_families=[], boundaries=False, max_partition_size=10 ** 9).partitions.values()
-        c = Case(p)
-        assert not T.fused_closures_apply(c.dpart)
+    c = cases[mesh] if mesh == "octree" else cc.adv2d_case(Case, adv_mesh)
     fluid = cfd.Fluid()
     Ph = euler_field(c.part.centers)
     Ph[:, 2:] = 30 * c.wavy(6)
