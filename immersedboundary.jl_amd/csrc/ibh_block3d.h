@@ -4,9 +4,13 @@
 // thread, the low-side block faces by 192 otherwise idle threads) and exchanged through LDS.
 // Sides: SAME / MIRROR / 2:1 COARSE; sides facing finer blocks are GENERAL (face-list body), so every
 // boundary cell has exactly one face.  LDS field layout: [tile 512 | halo 384], halo slot = side*64 + t.
+// Holds: pass B of the two-kernel sweeps (passB_adv, passB_euler) and the two thread-per-cell single kernels (sweep_adv,
+// sweep_euler: the `quad_variant` 512 A/B forms) over one slot frame (Slot3 ... halo_sensor).  Pass A of the two-kernel
+// sweeps is a wave-per-block form and lives in ibh_wave3d.h.
 #pragma once
 #include "ibh_block2d.h"
 #include "ibh_sweep2d.h"
+#include "ibh_wave3d.h"
 
 namespace blk3 {
 
@@ -234,6 +238,125 @@ __device__ __forceinline__ float jst_ratio(float g, float a, float rh) {
     return fmaf(fabsf(g), rh, 1e-7f) * __builtin_amdgcn_rcpf(fmaf(a, rh, 1e-7f));
 }
 
+// ---- the slot frame of the two single kernels (sweep_adv, sweep_euler).  Wavefront s (0..5) owns side s; its lane t holds
+// the halo cell(s) behind boundary cell t.  What follows is field-agnostic: the scalar u, or the pressure P[0].
+struct Slot3 {
+    int sw, ty, dnh;    // side = wavefront index (6, 7: the two idle wavefronts), its type, its normal dim (3: idle)
+    float qs;           // the side's weight q
+    bool low, slotw, isC, isF, mirror, rimw;   // rimw: this lane also holds a rim cell of the side's plane
+    int sd, sa, sb;     // strides of the normal and the two tangential dims in the tile
+    int t, t1, t2;      // the slot's boundary cell in the side's tangential coordinates
+    int n;              // halo cells along the side
+    int dd;             // from a halo cell to the cell one step deeper
+    int nrm, pos;       // the side's layer of the tile; the slot's boundary cell
+    int cm;             // 1: a coarse halo cell spans 2 x 2 slots
+    float rn, ra, rb;   // reciprocal widths of the halo cell along the normal and the two tangential dims
+};
+__device__ __forceinline__ Slot3 slot_frame(const BlockDesc3& bb, int tid) {
+    Slot3 sl;
+    sl.sw = __builtin_amdgcn_readfirstlane(tid >> 6);
+    sl.ty = SIDE_MIRROR;
+    sl.qs = 0.5f;
+    switch (sl.sw) {  // scalar registers, no dynamic indexing
+        case 0: sl.ty = bb.type[0]; sl.qs = bb.q[0]; break;
+        case 1: sl.ty = bb.type[1]; sl.qs = bb.q[1]; break;
+        case 2: sl.ty = bb.type[2]; sl.qs = bb.q[2]; break;
+        case 3: sl.ty = bb.type[3]; sl.qs = bb.q[3]; break;
+        case 4: sl.ty = bb.type[4]; sl.qs = bb.q[4]; break;
+        case 5: sl.ty = bb.type[5]; sl.qs = bb.q[5]; break;
+        default: break;
+    }
+    sl.dnh = sl.sw >> 1;
+    sl.low = (sl.sw & 1) == 0;
+    sl.slotw = sl.sw < 6;
+    sl.isC = sl.ty == SIDE_COARSE;
+    sl.isF = sl.ty == SIDE_FINE;
+    sl.mirror = sl.ty == SIDE_MIRROR;
+    sl.sd = sl.dnh == 0 ? 1 : sl.dnh == 1 ? 8 : 64;
+    sl.sa = sl.dnh == 0 ? 8 : 1;
+    sl.sb = sl.dnh == 2 ? 8 : 64;
+    sl.t = tid & 63;
+    sl.t1 = sl.t & 7;
+    sl.t2 = sl.t >> 3;
+    sl.n = sl.isF ? 16 : 8;
+    sl.rimw = sl.slotw && sl.t < 4 * sl.n;
+    sl.dd = sl.mirror ? 0 : (sl.low ? -sl.sd : sl.sd);
+    sl.nrm = (sl.low ? 0 : 7) * sl.sd;
+    sl.pos = sl.nrm + sl.t1 * sl.sa + sl.t2 * sl.sb;
+    sl.cm = sl.isC ? 1 : 0;
+    // reciprocal widths of the halo cell (selects, not branches: the block's first loads come right after)
+    const float irt = sl.isC ? 0.5f : sl.isF ? 2.0f : 1.0f;  // h / h_halo
+    const float rh0 = bb.rh[0], rh1 = bb.rh[1], rh2 = bb.rh[2];
+    sl.rn = (sl.dnh == 0 ? rh0 : sl.dnh == 1 ? rh1 : rh2) * irt;
+    sl.ra = (sl.dnh == 0 ? rh1 : rh0) * irt;
+    sl.rb = (sl.dnh == 2 ? rh1 : rh2) * irt;
+    return sl;
+}
+// the rim cell of this lane: one cell, or the four finer cells behind the rim position (issued with the block's other
+// loads, before anything is staged)
+__device__ __forceinline__ void rim_load(const Slot3& sl, const int32_t* __restrict__ rtab,
+                                         const int32_t* __restrict__ r4tab, const float* __restrict__ u, float (&rv)[4]) {
+    rv[0] = rv[1] = rv[2] = rv[3] = 0.0f;
+    if (sl.rimw) {
+        const int32_t rid = rtab[sl.sw * 64 + sl.t];
+        if (rid >= 0) {
+            rv[0] = rv[1] = rv[2] = rv[3] = ldg(u, (uint32_t)rid);
+        } else {
+            const int32_t* r4 = r4tab + (size_t)(-rid - 1) * 4;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) rv[k] = ldg(u, (uint32_t)r4[k]);
+        }
+    }
+}
+// stage the side's plane pl: the slot's halo cell(s) hv (four chunks on a FINE side) and the lane's rim cell.  Returns
+// the plane position of the halo cell next to that rim cell.  Wavefronts with a slot only.
+__device__ __forceinline__ int plane_stage(const Slot3& sl, float* pl, const float (&hv)[4], const float (&rv)[4]) {
+    int radj = 0;
+    if (sl.isF) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) pl[(2 * sl.t1 + (k & 1) + 1) + 18 * (2 * sl.t2 + (k >> 1) + 1)] = hv[k];
+    } else {
+        pl[(sl.t1 + 1) + 18 * (sl.t2 + 1)] = hv[0];
+    }
+    if (sl.rimw) {
+        const int n = sl.n, r = sl.isF ? sl.t >> 4 : sl.t >> 3, i = sl.isF ? sl.t & 15 : sl.t & 7;
+        const int p1 = r == 0 ? 0 : r == 1 ? n + 1 : i + 1, p2 = r == 2 ? 0 : r == 3 ? n + 1 : i + 1;
+        const int a1 = r == 0 ? 1 : r == 1 ? n : i + 1, a2 = r == 2 ? 1 : r == 3 ? n : i + 1;
+        pl[p1 + 18 * p2] = 0.25f * ((rv[0] + rv[1]) + (rv[2] + rv[3]));
+        radj = a1 + 18 * a2;
+    }
+    return radj;
+}
+// planeA: mean |difference| of the lane's rim cell(s) to the halo cell next to them (after the barrier behind plane_stage)
+__device__ __forceinline__ void plane_rim_abs(const Slot3& sl, const float* pl, int radj, const float (&rv)[4],
+                                              float* planeA) {
+    if (sl.rimw) {
+        const float ha = pl[radj];
+        planeA[sl.sw * 64 + sl.t] =
+            0.25f * ((fabsf(rv[0] - ha) + fabsf(rv[1] - ha)) + (fabsf(rv[2] - ha) + fabsf(rv[3] - ha)));
+    }
+}
+// JST sensor of the halo cell, chunk k of the slot: value h, the value one step deeper hde, the block's cells in front of
+// it (their mean, and the four values m4), its lateral neighbours from the side's plane pl and rim pA
+__device__ __forceinline__ float halo_sensor(const Slot3& sl, int k, float h, float hde, float mean, const float (&m4)[4],
+                                             const float* pl, const float* pA) {
+    const int n = sl.n, cm = sl.cm;
+    const float din = mean - h;
+    const float ain = 0.25f * ((fabsf(m4[0] - h) + fabsf(m4[1] - h)) + (fabsf(m4[2] - h) + fabsf(m4[3] - h)));
+    const float dde = hde - h;
+    // position in the plane; a coarse cell spans 2 x 2 slots
+    const int f1 = sl.isF ? 2 * sl.t1 + (k & 1) : sl.t1, f2 = sl.isF ? 2 * sl.t2 + (k >> 1) : sl.t2;
+    const int fa = f1 & ~cm, fb = f1 | cm, ga = f2 & ~cm, gb = f2 | cm;
+    const float ea0 = pl[fa + 18 * (f2 + 1)] - h, ea1 = pl[fb + 2 + 18 * (f2 + 1)] - h;
+    const float eb0 = pl[(f1 + 1) + 18 * ga] - h, eb1 = pl[(f1 + 1) + 18 * (gb + 2)] - h;
+    const float aa0 = fa == 0 ? pA[f2] : fabsf(ea0), aa1 = fb == n - 1 ? pA[n + f2] : fabsf(ea1);
+    const float ab0 = ga == 0 ? pA[2 * n + f1] : fabsf(eb0), ab1 = gb == n - 1 ? pA[3 * n + f1] : fabsf(eb1);
+    float dh = jst_ratio(din + dde, ain + fabsf(dde), sl.rn);
+    dh = fmaxf(dh, jst_ratio(ea0 + ea1, aa0 + aa1, sl.ra));
+    dh = fmaxf(dh, jst_ratio(eb0 + eb1, ab0 + ab1, sl.rb));
+    return fmaxf(dh, 1e-7f);
+}
+
 __device__ __forceinline__ void sweep_adv(const BlockDesc3* __restrict__ blocks, const int32_t* __restrict__ htab,
                                           const int32_t* __restrict__ ftab, const int32_t* __restrict__ rtab,
                                           const int32_t* __restrict__ r4tab, int32_t blk, const float* __restrict__ u,
@@ -250,25 +373,10 @@ __device__ __forceinline__ void sweep_adv(const BlockDesc3* __restrict__ blocks,
     float* plane = FF + 1536;         // [6][18 x 18]
     float* planeA = plane + 6 * 324;  // [6][64]  rim neighbours: mean |difference| to the halo cell next to them
     // ---- this thread's halo slot: side = wavefront index, boundary cell t
-    const int sw = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int ty = SIDE_MIRROR;
-    float qs = 0.5f;
-    switch (sw) {  // scalar registers, no dynamic indexing
-        case 0: ty = bb.type[0]; qs = bb.q[0]; break;
-        case 1: ty = bb.type[1]; qs = bb.q[1]; break;
-        case 2: ty = bb.type[2]; qs = bb.q[2]; break;
-        case 3: ty = bb.type[3]; qs = bb.q[3]; break;
-        case 4: ty = bb.type[4]; qs = bb.q[4]; break;
-        case 5: ty = bb.type[5]; qs = bb.q[5]; break;
-        default: break;
-    }
-    const int dnh = sw >> 1;                         // normal dim of the slot's side (3: the two idle wavefronts)
-    const bool low = (sw & 1) == 0, slotw = sw < 6;
-    const bool isC = ty == SIDE_COARSE, isF = ty == SIDE_FINE, mirror = ty == SIDE_MIRROR;
-    const int sd = dnh == 0 ? 1 : dnh == 1 ? 8 : 64, sa = dnh == 0 ? 8 : 1, sb = dnh == 2 ? 8 : 64;
-    const int t = tid & 63, t1 = t & 7, t2 = t >> 3;
-    const int n = isF ? 16 : 8;                      // halo cells along the side
-    const int dd = mirror ? 0 : (low ? -sd : sd);    // deeper cell of a halo cell
+    const Slot3 sl = slot_frame(bb, tid);
+    const int sw = sl.sw, dnh = sl.dnh, t = sl.t;
+    const bool low = sl.low, slotw = sl.slotw, isF = sl.isF, mirror = sl.mirror;
+    const float qs = sl.qs;
     const float* Cn = C + (size_t)(dnh < 3 ? dnh : 0) * ldc;
     // ---- loads: own cell; halo chunk(s): value, deeper value, normal velocity; rim cells
     const float uc = ldg(u, c);
@@ -279,7 +387,7 @@ __device__ __forceinline__ void sweep_adv(const BlockDesc3* __restrict__ blocks,
     {
         const uint32_t h0 = halo_cell3(bb, htab, blk, tid);
         hu[0] = ldg(u, h0);
-        hde[0] = ldg(u, (uint32_t)((int)h0 + dd));
+        hde[0] = ldg(u, (uint32_t)((int)h0 + sl.dd));
         hc[0] = ldg(Cn, h0);
 #pragma unroll
         for (int k = 1; k < 4; ++k) {
@@ -293,23 +401,13 @@ __device__ __forceinline__ void sweep_adv(const BlockDesc3* __restrict__ blocks,
             for (int k = 1; k < 4; ++k) {
                 const uint32_t hk = (uint32_t)ft[k - 1];
                 hu[k] = ldg(u, hk);
-                hde[k] = ldg(u, (uint32_t)((int)hk + dd));
+                hde[k] = ldg(u, (uint32_t)((int)hk + sl.dd));
                 hc[k] = ldg(Cn, hk);
             }
         }
     }
-    float rv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    const bool rimw = slotw && t < 4 * n;
-    if (rimw) {
-        const int32_t rid = rtab[sw * 64 + t];
-        if (rid >= 0) {
-            rv[0] = rv[1] = rv[2] = rv[3] = ldg(u, (uint32_t)rid);
-        } else {
-            const int32_t* r4 = r4tab + (size_t)(-rid - 1) * 4;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) rv[k] = ldg(u, (uint32_t)r4[k]);
-        }
-    }
+    float rv[4];
+    rim_load(sl, rtab, r4tab, u, rv);
     // ---- stage
     fU[tid] = uc;
 #pragma unroll
@@ -318,26 +416,11 @@ __device__ __forceinline__ void sweep_adv(const BlockDesc3* __restrict__ blocks,
     int radj = 0;  // plane position of the halo cell next to this lane's rim cell
     if (slotw) {
         fU[512 + tid] = hu[0];
-        if (isF) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) pl[(2 * t1 + (k & 1) + 1) + 18 * (2 * t2 + (k >> 1) + 1)] = hu[k];
-        } else {
-            pl[(t1 + 1) + 18 * (t2 + 1)] = hu[0];
-        }
-        if (rimw) {
-            const int r = isF ? t >> 4 : t >> 3, i = isF ? t & 15 : t & 7;
-            const int p1 = r == 0 ? 0 : r == 1 ? n + 1 : i + 1, p2 = r == 2 ? 0 : r == 3 ? n + 1 : i + 1;
-            const int a1 = r == 0 ? 1 : r == 1 ? n : i + 1, a2 = r == 2 ? 1 : r == 3 ? n : i + 1;
-            pl[p1 + 18 * p2] = 0.25f * ((rv[0] + rv[1]) + (rv[2] + rv[3]));
-            radj = a1 + 18 * a2;
-        }
+        radj = plane_stage(sl, pl, hu, rv);
     }
     const Lane3 L = lane_info(bb, tid);
     __syncthreads();
-    if (rimw) {
-        const float ha = pl[radj];
-        planeA[sw * 64 + t] = 0.25f * ((fabsf(rv[0] - ha) + fabsf(rv[1] - ha)) + (fabsf(rv[2] - ha) + fabsf(rv[3] - ha)));
-    }
+    plane_rim_abs(sl, pl, radj, rv, planeA);
     // ---- own cells: undivided slopes S = fr - fl and the sensor
     float S[3], D = 1e-7f;
     const int tt[3] = {L.j + 8 * L.k, L.i + 8 * L.k, L.i + 8 * L.j};
@@ -367,46 +450,22 @@ __device__ __forceinline__ void sweep_adv(const BlockDesc3* __restrict__ blocks,
     fD[tid] = D;
     // ---- halo cells of this thread's slot: slope along the normal, sensor
     float Sh[4], Dh[4];
-    const int nrm = (low ? 0 : 7) * sd;
-    const int pos = nrm + t1 * sa + t2 * sb;  // the slot's boundary cell
+    const int pos = sl.pos;  // the slot's boundary cell
     if (slotw) {
         blk2::wave_lds_sync();  // planeA of this side (written by this wavefront)
         // the block's cells behind the halo cell: one, or the 2 x 2 group in front of a coarse cell
-        const int cm = isC ? 1 : 0;
-        const int pa = t1 & ~cm, pb = t1 | cm, qa = t2 & ~cm, qb = t2 | cm;
-        const float m0 = fU[nrm + pa * sa + qa * sb], m1 = fU[nrm + pb * sa + qa * sb];
-        const float m2 = fU[nrm + pa * sa + qb * sb], m3 = fU[nrm + pb * sa + qb * sb];
-        const float irt = isC ? 0.5f : isF ? 2.0f : 1.0f;  // h / h_halo
-        float rn, ra, rb;  // reciprocal widths of the halo cell along the normal and the two tangential dims
-        if (dnh == 0) { rn = bb.rh[0]; ra = bb.rh[1]; rb = bb.rh[2]; }
-        else if (dnh == 1) { rn = bb.rh[1]; ra = bb.rh[0]; rb = bb.rh[2]; }
-        else { rn = bb.rh[2]; ra = bb.rh[0]; rb = bb.rh[1]; }
-        rn *= irt;
-        ra *= irt;
-        rb *= irt;
-        const float* pA = planeA + sw * 64;
+        const int pa = sl.t1 & ~sl.cm, pb = sl.t1 | sl.cm, qa = sl.t2 & ~sl.cm, qb = sl.t2 | sl.cm;
+        const float m4[4] = {fU[sl.nrm + pa * sl.sa + qa * sl.sb], fU[sl.nrm + pb * sl.sa + qa * sl.sb],
+                             fU[sl.nrm + pa * sl.sa + qb * sl.sb], fU[sl.nrm + pb * sl.sa + qb * sl.sb]};
+        const float mean = 0.25f * ((m4[0] + m4[1]) + (m4[2] + m4[3]));
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             Sh[k] = 0.0f;
             Dh[k] = 1e-7f;
             if (k == 0 || isF) {  // wave-uniform
-                const float h = hu[k];
-                const float din = 0.25f * ((m0 + m1) + (m2 + m3)) - h;
-                const float ain = 0.25f * ((fabsf(m0 - h) + fabsf(m1 - h)) + (fabsf(m2 - h) + fabsf(m3 - h)));
-                const float dde = hde[k] - h;
-                const float x = (1.0f - qs) * din - 0.5f * dde;
+                const float x = (1.0f - qs) * (mean - hu[k]) - 0.5f * (hde[k] - hu[k]);
                 Sh[k] = low ? x : -x;
-                // position in the plane; a coarse cell spans 2 x 2 slots
-                const int f1 = isF ? 2 * t1 + (k & 1) : t1, f2 = isF ? 2 * t2 + (k >> 1) : t2;
-                const int fa = f1 & ~cm, fb = f1 | cm, ga = f2 & ~cm, gb = f2 | cm;
-                const float ea0 = pl[fa + 18 * (f2 + 1)] - h, ea1 = pl[fb + 2 + 18 * (f2 + 1)] - h;
-                const float eb0 = pl[(f1 + 1) + 18 * ga] - h, eb1 = pl[(f1 + 1) + 18 * (gb + 2)] - h;
-                const float aa0 = fa == 0 ? pA[f2] : fabsf(ea0), aa1 = fb == n - 1 ? pA[n + f2] : fabsf(ea1);
-                const float ab0 = ga == 0 ? pA[2 * n + f1] : fabsf(eb0), ab1 = gb == n - 1 ? pA[3 * n + f1] : fabsf(eb1);
-                float dh = jst_ratio(din + dde, ain + fabsf(dde), rn);
-                dh = fmaxf(dh, jst_ratio(ea0 + ea1, aa0 + aa1, ra));
-                dh = fmaxf(dh, jst_ratio(eb0 + eb1, ab0 + ab1, rb));
-                Dh[k] = fmaxf(dh, 1e-7f);
+                Dh[k] = halo_sensor(sl, k, hu[k], hde[k], mean, m4, pl, planeA + sw * 64);
             }
         }
     }
@@ -451,13 +510,10 @@ __device__ __forceinline__ void sweep_adv(const BlockDesc3* __restrict__ blocks,
 
 // ------------------------------------------------------------------------------------------
 // Euler sweep in 3-D (P = [p T u v w], cfd.jl:106-151 / :459-508), the block form of the R2 residual.
-// pass A (passA_wave_nv below): gradients of the NV primitives along x, y, z + JST sensor of the pressure.
-//   G layout as the face-list kernels: grad of var v along dim d at G[(d*NV + v)*nc + c], sensor at G[3*NV*nc + c].
+// pass A (k_passA3e_wave over blk3::wave_gradient_pass, ibh_wave3d.h): gradients of the five primitives along x, y, z +
+//   JST sensor of the pressure.
+//   G layout as the face-list kernels: grad of var v along dim d at G[(d*5 + v)*nc + c], sensor at G[15*nc + c].
 // ------------------------------------------------------------------------------------------
-struct Gas3 {
-    float R, gamma;
-};
-
 __device__ __forceinline__ void euler_side3(const float* P, int dn, const Gas3& gas, float* Q, float* F, float& un,
                                             float& a) {
     const float p = P[0];
@@ -722,25 +778,10 @@ __device__ __forceinline__ void sweep_euler(const BlockDesc3* __restrict__ block
     float* plane = FF + 2560;         // [6][18 x 18] pressure
     float* planeA = plane + 6 * 324;  // [6][64]
     // ---- this thread's halo slot: side = wavefront index, boundary cell t
-    const int sw = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int ty = SIDE_MIRROR;
-    float qs = 0.5f;
-    switch (sw) {  // scalar registers, no dynamic indexing
-        case 0: ty = bb.type[0]; qs = bb.q[0]; break;
-        case 1: ty = bb.type[1]; qs = bb.q[1]; break;
-        case 2: ty = bb.type[2]; qs = bb.q[2]; break;
-        case 3: ty = bb.type[3]; qs = bb.q[3]; break;
-        case 4: ty = bb.type[4]; qs = bb.q[4]; break;
-        case 5: ty = bb.type[5]; qs = bb.q[5]; break;
-        default: break;
-    }
-    const int dnh = sw >> 1;                         // normal dim of the slot's side (3: the two idle wavefronts)
-    const bool low = (sw & 1) == 0, slotw = sw < 6;
-    const bool isC = ty == SIDE_COARSE, isF = ty == SIDE_FINE, mirror = ty == SIDE_MIRROR;
-    const int sd = dnh == 0 ? 1 : dnh == 1 ? 8 : 64, sa = dnh == 0 ? 8 : 1, sb = dnh == 2 ? 8 : 64;
-    const int t = tid & 63, t1 = t & 7, t2 = t >> 3;
-    const int n = isF ? 16 : 8;
-    const int dd = mirror ? 0 : (low ? -sd : sd);
+    const Slot3 sl = slot_frame(bb, tid);
+    const int sw = sl.sw, dnh = sl.dnh, t = sl.t, dd = sl.dd, pos = sl.pos;
+    const bool low = sl.low, slotw = sl.slotw, isF = sl.isF, mirror = sl.mirror;
+    const float qs = sl.qs;
     // ---- loads: own cell; halo chunk(s): the five primitives and their values one step deeper; rim cells (pressure)
     float Pc[5];
 #pragma unroll
@@ -776,18 +817,8 @@ __device__ __forceinline__ void sweep_euler(const BlockDesc3* __restrict__ block
             for (int v = 0; v < 5; ++v) hmean[v] = 0.25f * acc[v];
         }
     }
-    float rv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    const bool rimw = slotw && t < 4 * n;
-    if (rimw) {
-        const int32_t rid = rtab[sw * 64 + t];
-        if (rid >= 0) {
-            rv[0] = rv[1] = rv[2] = rv[3] = ldg(P, (uint32_t)rid);
-        } else {
-            const int32_t* r4 = r4tab + (size_t)(-rid - 1) * 4;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) rv[k] = ldg(P, (uint32_t)r4[k]);
-        }
-    }
+    float rv[4];
+    rim_load(sl, rtab, r4tab, P, rv);
     // ---- stage
 #pragma unroll
     for (int v = 0; v < 5; ++v) fP[v * 896 + tid] = Pc[v];
@@ -796,26 +827,11 @@ __device__ __forceinline__ void sweep_euler(const BlockDesc3* __restrict__ block
     if (slotw) {
 #pragma unroll
         for (int v = 0; v < 5; ++v) fP[v * 896 + 512 + tid] = hmean[v];
-        if (isF) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) pl[(2 * t1 + (k & 1) + 1) + 18 * (2 * t2 + (k >> 1) + 1)] = pf[k];
-        } else {
-            pl[(t1 + 1) + 18 * (t2 + 1)] = hu[0];
-        }
-        if (rimw) {
-            const int r = isF ? t >> 4 : t >> 3, i = isF ? t & 15 : t & 7;
-            const int p1 = r == 0 ? 0 : r == 1 ? n + 1 : i + 1, p2 = r == 2 ? 0 : r == 3 ? n + 1 : i + 1;
-            const int a1 = r == 0 ? 1 : r == 1 ? n : i + 1, a2 = r == 2 ? 1 : r == 3 ? n : i + 1;
-            pl[p1 + 18 * p2] = 0.25f * ((rv[0] + rv[1]) + (rv[2] + rv[3]));
-            radj = a1 + 18 * a2;
-        }
+        radj = plane_stage(sl, pl, pf, rv);
     }
     const Lane3 L = lane_info(bb, tid);
     __syncthreads();
-    if (rimw) {
-        const float ha = pl[radj];
-        planeA[sw * 64 + t] = 0.25f * ((fabsf(rv[0] - ha) + fabsf(rv[1] - ha)) + (fabsf(rv[2] - ha) + fabsf(rv[3] - ha)));
-    }
+    plane_rim_abs(sl, pl, radj, rv, planeA);
     const int tt[3] = {L.j + 8 * L.k, L.i + 8 * L.k, L.i + 8 * L.j};
     // ---- own cells: pressure sensor
     float D = 1e-7f;
@@ -841,46 +857,22 @@ __device__ __forceinline__ void sweep_euler(const BlockDesc3* __restrict__ block
     }
     fD[tid] = D;
     // ---- halo cell (chunk k) of this thread's slot: slopes of the five primitives along the normal, pressure sensor
-    const int nrm = (low ? 0 : 7) * sd;
-    const int pos = nrm + t1 * sa + t2 * sb;  // the slot's boundary cell
-    const int cm = isC ? 1 : 0;
-    const float irt = isC ? 0.5f : isF ? 2.0f : 1.0f;  // h / h_halo
-    float rn, ra, rb;  // reciprocal widths of the halo cell along the normal and the two tangential dims
-    if (dnh == 0) { rn = bb.rh[0]; ra = bb.rh[1]; rb = bb.rh[2]; }
-    else if (dnh == 1) { rn = bb.rh[1]; ra = bb.rh[0]; rb = bb.rh[2]; }
-    else { rn = bb.rh[2]; ra = bb.rh[0]; rb = bb.rh[1]; }
-    rn *= irt;
-    ra *= irt;
-    rb *= irt;
     // mean[v]: the block's cells in front of the halo cell (one, or the 2 x 2 group of a coarse cell); m4: their pressures
-    auto halo_eval = [&](int k, const float* h, const float* hd, const float* mean, const float* m4, float* Sh, float& Dh) {
+    auto halo_eval = [&](int k, const float* h, const float* hd, const float* mean, const float (&m4)[4], float* Sh,
+                         float& Dh) {
 #pragma unroll
         for (int v = 0; v < 5; ++v) {
             const float x = (1.0f - qs) * (mean[v] - h[v]) - 0.5f * (hd[v] - h[v]);
             Sh[v] = low ? x : -x;
         }
-        const float* pA = planeA + sw * 64;
-        const float p = h[0];
-        const float din = mean[0] - p;
-        const float ain = 0.25f * ((fabsf(m4[0] - p) + fabsf(m4[1] - p)) + (fabsf(m4[2] - p) + fabsf(m4[3] - p)));
-        const float dde = hd[0] - p;
-        const int f1 = isF ? 2 * t1 + (k & 1) : t1, f2 = isF ? 2 * t2 + (k >> 1) : t2;
-        const int fa = f1 & ~cm, fb = f1 | cm, ga = f2 & ~cm, gb = f2 | cm;
-        const float ea0 = pl[fa + 18 * (f2 + 1)] - p, ea1 = pl[fb + 2 + 18 * (f2 + 1)] - p;
-        const float eb0 = pl[(f1 + 1) + 18 * ga] - p, eb1 = pl[(f1 + 1) + 18 * (gb + 2)] - p;
-        const float aa0 = fa == 0 ? pA[f2] : fabsf(ea0), aa1 = fb == n - 1 ? pA[n + f2] : fabsf(ea1);
-        const float ab0 = ga == 0 ? pA[2 * n + f1] : fabsf(eb0), ab1 = gb == n - 1 ? pA[3 * n + f1] : fabsf(eb1);
-        float dh = jst_ratio(din + dde, ain + fabsf(dde), rn);
-        dh = fmaxf(dh, jst_ratio(ea0 + ea1, aa0 + aa1, ra));
-        dh = fmaxf(dh, jst_ratio(eb0 + eb1, ab0 + ab1, rb));
-        Dh = fmaxf(dh, 1e-7f);
+        Dh = halo_sensor(sl, k, h[0], hd[0], mean[0], m4, pl, planeA + sw * 64);
     };
     float Sh0[5] = {0.f, 0.f, 0.f, 0.f, 0.f}, Dh0 = 1e-7f;
     if (slotw) {
         blk2::wave_lds_sync();  // planeA of this side (written by this wavefront)
-        const int pa = t1 & ~cm, pb = t1 | cm, qa = t2 & ~cm, qb = t2 | cm;
-        const int g0 = nrm + pa * sa + qa * sb, g1 = nrm + pb * sa + qa * sb, g2 = nrm + pa * sa + qb * sb,
-                  g3 = nrm + pb * sa + qb * sb;
+        const int pa = sl.t1 & ~sl.cm, pb = sl.t1 | sl.cm, qa = sl.t2 & ~sl.cm, qb = sl.t2 | sl.cm;
+        const int g0 = sl.nrm + pa * sl.sa + qa * sl.sb, g1 = sl.nrm + pb * sl.sa + qa * sl.sb,
+                  g2 = sl.nrm + pa * sl.sa + qb * sl.sb, g3 = sl.nrm + pb * sl.sa + qb * sl.sb;
         float mean[5], m4[4];
 #pragma unroll
         for (int v = 0; v < 5; ++v) {
@@ -992,318 +984,6 @@ __device__ __forceinline__ void sweep_euler(const BlockDesc3* __restrict__ block
     }
 #pragma unroll
     for (int v = 0; v < 5; ++v) stg(Rr + (size_t)v * ldr, c, res[v]);
-}
-
-// ==========================================================================================
-// Wave-per-block form ("plane marching"): ONE wavefront per 8x8x8 block, lane = (i, j), the eight z-planes of the
-// block handled in turn.  Each lane keeps its whole z-column in registers; x/y neighbours go through wave-private
-// LDS (no workgroup barrier anywhere), z neighbours are the registers of the planes above and below.  All loads of a
-// block -- the eight own values and the six halo slots of every lane -- are issued up front: one memory trip.
-// The halo slots are reduced by the lanes that load them to (mean value, mean |difference to the boundary cell|), so
-// a side facing finer blocks (four cells per slot) costs the consumers nothing.
-// ==========================================================================================
-// halo cell of boundary cell t of side S (compile-time) -- the arithmetic of halo_cell3
-template <int S>
-__device__ __forceinline__ uint32_t halo_cell3s(const BlockDesc3& bb, const int32_t* __restrict__ htab, int32_t blk,
-                                                int t) {
-    const int ty = bb.type[S];
-    // wave-uniform: FINE sides, and sides whose neighbour block is not complete in this partition (nb < 0: a skirt
-    // fragment, image-only sweeps) take the ids from the table
-    if (ty == SIDE_FINE || ((ty == SIDE_SAME || ty == SIDE_COARSE) && bb.nb[S] < 0))
-        return (uint32_t)htab[(size_t)blk * 384 + S * 64 + t];
-    constexpr int d = S >> 1;
-    constexpr bool low = (S & 1) == 0;
-    constexpr int sd = d == 0 ? 1 : d == 1 ? 8 : 64;
-    constexpr int sa = d == 0 ? 8 : 1;
-    constexpr int sb = d == 2 ? 8 : 64;
-    int t1 = t & 7, t2 = t >> 3;
-    int n, base;
-    if (ty == SIDE_SAME) {
-        n = low ? 7 : 0;
-        base = bb.nb[S];
-    } else if (ty == SIDE_COARSE) {
-        n = low ? 7 : 0;
-        base = bb.nb[S];
-        t1 = 4 * (bb.sub[S] & 1) + (t1 >> 1);
-        t2 = 4 * (bb.sub[S] >> 1) + (t2 >> 1);
-    } else {
-        n = low ? 0 : 7;
-        base = bb.base;
-    }
-    return (uint32_t)(base + n * sd + t1 * sa + t2 * sb);
-}
-
-// pass A, scalar field.  LDS per wave: tile 512 | Hm 6x64 | Ha 6x64 = 1280 floats
-#define BLK3W_PASSA_LDS (512 + 384 + 384)
-
-__device__ __forceinline__ void passA_wave(const BlockDesc3* __restrict__ blocks, const int32_t* __restrict__ htab,
-                                           const int32_t* __restrict__ ftab, int32_t blk, uint32_t nc,
-                                           const float* __restrict__ u, float* __restrict__ G, float* lds, int lane) {
-    const BlockDesc3 bb = blocks[blk];
-    float* tile = lds;          // [k][lane]
-    float* Hm = lds + 512;      // [side][t]: mean neighbour value across the side
-    float* Ha = lds + 896;      // [side][t]: mean |neighbour - boundary cell|
-    float uk[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) uk[k] = ldg(u, (uint32_t)bb.base + lane + 64 * k);
-    // this lane loads slot t = lane of every side
-    uint32_t hid[6];
-    hid[0] = halo_cell3s<0>(bb, htab, blk, lane);
-    hid[1] = halo_cell3s<1>(bb, htab, blk, lane);
-    hid[2] = halo_cell3s<2>(bb, htab, blk, lane);
-    hid[3] = halo_cell3s<3>(bb, htab, blk, lane);
-    hid[4] = halo_cell3s<4>(bb, htab, blk, lane);
-    hid[5] = halo_cell3s<5>(bb, htab, blk, lane);
-    float hv[6];
-#pragma unroll
-    for (int s = 0; s < 6; ++s) hv[s] = ldg(u, hid[s]);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) tile[k * 64 + lane] = uk[k];
-    blk2::wave_lds_sync();
-    // reduce every slot to (mean value, mean |difference|) against its boundary cell: slot t of side s belongs to
-    // cell pos(s, t) = n*sd + t1*sa + t2*sb of the tile
-#pragma unroll
-    for (int s = 0; s < 6; ++s) {
-        const int d = s >> 1;
-        const bool low = (s & 1) == 0;
-        const int sd = d == 0 ? 1 : d == 1 ? 8 : 64, sa = d == 0 ? 8 : 1, sb = d == 2 ? 8 : 64;
-        const int pos = (low ? 0 : 7) * sd + (lane & 7) * sa + (lane >> 3) * sb;
-        const float ub = tile[pos];
-        float vm = hv[s], am = fabsf(hv[s] - ub);
-        if (bb.type[s] == SIDE_FINE) {  // wave-uniform: three more fine cells behind this slot
-            const int32_t* ft = ftab + (((size_t)bb.fine * 6 + s) * 64 + lane) * 3;
-            const float v1 = ldg(u, (uint32_t)ft[0]), v2 = ldg(u, (uint32_t)ft[1]), v3 = ldg(u, (uint32_t)ft[2]);
-            vm = 0.25f * (hv[s] + v1 + v2 + v3);
-            am = 0.25f * (fabsf(hv[s] - ub) + fabsf(v1 - ub) + fabsf(v2 - ub) + fabsf(v3 - ub));
-        }
-        Hm[s * 64 + lane] = vm;
-        Ha[s * 64 + lane] = am;
-    }
-    blk2::wave_lds_sync();
-    const int i = lane & 7, j = lane >> 3;
-    const bool e0 = i == 0, e1 = i == 7, e2 = j == 0, e3 = j == 7;
-    bool general = (e0 && bb.type[0] == SIDE_GENERAL) || (e1 && bb.type[1] == SIDE_GENERAL) ||
-                   (e2 && bb.type[2] == SIDE_GENERAL) || (e3 && bb.type[3] == SIDE_GENERAL);
-    const float q0 = e0 ? bb.q[0] : 0.5f, q1 = e1 ? bb.q[1] : 0.5f, q2 = e2 ? bb.q[2] : 0.5f, q3 = e3 ? bb.q[3] : 0.5f;
-    const float zlm = Hm[4 * 64 + lane], zla = Ha[4 * 64 + lane], zhm = Hm[5 * 64 + lane], zha = Ha[5 * 64 + lane];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const float uc = uk[k];
-        const float* tk = tile + k * 64;
-        // x, y: inside the plane or the side's reduced slot (x sides: t = j + 8k, y sides: t = i + 8k)
-        float vm[6], am[6];
-        vm[0] = e0 ? Hm[0 * 64 + j + 8 * k] : tk[lane - 1];
-        vm[1] = e1 ? Hm[1 * 64 + j + 8 * k] : tk[lane + 1];
-        vm[2] = e2 ? Hm[2 * 64 + i + 8 * k] : tk[lane - 8];
-        vm[3] = e3 ? Hm[3 * 64 + i + 8 * k] : tk[lane + 8];
-        am[0] = e0 ? Ha[0 * 64 + j + 8 * k] : fabsf(vm[0] - uc);
-        am[1] = e1 ? Ha[1 * 64 + j + 8 * k] : fabsf(vm[1] - uc);
-        am[2] = e2 ? Ha[2 * 64 + i + 8 * k] : fabsf(vm[2] - uc);
-        am[3] = e3 ? Ha[3 * 64 + i + 8 * k] : fabsf(vm[3] - uc);
-        // z: registers
-        vm[4] = k == 0 ? zlm : uk[k > 0 ? k - 1 : 0];
-        am[4] = k == 0 ? zla : fabsf(vm[4] - uc);
-        vm[5] = k == 7 ? zhm : uk[k < 7 ? k + 1 : 7];
-        am[5] = k == 7 ? zha : fabsf(vm[5] - uc);
-        const float ql[3] = {q0, q2, k == 0 ? bb.q[4] : 0.5f}, qh[3] = {q1, q3, k == 7 ? bb.q[5] : 0.5f};
-        float D = 1e-7f, g[3];
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            const float rh = bb.rh[d];
-            const float fr = uc + qh[d] * (vm[2 * d + 1] - uc);
-            const float fl = uc + ql[d] * (vm[2 * d] - uc);
-            g[d] = (fr - fl) * rh;
-            const float gg = ((vm[2 * d + 1] - uc) - (uc - vm[2 * d])) * rh;
-            const float ugg = (am[2 * d + 1] + am[2 * d]) * rh;
-            D = fmaxf(D, (1e-7f + fabsf(gg)) * __builtin_amdgcn_rcpf(1e-7f + ugg));
-        }
-        const bool gen = general || (k == 0 && bb.type[4] == SIDE_GENERAL) || (k == 7 && bb.type[5] == SIDE_GENERAL);
-        if (!gen) {
-            const uint32_t c = (uint32_t)bb.base + lane + 64 * k;
-            stg(G, c, g[0]);
-            stg(G + nc, c, g[1]);
-            stg(G + (size_t)2 * nc, c, g[2]);
-            stg(G + (size_t)3 * nc, c, D);
-        }
-    }
-}
-
-// the same for NV variables (Euler: 5 primitives), one variable after the other through the same LDS region;
-// G layout of the face-list kernels: grad of var v along dim d at G[(d*NV + v)*nc + c], sensor of var 0 at G[3*NV*nc + c]
-template <int NV>
-__device__ __forceinline__ void passA_wave_nv(const BlockDesc3* __restrict__ blocks, const int32_t* __restrict__ htab,
-                                              const int32_t* __restrict__ ftab, int32_t blk, uint32_t nc,
-                                              const float* __restrict__ P, uint32_t ldp, float* __restrict__ G,
-                                              float* lds, int lane) {
-    const BlockDesc3 bb = blocks[blk];
-    float* tile = lds;          // [k][lane]
-    float* Hm = lds + 512;      // [side][t]: mean neighbour value across the side
-    float* Ha = lds + 896;      // [side][t]: mean |neighbour - boundary cell|
-    // this lane loads slot t = lane of every side
-    uint32_t hid[6];
-    hid[0] = halo_cell3s<0>(bb, htab, blk, lane);
-    hid[1] = halo_cell3s<1>(bb, htab, blk, lane);
-    hid[2] = halo_cell3s<2>(bb, htab, blk, lane);
-    hid[3] = halo_cell3s<3>(bb, htab, blk, lane);
-    hid[4] = halo_cell3s<4>(bb, htab, blk, lane);
-    hid[5] = halo_cell3s<5>(bb, htab, blk, lane);
-    const int i = lane & 7, j = lane >> 3;
-    const bool e0 = i == 0, e1 = i == 7, e2 = j == 0, e3 = j == 7;
-    const bool general = (e0 && bb.type[0] == SIDE_GENERAL) || (e1 && bb.type[1] == SIDE_GENERAL) ||
-                         (e2 && bb.type[2] == SIDE_GENERAL) || (e3 && bb.type[3] == SIDE_GENERAL);
-    const float q0 = e0 ? bb.q[0] : 0.5f, q1 = e1 ? bb.q[1] : 0.5f, q2 = e2 ? bb.q[2] : 0.5f, q3 = e3 ? bb.q[3] : 0.5f;
-    // all loads of the block up front (one memory trip), then one variable after the other through the LDS region
-    float uka[NV][8], hva[NV][6];
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        const float* Pv = P + (size_t)v * ldp;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) uka[v][k] = ldg(Pv, (uint32_t)bb.base + lane + 64 * k);
-#pragma unroll
-        for (int s = 0; s < 6; ++s) hva[v][s] = ldg(Pv, hid[s]);
-    }
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-    const float* u = P + (size_t)v * ldp;
-    float uk[8], hv[6];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) uk[k] = uka[v][k];
-#pragma unroll
-    for (int s = 0; s < 6; ++s) hv[s] = hva[v][s];
-    if (v) blk2::wave_lds_sync();  // the previous variable's LDS reads are done
-#pragma unroll
-    for (int k = 0; k < 8; ++k) tile[k * 64 + lane] = uk[k];
-    blk2::wave_lds_sync();
-    // reduce every slot to (mean value, mean |difference|) against its boundary cell: slot t of side s belongs to
-    // cell pos(s, t) = n*sd + t1*sa + t2*sb of the tile
-#pragma unroll
-    for (int s = 0; s < 6; ++s) {
-        const int d = s >> 1;
-        const bool low = (s & 1) == 0;
-        const int sd = d == 0 ? 1 : d == 1 ? 8 : 64, sa = d == 0 ? 8 : 1, sb = d == 2 ? 8 : 64;
-        const int pos = (low ? 0 : 7) * sd + (lane & 7) * sa + (lane >> 3) * sb;
-        const float ub = tile[pos];
-        float vm = hv[s], am = fabsf(hv[s] - ub);
-        if (bb.type[s] == SIDE_FINE) {  // wave-uniform: three more fine cells behind this slot
-            const int32_t* ft = ftab + (((size_t)bb.fine * 6 + s) * 64 + lane) * 3;
-            const float v1 = ldg(u, (uint32_t)ft[0]), v2 = ldg(u, (uint32_t)ft[1]), v3 = ldg(u, (uint32_t)ft[2]);
-            vm = 0.25f * (hv[s] + v1 + v2 + v3);
-            am = 0.25f * (fabsf(hv[s] - ub) + fabsf(v1 - ub) + fabsf(v2 - ub) + fabsf(v3 - ub));
-        }
-        Hm[s * 64 + lane] = vm;
-        Ha[s * 64 + lane] = am;
-    }
-    blk2::wave_lds_sync();
-    const float zlm = Hm[4 * 64 + lane], zla = Ha[4 * 64 + lane], zhm = Hm[5 * 64 + lane], zha = Ha[5 * 64 + lane];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const float uc = uk[k];
-        const float* tk = tile + k * 64;
-        // x, y: inside the plane or the side's reduced slot (x sides: t = j + 8k, y sides: t = i + 8k)
-        float vm[6], am[6];
-        vm[0] = e0 ? Hm[0 * 64 + j + 8 * k] : tk[lane - 1];
-        vm[1] = e1 ? Hm[1 * 64 + j + 8 * k] : tk[lane + 1];
-        vm[2] = e2 ? Hm[2 * 64 + i + 8 * k] : tk[lane - 8];
-        vm[3] = e3 ? Hm[3 * 64 + i + 8 * k] : tk[lane + 8];
-        am[0] = e0 ? Ha[0 * 64 + j + 8 * k] : fabsf(vm[0] - uc);
-        am[1] = e1 ? Ha[1 * 64 + j + 8 * k] : fabsf(vm[1] - uc);
-        am[2] = e2 ? Ha[2 * 64 + i + 8 * k] : fabsf(vm[2] - uc);
-        am[3] = e3 ? Ha[3 * 64 + i + 8 * k] : fabsf(vm[3] - uc);
-        // z: registers
-        vm[4] = k == 0 ? zlm : uk[k > 0 ? k - 1 : 0];
-        am[4] = k == 0 ? zla : fabsf(vm[4] - uc);
-        vm[5] = k == 7 ? zhm : uk[k < 7 ? k + 1 : 7];
-        am[5] = k == 7 ? zha : fabsf(vm[5] - uc);
-        const float ql[3] = {q0, q2, k == 0 ? bb.q[4] : 0.5f}, qh[3] = {q1, q3, k == 7 ? bb.q[5] : 0.5f};
-        float D = 1e-7f, g[3];
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            const float rh = bb.rh[d];
-            const float fr = uc + qh[d] * (vm[2 * d + 1] - uc);
-            const float fl = uc + ql[d] * (vm[2 * d] - uc);
-            g[d] = (fr - fl) * rh;
-            const float gg = ((vm[2 * d + 1] - uc) - (uc - vm[2 * d])) * rh;
-            const float ugg = (am[2 * d + 1] + am[2 * d]) * rh;
-            D = fmaxf(D, (1e-7f + fabsf(gg)) * __builtin_amdgcn_rcpf(1e-7f + ugg));
-        }
-        const bool gen = general || (k == 0 && bb.type[4] == SIDE_GENERAL) || (k == 7 && bb.type[5] == SIDE_GENERAL);
-        if (!gen) {
-            const uint32_t c = (uint32_t)bb.base + lane + 64 * k;
-            stg(G + (size_t)(0 * NV + v) * nc, c, g[0]);
-            stg(G + (size_t)(1 * NV + v) * nc, c, g[1]);
-            stg(G + (size_t)(2 * NV + v) * nc, c, g[2]);
-            if (v == 0) stg(G + (size_t)(3 * NV) * nc, c, D);
-        }
-    }
-    }
-}
-
-
-// gradients of NV cell fields of one block in registers, g[v][k][d] (plane k of this lane's column, dimension d): the
-// arithmetic of passA_wave_nv without the stores and the sensor -- for kernels that consume the gradients where they
-// are made (shear rate of a velocity field, the Wray-Agarwal closure: ibh_turb.hip).  Blocks without GENERAL sides only.
-template <int NV>
-__device__ __forceinline__ void wave_gradients(const BlockDesc3& bb, const int32_t* __restrict__ htab,
-                                               const int32_t* __restrict__ ftab, int32_t blk, const float* const* F,
-                                               float* lds, int lane, float (&g)[NV][8][3]) {
-    float* tile = lds;          // [k][lane]
-    float* Hm = lds + 512;      // [side][t]: mean neighbour value across the side
-    uint32_t hid[6];
-    hid[0] = halo_cell3s<0>(bb, htab, blk, lane);
-    hid[1] = halo_cell3s<1>(bb, htab, blk, lane);
-    hid[2] = halo_cell3s<2>(bb, htab, blk, lane);
-    hid[3] = halo_cell3s<3>(bb, htab, blk, lane);
-    hid[4] = halo_cell3s<4>(bb, htab, blk, lane);
-    hid[5] = halo_cell3s<5>(bb, htab, blk, lane);
-    const int i = lane & 7, j = lane >> 3;
-    const bool e0 = i == 0, e1 = i == 7, e2 = j == 0, e3 = j == 7;
-    const float q0 = e0 ? bb.q[0] : 0.5f, q1 = e1 ? bb.q[1] : 0.5f, q2 = e2 ? bb.q[2] : 0.5f, q3 = e3 ? bb.q[3] : 0.5f;
-    float uka[NV][8], hva[NV][6];
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) uka[v][k] = ldg(F[v], (uint32_t)bb.base + lane + 64 * k);
-#pragma unroll
-        for (int s = 0; s < 6; ++s) hva[v][s] = ldg(F[v], hid[s]);
-    }
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        const float* u = F[v];
-        if (v) blk2::wave_lds_sync();  // the previous field's LDS reads are done
-#pragma unroll
-        for (int k = 0; k < 8; ++k) tile[k * 64 + lane] = uka[v][k];
-#pragma unroll
-        for (int s = 0; s < 6; ++s) {
-            float vm = hva[v][s];
-            if (bb.type[s] == SIDE_FINE) {  // wave-uniform: three more fine cells behind this slot
-                const int32_t* ft = ftab + (((size_t)bb.fine * 6 + s) * 64 + lane) * 3;
-                const float v1 = ldg(u, (uint32_t)ft[0]), v2 = ldg(u, (uint32_t)ft[1]), v3 = ldg(u, (uint32_t)ft[2]);
-                vm = 0.25f * (hva[v][s] + v1 + v2 + v3);
-            }
-            Hm[s * 64 + lane] = vm;
-        }
-        blk2::wave_lds_sync();
-        const float zlm = Hm[4 * 64 + lane], zhm = Hm[5 * 64 + lane];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const float uc = uka[v][k];
-            const float* tk = tile + k * 64;
-            float vm[6];
-            vm[0] = e0 ? Hm[0 * 64 + j + 8 * k] : tk[lane - 1];
-            vm[1] = e1 ? Hm[1 * 64 + j + 8 * k] : tk[lane + 1];
-            vm[2] = e2 ? Hm[2 * 64 + i + 8 * k] : tk[lane - 8];
-            vm[3] = e3 ? Hm[3 * 64 + i + 8 * k] : tk[lane + 8];
-            vm[4] = k == 0 ? zlm : uka[v][k > 0 ? k - 1 : 0];
-            vm[5] = k == 7 ? zhm : uka[v][k < 7 ? k + 1 : 7];
-            const float ql[3] = {q0, q2, k == 0 ? bb.q[4] : 0.5f}, qh[3] = {q1, q3, k == 7 ? bb.q[5] : 0.5f};
-#pragma unroll
-            for (int d = 0; d < 3; ++d) {
-                const float fr = uc + qh[d] * (vm[2 * d + 1] - uc);
-                const float fl = uc + ql[d] * (vm[2 * d] - uc);
-                g[v][k][d] = (fr - fl) * bb.rh[d];
-            }
-        }
-    }
 }
 
 #pragma clang fp contract(off)

@@ -4,7 +4,8 @@
 //                                           ibh_strip3d_euler.h): the default forms
 //     k_sweep3_adv / k_sweep3_euler         thread per cell, one 512-thread workgroup per block (ibh_block3d.h), A/B
 //   two-kernel form through the workspace, the face-list cells (ibh_facelist.h) in the same launch as the blocks:
-//     k_passA3_wave, k_passB3_adv_blk, k_passA3e_wave, k_passB3e_blk
+//     k_passA3_wave, k_passA3e_wave         pass A, one wavefront per block: the gradient sweep of ibh_wave3d.h
+//     k_passB3_adv_blk, k_passB3e_blk       pass B, one 512-thread workgroup per block (ibh_block3d.h)
 // and their launchers (adv3_*, euler3_*; ibh_fused.hip decides which one runs).
 #include "ibh_facelist.h"
 #include "ibh_strip3d_euler.h"
@@ -109,7 +110,8 @@ __global__ __launch_bounds__(64 * WPB3E) __attribute__((amdgpu_waves_per_eu(WAVE
                                      lds + wave * S3E_LDS, lane, STAMP ? ibh_dbg_buf : nullptr, TAB ? dtab : nullptr);
 }
 
-// wave-per-block form of the 3-D scalar pass A (blk3::passA_wave): 4 blocks per 256-thread workgroup
+// wave-per-block form of the 3-D scalar pass A (blk3::wave_gradient_pass, ibh_wave3d.h): 4 blocks per 256-thread
+// workgroup; G layout: gradient along dim d at G[d*nc + c], sensor at G[3*nc + c]
 __global__ __launch_bounds__(256) void k_passA3_wave(PartView p, const float* __restrict__ u, float* __restrict__ G,
                                                      const BlockDesc3* __restrict__ blocks,
                                                      const int32_t* __restrict__ htab,
@@ -123,7 +125,18 @@ __global__ __launch_bounds__(256) void k_passA3_wave(PartView p, const float* __
         const int32_t pos = __builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x - gI, nwg) * 4 + wave);
         if (pos < nblk) {
             const int32_t blk = blist ? __builtin_amdgcn_readfirstlane(blist[pos]) : pos;
-            blk3::passA_wave(blocks, htab, ftab, blk, (uint32_t)p.nc, u, G, lds + wave * BLK3W_PASSA_LDS, lane);
+            const BlockDesc3 bb = blocks[blk];
+            const uint32_t nc = (uint32_t)p.nc;
+            blk3::wave_gradient_pass<1, true>(
+                bb, htab, ftab, blk, [&](int) { return u; }, lds + wave * BLK3W_PASSA_LDS, lane,
+                [&](int, int k, const float (&g)[3], float D, bool general) {
+                    if (general) return;
+                    const uint32_t c = (uint32_t)bb.base + lane + 64 * k;
+                    blk2::stg(G, c, g[0]);
+                    blk2::stg(G + nc, c, g[1]);
+                    blk2::stg(G + (size_t)2 * nc, c, g[2]);
+                    blk2::stg(G + (size_t)3 * nc, c, D);
+                });
         }
         return;
     }
@@ -134,7 +147,8 @@ __global__ __launch_bounds__(256) void k_passA3_wave(PartView p, const float* __
     }
 }
 
-// wave-per-block form of the 3-D Euler pass A (blk3::passA_wave_nv<5>)
+// wave-per-block form of the 3-D Euler pass A, the five primitives through the same body; G layout of the face-list
+// kernels: grad of var v along dim d at G[(d*5 + v)*nc + c], sensor of the pressure (var 0) at G[15*nc + c]
 __global__ __launch_bounds__(256) void k_passA3e_wave(PartView p, const float* __restrict__ P, int64_t ldp,
                                                       float* __restrict__ G, const BlockDesc3* __restrict__ blocks,
                                                       const int32_t* __restrict__ htab,
@@ -145,9 +159,20 @@ __global__ __launch_bounds__(256) void k_passA3e_wave(PartView p, const float* _
     if ((int32_t)blockIdx.x >= gI) {
         const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
         const int32_t blk = __builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x - gI, nwg) * 4 + wave);
-        if (blk < nblk)
-            blk3::passA_wave_nv<5>(blocks, htab, ftab, blk, (uint32_t)p.nc, P, (uint32_t)ldp, G,
-                                   lds + wave * BLK3W_PASSA_LDS, lane);
+        if (blk < nblk) {
+            const BlockDesc3 bb = blocks[blk];
+            const uint32_t nc = (uint32_t)p.nc;
+            blk3::wave_gradient_pass<5, true>(
+                bb, htab, ftab, blk, [&](int v) { return P + (size_t)v * (uint32_t)ldp; }, lds + wave * BLK3W_PASSA_LDS, lane,
+                [&](int v, int k, const float (&g)[3], float D, bool general) {
+                    if (general) return;
+                    const uint32_t c = (uint32_t)bb.base + lane + 64 * k;
+                    blk2::stg(G + (size_t)(0 * 5 + v) * nc, c, g[0]);
+                    blk2::stg(G + (size_t)(1 * 5 + v) * nc, c, g[1]);
+                    blk2::stg(G + (size_t)(2 * 5 + v) * nc, c, g[2]);
+                    if (v == 0) blk2::stg(G + (size_t)(3 * 5) * nc, c, D);
+                });
+        }
         return;
     }
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -5,7 +5,7 @@
 // positions a lane writes and reads in that plane depend on the lane alone and are worked out here.
 // (The file is named after the strip form of the scalar sweep, which it held until the column form replaced it: DESIGN.md.)
 #pragma once
-#include "ibh_block3d.h"
+#include "ibh_wave3d.h"
 #include "ibh_quad2d.h"
 
 namespace strip3 {

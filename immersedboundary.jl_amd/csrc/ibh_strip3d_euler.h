@@ -794,12 +794,7 @@ __device__ __forceinline__ void sweep_block(const BlockDesc3* __restrict__ block
     float hp[6];
     {
         uint32_t hid[6];
-        hid[0] = halo_cell3s<0>(bb, htab, blk, lane);
-        hid[1] = halo_cell3s<1>(bb, htab, blk, lane);
-        hid[2] = halo_cell3s<2>(bb, htab, blk, lane);
-        hid[3] = halo_cell3s<3>(bb, htab, blk, lane);
-        hid[4] = halo_cell3s<4>(bb, htab, blk, lane);
-        hid[5] = halo_cell3s<5>(bb, htab, blk, lane);
+        blk3::halo_ids(bb, htab, blk, lane, hid);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int s = 0; s < 6; ++s) ridk[s] = rtab[(size_t)blk * 384 + s * 64 + lane];

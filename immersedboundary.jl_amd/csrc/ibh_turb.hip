@@ -149,12 +149,12 @@ __global__ void k_scalar_transport(int32_t nc, TransportDims T, const float* __r
 
 }  // namespace
 
-#include "ibh_block3d.h"  // (here, not at the top: the pointwise kernels above are compiled as before without it)
+#include "ibh_wave3d.h"  // (here, not at the top: the pointwise kernels above are compiled as before without it)
 
 namespace {
 
 // ---- closures of a turbulence model on an all-block 3-D partition, gradients consumed where they are made (one wavefront
-// per 8^3 block, blk3::wave_gradients: the arithmetic of the tuple cell_gradient's block sweep; the pointwise formulas are
+// per 8^3 block, blk3::wave_gradients of ibh_wave3d.h: the arithmetic of the tuple cell_gradient's block sweep; the pointwise formulas are
 // those of the kernels above, from ibh_les_dev.h, evaluated without contraction).  What the block kernels share:
 template <int NV>
 struct FieldPtrs {
@@ -221,7 +221,8 @@ __global__ __launch_bounds__(256) void k_wray_agarwal_of3(const BlockDesc3* __re
     if (blk >= nblk) return;
     const BlockDesc3 bb = blocks[blk];
     float g[2][8][3];
-    blk3::wave_gradients<2>(bb, htab, ftab, blk, RS.f, lds + wave * BLK3W_PASSA_LDS, lane, g);
+    // (the written-out form: over the shared body this kernel measured slower, profiles/wave3d_gradients/README.md)
+    blk3::wave_gradients_written_out<2>(bb, htab, ftab, blk, RS.f, lds + wave * BLK3W_PASSA_LDS, lane, g);
     const float C2 = sigmaR + C1 / (kappa * kappa);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
@@ -404,12 +405,7 @@ __device__ __forceinline__ void tr3_shared(const BlockDesc3& bb, const int32_t* 
     for (int k = 0; k < 8; ++k)
 #pragma unroll
         for (int d = 0; d < 3; ++d) W.Vk[d][k] = ldg(vel + (size_t)d * ldv, base + lane + 64 * k);
-    W.hid[0] = blk3::halo_cell3s<0>(bb, htab, blk, lane);
-    W.hid[1] = blk3::halo_cell3s<1>(bb, htab, blk, lane);
-    W.hid[2] = blk3::halo_cell3s<2>(bb, htab, blk, lane);
-    W.hid[3] = blk3::halo_cell3s<3>(bb, htab, blk, lane);
-    W.hid[4] = blk3::halo_cell3s<4>(bb, htab, blk, lane);
-    W.hid[5] = blk3::halo_cell3s<5>(bb, htab, blk, lane);
+    blk3::halo_ids(bb, htab, blk, lane, W.hid);
 #pragma unroll
     for (int s = 0; s < 6; ++s) {
         const int d = s >> 1;

@@ -7,8 +7,12 @@ dumps: the check that a build computes what another build computed, bit for bit.
 Per mesh (``octree``, ``single``: wave per 8^3 block; ``bs4 2d``, ``bs4 3d``: thread per cell over the side table), on the
 seeded fields of tests/kepsilon_model.py, once as they are and once with a NaN velocity entry: ``shear_rate_of_velocity`` with
 the gradients, ``les_closure_of`` with every output (Smagorinsky, and WALE in 3-D), ``Wray_Agarwal_of``, ``k_epsilon_rhs``
-with ``S`` and the gradients, and ``scalar_transport``.  Two arrays are the same when their NaN patterns are equal and every
-other element has the same bits.
+with ``S`` and the gradients, and ``scalar_transport``.  Then the users of the 3-D gradient sweep below the closures
+(``dump_sweeps``), on ``octree``, ``single`` and the second of two partitions of the octree (``skirt``: GENERAL sides and
+skirt fragments), with and without a NaN entry: the tuple ``cell_gradient`` of one field and of a 5-column array,
+``JST_sensor``, ``residual_advection`` and ``residual_euler_hll`` with ``IBH_NO_FUSE`` (the two-kernel form) and with
+``quad_variant`` 512 (the thread-per-cell single kernels).  Two arrays are the same when their NaN patterns are equal and
+every other element has the same bits.
 """
 import os
 import sys
@@ -50,8 +54,46 @@ def dump(path):
                 for key, a in d.items():
                     for j, b in enumerate(a if isinstance(a, tuple) else (a,)):
                         out[f"{name}{tag} | {call} | {key}{j if isinstance(a, tuple) else ''}"] = ibamd.to_host(b)
+    dump_sweeps(out, {"octree": meshes["octree"], "single": meshes["single"]})
     np.savez(path, **out)
     print(f"{len(out)} arrays written to {path}")
+
+
+def dump_sweeps(out, meshes):
+    import closure_cases
+    import ibamd
+    import les_model as lm
+    from ibamd import _lib
+    f32 = np.float32
+    parts = {name: lm.one_partition(msh) for name, msh in meshes.items()}
+    parts["skirt"] = closure_cases.skirt_case(closure_cases.Case).part
+    for name, part in parts.items():
+        dpart = ibamd.to_backend(part, ibamd.hip)
+        x, nc = part.centers, part.centers.shape[0]
+        rng = np.random.default_rng(31)
+        r = lambda: rng.uniform(-1, 1, nc)
+        for tag in ("", " nan"):
+            u = (np.sin(2 * x[:, 0]) * np.cos(3 * x[:, 1]) + 0.3 * x[:, 2] + 0.1 * r()).astype(f32)
+            C = np.stack([np.ones(nc), 0.5 + 0.1 * r(), -0.25 * np.ones(nc)], axis=1).astype(f32)
+            P = np.stack([1e5 * (1 + 0.05 * r()), 288.15 * (1 + 0.05 * r()), 100.0 * (1 + 0.1 * r()), 60.0 * (1 + 0.1 * r()),
+                          -40.0 * (1 + 0.1 * r())], axis=1).astype(f32)
+            if tag:
+                u[nc // 2] = np.nan
+                P[nc // 3, 0] = np.nan
+            du, dC, dP = ibamd.hip(u), ibamd.hip(C), ibamd.hip(P)
+            res = {"gradient of one field": ibamd.cell_gradient(dpart, du), "gradient of five columns": ibamd.cell_gradient(dpart, dP),
+                   "JST_sensor": ibamd.JST_sensor(dpart, du),
+                   "advection two-kernel": ibamd.residual_advection(dpart, du, dC, flags=ibamd.IBH_NO_FUSE),
+                   "euler two-kernel": ibamd.residual_euler_hll(dpart, dP, flags=ibamd.IBH_NO_FUSE)}
+            _lib.call("ibh_set_tuning", b"quad_variant", 512)
+            try:
+                res["advection 512"] = ibamd.residual_advection(dpart, du, dC)
+                res["euler 512"] = ibamd.residual_euler_hll(dpart, dP)
+            finally:
+                _lib.call("ibh_set_tuning", b"quad_variant", 0)
+            for call, a in res.items():
+                for j, b in enumerate(a if isinstance(a, tuple) else (a,)):
+                    out[f"{name}{tag} | {call} | {j}"] = ibamd.to_host(b)
 
 
 def compare(pa, pb):
