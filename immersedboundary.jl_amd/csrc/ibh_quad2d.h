@@ -1,18 +1,20 @@
 // Quad sweep (2-D scalar advection-JST-MUSCL residual, test/advection.jl:67-83): ONE wavefront sweeps the 16x16 tile
 // of four sibling 8x8 blocks, 4 cells per lane.  Same arithmetic as blk2::sweep_adv (ibh_sweep2d.h) -- undivided
 // slopes, flux_w -- but the 64 halo cells of the tile are 1/4 of its cells instead of as many as the block's own,
-// and the neighbours of a cell come from registers, DPP row shifts and a few cross-row permutes instead of LDS
-// tiles.  tests/quad_model.py is the lane-by-lane numpy statement of this file, checked against the oracle.
+// and the neighbours of a cell come from registers, a few cross-row permutes and one 18-row LDS tile per field that
+// holds the quad's halo in its frame.  tests/quad_model.py is the lane-by-lane numpy statement of this file, checked
+// against the oracle.
 //
 // Lane L = 16*g + t.
 //   own cells:  x = 4*g + r (r = 0..3: one float4 per field), y = t.
-//     y neighbours: lane -/+ 1 of the same 16-lane row  -> DPP row_shr:1 / row_shl:1 (lanes t = 0 / 15 keep `old`,
-//                   which is preloaded with the bottom / top ring of the tile);
-//     x neighbours: r -/+ 1 in registers, across strips lane -/+ 16 -> ds_bpermute (no LDS memory involved).
+//     y neighbours: the rows t -/+ 1 of the tile (one 16-byte LDS read per field and direction; rows -1 / 16 of tile U
+//                   hold the means of the bottom / top halo cells, so no lane is special);
+//     x neighbours: r -/+ 1 in registers; across strips the columns 4g - 1 / 4g + 4 of tile U (columns -1 / 16: the
+//                   means of the left / right halo cells), for slopes and fluxes lane -/+ 16 -> ds_bpermute.
 //   halo slots: the two sub-faces k = 0, 1 of boundary cell t of side [left, bottom, top, right][g] (arithmetic on
-//     (k0, k1) pairs); left / right halo values are therefore already in the lanes that own the boundary cells,
-//     bottom / top values go through a 16-entry LDS ring to the lanes t = 0 / 15.
-//   edge faces: the same lane computes both sub-faces of its boundary cell and hands their mean to the cell's lane.
+//     (k0, k1) pairs); every side writes the mean of its two halo values into the frame of tile U.
+//   edge faces: the same lane computes both sub-faces of its boundary cell and hands their mean to the cell's lane
+//     (left / right: its own; bottom / top: through the frame of tile U, which carries the y fluxes by then).
 // A face between cell a (towards -) and cell b (towards +) seen from the other side: F(a,b) = -F(b,a) with slopes
 // and velocities negated (every term of flux_w is odd or even under that swap), so low and high sides share one
 // evaluation: own cell first, halo cell second, sign = +1 on top / right, -1 on left / bottom.
@@ -30,23 +32,26 @@ typedef int v2i __attribute__((ext_vector_type(2)));
 // without skirt fragments in front of it (global_load/store_dwordx4 need dword alignment only)
 typedef float v4f_g __attribute__((ext_vector_type(4), aligned(4)));
 
-// LDS per wave (floats): tile U | tile SY | tile D | tile CY (16 rows, pitch 20: conflict-free ds_write_b128) |
-// lateral lines ext[8][20] | rings M, F, Q [4 rows][16] (row 0 bottom, 1 top, 2 neutral, 3 dump) | edge fluxes [4][16]
+// LDS per wave (floats): tile U | tile SY | tile D | tile CY | lateral lines ext[8][20] | rings F, Q [4 rows][16] (row 0
+// bottom, 1 top, 2 neutral, 3 dump).
+// A tile is a frame of 18 rows, pitch 20 (conflict-free ds_write_b128): frame row r + 1 holds tile row r = -1 .. 16, cell
+// (x, r) at column x.  Tile U carries the quad's halo in its frame: the means of the bottom / top halo cells in rows -1 /
+// 16 (pair tiles: 8), those of the left / right halo cells in columns -1 (column 19 of the row before) / 16 -- so the
+// four neighbours of a cell are plain reads of the tile, whatever the lane.  Once the slopes are taken, the same frame
+// hands the y fluxes down the rows: FT of row r in row r, the bottom edge flux in row -1, the top edge flux over FT of
+// the top row (QuadLane::p_exw).  Rows -1 and 16 of the other tiles are never written: what lanes t = 15 read there is
+// not used.
 #define QUAD_PITCH 20
-#define QUAD_TILE (16 * QUAD_PITCH)
+#define QUAD_TILE (18 * QUAD_PITCH)
 #define QUAD_OFF_EXT (4 * QUAD_TILE)
 #define QUAD_OFF_RING (QUAD_OFF_EXT + 160)
-#define QUAD_OFF_EX (QUAD_OFF_RING + 3 * 64)
-#define QUAD_LDS (QUAD_OFF_EX + 64)
+#define QUAD_LDS (QUAD_OFF_RING + 2 * 64)
 
 __device__ __forceinline__ float dpp_shr1(float old, float v) {  // lane i <- lane i-1 in rows of 16; lane 0 keeps old
     return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(v), 0x111, 0xf, 0xf, false));
 }
 __device__ __forceinline__ float dpp_shl1(float old, float v) {  // lane i <- lane i+1; lane 15 keeps old
     return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(v), 0x101, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float dpp_shl1z(float v) {  // lane i <- lane i+1; lane 15 gets 0
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x101, 0xf, 0xf, true));
 }
 __device__ __forceinline__ float bperm(int byte_addr, float v) {  // value of lane byte_addr/4
     return __int_as_float(__builtin_amdgcn_ds_bpermute(byte_addr, __float_as_int(v)));
@@ -62,6 +67,8 @@ __device__ __forceinline__ float lds_read(const float* p) {
 // interior faces (both cells same level, wa = 1/2), four at a time
 __device__ __forceinline__ v4f flux_half4(v4f ua, v4f ub, v4f Sa, v4f Sb, v4f Da, v4f Db, v4f Ca, v4f Cb) {
     const v4f d = ub - ua;
+    // (x + (-0.5) d instead of x - 0.5 d would spare the two instructions per pair that negate d -- measured: the compiler
+    // then contracts uf and A differently, the bits change; so it stays)
     const v4f gu = Sa - 0.5f * d;
     const v4f Du = Sb - 0.5f * d;
     v4f s, Df;
@@ -111,8 +118,11 @@ __device__ __forceinline__ float jst_max2(float g1, float a1, float rh1, float g
     return fmaxf(fmaxf(n1 * d2, n2 * d1) * __builtin_amdgcn_rcpf(d1 * d2), 1e-7f);
 }
 
-// Lane table of the quad sweep, built at compile time: per lane 8 words, LDS byte offsets packed two per word (see
-// sweep_quad for the meaning of the fields), the lane's cell offset inside the quad and its deeper-cell step.
+// Lane table of the quad sweep, built at compile time: per lane 8 words.  w0..w5: twelve LDS byte offsets packed two per
+// word (see QuadLane for the meaning of the fields), w6: byte offset of the lane's first cell inside the quad, w7: what
+// the second halo pair adds to its halo id (quad_load_halo_paired).
+// Everything a lane class decides and that is a constant of the lane is here or in a wave-wide constant mask (QL_MASK),
+// not in the instruction stream.
 // HALF: the tile of a PAIR of blocks (16 x 8 cells: lower-left, lower-right), swept by the same wave code -- lanes t >= 8
 // own no cells (they still own the slots of bottom / top boundary cells x = t), the top side sits on row 7
 template <bool HALF>
@@ -124,48 +134,56 @@ struct QuadLaneTab {
             const int ytop = HALF ? 7 : 15;
             const bool g0 = g == 0, g3 = g == 3, lr = g0 || g3, t0 = t == 0, t15 = t == ytop;
             const int bx = g0 ? 0 : g3 ? 15 : t, by = lr ? t : g == 1 ? 0 : ytop;
-            const int pos_b = by * QUAD_PITCH + bx;
-            const int pos_b1 = lr ? (t ^ 1) * QUAD_PITCH + bx : by * QUAD_PITCH + (t ^ 1);
-            const int pos_own = t * QUAD_PITCH + 4 * g;
+            const int pos_b = (by + 1) * QUAD_PITCH + bx;
+            const int pos_b1 = lr ? ((t ^ 1) + 1) * QUAD_PITCH + bx : (by + 1) * QUAD_PITCH + (t ^ 1);
+            const int pos_up = t * QUAD_PITCH + 4 * g;  // tile row t - 1
+            // halo slot of this lane's side in the frame of tile U; where its edge flux goes (left / right: a free slot)
+            const int pos_hm = g0 ? (t + 1) * QUAD_PITCH - 1 : g3 ? (t + 1) * QUAD_PITCH + 16 : g == 1 ? t : (ytop + 2) * QUAD_PITCH + t;
+            const int pos_exw = g == 1 ? t : g == 2 ? (ytop + 1) * QUAD_PITCH + t : 17 * QUAD_PITCH + 19;
             const int myrow = t0 ? 0 : t15 ? 1 : 2, rowB = t0 ? 0 : 2, rowT = t15 ? 1 : 2;
             const int wrow = g == 1 ? 0 : g == 2 ? 1 : 3;
             const int eline = (lane & 31) >> 2, ee = lane & 3;
             const int epos = QUAD_OFF_EXT + eline * 20 + (ee < 2 ? ee : 16 + ee);
             const int line = QUAD_OFF_EXT + lhs * 20;
-            const uint32_t f[14] = {
-                (uint32_t)pos_own, (uint32_t)pos_b, (uint32_t)pos_b1, (uint32_t)(line + 2 + 2 * tl), (uint32_t)epos,
+            const uint32_t f[12] = {
+                (uint32_t)pos_up, (uint32_t)pos_b, (uint32_t)pos_b1, (uint32_t)epos,
                 (uint32_t)(QUAD_OFF_RING + wrow * 16 + t), (uint32_t)(QUAD_OFF_RING + myrow * 16 + 4 * g),
                 (uint32_t)(QUAD_OFF_RING + rowB * 16 + 4 * g), (uint32_t)(QUAD_OFF_RING + rowT * 16 + 4 * g),
-                (uint32_t)(line + 2 * tl), (uint32_t)(line + 2 * (tl & ~1)), (uint32_t)(line + 2 * (tl | 1) + 4),
-                0u, 0u};
+                (uint32_t)(line + 2 * tl), (uint32_t)(line + 2 * (tl & ~1)), (uint32_t)pos_hm, (uint32_t)pos_exw};
             for (int k = 0; k < 6; ++k) w[lane][k] = (4u * f[2 * k]) | ((4u * f[2 * k + 1]) << 16);
-            w[lane][6] = 64u * ((g >> 1) + 2 * (t >> 3)) + 4u * (g & 1) + 8u * (t & 7);
-            w[lane][7] = (uint32_t)(g0 ? -1 : g == 1 ? -8 : g == 2 ? 8 : 1);
+            w[lane][6] = 4u * (64u * ((g >> 1) + (HALF ? 0 : 2 * (t >> 3))) + 4u * (g & 1) + 8u * (t & 7));
+            w[lane][7] = (uint32_t)(g0 ? -1 : g == 1 ? -8 : g == 2 ? 8 : 0);
         }
     }
 };
 __device__ const QuadLaneTab<false> lane_tab = QuadLaneTab<false>();
 __device__ const QuadLaneTab<true> lane_tab_half = QuadLaneTab<true>();
 
+// a lane class as a wave-wide constant: the select takes its condition from a scalar register pair that holds the
+// literal, where a compare of the lane id would cost a vector instruction per class
+#define QL_MASK(m) __builtin_amdgcn_inverse_ballot_w64(m)
+
 // ---- the wave's lane-only state: LDS pointers from a compile-time table (two 16-byte loads; computing them costs
-// ~90 vector instructions per wave, a fifth of a quad's arithmetic), lane classes from the lane id
+// ~90 vector instructions per wave, a fifth of a quad's arithmetic), lane classes from constant masks
 struct QuadLane {
-    float *p_own;    // this lane's four cells in a tile
+    float *p_up;     // the four cells BELOW this lane's in a tile (its own: + QUAD_PITCH, the ones above: + 2 QUAD_PITCH)
+    float *p_hm;     // where the mean of this lane's two halo cells goes in the frame of tile U
+    float *p_exw;    // where the edge flux of a bottom / top lane goes in that frame (left / right: a free slot)
     float *p_b;      // boundary cell of this lane's halo slots (in tile U)
     float *p_b1;     // its pair mate t ^ 1 (COARSE sides)
-    float *p_extw;   // this lane's two slots in the lateral line of its half-side
     float *p_epos;   // where lane & 31 puts its end value
     float *p_ringw;  // ring entry this lane's side writes (dump row for left / right)
     float *p_ringm;  // ring row this lane reads: bottom (t = 0), top (t = 15), neutral
-    float *p_ringB;  // weight row for the low y side: bottom or neutral
+    float *p_ringB;  // ring row for the low y side: bottom or neutral
     float *p_ringT;  // ... high y side: top or neutral
-    float *p_LbS;    // low lateral pair of this lane's slots, SAME / FINE half-sides (high pair: + 4)
-    float *p_LbC;    // ... COARSE half-sides
-    float *p_HbC;    // high lateral pair, COARSE
-    uint32_t a0off;  // this lane's first cell relative to the quad's
-    int delta;       // deeper cell of a halo cell: -1, -8, +8, +1
-    int lane, tl, lhs;
-    bool g0, g3, lr, dny, t15;   // t15: this lane's cells are the top row of the tile (t = 15; pair tiles: t = 7)
+    float *p_LbS;    // low lateral pair of this lane's slots, SAME / FINE half-sides (high pair: + 4; the lane's own
+                     // two slots in the lateral line: + 2)
+    float *p_LbC;    // ... COARSE half-sides (high pair: + 6)
+    uint32_t a0off4; // byte offset of this lane's first cell relative to the quad's
+    int offB;        // second halo pair: left -1 (the pair starts at the deeper cell), bottom -8, top +8, right 0
+    int lane;
+    bool g0, g3, lr, dny;
+    bool tl0, tl7;   // first / last lane of its half-side
     bool active;     // this lane owns cells (pair tiles: t < 8)
     float sgn;       // +1: the quad's cell is the owner of the edge face (top / right), -1 on left / bottom
 };
@@ -179,50 +197,47 @@ __device__ __forceinline__ QuadLane quad_lane(float* lds, int lane) {
     const uint4 w1 = *(const uint4*)(tab + 4);
 #define QL_LO(w) ((w) & 0xffffu)
 #define QL_HI(w) ((w) >> 16)
-    G.p_own = (float*)(L + QL_LO(w0.x));
+    G.p_up = (float*)(L + QL_LO(w0.x));
     G.p_b = (float*)(L + QL_HI(w0.x));
     G.p_b1 = (float*)(L + QL_LO(w0.y));
-    G.p_extw = (float*)(L + QL_HI(w0.y));
-    G.p_epos = (float*)(L + QL_LO(w0.z));
-    G.p_ringw = (float*)(L + QL_HI(w0.z));
-    G.p_ringm = (float*)(L + QL_LO(w0.w));
-    G.p_ringB = (float*)(L + QL_HI(w0.w));
-    G.p_ringT = (float*)(L + QL_LO(w1.x));
-    G.p_LbS = (float*)(L + QL_HI(w1.x));
-    G.p_LbC = (float*)(L + QL_LO(w1.y));
-    G.p_HbC = (float*)(L + QL_HI(w1.y));
+    G.p_epos = (float*)(L + QL_HI(w0.y));
+    G.p_ringw = (float*)(L + QL_LO(w0.z));
+    G.p_ringm = (float*)(L + QL_HI(w0.z));
+    G.p_ringB = (float*)(L + QL_LO(w0.w));
+    G.p_ringT = (float*)(L + QL_HI(w0.w));
+    G.p_LbS = (float*)(L + QL_LO(w1.x));
+    G.p_LbC = (float*)(L + QL_HI(w1.x));
+    G.p_hm = (float*)(L + QL_LO(w1.y));
+    G.p_exw = (float*)(L + QL_HI(w1.y));
 #undef QL_LO
 #undef QL_HI
-    // from the lane id (the own-cell loads then wait for the descriptor only):
-    // 64 ((g >> 1) + 2 (t >> 3)) + 4 (g & 1) + 8 (t & 7)
+    G.sgn = QL_MASK(0xffffffff00000000ull) ? 1.0f : -1.0f;
     // (pair tiles: lanes t >= 8 repeat the cells of t - 8 -- valid loads, nothing stored)
-    G.a0off = ((lane & 7) << 3) | (HALF ? 0 : ((lane & 8) << 4)) | ((lane & 16) >> 2) | ((lane & 32) << 1);
-    G.delta = (int)w1.w;
+    G.a0off4 = w1.z;
+    G.offB = (int)w1.w;
     G.lane = lane;
-    G.tl = lane & 7;
-    G.lhs = lane >> 3;  // outer half-side of this lane's slots
-    G.g0 = lane < 16;
-    G.g3 = lane >= 48;
-    G.lr = G.g0 || G.g3;
-    G.dny = !G.lr;
-    G.t15 = (lane & 15) == (HALF ? 7 : 15);
-    G.active = !HALF || (lane & 8) == 0;
-    G.sgn = lane >= 32 ? 1.0f : -1.0f;
-    // neutral ring rows: u ring unused, sensor correction 0, weight 1/2 (read by lanes that are not on the y edges)
-    ((float*)(L + 4 * (QUAD_OFF_RING + 64 + 32)))[lane & 15] = 0.0f;
-    ((float*)(L + 4 * (QUAD_OFF_RING + 128 + 32)))[lane & 15] = 0.5f;
+    G.g0 = QL_MASK(0x000000000000ffffull);
+    G.g3 = QL_MASK(0xffff000000000000ull);
+    G.lr = QL_MASK(0xffff00000000ffffull);
+    G.dny = QL_MASK(0x0000ffffffff0000ull);
+    G.tl0 = QL_MASK(0x0101010101010101ull);
+    G.tl7 = QL_MASK(0x8080808080808080ull);
+    G.active = QL_MASK(HALF ? 0x00ff00ff00ff00ffull : ~0ull);
+    // neutral ring rows: sensor correction 0, weight 1/2 (read by lanes that are not on the y edges)
+    ((float*)(L + 4 * (QUAD_OFF_RING + 32)))[lane & 15] = 0.0f;
+    ((float*)(L + 4 * (QUAD_OFF_RING + 64 + 32)))[lane & 15] = 0.5f;
     return G;
 }
 
 // ---- what a wave fetches for a quad, in three dependent steps
 struct QuadTab {   // needs the quad's index only
     QuadDesc2 d;   // wave-uniform
+    uint32_t ty;   // side class of this lane's half-side (lane >> 3)
     v2i hid;       // halo cells of this lane's two slots
     uint32_t eid;  // end cell of lane & 31
 };
 struct QuadOwn {   // needs the descriptor
     v4f U, CX, CY;
-    uint32_t a0;
 };
 struct QuadHalo {  // needs the table entries
     v2f hu, hd, hc;
@@ -234,14 +249,15 @@ __device__ __forceinline__ QuadTab quad_load_tab(const QuadDesc2* __restrict__ q
                                                  int32_t q, int lane, const int32_t* __restrict__ qaux = nullptr) {
     QuadTab T;
     T.d = qd[q];
+    T.ty = (T.d.cls >> ((lane >> 1) & 28)) & 15u;
     const int32_t* row = qtab + (size_t)q * IBH_QROW;
     if (qaux) {
         const int32_t* aux = qaux + (size_t)q * IBH_QAUX;
         const int lhs = lane >> 3, tl = lane & 7;
         const int32_t orig = aux[32 + lhs];
         T.eid = (uint32_t)aux[lane & 31];
-        const bool isC = ((T.d.cls >> (4 * lhs)) & 15u) == SIDE_COARSE;
-        const bool lr = lane < 16 || lane >= 48;
+        const bool isC = T.ty == SIDE_COARSE;
+        const bool lr = QL_MASK(0xffff00000000ffffull);
         const int32_t id = orig + (lr ? 8 : 1) * (isC ? tl >> 1 : tl);
         T.hid = v2i{id, id};
         if (orig < 0) T.hid = *(const v2i*)(row + 2 * lane);
@@ -251,13 +267,15 @@ __device__ __forceinline__ QuadTab quad_load_tab(const QuadDesc2* __restrict__ q
     T.eid = (uint32_t)row[128 + (lane & 31)];
     return T;
 }
+__device__ __forceinline__ size_t quad_base4(const QuadTab& T) { return (size_t)(uint32_t)T.d.base << 2; }
 __device__ __forceinline__ QuadOwn quad_load_own(const QuadLane& G, const QuadTab& T, const float* __restrict__ u,
                                                  const float* __restrict__ C, uint32_t ldc) {
     QuadOwn O;
-    O.a0 = (uint32_t)T.d.base + G.a0off;
-    O.U = *(const v4f_g*)((const char*)u + ((size_t)O.a0 << 2));
-    O.CX = *(const v4f_g*)((const char*)C + ((size_t)O.a0 << 2));
-    O.CY = *(const v4f_g*)((const char*)(C + ldc) + ((size_t)O.a0 << 2));
+    // the quad's base is wave-uniform: it goes into the scalar base address, the lane adds a 32-bit byte offset < 1 KB
+    const size_t b4 = quad_base4(T);
+    O.U = *(const v4f_g*)((const char*)u + b4 + G.a0off4);
+    O.CX = *(const v4f_g*)((const char*)C + b4 + G.a0off4);
+    O.CY = *(const v4f_g*)((const char*)(C + ldc) + b4 + G.a0off4);
     return O;
 }
 // Halo gathers: seven per quad.  Measured (scripts/probe_sweep.py, profiles/r2_final/README.md): alone each costs
@@ -279,22 +297,27 @@ __device__ __forceinline__ QuadHalo quad_load_halo_paired(const QuadLane& G, con
     auto pair = [](const float* p, int i) { return *(const v2f_g*)((const char*)p + ((size_t)(uint32_t)i << 2)); };
     QuadHalo H;
     const float* Cn = C + (G.dny ? ldc : 0u);
-    const bool isF = ((T.d.cls >> (4 * G.lhs)) & 15u) == SIDE_FINE;
-    const int lo = G.delta < 0 ? G.delta : 0;                       // left side: the pair starts at the deeper cell
-    const v2f PA = pair(u, G.lr ? T.hid.x + lo : T.hid.x);
-    const v2f PB = pair(u, G.lr ? T.hid.y + lo : T.hid.x + G.delta);
+    const bool isF = T.ty == SIDE_FINE;
+    // left side: the pair starts at the deeper cell, one in front of the halo cell
+    const v2f PA = pair(u, T.hid.x - (int)G.g0);
+    const v2f PB = pair(u, (G.lr ? T.hid.y : T.hid.x) + G.offB);
     const v2f PC = pair(Cn, T.hid.x);
     H.eu = ldg(u, T.eid);
     float hc1 = 0.0f;
     if (G.lr && isF) hc1 = ldg(Cn, (uint32_t)T.hid.y);              // few lanes, few quads
     asm volatile("" : "+v"(hc1));
-    const bool first = G.g0;                                         // left side: (deeper, halo); right side: (halo, deeper)
-    const float huA = first ? PA.y : PA.x, hdA = first ? PA.x : PA.y;
-    const float huB = first ? PB.y : PB.x, hdB = first ? PB.x : PB.y;
-    H.hu.x = G.lr ? huA : PA.x;
-    H.hd.x = G.lr ? hdA : PB.x;
-    H.hu.y = G.lr ? huB : (isF ? PA.y : PA.x);
-    H.hd.y = G.lr ? hdB : (isF ? PB.y : PB.x);
+    // which element of which pair is which value (one select per class that differs, conditions are scalar masks):
+    //            left (g0)      right (g3)     bottom / top FINE   bottom / top SAME, COARSE
+    //   hu.x     PA.y           PA.x           PA.x                PA.x
+    //   hd.x     PA.x           PA.y           PB.x                PB.x
+    //   hu.y     PB.y           PB.x           PA.y                PA.x
+    //   hd.y     PB.x           PB.y           PB.y                PB.x
+    const bool dF = G.dny && isF;
+    const float a = dF ? PA.y : PA.x;
+    H.hu.x = G.g0 ? PA.y : PA.x;
+    H.hd.x = G.g0 ? PA.x : (G.g3 ? PA.y : PB.x);
+    H.hu.y = G.g0 ? PB.y : (G.g3 ? PB.x : a);
+    H.hd.y = (G.g3 || dF) ? PB.y : PB.x;
     H.hc.x = PC.x;
     H.hc.y = isF ? (G.lr ? hc1 : PC.y) : PC.x;
     return H;
@@ -314,19 +337,20 @@ __device__ __forceinline__ void quad_compute(const QuadLane& G, const QuadTab& T
     };
     const v4f U = O.U, CX = O.CX, CY = O.CY;
     const v2f hu = H.hu, hd = H.hd, hc = H.hc;
-    const bool g0 = G.g0, g3 = G.g3, lr = G.lr, dny = G.dny, t15 = G.t15;
+    const bool g0 = G.g0, g3 = G.g3, lr = G.lr, dny = G.dny;
     const int lane = G.lane;
     const float sgn = G.sgn;
-    const uint32_t ty = (T.d.cls >> (4 * G.lhs)) & 15u;
+    const uint32_t ty = T.ty;
     const bool isC = ty == SIDE_COARSE, isF = ty == SIDE_FINE;
     const float qs = isC ? (1.0f / 3.0f) : isF ? (2.0f / 3.0f) : 0.5f;  // at_faces weight of the quad's cell
     const float irt = isC ? 0.5f : isF ? 2.0f : 1.0f;                   // h / h_halo
     const float rhx = T.d.rh[0], rhy = T.d.rh[1];
 
     // ---- stage: u tile, lateral lines
-    *(v4f*)G.p_own = U;
-    *(v4f*)(G.p_own + 3 * QUAD_TILE) = CY;
-    *(v2f*)G.p_extw = hu;
+    float* const p_own = G.p_up + QUAD_PITCH;
+    *(v4f*)p_own = U;
+    *(v4f*)(p_own + 3 * QUAD_TILE) = CY;
+    *(v2f*)(G.p_LbS + 2) = hu;
     *G.p_epos = H.eu;
     wave_lds_sync();
     stamp(4);
@@ -336,9 +360,9 @@ __device__ __forceinline__ void quad_compute(const QuadLane& G, const QuadTab& T
     const float hm = 0.5f * (hu.x + hu.y);
     // sensor correction of a boundary cell that faces two finer cells: its |d| sum counts both of them
     const float fix = 0.5f * (fabsf(hu.x - m0) + fabsf(hu.y - m0)) - fabsf(hm - m0);
-    G.p_ringw[0] = hm;
-    G.p_ringw[64] = fix;
-    G.p_ringw[128] = qs;
+    *G.p_hm = hm;
+    G.p_ringw[0] = fix;
+    G.p_ringw[64] = qs;
     wave_lds_sync();
     stamp(5);
 
@@ -346,25 +370,22 @@ __device__ __forceinline__ void quad_compute(const QuadLane& G, const QuadTab& T
     v4f SX, SY, D;
     v4f uT;
     {
-        const float uLm = bperm((lane - 16) << 2, U.w), uRp = bperm((lane + 16) << 2, U.x);
-        const v4f UL = v4f{g0 ? hm : uLm, U.x, U.y, U.z};
-        const v4f UR = v4f{U.y, U.z, U.w, g3 ? hm : uRp};
+        // the neighbours across the lane's edges, from the frame of tile U: cells of the tile or the halo means
+        const v4f UL = v4f{p_own[-1], U.x, U.y, U.z};
+        const v4f UR = v4f{U.y, U.z, U.w, p_own[4]};
         const v4f qL = v4f{g0 ? qs : 0.5f, 0.5f, 0.5f, 0.5f};
         const v4f qR = v4f{0.5f, 0.5f, 0.5f, g3 ? qs : 0.5f};
         const v4f dR = UR - U, dL = U - UL;
-        SX = qR * dR + qL * dL;
-        const v4f gx = dR - dL;
-        const v4f rM = *(const v4f*)G.p_ringm;
-        const v4f rF = *(const v4f*)(G.p_ringm + 64);
-        const v4f qB = *(const v4f*)(G.p_ringB + 128);
-        const v4f qT = *(const v4f*)(G.p_ringT + 128);
-        v4f uB;
+        // one multiply and one fma per cell, as the packed form qR * dR + qL * dL contracts: dR of a cell is dL of the next
+        // one, so packed operands would be register pairs that overlap and have to be copied apart first
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            uB[c] = dpp_shr1(rM[c], U[c]);
-            uT[c] = dpp_shl1(rM[c], U[c]);
-            if constexpr (HALF) uT[c] = t15 ? rM[c] : uT[c];  // (lane t = 8 exists: the top row takes the ring itself)
-        }
+        for (int c = 0; c < 4; ++c) SX[c] = fmaf(qR[c], dR[c], qL[c] * dL[c]);
+        const v4f gx = dR - dL;
+        const v4f rF = *(const v4f*)G.p_ringm;
+        const v4f qB = *(const v4f*)(G.p_ringB + 64);
+        const v4f qT = *(const v4f*)(G.p_ringT + 64);
+        const v4f uB = *(const v4f*)G.p_up;
+        uT = *(const v4f*)(G.p_up + 2 * QUAD_PITCH);
         const v4f dT = uT - U, dB = U - uB;
         SY = qT * dT + qB * dB;
         const v4f gy = dT - dB;
@@ -378,8 +399,8 @@ __device__ __forceinline__ void quad_compute(const QuadLane& G, const QuadTab& T
             D[c] = jst_max2(gx[c], ax, rhx, gy[c], ay, rhy);
         }
     }
-    *(v4f*)(G.p_own + QUAD_TILE) = SY;
-    *(v4f*)(G.p_own + 2 * QUAD_TILE) = D;
+    *(v4f*)(p_own + QUAD_TILE) = SY;
+    *(v4f*)(p_own + 2 * QUAD_TILE) = D;
 
     // ---- halo cells of this lane's two slots: slope along the side normal and sensor
     v2f Shn, Dh;  // Shn: slope of the halo cell seen from the quad outwards (sign folded for the edge flux below)
@@ -391,8 +412,8 @@ __device__ __forceinline__ void quad_compute(const QuadLane& G, const QuadTab& T
         Shn = 0.5f * dde - (1.0f - qs) * din;
         // lateral neighbours (ibh_sweep2d.h:246-255 in pair form; quad_model.py checks the equivalence)
         const v2f Lp = *(const v2f*)(isC ? G.p_LbC : G.p_LbS);
-        const v2f Hp = *(const v2f*)(isC ? G.p_HbC : G.p_LbS + 4);
-        const bool t0l = G.tl == 0, t7l = G.tl == 7;
+        const v2f Hp = *(const v2f*)((isC ? G.p_LbC + 2 : G.p_LbS) + 4);
+        const bool t0l = G.tl0, t7l = G.tl7;
         const v2f lo0 = v2f{(isF && !t0l) ? Lp.y : Lp.x, isF ? hu.x : Lp.x};
         const v2f lo1 = v2f{Lp.y, isF ? hu.x : Lp.y};
         const v2f hi0 = v2f{isF ? hu.y : Hp.x, Hp.x};
@@ -410,6 +431,8 @@ __device__ __forceinline__ void quad_compute(const QuadLane& G, const QuadTab& T
     }
 
     // ---- interior faces: right (x+) and top (y+) face of every cell
+    wave_lds_sync();  // SY, D tiles
+    stamp(6);
     v4f FR, FT;
     {
         const int up = (lane + 16) << 2;
@@ -418,32 +441,31 @@ __device__ __forceinline__ void quad_compute(const QuadLane& G, const QuadTab& T
         const v4f Db = v4f{D.y, D.z, D.w, bperm(up, D.x)};
         const v4f Cb = v4f{CX.y, CX.z, CX.w, bperm(up, CX.x)};
         FR = flux_half4(U, Ub, SX, Sb, D, Db, CX, Cb);
-        v4f St, Dt, Ct;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            St[c] = dpp_shl1z(SY[c]);  // lanes t = 15: zero (their top face is an edge face, taken from `ex` below)
-            Dt[c] = dpp_shl1z(D[c]);
-            Ct[c] = dpp_shl1z(CY[c]);
-        }
+        // the cells above are the next row of the tiles: one LDS read per field instead of four DPP moves.  Lanes t = 15
+        // read row 16, which nobody writes in these tiles: whatever is there, their top face is an edge face -- the top
+        // edge flux replaces their FT below (pair tiles: lanes t = 7, and what t >= 8 compute is never stored)
+        const v4f St = *(const v4f*)(p_own + QUAD_TILE + QUAD_PITCH);
+        const v4f Dt = *(const v4f*)(p_own + 2 * QUAD_TILE + QUAD_PITCH);
+        const v4f Ct = *(const v4f*)(p_own + 3 * QUAD_TILE + QUAD_PITCH);
         FT = flux_half4(U, uT, SY, St, D, Dt, CY, Ct);
     }
+    *(v4f*)p_own = FT;  // tile U is done with u: its frame now hands the y fluxes down the rows
 
     // ---- edge faces: both sub-faces of this lane's boundary cell
-    wave_lds_sync();  // SY, D tiles
-    stamp(6);
     float edge;
     {
-        const float So_lr = g3 ? SX.w : SX.x, Do_lr = g3 ? D.w : D.x, Co_lr = g3 ? CX.w : CX.x;
-        const float So_bt = lds_read(G.p_b + QUAD_TILE), Do_bt = lds_read(G.p_b + 2 * QUAD_TILE),
+        // the sensor of the boundary cell is in tile D for every side (left / right lanes read back their own D.x / D.w);
+        // there is no tile of SX and CX
+        const float So_lr = g3 ? SX.w : SX.x, Co_lr = g3 ? CX.w : CX.x;
+        const float So_bt = lds_read(G.p_b + QUAD_TILE), Do = lds_read(G.p_b + 2 * QUAD_TILE),
                     Co_bt = lds_read(G.p_b + 3 * QUAD_TILE);
         const float So = lr ? So_lr : So_bt;
-        const float Do = lr ? Do_lr : Do_bt;
         const float Co = lr ? Co_lr : Co_bt;
         // own cell first, halo second; on low sides everything that is odd under the swap is negated (sgn = -1)
         const v2f F = flux_w2(m0, hu, sgn * So, Shn, Do, Dh, sgn * Co, sgn * hc, qs);
         edge = sgn * (0.5f * (F.x + F.y));
     }
-    G.p_ringw[QUAD_OFF_EX - QUAD_OFF_RING] = edge;
+    *G.p_exw = edge;  // bottom: row -1; top: over FT of the top row
     wave_lds_sync();
     stamp(7);
 
@@ -452,22 +474,19 @@ __device__ __forceinline__ void quad_compute(const QuadLane& G, const QuadTab& T
         const float FRm = bperm((lane - 16) << 2, FR.w);
         const v4f FL = v4f{g0 ? edge : FRm, FR.x, FR.y, FR.z};
         const v4f FRf = v4f{FR.x, FR.y, FR.z, g3 ? edge : FR.w};
-        const v4f ex = *(const v4f*)(G.p_ringm + (QUAD_OFF_EX - QUAD_OFF_RING));
-        v4f FB, FTf;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            FB[c] = dpp_shr1(ex[c], FT[c]);
-            FTf[c] = t15 ? ex[c] : FT[c];
-        }
+        // the flux through the lower face is what the row below stored, through the upper face what this row holds now
+        const v4f FB = *(const v4f*)G.p_up;
+        const v4f FTf = *(const v4f*)p_own;
         const v4f res = -((FRf - FL) * rhx) - ((FTf - FB) * rhy);
+        float* const out = (float*)((char*)ud + quad_base4(T) + G.a0off4);
         // the residual is not read again by this sweep: stores that do not allocate in L2 (`nt`) -- 6.03 -> 5.86 us per sweep at
         // 0.87 M cells, 15.05 -> 14.89 at 3.47 M (same box, alternating builds).  Not for STEP, whose output the next step reads.
 #ifdef Q2_NO_NT_STORE   // (A/B)
-        if (!HALF || G.active) *(v4f_g*)((char*)ud + ((size_t)O.a0 << 2)) = STEP ? U + dt * res : res;
+        if (!HALF || G.active) *(v4f_g*)out = STEP ? U + dt * res : res;
 #else
         if (!HALF || G.active) {
-            if constexpr (STEP) *(v4f_g*)((char*)ud + ((size_t)O.a0 << 2)) = U + dt * res;
-            else __builtin_nontemporal_store(res, (v4f_g*)((char*)ud + ((size_t)O.a0 << 2)));
+            if constexpr (STEP) *(v4f_g*)out = U + dt * res;
+            else __builtin_nontemporal_store(res, (v4f_g*)out);
         }
 #endif
     }
