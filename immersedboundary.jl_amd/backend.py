@@ -953,6 +953,74 @@ def stage_euler_ssp(part, P, P0, dt, a, b, c, out, fluid=None, scheme="hll", wor
     return out
 
 
+def _smoothing(what, eps, n_iter):
+    """``(eps, n_iter)`` of a residual smoothing, checked: ``eps`` finite and >= 0, ``n_iter`` an integer >= 1."""
+    eps = float(eps)
+    if not (eps >= 0.0 and eps != float("inf")):
+        raise ValueError(f"{what}: eps must be finite and >= 0")
+    if isinstance(n_iter, bool) or int(n_iter) != n_iter or int(n_iter) < 1:
+        raise ValueError(f"{what}: n_iter must be an integer >= 1")
+    return eps, int(n_iter)
+
+
+@_hipaware
+def smooth_residual(part, R, eps, n_iter, out=None, tmp=None):
+    """Implicit residual smoothing (not in the reference): ``n_iter`` Jacobi iterations on ``(I + eps L) S = R``, ``L`` the
+    unweighted Laplacian of the partition's face graph,
+    ``S_i <- (R_i + eps * sum(S[across(f, i)] for f in faces(i))) / (1 + eps * n_i)`` from ``S = R``, per column of ``R``
+    (``(nc,)`` or ``(nc, nv)``, ``nv <= 8``), one launch per iteration.  Returns ``out`` (None: a new array).  ``tmp``, the
+    ping-pong partner from ``n_iter = 2``, is allocated when it is not given; ``out`` and ``tmp`` alias neither each other nor
+    ``R``."""
+    part = _part(part)
+    eps, n_iter = _smoothing("smooth_residual", eps, n_iter)
+    R, nv, ldr = _field(R, part.nc)
+    if nv > 8:
+        raise ValueError("smooth_residual: R has more than 8 columns")
+    if out is None:
+        out = _like(R, part.nc)
+    o, nvo, ldo = _field_inplace(out, part.nc, "out")
+    if nvo != nv or o.ndim != R.ndim:
+        raise ValueError(f"out must have the shape of R, {tuple(R.shape)}")
+    t, ldt = None, 0
+    if n_iter >= 2:
+        if tmp is None:
+            tmp = _like(R, part.nc)
+        t, nvt, ldt = _field_inplace(tmp, part.nc, "tmp")
+        if nvt != nv:
+            raise ValueError(f"tmp must have the shape of R, {tuple(R.shape)}")
+    _stream()
+    call("ibh_smooth_residual", part.handle, _ptr(R), nv, ldr, C.c_float(eps), n_iter, _ptr(o), ldo, _ptr(t), ldt)
+    return out
+
+
+@_hipaware
+def update_euler_smoothed(part, P0, P, R, Sprev, eps, dt, coef, fluid=None, out=None):
+    """The last Jacobi iteration of a residual smoothing inside the update, in one launch: with ``S`` one iteration of
+    ``smooth_residual`` from ``Sprev`` (``Sprev`` may be ``R``: the only iteration), ``coef = (c,)`` gives
+    ``update_euler_stage(P0, S, dt, c)`` (``P`` is ignored and may be None) and ``coef = (a, b, c)`` gives
+    ``update_euler_ssp(P0, P, S, dt, a, b, c)``, bit for bit, without ``S`` being written.  ``out`` may be ``P0`` or ``P``,
+    not ``R`` or ``Sprev``."""
+    part = _part(part)
+    eps, _ = _smoothing("update_euler_smoothed", eps, 1)
+    coef = tuple(float(x) for x in coef)
+    if len(coef) not in (1, 3):
+        raise ValueError("update_euler_smoothed: coef must be (c,) or (a, b, c)")
+    blend = len(coef) == 3
+    a, b, c = coef if blend else (0.0, 1.0, coef[0])
+    states = (P0, P) if blend else (P0,)
+    _, nv, S, Ra, D, O, out, keep = _update_args("update_euler_smoothed", states, dt, out, R, n=part.nc, nd=part.nd)
+    if not blend:
+        S += [c_vp(None), 0]
+    Sp, nvs, lds = _field(Sprev, part.nc)
+    if nvs != nv:
+        raise ValueError(f"Sprev must be (nc, {nv})")
+    f = _cfluid(fluid)
+    _stream()
+    call("ibh_update_euler_smoothed", part.handle, C.byref(f), int(blend), *S, *Ra, _ptr(Sp), lds, C.c_float(eps), *D,
+         C.c_float(a), C.c_float(b), C.c_float(c), *O)
+    return out
+
+
 # ---------------------------------------------------------------------------
 # partition runtime and ghost-cell BC
 # ---------------------------------------------------------------------------

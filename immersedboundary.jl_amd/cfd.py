@@ -128,6 +128,8 @@ update_euler_stage = B.update_euler_stage          # (ibh_update_euler_stage / i
 stage_euler = B.stage_euler
 update_euler_ssp = B.update_euler_ssp              # (ibh_update_euler_ssp / ibh_stage_euler_ssp: a Shu-Osher stage)
 stage_euler_ssp = B.stage_euler_ssp
+smooth_residual = B.smooth_residual                # (ibh_smooth_residual / ibh_update_euler_smoothed: implicit residual smoothing)
+update_euler_smoothed = B.update_euler_smoothed
 
 
 def inviscid_fluxes(fluid, PL, PR, *args):

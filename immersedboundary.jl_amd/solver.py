@@ -209,10 +209,19 @@ class EulerMarch:
     ``Q_k = a Q_0 + b Q_{k-1} + c dt R(P_{k-1})``: a stage with ``(a, b) == (0, 1)`` is ``stage_euler(P_{k-1}, P_{k-1}, dt, c)``
     -- no blend -- and every other one ``stage_euler_ssp(P_{k-1}, P_0, dt, a, b, c)`` (with ``residual``: the callable into
     ``work``, then ``update_euler_stage`` / ``update_euler_ssp``); time step, ``bcs``, ``average`` and the three arrays as
-    above."""
+    above.
+
+    ``smoothing=(eps, n_iter)``: implicit residual smoothing, the third acceleration of a pseudo-time march beside
+    ``local_dt`` and the stages -- it lets ``scale`` exceed the explicit limit of the scheme.  Every stage becomes the
+    residual into ``work`` (the sweep alone, or ``residual``), ``smooth_residual(work, eps, n_iter - 1)`` when
+    ``n_iter >= 2`` and ``update_euler_smoothed`` with the stage's form, which does the last iteration itself:
+    ``n_iter + 1`` launches.  A forward-Euler step is the stage form on the step's input with ``c = 1``.  The smoothing
+    arrays (none for ``n_iter = 1``, one for 2, two from 3) are allocated here.  The march is no longer time accurate:
+    ``smoothing`` with ``average`` raises, and so do the image-only, phase and single-pass ``flags`` -- the smoothing
+    would gather rows the sweep never wrote."""
 
     def __init__(self, part, fluid=None, scheme="hll", scale=0.75, bcs=None, average=None, local_dt=False, dt_every=1,
-                 residual=None, flags=0, stages=1):
+                 residual=None, flags=0, stages=1, smoothing=None):
         from . import cfd
         self.part = B._part(part)
         self.fluid = fluid if fluid is not None else cfd.Fluid()
@@ -246,6 +255,18 @@ class EulerMarch:
         self._buf = tuple(B.colmajor_empty(nc, nv) for _ in range(3 if self._staged else 2))
         self.work = B.colmajor_empty(nc, nv)
         self.dt = B.colmajor_empty(nc) if self.local_dt else torch.empty(1, dtype=torch.float32, device=self.work.device)
+        self.smoothing, self._smooth = None, ()
+        if smoothing is not None:
+            if not isinstance(smoothing, (tuple, list)) or len(smoothing) != 2:
+                raise ValueError("smoothing must be (eps, n_iter)")
+            self.smoothing = B._smoothing("EulerMarch", *smoothing)
+            if average is not None:
+                raise ValueError("a time average needs a time-accurate march: residual smoothing marches in pseudo-time")
+            if self.flags & (B.IBH_IMAGE_ONLY | B.IBH_PHASE_INTERIOR | B.IBH_PHASE_BOUNDARY | B.IBH_PASS_A_ONLY
+                             | B.IBH_PASS_B_ONLY):
+                raise ValueError("smoothing: IBH_IMAGE_ONLY, the overlap phases and the single-pass flags are not taken: "
+                                 "the smoothing gathers the residual of every cell")
+            self._smooth = tuple(B.colmajor_empty(nc, nv) for _ in range(min(self.smoothing[1] - 1, 2)))
         self.nsteps = 0
 
     def step(self, P):
@@ -276,6 +297,23 @@ class EulerMarch:
         update of the record's form into ``out``."""
         form, base, coef = record
         base = src if base == "src" else P0
+        if self.smoothing is not None:
+            eps, n_iter = self.smoothing
+            if self.residual is not None:
+                self.residual(self.part, src, self.work)
+            else:
+                sweep = B.residual_euler_hll if self.scheme == "hll" else B.residual_euler_sensor
+                sweep(self.part, src, out=self.work, flags=self.flags, fluid=self.fluid)
+            prev = self.work
+            if n_iter >= 2:
+                prev = B.smooth_residual(self.part, self.work, eps, n_iter - 1, out=self._smooth[0],
+                                         tmp=self._smooth[1] if n_iter >= 3 else None)
+            if form == "ssp":
+                B.update_euler_smoothed(self.part, P0, src, self.work, prev, eps, self.dt, coef, self.fluid, out=out)
+            else:   # a forward-Euler step is the stage on the step's input with c = 1: 1 * dt is exact
+                B.update_euler_smoothed(self.part, base, None, self.work, prev, eps, self.dt, coef or (1.0,), self.fluid,
+                                        out=out)
+            return
         if self.residual is not None:
             self.residual(self.part, src, self.work)
             if form == "step":

@@ -487,6 +487,31 @@ int ibh_update_euler_ssp(const ibh_fluid*, int nd, int64_t n, const float* P0, i
 int ibh_stage_euler_ssp(ibh_part*, const ibh_fluid*, int scheme /* IBH_EULER_HLL | IBH_EULER_SENSOR */, const float* P,
                         int64_t ldp, const float* P0, int64_t ld0, float* P_out, int64_t ldo, const float* dt, int dt_per_cell,
                         float a, float b, float c, float* work /* nc x (nd+2) or NULL */, int64_t ldw, int flags);
+/* ---- implicit residual smoothing (not in the reference): between the sweep and the update of a stage the residual R is
+ *   replaced by n_iter Jacobi iterations on (I + eps L) S = R, L the unweighted Laplacian of the partition's face graph.
+ *   With F(i) the faces of cell i -- dimensions ascending, in a dimension its left faces in list order (the cell across is the
+ *   face's owner), then its right faces (the face's neighbour; a mirror face is across from i itself) -- and n_i = |F(i)|:
+ *     S^m_i = (R_i + eps * sum_{f in F(i)} S^{m-1}_{across(f, i)}) / (1 + eps * float(n_i)),   S^0 = R,   m = 1 .. n_iter,
+ *   per variable, the sum started from its first term and added in the order of F(i), every product, sum and the divide
+ *   rounded on its own in Float32.  eps >= 0 is one value for all variables; eps = 0 returns R (a zero may change its sign).
+ *   Ghost cells take part like any other cell.  The converged S keeps sum(S) = sum(R); a constant R is a fixed point.
+ * ibh_smooth_residual: n_iter >= 1 iterations on the nv <= 8 columns of R, one launch each; the result lands in S.  tmp, the
+ *   ping-pong partner of S, is required from n_iter = 2.  S and tmp may alias neither each other nor R.
+ * ibh_update_euler_smoothed: ONE more iteration from (R, Sprev) inside the update, in one launch; the smoothed residual is
+ *   never written.  blend = 0: ibh_update_euler_stage(P0, S, dt, c) -- P, a and b are ignored; blend = 1:
+ *   ibh_update_euler_ssp(P0, P, S, dt, a, b, c).  Bit for bit ibh_smooth_residual(n_iter = 1 from Sprev) followed by that
+ *   update.  Sprev == R is the only iteration.  P_out may be P0 or P; it may not be R or Sprev, which other cells
+ *   gather.  A smoothed stage with n_iter iterations is the sweep, ibh_smooth_residual(n_iter - 1) and this: n_iter + 1
+ *   launches.
+ * Every misuse (null pointer, nd other than 2 or 3, nv outside 1 .. 8, a leading dimension below nc, eps negative or not
+ * finite, n_iter < 1, a missing tmp, a partition without side table, the aliasing above) is an error before any launch; nc == 0
+ * is no error and no launch. */
+int ibh_smooth_residual(const ibh_part*, const float* R, int nv, int64_t ldr, float eps, int n_iter, float* S, int64_t lds,
+                        float* tmp /* NULL for n_iter == 1 */, int64_t ldt);
+int ibh_update_euler_smoothed(const ibh_part*, const ibh_fluid*, int blend /* 0 stage, 1 Shu-Osher */, const float* P0,
+                              int64_t ld0, const float* P, int64_t ldp, const float* R, int64_t ldr, const float* Sprev,
+                              int64_t lds, float eps, const float* dt, int dt_per_cell, float a, float b, float c,
+                              float* P_out, int64_t ldo);
 int ibh_axpy_clamped(int64_t n, float omega, const float* r, float* q);
 /* y = a*x + y */
 int ibh_axpy(int64_t n, float a, const float* x, float* y);

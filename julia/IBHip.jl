@@ -909,6 +909,38 @@ function stage_euler_ssp!(P_out::HipArray{Float32}, part::HipPartition, P::HipAr
     P_out
 end
 
+"Implicit residual smoothing (not in ImmersedBoundary.jl): `n_iter` Jacobi iterations on `(I + eps L) S = R`, `L` the unweighted
+Laplacian of the partition's face graph, `S_i = (R_i + eps * Σ_f S[across(f, i)]) / (1 + eps * n_i)` from `S = R`, per column of
+`R` (at most 8), one launch each.  The result lands in `S`; `tmp`, its ping-pong partner, is required from `n_iter = 2`.  `S` and
+`tmp` alias neither each other nor `R`."
+function smooth_residual!(S::HipArray{Float32}, part::HipPartition, R::HipArray{Float32}, eps::Real, n_iter::Integer;
+                          tmp::Union{HipArray{Float32}, Nothing} = nothing)
+    check(ccall((:ibh_smooth_residual, lib), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Int64, Cfloat, Cint, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64),
+        part.handle, R.ptr, size(R, 2), ld(R), Float32(eps), n_iter, S.ptr, ld(S), isnothing(tmp) ? C_NULL : tmp.ptr,
+        isnothing(tmp) ? 0 : ld(tmp)))
+    S
+end
+
+"The last iteration of a residual smoothing inside the update, in one launch: with `S` one iteration of `smooth_residual!` from
+`Sprev` (which may be `R`: the only iteration), `coef = (c,)` is `update_euler_stage!(P_out, fluid, P0, S, dt, c)` (`P` is
+ignored and may be `nothing`) and `coef = (a, b, c)` is `update_euler_ssp!(P_out, fluid, P0, P, S, dt, a, b, c)`, bit for bit and
+without `S` being written.  `P_out` may be `P0` or `P`, not `R` or `Sprev`."
+function update_euler_smoothed!(P_out::HipArray{Float32}, part::HipPartition, fluid, P0::HipArray{Float32},
+                                P::Union{HipArray{Float32}, Nothing}, R::HipArray{Float32}, Sprev::HipArray{Float32}, eps::Real,
+                                dt::HipArray{Float32}, coef::Tuple)
+    blend = length(coef) == 3
+    a, b, c = blend ? coef : (0, 1, coef[1])
+    f = Ref(IbhFluid(fluid))
+    check(ccall((:ibh_update_euler_smoothed, lib), Cint,
+        (Ptr{Cvoid}, Ptr{IbhFluid}, Cint, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Cfloat,
+         Ptr{Cvoid}, Cint, Cfloat, Cfloat, Cfloat, Ptr{Cvoid}, Int64),
+        part.handle, f, blend ? 1 : 0, P0.ptr, ld(P0), isnothing(P) ? C_NULL : P.ptr, isnothing(P) ? 0 : ld(P), R.ptr, ld(R),
+        Sprev.ptr, ld(Sprev), Float32(eps), dt.ptr, length(dt) == 1 ? 0 : 1, Float32(a), Float32(b), Float32(c), P_out.ptr,
+        ld(P_out)))
+    P_out
+end
+
 "`S .+ Σ_d green_gauss(at_faces(ν .+ νR, d) .* face_gradient(R, d) .- at_faces(vel[:, d] .* R, d), d)` in one launch
 (the transport residual closed by `Wray_Agarwal`, src/turbulence.jl:222-241), bit-identical to the composition."
 function scalar_transport!(out::HipArray{Float32}, part::HipPartition, R::HipArray{Float32}, νR::HipArray{Float32},
