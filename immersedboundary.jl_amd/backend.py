@@ -835,7 +835,8 @@ def timestep_euler(part, P, fluid=None, scale=1.0, out=None, cells=None):
 def _update_args(what, states, dt, out, R=None, n=None, nd=None):
     """The arguments of an Euler update ``what``, checked: the primitive ``states`` in the order of the C call (the first one
     gives ``n`` and ``nd`` where the partition does not), the residual ``R`` (None for a step, which sweeps it itself), ``dt``
-    and ``out`` (None: a new array).  Returns ``(n, nv, S, R, D, O, out, keep)``: ``S``, ``R``, ``D``, ``O`` are the C arguments
+    (None where the call takes none: ``D`` is then empty) and ``out`` (None: a new array).  Returns
+    ``(n, nv, S, R, D, O, out, keep)``: ``S``, ``R``, ``D``, ``O`` are the C arguments
     of the states (pointer, leading dimension, ...), of ``R``, of ``dt`` (pointer, per_cell) and of ``out``; ``keep`` holds
     the tensors they point into and stays with the caller until the call has returned."""
     rows, nv, S, keep = "n" if n is None else "nc", None, [], []
@@ -851,13 +852,16 @@ def _update_args(what, states, dt, out, R=None, n=None, nd=None):
             raise ValueError(f"R must be (n, {nv})")
         Ra = [_ptr(R), ldr]
         keep.append(R)
-    dt, per_cell = _device_dt(dt, n, what)
+    D = []
+    if dt is not None:   # (dual_source alone takes no time step)
+        dt, per_cell = _device_dt(dt, n, what)
+        D = [_ptr(dt), per_cell]
     if out is None:
         out = colmajor_empty(n, nv)
     o, nvo, ldo = _field_inplace(out, n, "out")
     if nvo != nv:
         raise ValueError(f"out must be ({rows}, {nv})")
-    return n, nv, S, Ra, [_ptr(dt), per_cell], [_ptr(o), ldo], out, keep + [dt, o]
+    return n, nv, S, Ra, D, [_ptr(o), ldo], out, keep + [dt, o]
 
 
 def _step_args(what, part, states, dt, out, work, scheme):
@@ -950,6 +954,78 @@ def stage_euler_ssp(part, P, P0, dt, a, b, c, out, fluid=None, scheme="hll", wor
     _stream()
     call("ibh_stage_euler_ssp", part.handle, C.byref(f), sch, *S, *O, *D, C.c_float(a), C.c_float(b), C.c_float(c),
          *W, int(flags))
+    return out
+
+
+def _dual_g(what, g):
+    """``g`` of a dual time step, checked: finite and >= 0."""
+    g = float(g)
+    if not (g >= 0.0 and g != float("inf")):
+        raise ValueError(f"{what}: g must be finite and >= 0")
+    return g
+
+
+def _dual_S(what, S, n, nv, others):
+    """The C arguments (pointer, leading dimension) of the source ``S`` of a dual time step, ``(n, nv)`` in conserved
+    variables; it is none of the arrays ``others`` that the call writes."""
+    S, nvs, lds = _field(S, n)
+    if nvs != nv:
+        raise ValueError(f"{what}: S must be ({n}, {nv})")
+    for name, t in others:
+        if t is not None and t.data_ptr() == S.data_ptr():
+            raise ValueError(f"{what}: S may not be {name}")
+    return S, [_ptr(S), lds]
+
+
+@_hipaware
+def dual_source(Pn, Pm, cn, cm, fluid=None, out=None):
+    """The source of a physical step of a dual time march, ``primitive2state(fluid, Pn) .* cn .+ primitive2state(fluid, Pm)
+    .* cm`` in one launch -- the part of the backward difference that the inner iterations leave alone -- or, with
+    ``Pm=None`` (BDF1, the first step), ``primitive2state(fluid, Pn) .* cn``: bit for bit those launches.  ``cn``, ``cm``:
+    ``solver.bdf_coefficients``.  Returns ``out`` (None: a new array), conserved variables ``(n, nd+2)``."""
+    states = (Pn,) if Pm is None else (Pn, Pm)
+    n, nv, S, _, _, O, out, keep = _update_args("dual_source", states, None, out)
+    if Pm is None:
+        S += [c_vp(None), 0]
+    if any(out.data_ptr() == P.data_ptr() for P in keep[:len(states)]):
+        raise ValueError("dual_source: out may not be Pn or Pm")
+    f = _cfluid(fluid)
+    _stream()
+    call("ibh_dual_source", C.byref(f), nv - 2, n, *S, C.c_float(cn), C.c_float(cm), *O)
+    return out
+
+
+@_hipaware
+def update_euler_dual(P0, R, S, dt, alpha, g, fluid=None, out=None):
+    """A pseudo-time stage of a dual time step, ``state2primitive(fluid, (primitive2state(fluid, P0) .+ (R .+ S) .* h) ./ (h
+    .* g .+ 1))`` with ``h = dt .* alpha`` in one launch, every sum, product and the divide rounded on its own: bit for bit
+    that composition of launches.  ``S``: ``dual_source``; ``g``: the coefficient of the new state in the backward
+    difference, taken point-implicitly (``g = 0`` with ``S`` zeros: ``update_euler_stage``).  ``dt``: a one-element device
+    tensor, or ``(n,)`` for a per-cell time step.  ``out`` may be ``P0`` itself."""
+    g = _dual_g("update_euler_dual", g)
+    n, nv, Sa, Ra, D, O, out, keep = _update_args("update_euler_dual", (P0,), dt, out, R)
+    S, Sc = _dual_S("update_euler_dual", S, n, nv, (("out", out),))
+    f = _cfluid(fluid)
+    _stream()
+    call("ibh_update_euler_dual", C.byref(f), nv - 2, n, *Sa, *Ra, *Sc, *D, C.c_float(alpha), C.c_float(g), *O)
+    return out
+
+
+@_hipaware
+def stage_euler_dual(part, P, P0, S, dt, alpha, g, out, fluid=None, scheme="hll", work=None, flags=0):
+    """One pseudo-time stage of a dual time step, ``out = update_euler_dual(P0, residual_euler_hll | residual_euler_sensor(
+    part, P, flags), S, dt, alpha, g)``: ``P`` is the previous stage, ``P0`` the state the pseudo-step started from, ``S``
+    the source of the physical step.  ``stage_euler``'s dispatch: one launch where the 2-D single-kernel sweep takes the whole
+    partition and ``out`` is not ``P``, with a one-element and with a per-cell ``dt``; elsewhere the sweep goes into ``work``
+    -- ``(nc, nd+2)``, required there: the stage allocates nothing -- and the update follows.  ``out`` may be ``P0`` when
+    ``P0`` is not ``P``; ``S`` is neither ``out`` nor ``work``.  Same bits either way."""
+    g = _dual_g("stage_euler_dual", g)
+    part, sch, Sa, D, O, W, out, keep = _step_args("stage_euler_dual", part, (P, P0), dt, out, work, scheme)
+    S, Sc = _dual_S("stage_euler_dual", S, part.nc, part.nd + 2, (("out", out), ("work", work)))
+    f = _cfluid(fluid)
+    _stream()
+    call("ibh_stage_euler_dual", part.handle, C.byref(f), sch, *Sa, *Sc, *O, *D, C.c_float(alpha), C.c_float(g), *W,
+         int(flags))
     return out
 
 

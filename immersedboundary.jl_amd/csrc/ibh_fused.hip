@@ -8,6 +8,7 @@
 //   ibh_fused3d.hip        3-D sweeps: column and thread-per-cell forms, the 3-D block kernels of the two-kernel form
 //   ibh_fused_general.hip  the two-kernel form through the gradient workspace (face-list threads + 2-D block bodies)
 // and the block closures of the turbulence model in ibh_turb.hip.  No kernel and no kernel header here.
+#include <float.h>
 #include <string.h>
 
 #include "ibh_common.h"
@@ -146,8 +147,9 @@ int ibh_residual_euler_sensor(ibh_part* p, const float* P, int64_t ldp, const fl
                           "eligible for the single-kernel sweep; run the sweep unphased after the exchange");
 }
 
-// The Euler step in its three forms (EulerForm), P_out = the form's update with R = R(P): what ibh_step_euler,
-// ibh_stage_euler and ibh_stage_euler_ssp share -- the checks, the one-launch condition and the two-launch tail.  `e` holds the
+// The Euler step in its four forms (EulerForm), P_out = the form's update with R = R(P): what ibh_step_euler,
+// ibh_stage_euler, ibh_stage_euler_ssp and ibh_stage_euler_dual share -- the checks, the one-launch condition and the
+// two-launch tail.  `e` holds the
 // entry's arguments (e.R is P_out; the step form's base state is P itself), `name` the entry for its messages.
 // One launch where the 2-D single-kernel sweep takes the whole partition (EUL2_SINGLE without image / phase flags) and P_out
 // != P: the sweep's store epilogue writes the form itself.  The step form also needs a global dt there; the stage forms load
@@ -156,10 +158,11 @@ int ibh_residual_euler_sensor(ibh_part* p, const float* P, int64_t ldp, const fl
 // ibh_update_euler* runs: two launches.  Same bits either way.
 static int euler_form(const char* name, ibh_part* p, int scheme, EulerArgs e, int dt_per_cell, float* work, int64_t ldw,
                       int flags) {
-    const bool step = e.form == FORM_STEP;
-    const char* const update = step ? "ibh_update_euler" : e.form == FORM_STAGE ? "ibh_update_euler_stage" : "ibh_update_euler_ssp";
+    const bool step = e.form == FORM_STEP, dual = e.form == FORM_DUAL;
+    const char* const update = step ? "ibh_update_euler" : e.form == FORM_STAGE ? "ibh_update_euler_stage"
+                               : dual ? "ibh_update_euler_dual" : "ibh_update_euler_ssp";
 #define FORM_REQUIRE(cond, ...) IBH_REQUIRE(cond, (std::string(name) + __VA_ARGS__).c_str())  // (the text is built on failure only)
-    FORM_REQUIRE(p && e.fluid && e.P && e.P0 && e.R && e.dt, ": null argument");
+    FORM_REQUIRE(p && e.fluid && e.P && e.P0 && e.R && e.dt && (!dual || e.S), ": null argument");
     FORM_REQUIRE(scheme == EULER_HLL || scheme == EULER_SENSOR, ": scheme must be 0 (HLL) or 1 (sensor)");
     FORM_REQUIRE(!(flags & IBH_IMAGE_ONLY), ": IBH_IMAGE_ONLY is not taken: the update would read skirt rows that the sweep never "
                                             "wrote (the multi-GPU step is out of scope)");
@@ -168,8 +171,13 @@ static int euler_form(const char* name, ibh_part* p, int scheme, EulerArgs e, in
     FORM_REQUIRE(!(flags & (IBH_PASS_A_ONLY | IBH_PASS_B_ONLY)), ": a single pass of the sweep is no " + (step ? "step" : "stage"));
     FORM_REQUIRE(p->nd == 2 || p->nd == 3, ": nd must be 2 or 3");
     FORM_REQUIRE(e.ldp >= p->nc && e.ld0 >= p->nc && e.ldr >= p->nc, ": a leading dimension is smaller than the number of cells");
-    FORM_REQUIRE(!work || (work != e.P && work != e.P0 && work != e.R),
-                 ": work may not alias " + (step ? "P or P_out" : "P, P0 or P_out"));
+    FORM_REQUIRE(!work || (work != e.P && work != e.P0 && work != e.R && work != e.S),
+                 ": work may not alias " + (step ? "P or P_out" : dual ? "P, P0, S or P_out" : "P, P0 or P_out"));
+    if (dual) {
+        FORM_REQUIRE(e.lds >= p->nc, ": lds is smaller than the number of cells");
+        FORM_REQUIRE(e.g >= 0.0f && e.g <= FLT_MAX, ": g must be finite and >= 0");
+        FORM_REQUIRE(e.S != e.R, ": S may not alias P_out");
+    }
     if (p->nc == 0) return 0;
     e.scheme = scheme == EULER_SENSOR ? EULER_SENSOR : EULER_HLL;
     e.dt_cells = dt_per_cell != 0;
@@ -188,6 +196,9 @@ static int euler_form(const char* name, ibh_part* p, int scheme, EulerArgs e, in
     if (step) return ibh_update_euler(e.fluid, p->nd, p->nc, e.P, e.ldp, work, ldw, e.dt, dt_per_cell, e.R, e.ldr);
     if (e.form == FORM_STAGE)
         return ibh_update_euler_stage(e.fluid, p->nd, p->nc, e.P0, e.ld0, work, ldw, e.dt, dt_per_cell, e.c, e.R, e.ldr);
+    if (dual)
+        return ibh_update_euler_dual(e.fluid, p->nd, p->nc, e.P0, e.ld0, work, ldw, e.S, e.lds, e.dt, dt_per_cell, e.c, e.g, e.R,
+                                     e.ldr);
     return ibh_update_euler_ssp(e.fluid, p->nd, p->nc, e.P0, e.ld0, e.P, e.ldp, work, ldw, e.dt, dt_per_cell, e.a, e.b, e.c, e.R,
                                 e.ldr);
 }
@@ -226,6 +237,20 @@ int ibh_stage_euler_ssp(ibh_part* p, const ibh_fluid* fluid, int scheme, const f
     e.form = FORM_SSP, e.dt = dt;
     e.P0 = P0, e.ld0 = ld0, e.c = c, e.a = a, e.b = b;
     return euler_form("ibh_stage_euler_ssp", p, scheme, e, dt_per_cell, work, ldw, flags);
+}
+
+// One pseudo-time stage of a dual time step, P_out = state2primitive((primitive2state(P0) + (R(P) + S) * (alpha * dt)) / (1 +
+// (alpha * dt) * g)): ibh_stage_euler with the physical time derivative g Q - S of the implicit step taken point-implicitly
+// (S: ibh_dual_source, conserved variables, constant during the inner iterations).  P_out may be P0 where P0 is not P; S
+// aliases neither P_out nor work.  Same bits as ibh_update_euler_dual(P0, R(P), S, dt, alpha, g) in one launch or two.
+int ibh_stage_euler_dual(ibh_part* p, const ibh_fluid* fluid, int scheme, const float* P, int64_t ldp, const float* P0,
+                         int64_t ld0, const float* S, int64_t lds, float* P_out, int64_t ldo, const float* dt, int dt_per_cell,
+                         float alpha, float g, float* work, int64_t ldw, int flags) {
+    EulerArgs e{P, ldp, P_out, ldo, fluid};
+    e.form = FORM_DUAL, e.dt = dt;
+    e.P0 = P0, e.ld0 = ld0, e.c = alpha;
+    e.S = S, e.lds = lds, e.g = g;
+    return euler_form("ibh_stage_euler_dual", p, scheme, e, dt_per_cell, work, ldw, flags);
 }
 
 // One step, u_out = u + dt * residual: in one launch where the quad sweep covers the whole partition (it stores the update,

@@ -212,7 +212,7 @@ __global__ __launch_bounds__(64 * WPB) void k_step_quad(float* __restrict__ u, c
 #endif
 // FORM (EulerForm, ibh_euler_step_dev.h): beyond FORM_RESIDUAL `R` is P_out and receives the updated primitives; dt = *dtp,
 // one scalar load per wave as in k_sweep_quad<..., STEP>, or (DTC, the stage forms) dtp holds one time step per cell and is
-// read where the cell is.  P0, ld0, c, sa, sb: euler_step::FormArgs
+// read where the cell is.  P0, ld0, c, sa, sb, Sd, ldsd, g: euler_step::FormArgs (Sd, ldsd: the source S of FORM_DUAL)
 template <int SCH = EULER_HLL, int FORM = FORM_RESIDUAL, bool DTC = false>
 __global__ __launch_bounds__(64 * WPBE) void k_sweep_euler(const float* __restrict__ P, uint32_t ldp,
                                                            float* __restrict__ R, uint32_t ldr, float Rgas, float gamma,
@@ -223,7 +223,8 @@ __global__ __launch_bounds__(64 * WPBE) void k_sweep_euler(const float* __restri
                                                            int32_t iters, const int32_t* __restrict__ blist,
                                                            const float* __restrict__ dtp = nullptr,
                                                            const float* P0 = nullptr, uint32_t ld0 = 0, float c = 1.0f,
-                                                           float sa = 0.0f, float sb = 1.0f) {
+                                                           float sa = 0.0f, float sb = 1.0f, const float* Sd = nullptr,
+                                                           uint32_t ldsd = 0, float g = 0.0f) {
     __shared__ float lds[WPBE * BLK2_SWEEP_EULER_LDS];
     float dt = 0.0f;
     if constexpr (FORM != FORM_RESIDUAL && !DTC) dt = *dtp;
@@ -232,7 +233,8 @@ __global__ __launch_bounds__(64 * WPBE) void k_sweep_euler(const float* __restri
     if (first >= nblk) return;
     const int32_t nb = __builtin_amdgcn_readfirstlane(min(iters, (nblk - first + WPBE - 1) / WPBE));
     blk2::sweep_euler<SCH, FORM, DTC>(blocks, htab, etab, dtab, blist, first, WPBE, nb, P, ldp, R, ldr, blk2::Gas{Rgas, gamma},
-                                      lds + wave * BLK2_SWEEP_EULER_LDS, lane, dt, euler_step::FormArgs{P0, ld0, c, dtp, sa, sb});
+                                      lds + wave * BLK2_SWEEP_EULER_LDS, lane, dt,
+                                      euler_step::FormArgs{P0, ld0, c, dtp, sa, sb, Sd, ldsd, g});
 }
 
 // Quad form of the Euler sweep (quad2::sweep_quad_euler): grid = [quad workgroups | single-block workgroups], like
@@ -260,11 +262,12 @@ __global__ __launch_bounds__(64 * WPBE) __attribute__((amdgpu_waves_per_eu(QE_WA
                                                                 const float* __restrict__ dtp = nullptr,
                                                                 const float* P0 = nullptr, uint32_t ld0 = 0,
                                                                 float c = 1.0f, float sa = 0.0f,
-                                                                float sb = 1.0f) {
+                                                                float sb = 1.0f, const float* Sd = nullptr,
+                                                                uint32_t ldsd = 0, float g = 0.0f) {
     __shared__ __attribute__((aligned(16))) float lds[QUADE_WG_LDS];
     float dt = 0.0f;
     if constexpr (FORM != FORM_RESIDUAL && !DTC) dt = *dtp;  // (scalar load: the time step lives on the device, ibh_timestep_euler)
-    const euler_step::FormArgs fa{P0, ld0, c, dtp, sa, sb};
+    const euler_step::FormArgs fa{P0, ld0, c, dtp, sa, sb, Sd, ldsd, g};
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int32_t wg = singles_first ? ((int32_t)blockIdx.x < nwgs ? (int32_t)blockIdx.x + nwgq : (int32_t)blockIdx.x - nwgs)
                                      : (int32_t)blockIdx.x;
@@ -312,9 +315,10 @@ BlockList block_list(const ibh_part* p, const int32_t* list, Range r, int wpb, i
 }
 
 // The map (scheme, form, per-cell dt) -> instantiation of an Euler sweep kernel template K, written once for k_sweep_euler and
-// k_sweep_quad_euler: twelve of each.  FORM_STEP with a per-cell dt is none of them (ibh_step_euler sends it to two launches)
+// k_sweep_quad_euler: sixteen of each.  FORM_STEP with a per-cell dt is none of them (ibh_step_euler sends it to two launches)
 #define EULER_FORM_OF(K, S, e)                                                            \
-    ((e).form == FORM_SSP     ? ((e).dt_cells ? K<S, FORM_SSP, true> : K<S, FORM_SSP>)     \
+    ((e).form == FORM_DUAL    ? ((e).dt_cells ? K<S, FORM_DUAL, true> : K<S, FORM_DUAL>)   \
+     : (e).form == FORM_SSP   ? ((e).dt_cells ? K<S, FORM_SSP, true> : K<S, FORM_SSP>)     \
      : (e).form == FORM_STAGE ? ((e).dt_cells ? K<S, FORM_STAGE, true> : K<S, FORM_STAGE>) \
      : (e).form == FORM_STEP  ? K<S, FORM_STEP>                                            \
                               : K<S>)
@@ -391,8 +395,8 @@ void adv2_single(const ibh_part* p, const AdvArgs& a, int flags, Phase ph, int k
 }
 
 // every block eligible, or only the image blocks wanted and all of them eligible: one launch per phase, no workspace
-// e.form beyond FORM_RESIDUAL (ibh_step_euler, ibh_stage_euler, ibh_stage_euler_ssp): that form of the same kernels -- e.R is
-// P_out and receives the updated primitives
+// e.form beyond FORM_RESIDUAL (ibh_step_euler, ibh_stage_euler, ibh_stage_euler_ssp, ibh_stage_euler_dual): that form of the
+// same kernels -- e.R is P_out and receives the updated primitives
 void euler2_single(const ibh_part* p, const EulerArgs& e, int flags, Phase ph) {
     const int k = p->fuse_all ? 0 : 1;  // quad set; block list: all blocks / the image blocks
     if (quads_usable(p, k, flags)) {
@@ -403,7 +407,7 @@ void euler2_single(const ibh_part* p, const EulerArgs& e, int flags, Phase ph) {
                                (uint32_t)e.ldp, e.R, (uint32_t)e.ldr, e.fluid->R, e.fluid->gamma, p->qd[k] + r.q.first,
                                p->qtab[k] + (size_t)r.q.first * IBH_QROW, r.q.count(), nwgq, p->blocks2, p->htab, p->etab,
                                p->dtab, p->qsingles[k] + r.s.first, r.s.count(), nwgs, T.quad_singles_first, e.dt, e.P0,
-                               (uint32_t)e.ld0, e.c, e.a, e.b);
+                               (uint32_t)e.ld0, e.c, e.a, e.b, e.S, (uint32_t)e.lds, e.g);
         return;
     }
     const Range b = p->fuse_all ? ph.of(p->nB1, p->nblk) : ph.of(p->n_img_int, p->n_img);
@@ -411,7 +415,7 @@ void euler2_single(const ibh_part* p, const EulerArgs& e, int flags, Phase ph) {
     const BlockList L = block_list(p, p->fuse_all ? nullptr : p->img_list, b, WPBE, 4);
     hipLaunchKernelGGL(EULER_KERNEL(k_sweep_euler, e), dim3(L.nwg), dim3(64 * WPBE), 0, ibh_stream, e.P, (uint32_t)e.ldp, e.R,
                        (uint32_t)e.ldr, e.fluid->R, e.fluid->gamma, L.bl, L.ht, L.et, p->dtab, L.count, L.nwg, L.iters, L.ls, e.dt,
-                       e.P0, (uint32_t)e.ld0, e.c, e.a, e.b);
+                       e.P0, (uint32_t)e.ld0, e.c, e.a, e.b, e.S, (uint32_t)e.lds, e.g);
 }
 
 // sweep and update in one launch: the quad sweep stores u + dt * residual (its cells of u are in registers)

@@ -81,13 +81,16 @@ struct AdvArgs { const float *u, *C; int64_t ldc; float* ud; };
 struct EulerArgs {  // (the entries' fields)
     const float* P; int64_t ldp; float* R; int64_t ldr; const ibh_fluid* fluid;
     EulerScheme scheme = EULER_HLL; const float* nu = nullptr;
-    // ibh_step_euler, ibh_stage_euler, ibh_stage_euler_ssp on a single-kernel path: the form the sweep stores (R is then P_out)
+    // ibh_step_euler, ibh_stage_euler, ibh_stage_euler_ssp, ibh_stage_euler_dual on a single-kernel path: the form the sweep
+    // stores (R is then P_out)
     // and what the form reads (euler_step::FormArgs) -- from FORM_STEP on dt, one value or (dt_cells, the stage forms only) one
-    // per cell; from FORM_STAGE on the base state P0 (it may be R) and the coefficient c of dt; FORM_SSP the weights a and b
+    // per cell; from FORM_STAGE on the base state P0 (it may be R) and the coefficient c of dt; FORM_SSP the weights a and b;
+    // FORM_DUAL the source S of the physical step and the coefficient g
     EulerForm form = FORM_RESIDUAL;
     const float* dt = nullptr; bool dt_cells = false;
     const float* P0 = nullptr; int64_t ld0 = 0; float c = 1.0f;
     float a = 0.0f, b = 1.0f;
+    const float* S = nullptr; int64_t lds = 0; float g = 0.0f;
 };
 
 // ---- advection: paths

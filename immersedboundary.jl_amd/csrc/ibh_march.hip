@@ -13,8 +13,12 @@
 //     the low-storage family; the stage around it is ibh_stage_euler in ibh_fused.hip.
 //   * ibh_update_euler_ssp: a Shu-Osher stage, the update of the blend a primitive2state(P0) + b primitive2state(P) with the
 //     time step c * dt (euler_step::blend_row); the stage around it is ibh_stage_euler_ssp in ibh_fused.hip.
+//   * ibh_update_euler_dual, ibh_dual_source: a pseudo-time stage of a dual time step with the physical time derivative taken
+//     point-implicitly (euler_step::dual_row), and the constant part of that derivative; the stage around the first is
+//     ibh_stage_euler_dual in ibh_fused.hip.
 // Arithmetic: the operator kernels' (ibh_ops.hip): -ffp-contract=off, the reference's evaluation order.
 #include <algorithm>
+#include <cfloat>
 #include <cstdlib>
 #include <vector>
 
@@ -114,8 +118,9 @@ __global__ void k_update_dev(int64_t n, const float* __restrict__ dt, const floa
 }
 
 // The update kernels of an Euler step, one per form (EulerForm, ibh_euler_step_dev.h) and each with its entry's own argument
-// list.  The three grid-stride loops are written out: moved into one device function template over the form, the same loop
-// compiles to other instruction orders in all twelve instantiations (scripts/kernel_bodies.py), and these kernels are held
+// list.  The grid-stride loops are written out, k_update_euler_dual's too: moved into one device function template over the
+// form, the same loop compiles to other instruction orders in all twelve instantiations of the first three
+// (scripts/kernel_bodies.py), and these kernels are held
 // instruction for instruction.  What differs between them is which rows are loaded and the one call of a row function.
 // P_out = state2primitive(primitive2state(P) + dt R), one thread per row: the row is read whole before it is written, so
 // P_out may be P (no __restrict__ on the two).  dt: one value, or one per row (PER_CELL)
@@ -187,6 +192,52 @@ __global__ __launch_bounds__(MARCH_BLOCK) void k_update_euler_ssp(float Rgas, fl
         euler_step::blend_row<ND>(Rgas, gamma, Br, Pr, r, a, b, h, o);
 #pragma unroll
         for (int v = 0; v < NV; ++v) P_out[i + v * ldo] = o[v];
+    }
+}
+
+// A pseudo-time stage of a dual time step: P_out = state2primitive((primitive2state(P0) + (R + S) (alpha dt)) / (1 + (alpha dt)
+// g)) (euler_step::dual_row).  The rows of P0, R and S are read whole before the row of P_out is written: P_out may be P0
+template <int ND, bool PER_CELL>
+__global__ __launch_bounds__(MARCH_BLOCK) void k_update_euler_dual(float Rgas, float gamma, int64_t n, const float* P0,
+                                                                   int64_t ld0, const float* __restrict__ R, int64_t ldr,
+                                                                   const float* __restrict__ S, int64_t lds,
+                                                                   const float* __restrict__ dt, float alpha, float g,
+                                                                   float* P_out, int64_t ldo) {
+    constexpr int NV = ND + 2;
+    float h = 0.0f;
+    if constexpr (!PER_CELL) h = euler_step::stage_dt(alpha, *dt);
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        float Pr[NV], r[NV], s[NV], o[NV];
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+            Pr[v] = P0[i + v * ld0];
+            r[v] = R[i + v * ldr];
+            s[v] = S[i + v * lds];
+        }
+        if constexpr (PER_CELL) h = euler_step::stage_dt(alpha, dt[i]);
+        euler_step::dual_row<ND>(Rgas, gamma, Pr, r, s, h, g, o);
+#pragma unroll
+        for (int v = 0; v < NV; ++v) P_out[i + v * ldo] = o[v];
+    }
+}
+
+// The source of a physical step, S = primitive2state(Pn) cn [+ primitive2state(Pm) cm] (euler_step::dual_source_row), one
+// thread per row.  S aliases neither state (ibh_dual_source checks it)
+template <int ND, bool BDF2>
+__global__ __launch_bounds__(MARCH_BLOCK) void k_dual_source(float Rgas, float gamma, int64_t n, const float* __restrict__ Pn,
+                                                             int64_t ldn, const float* __restrict__ Pm, int64_t ldm, float cn,
+                                                             float cm, float* __restrict__ S, int64_t lds) {
+    constexpr int NV = ND + 2;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        float a[NV], b[NV] = {}, s[NV];
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+            a[v] = Pn[i + v * ldn];
+            if constexpr (BDF2) b[v] = Pm[i + v * ldm];
+        }
+        euler_step::dual_source_row<ND, BDF2>(Rgas, gamma, a, b, cn, cm, s);
+#pragma unroll
+        for (int v = 0; v < NV; ++v) S[i + v * lds] = s[v];
     }
 }
 
@@ -395,6 +446,47 @@ int ibh_update_euler_ssp(const ibh_fluid* f, int nd, int64_t n, const float* P0,
     if (n == 0) return 0;
     static constexpr decltype(&k_update_euler_ssp<2, false>) k[2][2] = UPDATE_KERNELS(k_update_euler_ssp);
     return launch_update(k, nd, dt_per_cell, n, f->R, f->gamma, n, P0, ld0, P, ldp, R, ldr, dt, a, b, c, P_out, ldo);
+}
+
+// A pseudo-time stage of a dual time step in one launch,
+//     P_out = state2primitive((primitive2state(P0) + (R + S) * (alpha * dt)) / (1 + (alpha * dt) * g)):
+// bit for bit primitive2state, the broadcasts R .+ S, dt .* alpha and h .* g .+ 1, the column updates, the broadcast ./ and
+// state2primitive.  S (conserved variables) and g come from the physical step's backward difference (ibh_dual_source)
+int ibh_update_euler_dual(const ibh_fluid* f, int nd, int64_t n, const float* P0, int64_t ld0, const float* R, int64_t ldr,
+                          const float* S, int64_t lds, const float* dt, int dt_per_cell, float alpha, float g, float* P_out,
+                          int64_t ldo) {
+    IBH_REQUIRE(f && P0 && R && S && dt && P_out, "ibh_update_euler_dual: null argument");
+    IBH_REQUIRE(nd == 2 || nd == 3, "ibh_update_euler_dual: nd must be 2 or 3");
+    IBH_REQUIRE(n >= 0 && ld0 >= n && ldr >= n && lds >= n && ldo >= n,
+                "ibh_update_euler_dual: a leading dimension is smaller than n");
+    IBH_REQUIRE(g >= 0.0f && g <= FLT_MAX, "ibh_update_euler_dual: g must be finite and >= 0");
+    IBH_REQUIRE(P_out != R && P0 != R && P_out != S && R != S,
+                "ibh_update_euler_dual: R and S may alias neither each other nor P_out, R not P0 (P_out may be P0)");
+    if (n == 0) return 0;
+    static constexpr decltype(&k_update_euler_dual<2, false>) k[2][2] = UPDATE_KERNELS(k_update_euler_dual);
+    return launch_update(k, nd, dt_per_cell, n, f->R, f->gamma, n, P0, ld0, R, ldr, S, lds, dt, alpha, g, P_out, ldo);
+}
+
+// The source of a physical step of a dual time march, S = primitive2state(Pn) * cn + primitive2state(Pm) * cm -- the terms of
+// the backward difference that the inner iterations do not change -- or, with Pm null (BDF1, the first step),
+// primitive2state(Pn) * cn: bit for bit primitive2state and the broadcasts Qn .* cn .+ Qm .* cm
+int ibh_dual_source(const ibh_fluid* f, int nd, int64_t n, const float* Pn, int64_t ldn, const float* Pm, int64_t ldm, float cn,
+                    float cm, float* S, int64_t lds) {
+    IBH_REQUIRE(f && Pn && S, "ibh_dual_source: null argument");
+    IBH_REQUIRE(nd == 2 || nd == 3, "ibh_dual_source: nd must be 2 or 3");
+    IBH_REQUIRE(n >= 0 && ldn >= n && lds >= n && (!Pm || ldm >= n), "ibh_dual_source: a leading dimension is smaller than n");
+    IBH_REQUIRE(S != Pn && S != Pm, "ibh_dual_source: S may not alias Pn or Pm");
+    if (n == 0) return 0;
+    const dim3 grid(ibh_grid_cap(n, MARCH_BLOCK, 2048)), block(MARCH_BLOCK);
+    if (Pm) {
+        auto k = nd == 2 ? k_dual_source<2, true> : k_dual_source<3, true>;
+        hipLaunchKernelGGL(k, grid, block, 0, ibh_stream, f->R, f->gamma, n, Pn, ldn, Pm, ldm, cn, cm, S, lds);
+    } else {
+        auto k = nd == 2 ? k_dual_source<2, false> : k_dual_source<3, false>;
+        hipLaunchKernelGGL(k, grid, block, 0, ibh_stream, f->R, f->gamma, n, Pn, ldn, Pn, ldn, cn, cm, S, lds);
+    }
+    IBH_LAUNCH_CHECK();
+    return 0;
 }
 
 }  // extern "C"

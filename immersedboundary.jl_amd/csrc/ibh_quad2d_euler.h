@@ -19,6 +19,9 @@
 // FORM_SSP (ibh_stage_euler_ssp): a Shu-Osher stage -- the cell's own state U stays in registers as in the step form, the row
 // of P0 and the time step are loaded as in the stage form, and euler_step::blend_row updates the blend
 // fa.a primitive2state(P0) + fa.b primitive2state(U).
+// FORM_DUAL (ibh_stage_euler_dual): a pseudo-time stage of a dual time step -- the row of P0 and the time step as in the stage
+// form, the row of the source fa.S at the same offsets (four more v4f loads after the last flux pass), through
+// euler_step::dual_row with fa.g.  U is dead as in the stage form.
 #pragma once
 #include "ibh_quad2d.h"
 #include "ibh_euler_step_dev.h"
@@ -430,12 +433,16 @@ __device__ __forceinline__ void sweep_quad_euler(const QuadDesc2* __restrict__ q
         }
         if constexpr (FORM != FORM_RESIDUAL) {
             // (no __restrict__ on P0: it may be the output; all of this lane's rows of P0 are loaded before its first store)
-            v4f B[QE_NV], O[QE_NV];
+            v4f B[QE_NV], O[QE_NV], Sr[QE_NV];
             v4f h = v4f{dt, dt, dt, dt};
             if constexpr (FORM >= FORM_STAGE) {
 #pragma unroll
                 for (int v = 0; v < QE_NV; ++v) B[v] = *(const v4f_g*)((const char*)(fa.P0 + (size_t)v * fa.ld0) + ((size_t)a0 << 2));
                 if constexpr (DTC) h = *(const v4f_g*)((const char*)fa.dtc + ((size_t)a0 << 2));
+            }
+            if constexpr (FORM == FORM_DUAL) {
+#pragma unroll
+                for (int v = 0; v < QE_NV; ++v) Sr[v] = *(const v4f_g*)((const char*)(fa.S + (size_t)v * fa.lds) + ((size_t)a0 << 2));
             }
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
@@ -445,7 +452,10 @@ __device__ __forceinline__ void sweep_quad_euler(const QuadDesc2* __restrict__ q
                 if constexpr (FORM >= FORM_STAGE) {
                     const float Bc[QE_NV] = {B[0][c], B[1][c], B[2][c], B[3][c]};
                     const float hc = euler_step::stage_dt(fa.c, h[c]);
-                    if constexpr (FORM == FORM_SSP) euler_step::blend_row<2>(gas.R, gas.gamma, Bc, Pc, rc, fa.a, fa.b, hc, o);
+                    if constexpr (FORM == FORM_DUAL) {
+                        const float sc[QE_NV] = {Sr[0][c], Sr[1][c], Sr[2][c], Sr[3][c]};
+                        euler_step::dual_row<2>(gas.R, gas.gamma, Bc, rc, sc, hc, fa.g, o);
+                    } else if constexpr (FORM == FORM_SSP) euler_step::blend_row<2>(gas.R, gas.gamma, Bc, Pc, rc, fa.a, fa.b, hc, o);
                     else euler_step::update_row<2>(gas.R, gas.gamma, Bc, rc, hc, o);
                 } else euler_step::update_row<2>(gas.R, gas.gamma, Pc, rc, dt, o);
 #pragma unroll

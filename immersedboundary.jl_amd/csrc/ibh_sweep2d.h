@@ -434,6 +434,8 @@ __device__ __forceinline__ SweepPreE sweep_prefetch_e(const BlockDesc2* __restri
 // output: a lane reads its row before it stores), and the time step is fa.c * dt -- dt per wave or (DTC) one per lane
 // FORM_SSP (ibh_stage_euler_ssp): a Shu-Osher stage -- T.Pc as in the step form, the row of P0 and the time step as in the
 // stage form, through euler_step::blend_row with the weights fa.a, fa.b
+// FORM_DUAL (ibh_stage_euler_dual): a pseudo-time stage of a dual time step -- the row of P0 and the time step as in the stage
+// form, the cell's row of the source fa.S beside them, through euler_step::dual_row with fa.g
 template <int SCH = EULER_HLL, int FORM = FORM_RESIDUAL, bool DTC = false>
 __device__ __forceinline__ void sweep_euler(const BlockDesc2* __restrict__ blocks, const int32_t* __restrict__ htab,
                                             const int32_t* __restrict__ etab, const int32_t* __restrict__ dtab,
@@ -645,7 +647,12 @@ __device__ __forceinline__ void sweep_euler(const BlockDesc2* __restrict__ block
                 if constexpr (DTC) h = *(const float*)((const char*)fa.dtc + (size_t)(c << 2));
                 h = euler_step::stage_dt(fa.c, h);
             }
-            if constexpr (FORM == FORM_SSP) euler_step::blend_row<2>(gas.R, gas.gamma, b, T.Pc, rv, fa.a, fa.b, h, o);
+            if constexpr (FORM == FORM_DUAL) {
+                float s[4];
+#pragma unroll
+                for (int v = 0; v < 4; ++v) s[v] = *(const float*)((const char*)(fa.S + (size_t)v * fa.lds) + (size_t)(c << 2));
+                euler_step::dual_row<2>(gas.R, gas.gamma, b, rv, s, h, fa.g, o);
+            } else if constexpr (FORM == FORM_SSP) euler_step::blend_row<2>(gas.R, gas.gamma, b, T.Pc, rv, fa.a, fa.b, h, o);
             else if constexpr (FORM == FORM_STAGE) euler_step::update_row<2>(gas.R, gas.gamma, b, rv, h, o);
             else euler_step::update_row<2>(gas.R, gas.gamma, T.Pc, rv, h, o);
 #pragma unroll

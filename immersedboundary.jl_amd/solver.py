@@ -273,7 +273,16 @@ class EulerMarch:
         """One step from ``P`` (any ``(nc, nd+2)`` device array, e.g. the previous return value); returns the new array."""
         if not isinstance(P, torch.Tensor):
             P = P.t                                    # a HipArray: its pending broadcasts are evaluated here
-        if self.nsteps % self.dt_every == 0:
+        src = self._stages(P, self.nsteps)
+        if self.average is not None:
+            self.average.push(src, self.dt)
+        self.nsteps += 1
+        return src
+
+    def _stages(self, P, count, last=None):
+        """The time step -- on every ``dt_every``-th ``count`` -- and the stages of one step from ``P``, ``bcs`` after every
+        one; returns the array of the last stage: one of the ping-pong arrays, or ``last`` where that is given."""
+        if count % self.dt_every == 0:
             if self.local_dt:
                 B.timestep_euler(self.part, P, self.fluid, self.scale, out=False, cells=self.dt)
             else:
@@ -282,14 +291,11 @@ class EulerMarch:
         free = [b for b in self._buf if b.data_ptr() != P.data_ptr()][:2]
         src = P
         for k, record in enumerate(self._records):
-            out = free[k % 2]
+            out = last if last is not None and k == len(self._records) - 1 else free[k % 2]
             self._stage(record, src, P, out)
             if self.bcs is not None:
                 self.bcs(out)
             src = out
-        if self.average is not None:
-            self.average.push(src, self.dt)
-        self.nsteps += 1
         return src
 
     def _stage(self, record, src, P0, out):
@@ -316,7 +322,9 @@ class EulerMarch:
             return
         if self.residual is not None:
             self.residual(self.part, src, self.work)
-            if form == "step":
+            if form == "dual":
+                B.update_euler_dual(base, self.work, self.S, self.dt, *coef, self.g, self.fluid, out=out)
+            elif form == "step":
                 B.update_euler(src, self.work, self.dt, self.fluid, out=out)
             elif form == "stage":
                 B.update_euler_stage(base, self.work, self.dt, *coef, self.fluid, out=out)
@@ -324,9 +332,100 @@ class EulerMarch:
                 B.update_euler_ssp(P0, src, self.work, self.dt, *coef, self.fluid, out=out)
             return
         tail = dict(fluid=self.fluid, scheme=self.scheme, work=self.work, flags=self.flags)
-        if form == "step":
+        if form == "dual":
+            B.stage_euler_dual(self.part, src, base, self.S, self.dt, *coef, self.g, out, **tail)
+        elif form == "step":
             B.step_euler(self.part, src, self.dt, out, **tail)
         elif form == "stage":
             B.stage_euler(self.part, src, base, self.dt, *coef, out, **tail)
         else:
             B.stage_euler_ssp(self.part, src, P0, self.dt, *coef, out, **tail)
+
+
+def bdf_coefficients(order, dt_real):
+    """``(cn, cm, g)`` of the backward difference of ``order`` 1 or 2 with the physical step ``dt_real``:
+    ``dQ/dt ~ g Q^{n+1} - cn Q^n - cm Q^{n-1}``, BDF2 ``(2, -0.5, 1.5) / dt_real``, BDF1 ``(1, 0, 1) / dt_real``.  Computed in
+    float64 and rounded once to Float32 -- the numbers ``dual_source`` and ``stage_euler_dual`` receive -- returned as Python
+    floats."""
+    if isinstance(order, bool) or order not in (1, 2):
+        raise ValueError("bdf_coefficients: order must be 1 or 2")
+    dt_real = float(dt_real)
+    if not (dt_real > 0.0 and dt_real != float("inf")):
+        raise ValueError("bdf_coefficients: dt_real must be positive and finite")
+    w = (2.0, -0.5, 1.5) if int(order) == 2 else (1.0, 0.0, 1.0)
+    return tuple(float(np.float32(x / dt_real)) for x in w)
+
+
+class DualTimeMarch(EulerMarch):
+    """Dual time stepping: an implicit, time-accurate march whose every physical step of size ``dt_real`` is solved by the
+    pseudo-time march of ``EulerMarch`` -- per-cell pseudo-time steps and Runge-Kutta stages included -- so that the physical
+    step is not bound by the CFL limit of the smallest cell.  With ``dQ/dt = R(P)``, ``Q = primitive2state(P)``, a step solves
+
+        g Q^{n+1} = R(P^{n+1}) + S,      S = cn Q^n + cm Q^{n-1}          (``bdf_coefficients``: BDF2, the first step BDF1)
+
+    by ``n_inner`` pseudo-steps from ``P^n``, each one ``timestep_euler`` (on every ``dt_every``-th pseudo-step of the
+    physical step, into the pseudo-time step ``dtau``, per cell with ``local_dt``) and the stages
+
+        P_k = state2primitive((primitive2state(P_0) + (R(P_{k-1}) + S) * h) / (1 + h * g)),      h = alpha_k * dtau
+
+    -- ``stage_euler_dual(P_{k-1}, P_0, S, dtau, alpha_k, g)``, one launch where the 2-D single-kernel sweep applies; with
+    ``residual``: the callable into ``work``, then ``update_euler_dual`` -- with ``bcs`` after every stage.  The ``g Q`` term
+    is point-implicit (Melson, Sanetrik and Atkins), so ``dtau`` is bound by the explicit scheme alone, and the fixed point
+    is the backward-difference equation whatever ``dtau`` and the stages are.  ``step(P)`` is
+
+    1. ``dual_source`` from ``P`` and the state the previous ``step`` started from, into ``S``,
+    2. the ``n_inner`` pseudo-steps,
+    3. ``average.push(P_new, dt_real)`` with the host number: the march is time accurate in ``dt_real``, a time average is
+       legal here with ``local_dt``.
+
+    ``stages``: ``m`` (``rk_stages(m)``) or the tuple of coefficients.  Shu-Osher triples raise, and so does ``smoothing``:
+    a smoothed residual moves the fixed point to ``smooth(R) + S = g Q``, which is not the backward-difference equation.
+
+    Everything is allocated here: ``S``, the ping-pong arrays of the stages and four arrays for the history.  ``step``
+    returns one of those four; it stays valid during the next ``step`` and is overwritten by a later one.  An array that
+    the march did not return (the caller's, on the first step) is copied into the history once and never written.  No host
+    read-back in ``step``: it can be captured in ``torch.cuda.graph`` and replayed (the replay reads the history arrays the
+    capture saw: it continues the march once; to repeat it, restore them).  ``n_inner`` is fixed: a stopping criterion would
+    need a read-back."""
+
+    def __init__(self, part, dt_real, n_inner, order=2, fluid=None, scheme="hll", scale=0.75, bcs=None, average=None,
+                 local_dt=True, dt_every=1, residual=None, flags=0, stages=1, smoothing=None):
+        later = bdf_coefficients(order, dt_real)
+        self._bdf = {int(order): later, 1: bdf_coefficients(1, dt_real)}        # (the first step is BDF1)
+        if isinstance(n_inner, bool) or int(n_inner) != n_inner or int(n_inner) < 1:
+            raise ValueError("DualTimeMarch: n_inner must be an integer >= 1")
+        if smoothing is not None:
+            raise ValueError("DualTimeMarch: residual smoothing is not taken: the smoothed residual changes the fixed point of "
+                             "the inner iterations to smooth(R) + S = g Q, which is not the backward-difference equation")
+        if isinstance(stages, (tuple, list)) and any(isinstance(a, (tuple, list)) for a in stages):
+            raise ValueError("DualTimeMarch: stages are rk_stages(m) or plain coefficients; Shu-Osher triples are not taken")
+        super().__init__(part, fluid, scheme, scale, bcs, None, local_dt, dt_every, residual, flags, stages)
+        self.average, self.dt_real, self.n_inner, self.order = average, dt_real, int(n_inner), int(order)
+        self._records = [("dual", "P0", (alpha,)) for alpha in self.stages]
+        nc, nv = self.part.nc, self.part.nd + 2
+        self.S, self.g = B.colmajor_empty(nc, nv), 0.0
+        self._hist = tuple(B.colmajor_empty(nc, nv) for _ in range(4))
+        self._prev = self._last = None        # the state the previous step started from; the array it returned
+
+    def step(self, P):
+        """One physical step from ``P`` (any ``(nc, nd+2)`` device array, e.g. the previous return value); returns the new
+        array."""
+        if not isinstance(P, torch.Tensor):
+            P = P.t
+        held = [h.data_ptr() for h in (self._prev, self._last) if h is not None]
+        if P.data_ptr() not in [h.data_ptr() for h in self._hist]:      # not ours: it may change under us before the next step
+            cur = next(h for h in self._hist if h.data_ptr() not in held)
+            cur.copy_(B._primitives(P, self.part.nc, self.part.nd)[0])
+        else:
+            cur = P
+        new = next(h for h in self._hist if h.data_ptr() not in held + [cur.data_ptr()])
+        cn, cm, self.g = self._bdf[1 if self._prev is None else self.order]
+        B.dual_source(cur, self._prev if self.order == 2 else None, cn, cm, self.fluid, out=self.S)
+        src = cur
+        for k in range(self.n_inner):
+            src = self._stages(src, k, new if k == self.n_inner - 1 else None)
+        self._prev, self._last = cur, src
+        if self.average is not None:
+            self.average.push(src, self.dt_real)
+        self.nsteps += 1
+        return src

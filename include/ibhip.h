@@ -512,6 +512,39 @@ int ibh_update_euler_smoothed(const ibh_part*, const ibh_fluid*, int blend /* 0 
                               int64_t ld0, const float* P, int64_t ldp, const float* R, int64_t ldr, const float* Sprev,
                               int64_t lds, float eps, const float* dt, int dt_per_cell, float a, float b, float c,
                               float* P_out, int64_t ldo);
+/* ---- dual time stepping (not in the reference): a physical step of size dt_real is the implicit backward-difference equation
+ *     g * Q^{n+1} = R(P^{n+1}) + S,   S = cn * Q^n + cm * Q^{n-1},   Q = primitive2state(P), dQ/dt = R(P),
+ *   BDF2: cn = 2/dt_real, cm = -0.5/dt_real, g = 1.5/dt_real; BDF1 (the first step): cn = g = 1/dt_real, no Q^{n-1}.  It is
+ *   solved by a march in pseudo-time whose stage takes the g * Q term point-implicitly (Melson, Sanetrik and Atkins): with
+ *   h = alpha * dt, dt the pseudo-time step (global or per cell),
+ *     P_out = state2primitive((primitive2state(P0) + (R(P) + S) * h) / (1 + h * g)),
+ *   every sum, product and the IEEE divide rounded on its own, in this order.  The fixed point P_out = P = P0 is the
+ *   backward-difference equation whatever alpha and dt are; g = 0 with S = 0 gives ibh_update_euler_stage's values (a zero may
+ *   change its sign).  The entries take any cn, cm, g: a variable dt_real is the caller's arithmetic.
+ * ibh_dual_source: S = primitive2state(Pn) * cn + primitive2state(Pm) * cm in one launch, or primitive2state(Pn) * cn with Pm
+ *   NULL (ldm and cm are then ignored); bit for bit primitive2state and the broadcasts.  S may alias neither state.
+ * ibh_update_euler_dual: the update above in one launch for a given R, bit for bit the composition primitive2state(P0), the
+ *   broadcasts R .+ S, dt .* alpha and h .* g .+ 1, ibh_update_dev per column (per-cell dt: the broadcasts * and +), the
+ *   broadcast ./ and state2primitive.  dt: one device value, or n of them (dt_per_cell != 0).  P_out may be P0; R and S may
+ *   alias neither each other nor P_out, R not P0.  n == 0 launches nothing.
+ * ibh_stage_euler_dual: the update with R = ibh_residual_euler_hll / _sensor(P, flags).  ibh_stage_euler's dispatch: ONE launch
+ *   where the 2-D single-kernel sweep takes the whole partition and P_out != P, with a global and with a per-cell dt (the
+ *   sweep loads the cell's rows of P0 and of S and its time step in its store epilogue); two launches everywhere else (3-D,
+ *   face-list or mixed partitions, IBH_FORCE_GENERAL, IBH_NO_FUSE, IBH_EXACT, P_out == P): the sweep into `work` -- an
+ *   argument check there, never an allocation -- then ibh_update_euler_dual.  Same bits either way.  P_out may be P0 when P0 is
+ *   not P; S may alias neither P_out nor work; work may alias none of P, P0, S, P_out.  IBH_IMAGE_ONLY, the overlap phases
+ *   and the single-pass flags are rejected as by ibh_stage_euler.
+ * Every misuse (null pointer, nd other than 2 or 3, a leading dimension below n, g negative or not finite, the aliasing above)
+ * is an error before any launch. */
+int ibh_dual_source(const ibh_fluid*, int nd, int64_t n, const float* Pn, int64_t ldn, const float* Pm /* NULL: BDF1 */,
+                    int64_t ldm, float cn, float cm, float* S, int64_t lds);
+int ibh_update_euler_dual(const ibh_fluid*, int nd, int64_t n, const float* P0, int64_t ld0, const float* R, int64_t ldr,
+                          const float* S, int64_t lds, const float* dt, int dt_per_cell, float alpha, float g, float* P_out,
+                          int64_t ldo);
+int ibh_stage_euler_dual(ibh_part*, const ibh_fluid*, int scheme /* IBH_EULER_HLL | IBH_EULER_SENSOR */, const float* P,
+                         int64_t ldp, const float* P0, int64_t ld0, const float* S, int64_t lds, float* P_out, int64_t ldo,
+                         const float* dt, int dt_per_cell, float alpha, float g, float* work /* nc x (nd+2) or NULL */,
+                         int64_t ldw, int flags);
 int ibh_axpy_clamped(int64_t n, float omega, const float* r, float* q);
 /* y = a*x + y */
 int ibh_axpy(int64_t n, float a, const float* x, float* y);

@@ -909,6 +909,51 @@ function stage_euler_ssp!(P_out::HipArray{Float32}, part::HipPartition, P::HipAr
     P_out
 end
 
+"The source of a physical step of a dual time march, `S = primitive2state(fluid, Pn) .* cn .+ primitive2state(fluid, Pm) .* cm`
+in one launch, or `primitive2state(fluid, Pn) .* cn` with `Pm = nothing` (BDF1, the first step).  BDF2 with the step `dt_real`:
+`cn = 2 / dt_real`, `cm = -0.5 / dt_real`, and `g = 1.5 / dt_real` for the stages.  `S` aliases neither state."
+function dual_source!(S::HipArray{Float32}, fluid, Pn::HipArray{Float32}, Pm::Union{HipArray{Float32}, Nothing}, cn::Real,
+                      cm::Real)
+    f = Ref(IbhFluid(fluid))
+    check(ccall((:ibh_dual_source, lib), Cint,
+        (Ptr{IbhFluid}, Cint, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Cfloat, Cfloat, Ptr{Cvoid}, Int64),
+        f, size(Pn, 2) - 2, size(Pn, 1), Pn.ptr, ld(Pn), isnothing(Pm) ? C_NULL : Pm.ptr, isnothing(Pm) ? 0 : ld(Pm), Float32(cn),
+        Float32(cm), S.ptr, ld(S)))
+    S
+end
+
+"A pseudo-time stage of a dual time step, `P_out = state2primitive(fluid, (primitive2state(fluid, P0) .+ (R .+ S) .* h) ./ (h .* g
+.+ 1))` with `h = dt .* alpha` in one launch, every sum, product and the divide rounded on its own; `dt` of length 1, or one per
+row.  `P_out` may be `P0`."
+function update_euler_dual!(P_out::HipArray{Float32}, fluid, P0::HipArray{Float32}, R::HipArray{Float32}, S::HipArray{Float32},
+                            dt::HipArray{Float32}, alpha::Real, g::Real)
+    f = Ref(IbhFluid(fluid))
+    check(ccall((:ibh_update_euler_dual, lib), Cint,
+        (Ptr{IbhFluid}, Cint, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Cint, Cfloat, Cfloat,
+         Ptr{Cvoid}, Int64),
+        f, size(P0, 2) - 2, size(P0, 1), P0.ptr, ld(P0), R.ptr, ld(R), S.ptr, ld(S), dt.ptr, length(dt) == 1 ? 0 : 1,
+        Float32(alpha), Float32(g), P_out.ptr, ld(P_out)))
+    P_out
+end
+
+"One pseudo-time stage of a dual time step, `update_euler_dual!(P_out, fluid, P0, residual_euler_hll!/sensor!(work, part, P, fluid;
+flags), S, dt, alpha, g)`: `P` is the previous stage, `P0` the state the pseudo-step started from, `S` the source of the
+physical step (`dual_source!`).  One launch where the 2-D single-kernel sweep takes the whole partition and `P_out !== P` (with
+`dt` of length 1 or one per cell), the sweep into `work` and the update elsewhere (`work` is `nc × (nd + 2)` and must be given
+there).  `P_out` may be `P0` when `P0 !== P`; `S` is neither `P_out` nor `work`."
+function stage_euler_dual!(P_out::HipArray{Float32}, part::HipPartition, P::HipArray{Float32}, P0::HipArray{Float32},
+                           S::HipArray{Float32}, dt::HipArray{Float32}, alpha::Real, g::Real, fluid; scheme::Symbol = :hll,
+                           work::Union{HipArray{Float32}, Nothing} = nothing, flags::Integer = 0)
+    f = Ref(IbhFluid(fluid))
+    check(ccall((:ibh_stage_euler_dual, lib), Cint,
+        (Ptr{Cvoid}, Ptr{IbhFluid}, Cint, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid},
+         Cint, Cfloat, Cfloat, Ptr{Cvoid}, Int64, Cint),
+        part.handle, f, scheme === :sensor ? 1 : 0, P.ptr, ld(P), P0.ptr, ld(P0), S.ptr, ld(S), P_out.ptr, ld(P_out), dt.ptr,
+        length(dt) == 1 ? 0 : 1, Float32(alpha), Float32(g), isnothing(work) ? C_NULL : work.ptr,
+        isnothing(work) ? 0 : ld(work), flags))
+    P_out
+end
+
 "Implicit residual smoothing (not in ImmersedBoundary.jl): `n_iter` Jacobi iterations on `(I + eps L) S = R`, `L` the unweighted
 Laplacian of the partition's face graph, `S_i = (R_i + eps * Σ_f S[across(f, i)]) / (1 + eps * n_i)` from `S = R`, per column of
 `R` (at most 8), one launch each.  The result lands in `S`; `tmp`, its ping-pong partner, is required from `n_iter = 2`.  `S` and
