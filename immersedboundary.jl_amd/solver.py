@@ -243,14 +243,14 @@ class EulerMarch:
         if not self.stages:
             raise ValueError("stages must name at least one stage coefficient")
         self._staged = self.stages != (1.0,)
-        # one record per stage, (form, base, coefficients): what `_stage` calls, which state it updates and with what
+        # one record per stage, (form, base, coefficients, update, fused): which state `_stage` updates, with what, its calls
         if not self._staged:
-            self._records = [("step", "src", ())]
+            records = [("step", "src", ())]
         elif ssp:   # (a, b) == (0, 1): no blend, the low-storage stage on the previous stage itself
-            self._records = [("stage", "src", (c,)) if (a, b) == (0.0, 1.0) else ("ssp", "P0", (a, b, c))
-                             for a, b, c in self.stages]
+            records = [("stage", "src", (c,)) if (a, b) == (0.0, 1.0) else ("ssp", "P0", (a, b, c)) for a, b, c in self.stages]
         else:
-            self._records = [("stage", "P0", (alpha,)) for alpha in self.stages]
+            records = [("stage", "P0", (alpha,)) for alpha in self.stages]
+        self._records = [r + _stage_calls(r[0], r[2]) for r in records]
         nc, nv = self.part.nc, self.part.nd + 2
         self._buf = tuple(B.colmajor_empty(nc, nv) for _ in range(3 if self._staged else 2))
         self.work = B.colmajor_empty(nc, nv)
@@ -301,7 +301,7 @@ class EulerMarch:
     def _stage(self, record, src, P0, out):
         """One stage of a step from ``P0`` (the time step is in ``self.dt``): the sweep of the previous stage ``src`` and the
         update of the record's form into ``out``."""
-        form, base, coef = record
+        form, base, coef, update, fused = record
         base = src if base == "src" else P0
         if self.smoothing is not None:
             eps, n_iter = self.smoothing
@@ -322,24 +322,27 @@ class EulerMarch:
             return
         if self.residual is not None:
             self.residual(self.part, src, self.work)
-            if form == "dual":
-                B.update_euler_dual(base, self.work, self.S, self.dt, *coef, self.g, self.fluid, out=out)
-            elif form == "step":
-                B.update_euler(src, self.work, self.dt, self.fluid, out=out)
-            elif form == "stage":
-                B.update_euler_stage(base, self.work, self.dt, *coef, self.fluid, out=out)
-            else:
-                B.update_euler_ssp(P0, src, self.work, self.dt, *coef, self.fluid, out=out)
-            return
-        tail = dict(fluid=self.fluid, scheme=self.scheme, work=self.work, flags=self.flags)
-        if form == "dual":
-            B.stage_euler_dual(self.part, src, base, self.S, self.dt, *coef, self.g, out, **tail)
-        elif form == "step":
-            B.step_euler(self.part, src, self.dt, out, **tail)
-        elif form == "stage":
-            B.stage_euler(self.part, src, base, self.dt, *coef, out, **tail)
+            update(self, base, src, self.work, out)
         else:
-            B.stage_euler_ssp(self.part, src, P0, self.dt, *coef, out, **tail)
+            fused(self, src, base, out)
+
+    def _tail(self):
+        return dict(fluid=self.fluid, scheme=self.scheme, work=self.work, flags=self.flags)
+
+
+def _stage_calls(form, coef):
+    """``(update, fused)`` of a stage of ``form`` with the coefficients ``coef``: ``update(m, base, src, R, out)``, the update
+    that follows a residual callable, and ``fused(m, src, base, out)``, the sweep and the update in one call.  ``m`` is the
+    march: what else they pass is read from it at the call, and no record holds it -- a march and its arrays go with the
+    last reference to it, without waiting for the cycle collector."""
+    if form == "step":
+        return (lambda m, base, src, R, out: B.update_euler(src, R, m.dt, m.fluid, out=out),
+                lambda m, src, base, out: B.step_euler(m.part, src, m.dt, out, **m._tail()))
+    if form == "stage":
+        return (lambda m, base, src, R, out: B.update_euler_stage(base, R, m.dt, *coef, m.fluid, out=out),
+                lambda m, src, base, out: B.stage_euler(m.part, src, base, m.dt, *coef, out, **m._tail()))
+    return (lambda m, base, src, R, out: B.update_euler_ssp(base, src, R, m.dt, *coef, m.fluid, out=out),
+            lambda m, src, base, out: B.stage_euler_ssp(m.part, src, base, m.dt, *coef, out, **m._tail()))
 
 
 def bdf_coefficients(order, dt_real):
@@ -354,6 +357,12 @@ def bdf_coefficients(order, dt_real):
         raise ValueError("bdf_coefficients: dt_real must be positive and finite")
     w = (2.0, -0.5, 1.5) if int(order) == 2 else (1.0, 0.0, 1.0)
     return tuple(float(np.float32(x / dt_real)) for x in w)
+
+
+def _dual_calls(alpha):
+    """``_stage_calls`` of the dual stage; ``S`` and ``g`` -- BDF1 on the first step -- are the march's at the call."""
+    return (lambda m, base, src, R, out: B.update_euler_dual(base, R, m.S, m.dt, alpha, m.g, m.fluid, out=out),
+            lambda m, src, base, out: B.stage_euler_dual(m.part, src, base, m.S, m.dt, alpha, m.g, out, **m._tail()))
 
 
 class DualTimeMarch(EulerMarch):
@@ -401,7 +410,7 @@ class DualTimeMarch(EulerMarch):
             raise ValueError("DualTimeMarch: stages are rk_stages(m) or plain coefficients; Shu-Osher triples are not taken")
         super().__init__(part, fluid, scheme, scale, bcs, None, local_dt, dt_every, residual, flags, stages)
         self.average, self.dt_real, self.n_inner, self.order = average, dt_real, int(n_inner), int(order)
-        self._records = [("dual", "P0", (alpha,)) for alpha in self.stages]
+        self._records = [("dual", "P0", (alpha,)) + _dual_calls(alpha) for alpha in self.stages]
         nc, nv = self.part.nc, self.part.nd + 2
         self.S, self.g = B.colmajor_empty(nc, nv), 0.0
         self._hist = tuple(B.colmajor_empty(nc, nv) for _ in range(4))

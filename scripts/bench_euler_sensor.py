@@ -36,25 +36,13 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-import bench  # noqa: E402
 import ibamd  # noqa: E402
+from graph_timing import noisy_euler_state, single_partition  # noqa: E402
 from ibamd import cfd  # noqa: E402
 
 IBH_FORCE_GENERAL = 1
 LABELS = {"a_sensor_default": "(a) `residual_euler_sensor`, default", "b_hll_default": "(b) `residual_euler_hll`, default",
           "c_operator_granularity": "(c) the closure at operator granularity", "d_sensor_literal": "(d) literal form"}
-
-
-def euler_state(centers, seed=12345):
-    """P = [p T u v (w)]: Mach 0.3, 5 % noise on p and T, 10 % on the velocities (tests/conftest.py::euler_field)."""
-    rng = np.random.default_rng(seed)
-    n, nd = centers.shape
-    P = np.empty((n, nd + 2), np.float32)
-    P[:, 0] = 1e5 * (1 + 0.05 * rng.uniform(-1, 1, n))
-    P[:, 1] = 288.15 * (1 + 0.05 * rng.uniform(-1, 1, n))
-    for d in range(nd):
-        P[:, 2 + d] = 100.0 * (1 + 0.1 * rng.uniform(-1, 1, n))
-    return P
 
 
 def variants(dpart, P, R, fluid):
@@ -122,11 +110,9 @@ class Launcher:
 
 def time_mesh(name, rounds, batch, warmup, block_seconds):
     import torch
-    msh = bench.build_mesh(name)
-    dom = ibamd.Domain(msh, max_partition_size=10 ** 9, boundaries=False)
-    (part,) = dom.partitions.values()
+    dom, part = single_partition(name)
     dpart = ibamd.to_backend(part, ibamd.hip)
-    P = ibamd.hip(euler_state(np.asarray(part.centers)))
+    P = noisy_euler_state(dpart.nc, dpart.nd)
     R = ibamd.hip(np.zeros(tuple(P.shape), np.float32))
     fns = variants(dpart, P, R, cfd.Fluid())
     nc, nd = P.shape[0], P.shape[1] - 2

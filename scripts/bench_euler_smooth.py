@@ -37,7 +37,6 @@ Written: ``bench_euler_smooth.json`` (everything) and ``timings.md`` (the table 
 import argparse
 import json
 import os
-import statistics
 import sys
 import time
 
@@ -49,7 +48,7 @@ sys.path.insert(0, os.path.join(ROOT, "scripts"))
 
 import bench  # noqa: E402
 import ibamd  # noqa: E402
-from bench_euler_step import Launcher  # noqa: E402
+from graph_timing import noisy_euler_state, single_partition, time_variants  # noqa: E402
 from ibamd import cfd  # noqa: E402
 from ibamd import backend as B  # noqa: E402
 from ibamd.solver import EulerMarch, rk_stages  # noqa: E402
@@ -60,16 +59,6 @@ LABELS = {"stage": "(a) `stage_euler`", "smoothed1": "(b) smoothed stage, n_iter
           "smoothed2": "(c) smoothed stage, n_iter = 2 (sweep + Jacobi + fused update)", "sweep": "(d) the sweep into `work`",
           "jacobi": "(e) one `smooth_residual` launch", "fused": "(f) `update_euler_smoothed` alone",
           "update": "(g) `update_euler_stage` alone (streamed yardstick)"}
-
-
-def noisy_state(nc, nd):
-    rng = np.random.default_rng(12345)
-    Ph = np.empty((nc, nd + 2), np.float32)
-    Ph[:, 0] = 1e5 * (1 + 0.05 * rng.uniform(-1, 1, nc))
-    Ph[:, 1] = 288.15 * (1 + 0.05 * rng.uniform(-1, 1, nc))
-    for d in range(nd):
-        Ph[:, 2 + d] = 100.0 * (1 + 0.1 * rng.uniform(-1, 1, nc))
-    return ibamd.hip(Ph)
 
 
 def variants(dpart, P0, fluid):
@@ -102,30 +91,15 @@ def variants(dpart, P0, fluid):
     return fns, ref
 
 
-def _time(fns, rounds, batch, warmup, block_seconds, side):
-    launchers, runs = {}, {}
-    for key, f in fns.items():
-        L = launchers[key] = Launcher(f, batch, warmup, side)
-        L.block_us(3)
-        first = L.block_us(5) * L.calls * 1e-6
-        runs[key] = max(3, int(block_seconds / max(first, 1e-7)) + 1)
-    times = {key: [] for key in launchers}
-    for _ in range(rounds):
-        for key, L in launchers.items():
-            times[key].append(L.block_us(runs[key]))
-    return {key: {"median_us": round(statistics.median(v), 2), "min_us": round(min(v), 2), "max_us": round(max(v), 2),
-                  "calls_per_block": runs[key] * launchers[key].calls} for key, v in times.items()}
-
-
 def time_mesh(name, part, rounds, batch, warmup, block_seconds):
     import torch
     dpart = ibamd.to_backend(part, ibamd.hip)
     nc, nd = dpart.nc, dpart.nd
     nv = nd + 2
     fluid = cfd.Fluid()
-    fns, ref = variants(dpart, noisy_state(nc, nd), fluid)
+    fns, ref = variants(dpart, noisy_euler_state(nc, nd), fluid)
     assert torch.equal(fns["smoothed2"](), ref), f"{name}: the fused last iteration differs from smooth_residual + the update"
-    st = _time(fns, rounds, batch, warmup, block_seconds, torch.cuda.Stream())
+    st = time_variants(fns, rounds, batch, warmup, block_seconds, torch.cuda.Stream())
     jb, ub = 4 * nv * 3 + 4 * 2 * nd, 4 * nv * 3 + 4
     rate = lambda b, k: b * nc / (st[k]["median_us"] * 1e-6)  # noqa: E731
     return {"mesh": name, "cells": int(nc), "nd": nd, "rounds": rounds, "eps": EPS, "alpha": ALPHA, "dt": "per cell",
@@ -226,9 +200,9 @@ def profile_pass(meshes):
     """The two new kernels, a few launches each, and the sweep that feeds them once."""
     import torch
     for name in meshes:
-        dom = ibamd.Domain(bench.build_mesh(name), max_partition_size=10 ** 9, boundaries=False)
-        dpart = ibamd.to_backend(next(iter(dom.partitions.values())), ibamd.hip)
-        fns, _ = variants(dpart, noisy_state(dpart.nc, dpart.nd), cfd.Fluid())
+        dom, part = single_partition(name)
+        dpart = ibamd.to_backend(part, ibamd.hip)
+        fns, _ = variants(dpart, noisy_euler_state(dpart.nc, dpart.nd), cfd.Fluid())
         for _ in range(20):
             fns["jacobi"]()
             fns["fused"]()
@@ -269,8 +243,7 @@ def main():
 
     for name in meshes:
         t0 = time.time()
-        dom = ibamd.Domain(bench.build_mesh(name), max_partition_size=10 ** 9, boundaries=False)
-        part = next(iter(dom.partitions.values()))
+        dom, part = single_partition(name)
         print(f"# {name}: {len(dom)} cells, built in {time.time() - t0:.0f} s", flush=True)
         r = time_mesh(name, part, a.rounds, a.batch, a.warmup, a.block_seconds)
         print(json.dumps(r), flush=True)

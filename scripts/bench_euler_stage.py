@@ -23,12 +23,8 @@ Written: ``bench_euler_stage.json`` (everything) and ``timings.md`` (the table o
     python scripts/bench_euler_stage.py [--meshes rae2822_0.87M,sphere3d_4.6M] [--scheme hll] [--rounds 5] [--batch 10]
                                         [--block-seconds 0.3] [--out-dir profiles/euler_stage]
 """
-import argparse
-import json
 import os
-import statistics
 import sys
-import time
 
 import numpy as np
 
@@ -36,9 +32,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "scripts"))
 
-import bench  # noqa: E402
 import ibamd  # noqa: E402
-from bench_euler_step import Launcher  # noqa: E402
+from graph_timing import noisy_euler_state, one_launch, run_meshes, time_variants  # noqa: E402
 from ibamd import cfd  # noqa: E402
 from ibamd import backend as B  # noqa: E402
 from ibamd.hiparray import HipArray as H  # noqa: E402
@@ -89,42 +84,20 @@ def variants(dpart, P0, fluid, scheme):
     return per_stage, per_step
 
 
-def _time(fns, rounds, batch, warmup, block_seconds, side):
-    launchers, runs = {}, {}
-    for key, f in fns.items():
-        L = launchers[key] = Launcher(f, batch, warmup, side)
-        L.block_us(3)
-        first = L.block_us(5) * L.calls * 1e-6
-        runs[key] = max(3, int(block_seconds / max(first, 1e-7)) + 1)
-    times = {key: [] for key in launchers}
-    for _ in range(rounds):
-        for key, L in launchers.items():
-            times[key].append(L.block_us(runs[key]))
-    return {key: {"median_us": round(statistics.median(v), 2), "min_us": round(min(v), 2), "max_us": round(max(v), 2),
-                  "calls_per_block": runs[key] * launchers[key].calls} for key, v in times.items()}
-
-
 def time_mesh(name, part, scheme, rounds, batch, warmup, block_seconds):
     import torch
     dpart = ibamd.to_backend(part, ibamd.hip)
     nc, nd = dpart.nc, dpart.nd
     fluid = cfd.Fluid()
-    rng = np.random.default_rng(12345)
-    Ph = np.empty((nc, nd + 2), np.float32)
-    Ph[:, 0] = 1e5 * (1 + 0.05 * rng.uniform(-1, 1, nc))
-    Ph[:, 1] = 288.15 * (1 + 0.05 * rng.uniform(-1, 1, nc))
-    for d in range(nd):
-        Ph[:, 2 + d] = 100.0 * (1 + 0.1 * rng.uniform(-1, 1, nc))
-    P0 = ibamd.hip(Ph)
-    i = dpart.info
-    one = nd == 2 and i["fusable_blocks"] == i["full_blocks"] > 0 and i["irregular_cells"] == 0
+    P0 = noisy_euler_state(nc, nd)
+    one = one_launch(dpart)
     per_stage, per_step = variants(dpart, P0, fluid, scheme)
     for fns in (per_stage, per_step):
         a = fns["stage"]().clone()
         assert torch.equal(a, fns["two"]()) and torch.equal(a, fns["composed"]()), f"{name}: the forms of a stage differ"
     side = torch.cuda.Stream()
-    st = _time(per_stage, rounds, batch, warmup, block_seconds, side)
-    sp = _time(per_step, rounds, max(1, batch // 4), warmup, block_seconds, side)
+    st = time_variants(per_stage, rounds, batch, warmup, block_seconds, side)
+    sp = time_variants(per_step, rounds, max(1, batch // 4), warmup, block_seconds, side)
     r = {"mesh": name, "cells": int(nc), "nd": nd, "scheme": scheme, "rounds": rounds, "alpha": ALPHA,
          "stage_launches": 1 if one else 2, "device": torch.cuda.get_device_name(0), "same_bits": True,
          "us_per_stage": st, "us_per_4_stage_step": sp,
@@ -169,34 +142,8 @@ def timings_md(results):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--meshes", default="rae2822_0.87M,sphere3d_4.6M")
-    ap.add_argument("--scheme", default="hll", choices=["hll", "sensor"])
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--batch", type=int, default=10, help="stages captured per HIP graph (a quarter as many 4-stage steps)")
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--block-seconds", type=float, default=0.3, help="GPU time a timed block is sized to")
-    ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles", "euler_stage"))
-    a = ap.parse_args()
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_euler_stage.py needs a GPU: nothing is measured without one")
-    os.makedirs(a.out_dir, exist_ok=True)
-    results = []
-    for name in a.meshes.split(","):
-        t0 = time.time()
-        dom = ibamd.Domain(bench.build_mesh(name), max_partition_size=10 ** 9, boundaries=False)
-        part = next(iter(dom.partitions.values()))
-        print(f"# {name}: {len(dom)} cells, built in {time.time() - t0:.0f} s", flush=True)
-        r = time_mesh(name, part, a.scheme, a.rounds, a.batch, a.warmup, a.block_seconds)
-        print(json.dumps(r), flush=True)
-        results.append(r)
-        with open(os.path.join(a.out_dir, "bench_euler_stage.json"), "w") as f:
-            json.dump({"meshes": results}, f, indent=1)
-        with open(os.path.join(a.out_dir, "timings.md"), "w") as f:
-            f.write(timings_md(results))
-        del dom, part
-    return 0
+    return run_meshes(sys.argv[1:], os.path.join(ROOT, "profiles", "euler_stage"), "bench_euler_stage.json", time_mesh,
+                      timings_md, batch_help="stages captured per HIP graph (a quarter as many 4-stage steps)")
 
 
 if __name__ == "__main__":

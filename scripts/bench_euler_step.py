@@ -22,20 +22,14 @@ Written: ``bench_euler_step.json`` (everything) and ``timings.md`` (the table of
     python scripts/bench_euler_step.py [--meshes rae2822_0.87M,sphere3d_4.6M] [--scheme hll] [--rounds 5] [--batch 10]
                                        [--block-seconds 0.3] [--out-dir profiles/euler_step]
 """
-import argparse
-import json
 import os
-import statistics
 import sys
-import time
-
-import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-import bench  # noqa: E402
 import ibamd  # noqa: E402
+from graph_timing import noisy_euler_state, one_launch, run_meshes, time_variants  # noqa: E402
 from ibamd import _lib, cfd  # noqa: E402
 from ibamd import backend as B  # noqa: E402
 from ibamd.hiparray import HipArray as H  # noqa: E402
@@ -79,67 +73,17 @@ def variants(dpart, P, fluid, scheme):
     return {"fused": fused, "composed": composed, "sweep": sweep, "step": step}
 
 
-class Launcher:
-    """``calls`` calls of one variant captured in a HIP graph; ``block_us(runs)`` replays it ``runs`` times."""
-
-    def __init__(self, f, calls, warmup, stream):
-        import torch
-        self.stream, self.calls = stream, calls
-        with torch.cuda.stream(stream):
-            for _ in range(warmup):
-                f()
-        stream.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, stream=stream):
-            for _ in range(calls):
-                self.keep = f()
-        torch.cuda.synchronize()
-        self.block_us(1)
-
-    def block_us(self, runs):
-        import torch
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        with torch.cuda.stream(self.stream):
-            t0.record()
-            for _ in range(runs):
-                self.graph.replay()
-            t1.record()
-        t1.synchronize()
-        return t0.elapsed_time(t1) * 1e3 / (runs * self.calls)
-
-
 def time_mesh(name, part, scheme, rounds, batch, warmup, block_seconds):
     import torch
     dpart = ibamd.to_backend(part, ibamd.hip)
     nc, nd = dpart.nc, dpart.nd
     fluid = cfd.Fluid()
-    rng = np.random.default_rng(12345)
-    Ph = np.empty((nc, nd + 2), np.float32)
-    Ph[:, 0] = 1e5 * (1 + 0.05 * rng.uniform(-1, 1, nc))
-    Ph[:, 1] = 288.15 * (1 + 0.05 * rng.uniform(-1, 1, nc))
-    for d in range(nd):
-        Ph[:, 2 + d] = 100.0 * (1 + 0.1 * rng.uniform(-1, 1, nc))
-    P = ibamd.hip(Ph)
-    i = dpart.info
-    one = nd == 2 and i["fusable_blocks"] == i["full_blocks"] > 0 and i["irregular_cells"] == 0
+    P = noisy_euler_state(nc, nd)
+    one = one_launch(dpart)
     fns = variants(dpart, P, fluid, scheme)
     a, b = fns["fused"](), fns["composed"]()
     assert torch.equal(a, b), f"{name}: the composed step differs from the fused one"
-    side = torch.cuda.Stream()
-    launchers, runs = {}, {}
-    for key, f in fns.items():
-        L = launchers[key] = Launcher(f, batch, warmup, side)
-        L.block_us(3)
-        first = L.block_us(5) * L.calls * 1e-6
-        runs[key] = max(3, int(block_seconds / max(first, 1e-7)) + 1)
-    times = {key: [] for key in launchers}
-    for _ in range(rounds):
-        for key, L in launchers.items():
-            times[key].append(L.block_us(runs[key]))
-    us = {}
-    for key, v in times.items():
-        us[key] = {"median_us": round(statistics.median(v), 2), "min_us": round(min(v), 2), "max_us": round(max(v), 2),
-                   "calls_per_block": runs[key] * launchers[key].calls}
+    us = time_variants(fns, rounds, batch, warmup, block_seconds, torch.cuda.Stream())
     f_, c_, s_, t_ = (us[k] for k in ("fused", "composed", "sweep", "step"))
     return {"mesh": name, "cells": int(nc), "nd": nd, "scheme": scheme, "rounds": rounds,
             "step_launches": 1 if one else 2, "device": torch.cuda.get_device_name(0), "same_bits": True, "us_per_step": us,
@@ -164,34 +108,8 @@ def timings_md(results):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--meshes", default="rae2822_0.87M,sphere3d_4.6M")
-    ap.add_argument("--scheme", default="hll", choices=["hll", "sensor"])
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--batch", type=int, default=10, help="steps captured per HIP graph")
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--block-seconds", type=float, default=0.3, help="GPU time a timed block is sized to")
-    ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles", "euler_step"))
-    a = ap.parse_args()
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_euler_step.py needs a GPU: nothing is measured without one")
-    os.makedirs(a.out_dir, exist_ok=True)
-    results = []
-    for name in a.meshes.split(","):
-        t0 = time.time()
-        dom = ibamd.Domain(bench.build_mesh(name), max_partition_size=10 ** 9, boundaries=False)
-        part = next(iter(dom.partitions.values()))
-        print(f"# {name}: {len(dom)} cells, built in {time.time() - t0:.0f} s", flush=True)
-        r = time_mesh(name, part, a.scheme, a.rounds, a.batch, a.warmup, a.block_seconds)
-        print(json.dumps(r), flush=True)
-        results.append(r)
-        with open(os.path.join(a.out_dir, "bench_euler_step.json"), "w") as f:
-            json.dump({"meshes": results}, f, indent=1)
-        with open(os.path.join(a.out_dir, "timings.md"), "w") as f:
-            f.write(timings_md(results))
-        del dom, part
-    return 0
+    return run_meshes(sys.argv[1:], os.path.join(ROOT, "profiles", "euler_step"), "bench_euler_step.json", time_mesh,
+                      timings_md, batch_help="steps captured per HIP graph")
 
 
 if __name__ == "__main__":

@@ -25,7 +25,6 @@ Written: ``bench_k_epsilon.json`` (everything) and ``timings.md`` (the table of 
 import argparse
 import json
 import os
-import statistics
 import sys
 import time
 
@@ -36,6 +35,7 @@ sys.path.insert(0, ROOT)
 
 import bench  # noqa: E402
 import ibamd  # noqa: E402
+from graph_timing import time_variants  # noqa: E402
 from ibamd import turbulence as T  # noqa: E402
 
 NU = 1.5e-5
@@ -59,35 +59,6 @@ def variants(dpart, vel, k, eps):
     return {"fused": fused, "composed": composed}
 
 
-class Launcher:
-    """``calls`` calls of one variant captured in a HIP graph; ``block_us(runs)`` replays it ``runs`` times."""
-
-    def __init__(self, f, calls, warmup, stream):
-        import torch
-        self.stream, self.calls = stream, calls
-        with torch.cuda.stream(stream):
-            for _ in range(warmup):
-                f()
-        stream.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, stream=stream):
-            for _ in range(calls):
-                self.keep = f()
-        torch.cuda.synchronize()
-        self.block_us(1)
-
-    def block_us(self, runs):
-        import torch
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        with torch.cuda.stream(self.stream):
-            t0.record()
-            for _ in range(runs):
-                self.graph.replay()
-            t1.record()
-        t1.synchronize()
-        return t0.elapsed_time(t1) * 1e3 / (runs * self.calls)
-
-
 def time_level(l, part, rounds, batch, warmup, block_seconds):
     import torch
     dpart = ibamd.to_backend(part, ibamd.hip)
@@ -104,23 +75,9 @@ def time_level(l, part, rounds, batch, warmup, block_seconds):
     ref, comp = fns["fused"](), fns["composed"]()
     for a, b, name in zip(ref, comp, ("rk", "reps", "nut")):
         assert torch.equal(a, b), f"level {l}: {name} of the composition differs from fused"
-    side = torch.cuda.Stream()
-    launchers, runs = {}, {}
-    for key, f in fns.items():
-        L = launchers[key] = Launcher(f, batch, warmup, side)
-        L.block_us(3)
-        first = L.block_us(5) * L.calls * 1e-6
-        runs[key] = max(3, int(block_seconds / max(first, 1e-7)) + 1)
-    times = {key: [] for key in launchers}
-    for _ in range(rounds):
-        for key, L in launchers.items():
-            times[key].append(L.block_us(runs[key]))
-    us = {}
-    for key, v in times.items():
-        med = statistics.median(v)
-        us[key] = {"median_us": round(med, 2), "min_us": round(min(v), 2), "max_us": round(max(v), 2),
-                   "calls_per_block": runs[key] * launchers[key].calls, "bytes_per_cell": BYTES[key],
-                   "counted_GB_per_s": round(BYTES[key] * nc / med * 1e-3, 1)}
+    us = time_variants(fns, rounds, batch, warmup, block_seconds, torch.cuda.Stream())
+    for key, v in us.items():
+        v.update(bytes_per_cell=BYTES[key], counted_GB_per_s=round(BYTES[key] * nc / v["median_us"] * 1e-3, 1))
     f_, c_ = us["fused"], us["composed"]
     return {"level": l, "cells": int(nc), "path": path, "rounds": rounds, "device": torch.cuda.get_device_name(0),
             "same_bits": True, "us_per_call": us, "bytes_per_cell": BYTES,

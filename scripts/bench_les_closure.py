@@ -27,7 +27,6 @@ Written: ``bench_les_closure.json`` (everything) and ``timings.md`` (the table o
 import argparse
 import json
 import os
-import statistics
 import sys
 import time
 
@@ -38,6 +37,7 @@ sys.path.insert(0, ROOT)
 
 import bench  # noqa: E402
 import ibamd  # noqa: E402
+from graph_timing import time_variants  # noqa: E402
 from ibamd import turbulence as T  # noqa: E402
 
 LABELS = {"fused": "(a) fused: `les_closure_of`", "composed_tuple": "(b) composed: tuple `cell_gradient` + 2 pointwise",
@@ -79,35 +79,6 @@ def variants(dpart, vel, Delta, R, S):
             "wray_agarwal": lambda: T.Wray_Agarwal_of(dpart, R, S)}
 
 
-class Launcher:
-    """``calls`` calls of one variant captured in a HIP graph; ``block_us(runs)`` replays it ``runs`` times."""
-
-    def __init__(self, f, calls, warmup, stream):
-        import torch
-        self.stream, self.calls = stream, calls
-        with torch.cuda.stream(stream):
-            for _ in range(warmup):
-                f()
-        stream.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, stream=stream):
-            for _ in range(calls):
-                self.keep = f()
-        torch.cuda.synchronize()
-        self.block_us(1)
-
-    def block_us(self, runs):
-        import torch
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        with torch.cuda.stream(self.stream):
-            t0.record()
-            for _ in range(runs):
-                self.graph.replay()
-            t1.record()
-        t1.synchronize()
-        return t0.elapsed_time(t1) * 1e3 / (runs * self.calls)
-
-
 def time_level(l, part, rounds, batch, warmup, block_seconds):
     import torch
     dpart = ibamd.to_backend(part, ibamd.hip)
@@ -131,23 +102,9 @@ def time_level(l, part, rounds, batch, warmup, block_seconds):
             for i in range(3):
                 gji = g[j][:, i] if k == "composed_tuple" else g[i][j]
                 assert torch.equal(gji, ref[2][j][:, i]), f"level {l}: {k} gradient ({i}, {j}) differs from fused"
-    side = torch.cuda.Stream()
-    launchers, runs = {}, {}
-    for k, f in fns.items():
-        L = launchers[k] = Launcher(f, batch, warmup, side)
-        L.block_us(3)
-        first = L.block_us(5) * L.calls * 1e-6
-        runs[k] = max(3, int(block_seconds / max(first, 1e-7)) + 1)
-    times = {k: [] for k in launchers}
-    for _ in range(rounds):
-        for k, L in launchers.items():
-            times[k].append(L.block_us(runs[k]))
-    us = {}
-    for k, v in times.items():
-        med = statistics.median(v)
-        us[k] = {"median_us": round(med, 2), "min_us": round(min(v), 2), "max_us": round(max(v), 2),
-                 "calls_per_block": runs[k] * launchers[k].calls, "bytes_per_cell": BYTES[k],
-                 "counted_GB_per_s": round(BYTES[k] * nc / med * 1e-3, 1)}
+    us = time_variants(fns, rounds, batch, warmup, block_seconds, torch.cuda.Stream())
+    for k, v in us.items():
+        v.update(bytes_per_cell=BYTES[k], counted_GB_per_s=round(BYTES[k] * nc / v["median_us"] * 1e-3, 1))
     f_ = us["fused"]
     return {"level": l, "cells": int(nc), "path": path, "rounds": rounds, "device": torch.cuda.get_device_name(0),
             "same_bits": True, "us_per_call": us, "bytes_per_cell": BYTES,

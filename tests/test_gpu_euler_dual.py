@@ -1,7 +1,7 @@
 """Dual time stepping on the device -- ``dual_source``, ``update_euler_dual``, ``stage_euler_dual``, ``DualTimeMarch`` -- bit
 for bit against the composition of the library's own launches that defines them, against the float64 model of
 tests/euler_dual_model.py, and the contraction of the inner iteration on the residual of the backward-difference equation.
-Meshes, states and helpers: those of tests/test_gpu_euler_step.py.
+Meshes, states and helpers: those of tests/euler_forms.py.
 
 The composition: ``primitive2state`` of ``P0``; ``h = dt .* alpha`` and ``den = h .* g .+ 1`` by the broadcast layer with
 Float32 scalars; per column ``RS = R .+ S``, ``ibh_update_dev(h, Q0, RS)`` (a per-cell ``dt``: the broadcasts ``RS .* h`` and
@@ -13,46 +13,19 @@ import pytest
 import torch
 
 import euler_dual_model as dm
+import euler_forms as ef
 import euler_step_model as em
 import ibamd
 import regimes as rg
+from euler_forms import FLUID, NAN, SCALE, STEP_CASES, THIRD, col, meshes, padded, same_bits  # noqa: F401
 from ibamd import _lib, cfd
 from ibamd import backend as B
 from ibamd.hiparray import HipArray as H
 from ibamd.solver import DualTimeMarch, bdf_coefficients, rk_stages
-from test_gpu_euler_step import (FLUID, ONE_LAUNCH, SCALE, STEP_CASES, meshes, padded, residual, same_bits)  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 f32, f64 = np.float32, np.float64
-THIRD = float(f32(1.0 / 3.0))
-NAN = float("nan")
-
-
-def col(A, v):
-    return A[:, v].contiguous()
-
-
-def composed_dual(P0d, Rd, Sd, dtd, alpha, g):
-    n, nv = P0d.shape
-    alpha, g = float(f32(alpha)), float(f32(g))
-    Q0 = cfd.primitive2state(FLUID, P0d)
-    h = (H(dtd) * alpha).t
-    den = (H(h) * g + 1.0).t
-    per_cell = dtd.numel() != 1
-    den1 = None if per_cell else float(den.item())       # (one element does not broadcast against n rows: the same Float32)
-    Q2 = B.colmajor_empty(n, nv)
-    num = B.colmajor_empty(n)
-    for v in range(nv):
-        RS = (H(col(Rd, v)) + H(col(Sd, v))).t
-        if per_cell:
-            t = (H(RS) * H(h)).t
-            num = (H(col(Q0, v)) + H(t)).t
-            Q2[:, v] = (H(num) / H(den)).t
-        else:
-            B._stream()
-            _lib.call("ibh_update_dev", n, B._ptr(h), B._ptr(col(Q0, v)), B._ptr(RS), B._ptr(num))
-            Q2[:, v] = (H(num) / den1).t
-    return cfd.state2primitive(FLUID, Q2)
+ALPHAS = ef.DUAL.coefs
 
 
 def composed_source(Pnd, Pmd, cn, cm):
@@ -69,18 +42,6 @@ def composed_source(Pnd, Pmd, cn, cm):
 # ---------------------------------------------------------------------------------------------------------------------
 # source and update
 # ---------------------------------------------------------------------------------------------------------------------
-_rows = {}
-
-
-def rows(n, nd, per_cell):
-    """Host and device (P0, R, S, dt) of ``euler_dual_model.dual_rows``, g, and the compositions computed so far."""
-    if (n, nd, per_cell) not in _rows:
-        P0, R, S, dt, g = dm.dual_rows(n, nd, per_cell)
-        dtd = ibamd.hip(dt) if per_cell else torch.tensor([float(dt)], dtype=torch.float32, device="cuda")
-        _rows[n, nd, per_cell] = (P0, R, S, dt, float(g), ibamd.hip(P0), ibamd.hip(R), ibamd.hip(S), dtd, {})
-    return _rows[n, nd, per_cell]
-
-
 @pytest.mark.parametrize("nd", [2, 3])
 @pytest.mark.parametrize("n", [1, 77, 2048 * 256 + 77])
 def test_dual_source_bit_for_bit(n, nd):
@@ -108,80 +69,31 @@ def test_dual_source_bit_for_bit(n, nd):
 
 
 @pytest.mark.parametrize("bdf2_g", [False, True], ids=["g0", "gbdf2"])
-@pytest.mark.parametrize("alpha", [1.0, THIRD], ids=["one", "third"])
+@pytest.mark.parametrize("alpha", list(ALPHAS.values()), ids=list(ALPHAS))
 @pytest.mark.parametrize("per_cell", [False, True], ids=["global_dt", "per_cell_dt"])
 @pytest.mark.parametrize("nd", [2, 3])
 @pytest.mark.parametrize("n", [1, 77, 2048 * 256 + 77])
 def test_update_dual_bit_for_bit(n, nd, per_cell, alpha, bdf2_g):
     """One row, less than a workgroup, and past the grid cap of 2 048 workgroups of 256 (the grid-stride loop); g = 0 and
     the BDF2 value of a physical step of 8 x the rows' time step."""
-    _, _, _, _, g, P0d, Rd, Sd, dtd, refs = rows(n, nd, per_cell)
-    g = g if bdf2_g else 0.0
-    if (alpha, g) not in refs:
-        refs[alpha, g] = composed_dual(P0d, Rd, Sd, dtd, alpha, g)
-    ref = refs[alpha, g]
-    out = B.colmajor_empty(n, nd + 2)
-    out.fill_(NAN)
-    assert ibamd.update_euler_dual(P0d, Rd, Sd, dtd, alpha, g, FLUID, out=out) is out
-    same_bits(out, ref, "out of place")
-    assert np.isfinite(ibamd.to_host(out)).all()
-    same_bits(ibamd.update_euler_dual(P0d, Rd, Sd, dtd, alpha, g, FLUID), ref, "allocated")
-    inplace = P0d.clone()
-    ibamd.update_euler_dual(inplace, Rd, Sd, dtd, alpha, g, FLUID, out=inplace)
-    same_bits(inplace, ref, "out is P0")
-    base = torch.full((nd + 2, n + 29), NAN, dtype=torch.float32, device="cuda")
-    Bp, Rp, Sp, Op = padded(n, nd + 2, 7), padded(n, nd + 2, 5), padded(n, nd + 2, 13), base.T[:n]
-    Bp.copy_(P0d)
-    Rp.copy_(Rd)
-    Sp.copy_(Sd)
-    ibamd.update_euler_dual(Bp, Rp, Sp, dtd, alpha, g, FLUID, out=Op)
-    same_bits(Op, ref, "padded")
-    assert torch.isnan(base[:, n:]).all()                                       # nothing written past row n
-    if per_cell:                                     # a per-cell dt that starts one element into a larger array
-        big = torch.full((n + 3,), NAN, dtype=torch.float32, device="cuda")
-        view = big[1:n + 1]
-        view.copy_(dtd)
-        assert view.data_ptr() % 16 == 4
-        same_bits(ibamd.update_euler_dual(P0d, Rd, Sd, view, alpha, g, FLUID), ref, "per-cell dt off the 16-byte grid")
+    ef.check_update_bit_for_bit(ef.DUAL, n, nd, per_cell, alpha, g=None if bdf2_g else 0.0)
 
 
 @pytest.mark.parametrize("nd", [2, 3])
 def test_update_dual_nan_and_vacuum_rows(nd):
     """The rows of test_update_stage_nan_and_vacuum_rows -- a NaN row, a NaN temperature, p = 0, a NaN residual, rho -> 0 --
     and a NaN in the source: the NaN / Inf pattern of the composition."""
-    P, R, S, dt, g = dm.dual_rows(300, nd)
-    h = f32(dt) * f32(THIRD)
-    P[7] = np.nan
-    P[11, 1] = np.nan
-    P[19, 0] = 0.0
-    R[19] = 0.0
-    S[19] = 0.0
-    R[23, 0] = np.nan
-    rho = P[31, 0] / (f32(283.0) * P[31, 1])
-    R[31, 0] = -rho / h - S[31, 0]                         # (R + S) h = -rho
-    P[40, 0] = 0.0
-    S[47, 1] = np.nan
-    special = [7, 11, 19, 23, 31, 40, 47]
-    Pd, Rd, Sd = ibamd.hip(P), ibamd.hip(R), ibamd.hip(S)
-    dtd = torch.tensor([float(dt)], dtype=torch.float32, device="cuda")
-    ref = composed_dual(Pd, Rd, Sd, dtd, THIRD, g)
-    got = ibamd.update_euler_dual(Pd, Rd, Sd, dtd, THIRD, g, FLUID)
-    same_bits(got, ref, "special rows")
-    gh, r = ibamd.to_host(got), ibamd.to_host(ref)
-    assert np.array_equal(np.isinf(gh), np.isinf(r)) and np.array_equal(np.signbit(gh)[np.isinf(r)], np.signbit(r)[np.isinf(r)])
-    assert np.isnan(gh[7]).all() and not np.isfinite(gh[19]).all() and not np.isfinite(gh[47]).all()
-    ok = np.setdiff1d(np.arange(300), special)
-    assert np.isfinite(gh[ok]).all()
+    ef.check_update_special_rows(ef.DUAL, nd)
 
 
 @pytest.mark.parametrize("per_cell", [False, True], ids=["global_dt", "per_cell_dt"])
 @pytest.mark.parametrize("nd", [2, 3])
 def test_zero_g_and_zero_source_is_the_stage(nd, per_cell):
-    _, _, _, _, _, P0d, Rd, _, dtd, _ = rows(20000, nd, per_cell)
-    Z = torch.zeros_like(Rd.T).T
+    a = ef.rows(ef.DUAL, 20000, nd, per_cell)[1]
+    Z = torch.zeros_like(a.R.T).T
     for alpha in (1.0, THIRD):
-        got = ibamd.to_host(ibamd.update_euler_dual(P0d, Rd, Z, dtd, alpha, 0.0, FLUID))
-        ref = ibamd.to_host(ibamd.update_euler_stage(P0d, Rd, dtd, alpha, FLUID))
+        got = ibamd.to_host(ibamd.update_euler_dual(a.P0, a.R, Z, a.dt, alpha, 0.0, FLUID))
+        ref = ibamd.to_host(ibamd.update_euler_stage(a.P0, a.R, a.dt, alpha, FLUID))
         assert np.isfinite(ref).all() and np.array_equal(got, ref)
 
 
@@ -191,14 +103,7 @@ def test_update_dual_against_float64(nd, per_cell):
     """Per element against the float64 model on the update's own scale (``euler_dual_model.update_dual_scale``): at most 4 x
     the Float32 numpy model's own deviation (``euler_dual_model.MODEL_DEVIATION_EPS``, measured in
     tests/test_euler_dual_model.py) -- the margin ``update_euler`` and ``update_euler_stage`` are held to."""
-    P0, R, S, dt, g, P0d, Rd, Sd, dtd, _ = rows(20000, nd, per_cell)
-    for alpha in (1.0, THIRD):
-        for gg in (0.0, g):
-            got = ibamd.to_host(ibamd.update_euler_dual(P0d, Rd, Sd, dtd, alpha, gg, FLUID))
-            dev = dm.update_dual_deviation(got, P0, R, S, dt, alpha, gg)
-            print(f"update_euler_dual nd={nd} per_cell={per_cell} alpha={alpha:.3f} g={gg:.1f}: device {dev:.3f} eps, bound "
-                  f"{4 * dm.MODEL_DEVIATION_EPS[nd]:.1f} eps")
-            assert dev <= 4 * dm.MODEL_DEVIATION_EPS[nd]
+    ef.check_update_against_float64(ef.DUAL, nd, per_cell)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -207,45 +112,7 @@ def test_update_dual_against_float64(nd, per_cell):
 @pytest.mark.parametrize("scheme", ["hll", "sensor"])
 @pytest.mark.parametrize("mesh,flags", STEP_CASES, ids=[f"{m}-{f}" for m, f in STEP_CASES])
 def test_stage_dual_bit_for_bit(meshes, mesh, flags, scheme):
-    c = meshes[mesh]
-    n, nv = c.part.spacing.shape[0], c.nd + 2
-    one_launch = (mesh, flags) in ONE_LAUNCH
-    for regime in ("transonic", "cold"):
-        P0 = ibamd.hip(rg.euler_regime(c.part, regime))
-        dt1 = ibamd.timestep_euler(c.dpart, P0, FLUID, SCALE)
-        cells = ibamd.timestep_euler(c.dpart, P0, FLUID, SCALE, out=False, cells=B.colmajor_empty(n))
-        work, out = B.colmajor_empty(n, nv), B.colmajor_empty(n, nv)
-        Pd = B.colmajor_empty(n, nv)
-        ibamd.step_euler(c.dpart, P0, dt1, Pd, FLUID, scheme, work=work, flags=flags)      # P: one step from P0
-        assert not torch.equal(Pd, P0)
-        cn, cm, g = bdf_coefficients(2, 8 * float(dt1.item()))
-        S = ibamd.dual_source(P0, Pd, cn, cm, FLUID)
-        R = residual(c.dpart, Pd, scheme, flags)
-        finite_R = np.isfinite(ibamd.to_host(R)).all(axis=1)
-        for dt, dname in ((dt1, "global dt"), (cells, "per-cell dt")):
-            for alpha in (1.0, THIRD):
-                what = f"{mesh} flags={flags} {scheme} {regime} {dname} alpha={alpha:.2f}"
-                ref = ibamd.update_euler_dual(P0, R, S, dt, alpha, g, FLUID)
-                work.fill_(NAN)                              # a row the sweep or the update leaves unwritten shows
-                out.fill_(NAN)
-                assert ibamd.stage_euler_dual(c.dpart, Pd, P0, S, dt, alpha, g, out, FLUID, scheme, work=work,
-                                              flags=flags) is out
-                same_bits(out, ref, what)
-                assert finite_R.any() and np.isfinite(ibamd.to_host(out)[finite_R]).all(), what
-                if one_launch:                               # the sweep stored the update itself: no work array
-                    assert torch.isnan(work).all(), what + ": the one-launch form left work alone"
-                    out.fill_(NAN)
-                    ibamd.stage_euler_dual(c.dpart, Pd, P0, S, dt, alpha, g, out, FLUID, scheme, flags=flags)
-                    same_bits(out, ref, what + " without work")
-                else:
-                    assert not torch.isnan(work[torch.from_numpy(finite_R).to(work.device)]).any(), what + ": swept into work"
-                    same_bits(work, R, what + ": work holds the residual")
-                # out is P0 (P0 is not P), and a padded S
-                base = P0.clone()
-                Sp = padded(n, nv, 11)
-                Sp.copy_(S)
-                ibamd.stage_euler_dual(c.dpart, Pd, base, Sp, dt, alpha, g, base, FLUID, scheme, work=work, flags=flags)
-                same_bits(base, ref, what + " out is P0, padded S")
+    ef.check_stage_bit_for_bit(ef.DUAL, meshes, mesh, flags, scheme)
 
 
 def test_rejections(meshes):
@@ -375,23 +242,8 @@ def test_dual_time_march(meshes, mesh, local_dt):
 
     # the same three steps captured after one warm-up step and replayed: steps 2 .. 4 of an eager march
     ref4 = m.step(P)
-    g_m = DualTimeMarch(c.dpart, dt_real, N_INNER, fluid=FLUID, scale=SCALE, local_dt=local_dt, stages=3)
-    stream = torch.cuda.Stream()
-    stream.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(stream):
-        Pw = g_m.step(P0)
-        first = Pw.clone()
-        stream.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, stream=stream):
-            Pg = Pw
-            for _ in range(NPHYS):
-                Pg = g_m.step(Pg)
-        Pg.fill_(NAN)
-        Pw.copy_(first)                  # (the history is a ring of four: the fourth step's array is the first step's)
-        graph.replay()
-    stream.synchronize()
-    B._stream()
+    Pg = ef.replayed_march(lambda: DualTimeMarch(c.dpart, dt_real, N_INNER, fluid=FLUID, scale=SCALE, local_dt=local_dt, stages=3),
+                           P0, NPHYS, warmup=1, onward=True)
     same_bits(Pg, ref4, f"dual march {mesh}, graph replay")
     same_bits(P0, start, "the caller's array is left alone by the replay")
 

@@ -1,6 +1,6 @@
 """Implicit residual smoothing on the device -- ``smooth_residual``, ``update_euler_smoothed``,
 ``EulerMarch(smoothing=(eps, n_iter))`` -- bit for bit against the float32 model of tests/smooth_model.py and against the
-composition of the library's own launches.  Meshes, states and helpers: those of tests/test_gpu_euler_step.py; the four
+composition of the library's own launches.  Meshes, states and helpers: those of tests/euler_forms.py; the four
 meshes hold one-face, multi-face and no-face sides, mirror faces and skirt cells, in 2-D and 3-D."""
 import numpy as np
 import pytest
@@ -12,7 +12,7 @@ import smooth_model as sm
 from ibamd import _lib, cfd
 from ibamd import backend as B
 from ibamd.solver import EulerMarch, rk_stages, ssp_stages
-from test_gpu_euler_step import FLUID, SCALE, TAU, march_dom, meshes, residual, same_bits  # noqa: F401
+from euler_forms import FLUID, FORMS, SCALE, TAU, arrays, march_dom, meshes, residual, same_bits  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -143,9 +143,9 @@ def test_smooth_residual_bit_for_bit(meshes, mesh, nvk):
 
 
 def composed(form, P0, P, S, dt, coef):
-    if form == "stage":
-        return ibamd.update_euler_stage(P0, S, dt, *coef, FLUID)
-    return ibamd.update_euler_ssp(P0, P, S, dt, *coef, FLUID)
+    """The defining composition of the form's update, on the smoothed residual ``S``."""
+    f = FORMS[form]
+    return f.composed(*f.args(arrays(P0=P0, P=P, R=S, dt=dt), coef))
 
 
 @pytest.mark.parametrize("form", ["stage", "ssp"])
