@@ -23,6 +23,6 @@ def __getattr__(name):
         return getattr(backend, name)
     if name == "HipArray":
         return getattr(importlib.import_module(__name__ + ".hiparray"), name)
-    if name in ("FAS", "EulerMarch", "DualTimeMarch", "rk_stages", "ssp_stages", "bdf_coefficients"):
+    if name in ("FAS", "EulerMarch", "DualTimeMarch", "MultigridMarch", "rk_stages", "ssp_stages", "bdf_coefficients"):
         return getattr(importlib.import_module(__name__ + ".solver"), name)
     raise AttributeError(name)

@@ -111,6 +111,8 @@ _SIGS = {
                               C.c_float, c_vp, c_i64],
     "ibh_stage_euler_dual": [c_vp, C.POINTER(ibh_fluid), c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_int,
                              C.c_float, C.c_float, c_vp, c_i64, c_int],
+    "ibh_restrict_euler": [c_vp, C.POINTER(ibh_fluid), c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64],
+    "ibh_prolong_euler": [c_vp, C.POINTER(ibh_fluid), c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64],
     "ibh_smooth_residual": [c_vp, c_vp, c_int, c_i64, C.c_float, c_int, c_vp, c_i64, c_vp, c_i64],
     "ibh_update_euler_smoothed": [c_vp, C.POINTER(ibh_fluid), c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64,
                                   C.c_float, c_vp, c_int, C.c_float, C.c_float, C.c_float, c_vp, c_i64],

@@ -1029,6 +1029,85 @@ def stage_euler_dual(part, P, P0, S, dt, alpha, g, out, fluid=None, scheme="hll"
     return out
 
 
+def _transfer(what, acc):
+    """The device Accumulator of a multigrid transfer ``what`` (``to_backend`` of one of the lists ``multigrid(dom)``
+    returns)."""
+    acc = to_backend(acc)
+    if not isinstance(acc, DeviceAccumulator):
+        raise TypeError(f"{what}: the operator must be an Accumulator (one of the lists multigrid(dom) returns)")
+    return acc
+
+
+def _coarse_out(what, name, t, n, nv):
+    """``t`` (None: a new array) as an output ``(n, nv)`` of a transfer, with its C arguments."""
+    if t is None:
+        t = colmajor_empty(n, nv)
+    o, nvo, ld = _field_inplace(t, n, name)
+    if nvo != nv:
+        raise ValueError(f"{what}: {name} must be ({n}, {nv})")
+    return t, [_ptr(o), ld]
+
+
+@_hipaware
+def restrict_euler(coarsener, P, R, S=None, fluid=None, out=None, out_D=None):
+    """The restriction of a multigrid cycle of the Euler march in conserved variables, one launch:
+    ``P_c = state2primitive(fluid, coarsener(primitive2state(fluid, P)))`` and ``D_c = coarsener(R .+ S)`` (``S=None``:
+    ``coarsener(R)``), bit for bit those launches.  ``P``: the fine primitives ``(n_input, nd+2)``; ``R``, ``S``: the fine
+    residual and forcing in conserved variables.  Returns ``(P_c, D_c)`` -- ``out`` and ``out_D`` where given, ``(n_output,
+    nd+2)``, which alias neither each other nor an input.  The coarse forcing of the cycle is ``D_c .- R_c(P_c)``."""
+    acc = _transfer("restrict_euler", coarsener)
+    P, nv, ldp = _primitives(P, acc.n_input)
+    R, nvr, ldr = _field(R, acc.n_input)
+    if nvr != nv:
+        raise ValueError(f"restrict_euler: R must be ({acc.n_input}, {nv})")
+    Sc = [c_vp(None), 0]
+    if S is not None:
+        S, nvs, lds = _field(S, acc.n_input)
+        if nvs != nv:
+            raise ValueError(f"restrict_euler: S must be ({acc.n_input}, {nv})")
+        Sc = [_ptr(S), lds]
+    out, O = _coarse_out("restrict_euler", "out", out, acc.n_output, nv)
+    out_D, D = _coarse_out("restrict_euler", "out_D", out_D, acc.n_output, nv)
+    if acc.n_output == 0:     # (no rows: nothing to launch, and an empty array has no address to pass)
+        return out, out_D
+    f = _cfluid(fluid)
+    _stream()
+    call("ibh_restrict_euler", acc.handle, C.byref(f), nv - 2, _ptr(P), ldp, _ptr(R), ldr, *Sc, *O, *D)
+    return out, out_D
+
+
+@_hipaware
+def prolong_euler(prolongator, P, Pc_new, Pc_old, fluid=None, out=None, pack=None):
+    """The prolongation of a multigrid cycle of the Euler march, the correction of the fine state by the change of the coarse
+    one in conserved variables: ``state2primitive(fluid, primitive2state(fluid, P) .+ prolongator(primitive2state(fluid,
+    Pc_new) .- primitive2state(fluid, Pc_old)))`` in two launches -- the difference of the coarse states packed once, 8 floats
+    per coarse row, then one thread per fine row -- bit for bit ``primitive2state`` three times, ``prolongator.diff_add`` and
+    ``state2primitive``.  ``out`` (None: a new array) may be ``P`` itself.  ``pack``: ``8 * n_input`` Float32 on the device,
+    32-byte aligned; None: an array kept with the operator, allocated on its first use (a caller that captures graphs passes
+    its own)."""
+    acc = _transfer("prolong_euler", prolongator)
+    P, nv, ldp = _primitives(P, acc.n_output)
+    Pn, _, ldn = _primitives(Pc_new, acc.n_input, nv - 2)
+    Po, _, ldo_ = _primitives(Pc_old, acc.n_input, nv - 2)
+    if ldn != ldo_:
+        raise ValueError("prolong_euler: Pc_new and Pc_old must have one leading dimension")
+    out, O = _coarse_out("prolong_euler", "out", out, acc.n_output, nv)
+    if pack is None:
+        pack = getattr(acc, "_pack", None)
+        if pack is None:
+            pack = acc._pack = torch.empty(8 * max(acc.n_input, 1), dtype=torch.float32, device=P.device)
+    if not isinstance(pack, torch.Tensor) or not pack.is_cuda or pack.dtype != torch.float32 or not pack.is_contiguous() \
+            or pack.numel() < 8 * acc.n_input:
+        raise ValueError(f"prolong_euler: pack must be a contiguous Float32 device tensor of at least {8 * acc.n_input} "
+                         "elements")
+    if acc.n_output == 0:
+        return out
+    f = _cfluid(fluid)
+    _stream()
+    call("ibh_prolong_euler", acc.handle, C.byref(f), nv - 2, _ptr(Pn), _ptr(Po), ldn, _ptr(pack), _ptr(P), ldp, *O)
+    return out
+
+
 def _smoothing(what, eps, n_iter):
     """``(eps, n_iter)`` of a residual smoothing, checked: ``eps`` finite and >= 0, ``n_iter`` an integer >= 1."""
     eps = float(eps)

@@ -130,6 +130,8 @@ update_euler_ssp = B.update_euler_ssp              # (ibh_update_euler_ssp / ibh
 stage_euler_ssp = B.stage_euler_ssp
 smooth_residual = B.smooth_residual                # (ibh_smooth_residual / ibh_update_euler_smoothed: implicit residual smoothing)
 update_euler_smoothed = B.update_euler_smoothed
+restrict_euler = B.restrict_euler                  # (ibh_restrict_euler / ibh_prolong_euler: the transfers of a multigrid cycle)
+prolong_euler = B.prolong_euler
 
 
 def inviscid_fluxes(fluid, PL, PR, *args):

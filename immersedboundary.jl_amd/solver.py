@@ -365,6 +365,182 @@ def _dual_calls(alpha):
             lambda m, src, base, out: B.stage_euler_dual(m.part, src, base, m.S, m.dt, alpha, m.g, out, **m._tail()))
 
 
+def _sub_into(a, b):
+    """``a .-= b`` of two compact device arrays as a libibhip broadcast, in place: no allocation."""
+    from .hiparray import HipArray
+    ha = HipArray(a)
+    ha -= HipArray(b)
+    return a
+
+
+class _Level(EulerMarch):
+    """One level of a ``MultigridMarch``: the arrays, the time step and the stage records of an ``EulerMarch`` on the
+    level's partition, and beside the records of the steady stages those of the forced ones, ``stage_euler_dual`` with the
+    level's forcing ``S`` and ``g`` -- picked per call of ``smooth``; the stage loop is ``EulerMarch._stages`` either way."""
+
+    def __init__(self, part, fluid, scheme, scale, bcs, local_dt, dt_every, flags, stages):
+        super().__init__(part, fluid, scheme, scale, bcs, None, local_dt, dt_every, None, flags, stages)
+        self._plain = self._records
+        self._forced = [("dual", "P0", (alpha,)) + _dual_calls(alpha) for alpha in self.stages]
+        self.S, self.g = None, 0.0
+
+    def smooth(self, P, n, S, g):
+        """``n`` smoothing steps from ``P`` with the forcing ``S`` (None with ``g == 0``: the steady step of ``EulerMarch``);
+        returns the last array, ``P`` itself for ``n == 0``.  ``P`` is not written."""
+        self.S, self.g = S, g
+        self._records = self._plain if S is None else self._forced
+        for _ in range(n):
+            P = self._stages(P, self.nsteps)
+            self.nsteps += 1
+        return P
+
+    def sweep(self, P):
+        """``R(P)`` into ``work``."""
+        fn = B.residual_euler_hll if self.scheme == "hll" else B.residual_euler_sensor
+        return fn(self.part, P, out=self.work, flags=self.flags, fluid=self.fluid)
+
+
+class MultigridMarch:
+    """Multigrid for the pseudo-time march of ``EulerMarch``, the fourth acceleration of a Jameson-type steady solver beside
+    the per-cell time step, the Runge-Kutta stages and the residual smoothing: a full-approximation-scheme (FAS) V-cycle
+    whose smoother on every level is the march's own step and whose transfers work on conserved variables.
+
+    ``parts``: one single-partition ``Partition`` per level (``to_backend(part, hip)``), finest first.  ``coarseners[l]`` /
+    ``prolongators[l]`` connect level ``l`` and ``l + 1``: the lists of ``multigrid(dom)``, whose return order is
+    ``(coarse_doms, prolongators, coarseners)``.  ``bcs``: None, or one callable per level (None for a level without).
+    EVERY level supplied is visited: the quirk of the reference's ``FAS!`` (and of ``solver.FAS``), whose recursion guard
+    leaves the last level out, is not copied.
+
+    ``cycle(P, S=None, g=0.0)`` is one V-cycle from level 0 and returns the new fine array.  On level ``l`` with state
+    ``P_l`` and forcing ``S_l`` (conserved variables):
+
+    1. ``pre`` smoothing steps, each ``timestep_euler`` on that level (per cell with ``local_dt``; every ``dt_every``-th
+       step of the level) and the stages, ``bcs[l]`` after every stage.  With ``S_l is None`` (then ``g == 0``: level 0 of a
+       steady run) the stages are ``step_euler`` / ``stage_euler`` and the step is exactly ``EulerMarch``'s; otherwise they
+       are ``stage_euler_dual(P, P0, S_l, dt, alpha, g)``, which with ``g = 0`` is the forced Runge-Kutta stage
+       ``s2p(p2s(P0) + (R(P) + S_l) h)``.
+    2. If there is a coarser level: the sweep ``R(P_l)`` into the level's ``work``; on level 0 the sum of squares of the
+       first column of ``work`` -- the density residual ``R`` alone, not ``R + S``, over every row of the array, ghost cells
+       included -- goes into the history; ``restrict_euler`` gives ``P_{l+1}^0`` and ``D = I(R + S_l)``; ``bcs[l+1]``
+       on ``P_{l+1}^0``; the sweep of ``P_{l+1}^0``; the coarse forcing ``S_{l+1} = D - R_{l+1}(P_{l+1}^0)`` in place in
+       ``D``; the recursion from ``P_{l+1}^0``, which is an array of its own that no step writes; ``prolong_euler(P_l,
+       P_{l+1}, P_{l+1}^0)`` into the level's next free ping-pong array; ``bcs[l]``.
+    3. ``post`` smoothing steps.  The coarsest level runs ``n_coarsest`` steps and no transfers -- with one level a cycle is
+       ``n_coarsest`` steps of ``EulerMarch``.
+
+    ``S`` and ``g`` on level 0 make the cycle the solver of a backward-difference step of a dual time march, ``g Q = R(P) +
+    S`` (``dual_source``, ``bdf_coefficients``): ``g`` goes to every level unchanged and the ``g Q`` terms cancel in the coarse
+    forcing, because ``P_{l+1}^0`` is the restriction of ``P_l`` and the restriction is linear.  ``g > 0`` needs ``S``.
+
+    ``history=n``: ``n`` device doubles, NaN until written; cycle ``k < n`` writes entry ``k`` (``ibh_sumsq``, which assigns:
+    nothing to zero).  ``residual_history()`` is the only read-back and ``cycle`` never calls it.  Everything is allocated
+    here; ``cycle`` makes no host read-back and no allocation, so it can be captured in ``torch.cuda.graph`` (run one eager
+    cycle first: the library's workspaces come with their first use).  The returned array is one of level 0's ping-pong
+    arrays: valid during the next cycle's first step, overwritten later.
+
+    Not taken, each with a message: ``smoothing`` (``update_euler_smoothed`` has no source row), Shu-Osher triples (as in
+    ``DualTimeMarch``), a ``residual`` callable, the image-only, phase and single-pass ``flags``, a ``TimeAverage``."""
+
+    def __init__(self, parts, coarseners=(), prolongators=(), fluid=None, scheme="hll", scale=0.75, bcs=None, local_dt=True,
+                 dt_every=1, stages=1, pre=1, post=1, n_coarsest=2, flags=0, history=0, smoothing=None, residual=None,
+                 average=None):
+        from . import cfd
+        if smoothing is not None:
+            raise ValueError("MultigridMarch: residual smoothing is not taken: update_euler_smoothed has no source row for the "
+                             "coarse forcing")
+        if isinstance(stages, (tuple, list)) and any(isinstance(a, (tuple, list)) for a in stages):
+            raise ValueError("MultigridMarch: stages are rk_stages(m) or plain coefficients; Shu-Osher triples are not taken")
+        if residual is not None:
+            raise ValueError("MultigridMarch: a residual callable is not taken: the levels sweep with the library's schemes")
+        if average is not None:
+            raise ValueError("MultigridMarch: a TimeAverage is not taken: the cycle marches in pseudo-time")
+        flags = int(flags)
+        if flags & (B.IBH_IMAGE_ONLY | B.IBH_PHASE_INTERIOR | B.IBH_PHASE_BOUNDARY | B.IBH_PASS_A_ONLY | B.IBH_PASS_B_ONLY):
+            raise ValueError("MultigridMarch: IBH_IMAGE_ONLY, the overlap phases and the single-pass flags are not taken: the "
+                             "restriction reads the residual of every cell")
+        parts = [B.to_backend(p) for p in parts]
+        if not parts:
+            raise ValueError("MultigridMarch: at least one level")
+        coarseners, prolongators = list(coarseners), list(prolongators)
+        if len(coarseners) != len(parts) - 1 or len(prolongators) != len(parts) - 1:
+            raise ValueError(f"MultigridMarch: {len(parts)} levels take {len(parts) - 1} coarseners and as many prolongators")
+        if bcs is None:
+            bcs = [None] * len(parts)
+        bcs = list(bcs)
+        if len(bcs) != len(parts):
+            raise ValueError("MultigridMarch: bcs is None or one callable per level")
+        for name, v in (("pre", pre), ("post", post), ("n_coarsest", n_coarsest), ("history", history)):
+            if isinstance(v, bool) or int(v) != v or int(v) < 0:
+                raise ValueError(f"MultigridMarch: {name} must be an integer >= 0")
+        self.pre, self.post, self.n_coarsest = int(pre), int(post), int(n_coarsest)
+        self.fluid = fluid if fluid is not None else cfd.Fluid()
+        self.levels = [_Level(p, self.fluid, scheme, scale, b, local_dt, dt_every, flags, stages) for p, b in zip(parts, bcs)]
+        for l, m in enumerate(self.levels):
+            host = getattr(m.part, "host", None)
+            if host is not None and (len(host.image) != m.part.nc or len(host.domain) != m.part.nc):
+                raise ValueError(f"MultigridMarch: level {l} is not a single partition: {len(host.image)} of its "
+                                 f"{m.part.nc} cells are its own")
+        self.coarseners = [B._transfer("MultigridMarch", a) for a in coarseners]
+        self.prolongators = [B._transfer("MultigridMarch", a) for a in prolongators]
+        for l, (c, p) in enumerate(zip(self.coarseners, self.prolongators)):
+            nf, nk = self.levels[l].part.nc, self.levels[l + 1].part.nc
+            if (c.n_input, c.n_output) != (nf, nk) or (p.n_input, p.n_output) != (nk, nf):
+                raise ValueError(f"MultigridMarch: levels {l} and {l + 1} have {nf} and {nk} cells; coarseners[{l}] maps "
+                                 f"{c.n_input} -> {c.n_output} and prolongators[{l}] {p.n_input} -> {p.n_output} (multigrid(dom) "
+                                 "returns (coarse_doms, prolongators, coarseners))")
+        for m in self.levels[1:]:
+            nc, nv = m.part.nc, m.part.nd + 2
+            m.P0, m.D = B.colmajor_empty(nc, nv), B.colmajor_empty(nc, nv)
+            m.pack = torch.empty(8 * max(nc, 1), dtype=torch.float32, device=m.work.device)
+        self._hist = None
+        if int(history):
+            self._hist = torch.full((int(history),), float("nan"), dtype=torch.float64, device=self.levels[0].work.device)
+        self.ncycles = 0
+
+    def cycle(self, P, S=None, g=0.0):
+        """One V-cycle from ``P`` (any ``(nc, nd+2)`` device array of level 0, e.g. the previous return value), with the
+        level-0 forcing ``S`` (conserved variables) and ``g`` of a backward-difference step; returns the new fine array."""
+        if not isinstance(P, torch.Tensor):
+            P = P.t
+        if S is not None and not isinstance(S, torch.Tensor):
+            S = S.t
+        g = B._dual_g("MultigridMarch.cycle", g)
+        if S is None and g != 0.0:
+            raise ValueError("MultigridMarch.cycle: g > 0 needs the source S of the physical step")
+        P = self._level(0, P, S, g)
+        self.ncycles += 1
+        return P
+
+    def _level(self, l, P, S, g):
+        m = self.levels[l]
+        if l == len(self.levels) - 1:
+            return m.smooth(P, self.n_coarsest, S, g)
+        P = m.smooth(P, self.pre, S, g)
+        m.sweep(P)
+        if l == 0 and self._hist is not None and self.ncycles < self._hist.numel():
+            B._stream()
+            B.call("ibh_sumsq", m.part.nc, B._ptr(m.work), B._ptr(self._hist[self.ncycles:]))
+        c = self.levels[l + 1]
+        B.restrict_euler(self.coarseners[l], P, m.work, S, self.fluid, out=c.P0, out_D=c.D)
+        if c.bcs is not None:
+            c.bcs(c.P0)
+        c.sweep(c.P0)
+        _sub_into(c.D, c.work)
+        Pc = self._level(l + 1, c.P0, c.D, g)
+        out = next(b for b in m._buf if b.data_ptr() != P.data_ptr())
+        B.prolong_euler(self.prolongators[l], P, Pc, c.P0, self.fluid, out=out, pack=c.pack)
+        if m.bcs is not None:
+            m.bcs(out)
+        return m.smooth(out, self.post, S, g)
+
+    def residual_history(self):
+        """The history as a host array of ``history`` doubles: entry ``k`` is the sum of squares of the density residual that
+        cycle ``k`` restricted, NaN where no cycle has written.  The one read-back of the class."""
+        if self._hist is None:
+            return np.zeros(0, dtype=np.float64)
+        return self._hist.cpu().numpy()
+
+
 class DualTimeMarch(EulerMarch):
     """Dual time stepping: an implicit, time-accurate march whose every physical step of size ``dt_real`` is solved by the
     pseudo-time march of ``EulerMarch`` -- per-cell pseudo-time steps and Runge-Kutta stages included -- so that the physical

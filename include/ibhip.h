@@ -545,6 +545,32 @@ int ibh_stage_euler_dual(ibh_part*, const ibh_fluid*, int scheme /* IBH_EULER_HL
                          int64_t ldp, const float* P0, int64_t ld0, const float* S, int64_t lds, float* P_out, int64_t ldo,
                          const float* dt, int dt_per_cell, float alpha, float g, float* work /* nc x (nd+2) or NULL */,
                          int64_t ldw, int flags);
+/* ---- multigrid for the Euler march (not in the reference, whose FAS! hands its operators whatever columns it is given): the
+ *   transfers between two levels in CONSERVED variables.  The coarsener and the prolongator are the Accumulators of
+ *   multigrid(dom) (ibh_acc_create); their n_input / n_output are the row counts of the fine and the coarse arrays.  The
+ *   stencil arithmetic is ibh_accumulate's -- t = x * w, the sum started from the first entry and added in entry order -- and
+ *   the state arithmetic ibh_cfd_primitive2state's / ibh_cfd_state2primitive's, nothing contracted.
+ * ibh_restrict_euler: P_c = state2primitive(coarsener(primitive2state(P_f))) and D_c = coarsener(R_f .+ S_f) -- S_f NULL:
+ *   coarsener(R_f), ldsf ignored -- in ONE launch, one thread per coarse row; r + s is rounded before the multiply, as the
+ *   broadcast does.  Bit for bit primitive2state, the broadcast +, ibh_accumulate twice and state2primitive.  R_f, S_f and D_c
+ *   are in conserved variables; the coarse forcing of a full-approximation-scheme cycle is D_c .- R_c(P_c), the caller's
+ *   broadcast.  P_c and D_c may overlap neither each other nor P_f, R_f, S_f.
+ * ibh_prolong_euler: P_out = state2primitive(primitive2state(P_f) .+ prolongator(primitive2state(Pc_new) .-
+ *   primitive2state(Pc_old))), the correction of a fine state by the change of the coarse one, in TWO launches: a pre-pass over
+ *   the coarse rows writes pack[j][0 .. 7] = primitive2state(Pc_new[j]) - primitive2state(Pc_old[j]), zeros past nd + 2, then
+ *   one thread per fine row takes each donor with two 16-byte gathers (a coarse row has ~4^nd readers: converting it inside
+ *   the gather would repeat both conversions that often).  Bit for bit primitive2state three times,
+ *   ibh_accumulate_diff_add and state2primitive.  pack: 8 * n_input floats of the caller's, 32-byte aligned, overlapping no
+ *   state; Pc_new and Pc_old share ldc.  P_out may be P_f itself (a thread reads its row whole before it writes, and nobody
+ *   else reads fine rows) and may overlap no other argument.
+ * Every misuse (null pointer, nd other than 2 or 3, a leading dimension below the row count, pack missing or misaligned, the
+ * aliasing above) is an error before any launch; an operator with zero output rows is no error and no launch. */
+int ibh_restrict_euler(const ibh_acc* coarsener, const ibh_fluid*, int nd, const float* P_f, int64_t ldpf, const float* R_f,
+                       int64_t ldrf, const float* S_f /* may be NULL */, int64_t ldsf, float* P_c, int64_t ldpc, float* D_c,
+                       int64_t lddc);
+int ibh_prolong_euler(const ibh_acc* prolongator, const ibh_fluid*, int nd, const float* Pc_new, const float* Pc_old,
+                      int64_t ldc, float* pack /* n_input x 8 floats, 32-byte aligned */, const float* P_f, int64_t ldpf,
+                      float* P_out, int64_t ldo);
 int ibh_axpy_clamped(int64_t n, float omega, const float* r, float* q);
 /* y = a*x + y */
 int ibh_axpy(int64_t n, float a, const float* x, float* y);

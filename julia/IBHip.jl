@@ -954,6 +954,37 @@ function stage_euler_dual!(P_out::HipArray{Float32}, part::HipPartition, P::HipA
     P_out
 end
 
+"The restriction of a multigrid cycle of the Euler march in conserved variables (not in ImmersedBoundary.jl), one launch:
+`P_c = state2primitive(fluid, coarsener(primitive2state(fluid, P)))` and `D_c = coarsener(R .+ S)`, or `coarsener(R)` with
+`S = nothing`, bit for bit those launches.  `coarsener`: `to_backend` of a coarsener of `multigrid(dom)`.  `P_c` and `D_c` alias
+neither each other nor an input; the coarse forcing of the cycle is `D_c .- R_c(P_c)`."
+function restrict_euler!(P_c::HipArray{Float32}, D_c::HipArray{Float32}, coarsener::HipAccumulator, fluid, P::HipArray{Float32},
+                         R::HipArray{Float32}, S::Union{HipArray{Float32}, Nothing} = nothing)
+    f = Ref(IbhFluid(fluid))
+    check(ccall((:ibh_restrict_euler, lib), Cint,
+        (Ptr{Cvoid}, Ptr{IbhFluid}, Cint, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid},
+         Int64),
+        coarsener.handle, f, size(P, 2) - 2, P.ptr, ld(P), R.ptr, ld(R), isnothing(S) ? C_NULL : S.ptr, isnothing(S) ? 0 : ld(S),
+        P_c.ptr, ld(P_c), D_c.ptr, ld(D_c)))
+    P_c, D_c
+end
+
+"The prolongation of a multigrid cycle of the Euler march: `P_out = state2primitive(fluid, primitive2state(fluid, P) .+
+prolongator(primitive2state(fluid, Pc_new) .- primitive2state(fluid, Pc_old)))` in two launches, bit for bit `primitive2state`
+three times, `accumulate_diff_add!` and `state2primitive`.  `pack`: `8 * n_input` Float32 of scratch on the device, 32-byte
+aligned (a `HipArray` is); `Pc_new` and `Pc_old` share their leading dimension.  `P_out` may be `P`."
+function prolong_euler!(P_out::HipArray{Float32}, prolongator::HipAccumulator, fluid, P::HipArray{Float32},
+                        Pc_new::HipArray{Float32}, Pc_old::HipArray{Float32}, pack::HipArray{Float32})
+    ld(Pc_new) == ld(Pc_old) || error("prolong_euler!: Pc_new and Pc_old must share their leading dimension")
+    length(pack) >= 8 * prolongator.n_input || error("prolong_euler!: pack holds fewer than 8 * n_input elements")
+    f = Ref(IbhFluid(fluid))
+    check(ccall((:ibh_prolong_euler, lib), Cint,
+        (Ptr{Cvoid}, Ptr{IbhFluid}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64),
+        prolongator.handle, f, size(P, 2) - 2, Pc_new.ptr, Pc_old.ptr, ld(Pc_new), pack.ptr, P.ptr, ld(P), P_out.ptr,
+        ld(P_out)))
+    P_out
+end
+
 "Implicit residual smoothing (not in ImmersedBoundary.jl): `n_iter` Jacobi iterations on `(I + eps L) S = R`, `L` the unweighted
 Laplacian of the partition's face graph, `S_i = (R_i + eps * Σ_f S[across(f, i)]) / (1 + eps * n_i)` from `S = R`, per column of
 `R` (at most 8), one launch each.  The result lands in `S`; `tmp`, its ping-pong partner, is required from `n_iter = 2`.  `S` and
