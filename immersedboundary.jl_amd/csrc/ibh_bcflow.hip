@@ -2,7 +2,7 @@
 // Boundary (ImmersedBoundary.jl:1197-1247 over cfd.jl:243-300 and turbulence.jl:72-98): one thread per ghost cell walks its
 // interpolation row once for the nd + 2 primitives and up to 4 scalar fields, evaluates the closure and blends.  The device
 // bodies are those of the kernels the composition launches (ibh_flowbc_dev.h, ibh_wall_dev.h; the row sum in the order of
-// k_accumulate / k_accumulate_rows, the blend of k_bc_blend), evaluated without contraction: the result is the composition's
+// ibh_stencil_dev.h, that of k_accumulate / k_accumulate_rows; the blend of k_bc_blend), evaluated without contraction: the result is the composition's
 // bit for bit.
 #include <algorithm>
 
@@ -48,7 +48,7 @@ __global__ __launch_bounds__(BCF_BLOCK) void k_bc_flow(BcFlowArgs A) {
     const int nf = NP + ns;
     for (int64_t g = IBH_WG_X() * (int64_t)blockDim.x + threadIdx.x; g < A.ng; g += (int64_t)gridDim.x * blockDim.x) {
         // 1. the row of the image-point interpolator, indices and weights read once for all fields; per field the sum of
-        // k_accumulate_rows: entries in CSR order, the first term assigned
+        // k_accumulate_rows (the order of ibh_stencil_dev.h): entries in CSR order, the first term assigned
         const int32_t b = A.off[g], e = A.off[g + 1];
         float s[NF];
 #pragma unroll

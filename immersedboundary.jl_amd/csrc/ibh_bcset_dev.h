@@ -1,11 +1,11 @@
-// libibhip: device bodies of the BC-set launches (ibh_march.hip) -- shared with the launches of ibh_ops.hip that carry the
+// libibhip: device bodies of the BC-set launches (ibh_march.hip) -- shared with the launches of ibh_timestep.hip that carry the
 // time-step evaluation of the next step beside them (ibh_bcset_apply_with_dt).
 #pragma once
 #include "ibh_common.h"
 
 namespace bcset_dev {
 
-// interpolated value of ghost g of the set: sum over its stencil in the order of k_accumulate (ibh_ops.hip)
+// interpolated value of ghost g of the set: sum over its stencil in the order of ibh_stencil_dev.h (k_accumulate's scalar walk)
 __device__ __forceinline__ float bc_interp1(const int32_t* __restrict__ off, const int32_t* __restrict__ donor,
                                             const float* __restrict__ w, const float* __restrict__ a, int32_t g) {
     const int32_t b = off[g], e = off[g + 1];

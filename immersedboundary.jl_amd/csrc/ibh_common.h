@@ -193,18 +193,7 @@ struct ibh_bcset {
     int32_t* mode = nullptr;
 };
 
-// internal: face-list forms of the fused turbulence closures (ibh_ops.hip), dispatched from ibh_turb.hip
-extern "C" int ibh_shear_rate_of_velocity_cells(const ibh_part* p, const float* vel, int64_t ldv, float* S, float* Gout,
-                                                int64_t ldg);
-extern "C" int ibh_wray_agarwal_of_cells(const ibh_part* p, const float* R, const float* S, float sigmaR, float C1,
-                                         float kappa, float* nut, float* nuR, float* Sout);
-extern "C" int ibh_les_of_cells(const ibh_part* p, const float* vel, int64_t ldv, const float* Delta, int model, float Cmodel,
-                                float* nusgs, float* ducros, float* shock, float* S, float* G, int64_t ldg);
-extern "C" int ibh_k_epsilon_rhs_cells(const ibh_part* p, const float* vel, int64_t ldv, const float* k, const float* eps,
-                                       float nu, const float* params5, float* rk, float* reps, float* nut, float* S, float* G,
-                                       int64_t ldg);
-
-// internal: the boundary-condition set with the next step's time step beside it (ibh_ops.hip), called from ibh_fused.hip
+// internal: the boundary-condition set with the next step's time step beside it (ibh_timestep.hip), called from ibh_fused.hip
 extern "C" int ibh_bcset_apply_with_dt(const ibh_bcset* s, float* a, ibh_part* p, const float* C, int64_t ldc, float scale,
                                        float* dt_next, int partials_done);
 

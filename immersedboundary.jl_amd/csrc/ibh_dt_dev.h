@@ -1,6 +1,6 @@
-// libibhip: device bodies of the time-step evaluation of an explicit step (ibh_timestep_advection, ibh_timestep_euler: ibh_ops.hip), with
+// libibhip: device bodies of the time-step evaluation of an explicit step (ibh_timestep_advection, ibh_timestep_euler: ibh_timestep.hip), with
 // the workgroup's index and count as arguments: the same code runs as its own launches and beside the BC-set workgroups of a
-// march step (ibh_ops.hip: k_bcinterp_dt / k_bcscatter_dt).
+// march step (ibh_timestep.hip: k_bcinterp_dt / k_bcscatter_dt).
 #pragma once
 #include "ibh_common.h"
 #include "ibh_reduce_dev.h"
@@ -64,7 +64,7 @@ struct AcousticLoad {
 };
 
 // (device bodies with the workgroup's index and count as arguments: the same code runs as its own launch and beside the
-// BC-set workgroups of a march step, k_bcinterp_dt / k_bcscatter_dt below)
+// BC-set workgroups of a march step, k_bcinterp_dt / k_bcscatter_dt of ibh_timestep.hip)
 // CELLS: the local time step of every cell, (0.5 / max_d(...)[c]) * scale, goes to dt_cells as well
 template <int ND, bool TILED, class Load, bool CELLS = false>
 __device__ __forceinline__ void dt_partial_wg(int wg, int nwg, int32_t nc, const GradDims& G, const Load& load,

@@ -272,7 +272,7 @@ int ibh_step_advection(ibh_part* p, const float* u, float* u_out, const float* C
 }
 
 // The step with the time step of the NEXT step evaluated beside its boundary conditions (ibh_bcset_apply_with_dt,
-// ibh_ops.hip): dt_next = scale * 0.5 / max(...) depends on C alone, so its two launches ride in the two launches of the BC
+// ibh_timestep.hip): dt_next = scale * 0.5 / max(...) depends on C alone, so its two launches ride in the two launches of the BC
 // set instead of standing in front of the next sweep.  dt_next may be dt_dev (the sweep has read it by then).
 // (Tried and dropped: the partial maxima beside the SWEEP instead -- its workgroups then carry the sweep's 27 KB of LDS and
 // its register budget, and the launch takes longer than the two side by side save: 26.8 against 26.1 us per step.)

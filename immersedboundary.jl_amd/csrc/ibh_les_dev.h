@@ -2,7 +2,7 @@
 // g[i][j] = d u_i / d x_j -- shear_rate (turbulence.jl:110-124), Smagorinsky_νSGS (:134-137), Ducros_sensor (:253-283),
 // WALE_νSGS (:292-337) and CFD.shock_sensor (cfd.jl:589-617) -- and of Wray_Agarwal (:222-241) at one cell, shared by the
 // pointwise kernels of ibh_turb.hip / ibh_cfd.hip and the fused closures that consume cell_gradient where it is made:
-// ibh_les_of (k_les_of3 in ibh_turb.hip, k_les_of_cells in ibh_ops.hip), ibh_shear_rate_of_velocity[_grad]
+// ibh_les_of (k_les_of3 and k_les_of_cells in ibh_turb.hip), ibh_shear_rate_of_velocity[_grad]
 // (k_shear_of_velocity3, k_shear_of_velocity_cells), ibh_k_epsilon_rhs (k_k_epsilon_rhs3, k_k_epsilon_rhs_cells: shear_rate)
 // and ibh_wray_agarwal_of (k_wray_agarwal_of3, k_wray_agarwal_of_cells).  Float32, the reference's operation order
 // (-ffp-contract=off).

@@ -4,11 +4,11 @@
 //     (ImmersedBoundary.jl:1197-1247: every ghost cell of a boundary is interpolated BEFORE any of them is written; a later
 //     boundary sees the earlier ones): boundaries that do not read each other's ghost cells form a level, a level is two
 //     launches (interpolate + closure + blend into a side buffer, scatter) whatever the number of boundaries;
-//   * ibh_timestep_advection (ibh_ops.hip): dt = scale * 0.5 / max over cells and dimensions of
+//   * ibh_timestep_advection (ibh_timestep.hip): dt = scale * 0.5 / max over cells and dimensions of
 //     unsigned_green_gauss(at_faces(C_d, d), d) (advection.jl:52-59) left in device memory -- no host read-back in the loop.
 // The step itself (sweep + u += dt ud in one launch) is ibh_step_advection in ibh_fused.hip.
 //   * ibh_update_euler: P_out = state2primitive(primitive2state(P) + dt R) in one launch (euler_step::update_row); the Euler
-//     step around it is ibh_step_euler in ibh_fused.hip, its time step ibh_timestep_euler in ibh_ops.hip.
+//     step around it is ibh_step_euler in ibh_fused.hip, its time step ibh_timestep_euler in ibh_timestep.hip.
 //   * ibh_update_euler_stage: the same row function on a base state P0 with the time step alpha * dt, a Runge-Kutta stage of
 //     the low-storage family; the stage around it is ibh_stage_euler in ibh_fused.hip.
 //   * ibh_update_euler_ssp: a Shu-Osher stage, the update of the blend a primitive2state(P0) + b primitive2state(P) with the

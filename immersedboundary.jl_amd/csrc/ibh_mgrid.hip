@@ -8,35 +8,21 @@
 //     states in `pack`, 8 floats per row (a coarse row is gathered by ~4^nd fine rows: converting inside the gather would
 //     repeat both conversions that many times), then one thread per fine row takes a donor with two 16-byte gathers.
 // Arithmetic: the row functions of ibh_euler_step_dev.h and the stencil sums of k_accumulate_rows / k_accumulate_packed_add
-// (ibh_ops.hip) -- t = x * w, the sum started from the first entry and added in entry order, indices and weights read four at
-// a time where the row starts on a 16-byte boundary -- without contraction: bit for bit the compositions of those launches.
+// (ibh_transfer.hip) -- the row walk of ibh_stencil_dev.h, which states the order -- without contraction: bit for bit the
+// compositions of those launches.
 #include <cstdint>
 
 #include "ibh_common.h"
 #include "ibh_euler_step_dev.h"
+#include "ibh_stencil_dev.h"
 
 #define MG_BLOCK 256
 
 namespace {
 
-// entries k .. k + n - 1 (n = 4: one dwordx4 of indices and one of weights; 1: the scalar tail) of a row that starts at b
-template <int N>
-struct Entries {
-    int32_t j[N];
-    float w[N];
-};
-__device__ __forceinline__ Entries<4> load4(const int32_t* __restrict__ idx, const float* __restrict__ w, int32_t k) {
-    const int4 j4 = *reinterpret_cast<const int4*>(idx + k);
-    Entries<4> e{{j4.x, j4.y, j4.z, j4.w}, {1.0f, 1.0f, 1.0f, 1.0f}};
-    if (w) {
-        const float4 w4 = *reinterpret_cast<const float4*>(w + k);
-        e.w[0] = w4.x, e.w[1] = w4.y, e.w[2] = w4.z, e.w[3] = w4.w;
-    }
-    return e;
-}
-__device__ __forceinline__ Entries<1> load1(const int32_t* __restrict__ idx, const float* __restrict__ w, int32_t k) {
-    return Entries<1>{{idx[k]}, {w ? w[k] : 1.0f}};   // (no weights: x * 1 is x, bit for bit)
-}
+using stencil_dev::Entries;
+using stencil_dev::load1;
+using stencil_dev::load4;
 
 // N donors of a coarse row: their conserved states and residuals [plus sources] times their weights, added to sq and sd in
 // entry order; `first`: entry 0 of these is the row's first and is assigned.  All gathers are issued before the arithmetic

@@ -1,7 +1,7 @@
 // libibhip: device pieces of the transport terms of a turbulence scalar,
 //   S + sum_d green_gauss(at_faces(nu + nuR, d) .* face_gradient(R, d) .- at_faces(vel_d .* R, d), d),
-// shared by the transport kernels of ibh_turb.hip and the fused k-epsilon right-hand sides (k_k_epsilon_rhs3 in
-// ibh_turb.hip, k_k_epsilon_rhs_cells in ibh_ops.hip).  Float32, the expressions and the order of the operator kernels of
+// shared by the transport kernels of ibh_turb.hip and the fused k-epsilon right-hand sides (k_k_epsilon_rhs3 and
+// k_k_epsilon_rhs_cells in ibh_turb.hip).  Float32, the expressions and the order of the operator kernels of
 // ibh_ops.hip (-ffp-contract=off): a sum made here is the operator-by-operator composition's bit for bit.
 #pragma once
 #include "ibh_common.h"

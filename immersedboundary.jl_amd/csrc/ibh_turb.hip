@@ -5,14 +5,23 @@
 // Velocity gradients: an nd x nd table of device pointers, g[i*nd + j] = d u_i / d x_j (the reference's Matrix of vectors).
 // After them: the closures on an all-block 3-D partition with the gradients made where they are consumed (block kernels
 // k_shear_of_velocity3, k_wray_agarwal_of3, k_les_of3, k_scalar_transport_blocks3, k_k_epsilon_rhs3),
-// and the C entries, which send the same closures on a partition without block structure to ibh_ops.hip's *_cells kernels.
+// and the C entries, which send the same closures on a partition without block structure to the thread-per-cell *_cells
+// kernels (before the block kernels: k_shear_of_velocity_cells, k_les_of_cells, k_k_epsilon_rhs_cells,
+// k_wray_agarwal_of_cells).
 #include "ibh_common.h"
 #include "ibh_fused_int.h"
 #include "ibh_wall_dev.h"
 #include "ibh_les_dev.h"
 #include "ibh_transport_dev.h"
+#include "ibh_grad_dev.h"
 
 namespace {
+
+using dt_dev::GradDims;
+using dt_dev::grad_dims;
+using grad_dev::cell_gradient_at;
+using grad_dev::cell_sides;
+using grad_dev::store_gradients;
 
 constexpr int TB = 256;
 
@@ -144,6 +153,105 @@ __global__ void k_scalar_transport(int32_t nc, TransportDims T, const float* __r
             f[0] = tr_flux_on(o, n, T.h[d], R, nuR, T.vel[d], nu);
         }, rt);
         out[c] = rt[0];
+    }
+}
+
+// ---- the fused closures on face-list partitions (thread per cell, the gradients never leave the registers) -- the
+// expressions of k_cell_gradient_all (ibh_grad_dev.h) and the pointwise formulas of ibh_les_dev.h / ibh_transport_dev.h,
+// bit-identical to the composition.  The loop of cell_gradient_at over the velocity components stays written in the
+// kernels: inside a function it reorders a third of their instructions, and the 3-D kernels measured 1 % slower.
+// ibh_shear_rate_of_velocity[_grad]: k_les_of_cells without a model, asked for S (and G) -- kept as a kernel of its own for
+// its registers (71 against 78 VGPRs in 3-D: seven waves per SIMD against six)
+template <int ND>
+__global__ void k_shear_of_velocity_cells(int32_t nc, GradDims G, const float* __restrict__ vel, int64_t ldv,
+                                          float* __restrict__ S, float* __restrict__ Gout, int64_t ldg) {
+    for (int64_t c = IBH_WG_X() * (int64_t)blockDim.x + threadIdx.x; c < nc; c += (int64_t)gridDim.x * blockDim.x) {
+        int32_t sd[2 * ND];
+        cell_sides<ND>(G, nc, c, sd);
+        float g[ND][ND];   // g[i][j] = d u_i / d x_j
+#pragma unroll
+        for (int i = 0; i < ND; ++i) cell_gradient_at<ND>(G, sd, nc, (int32_t)c, vel + (int64_t)i * ldv, g[i]);
+        S[c] = les_dev::shear_rate<ND>(g);
+        if (Gout) store_gradients<ND>(g, Gout, ldg, c);
+    }
+}
+// the LES closure of a velocity field (ibh_les_of): the requested outputs from registers
+template <int ND>
+__global__ void k_les_of_cells(int32_t nc, GradDims G, const float* __restrict__ vel, int64_t ldv,
+                               const float* __restrict__ Delta, int model, float Cmodel, les_dev::Outputs O) {
+    for (int64_t c = IBH_WG_X() * (int64_t)blockDim.x + threadIdx.x; c < nc; c += (int64_t)gridDim.x * blockDim.x) {
+        int32_t sd[2 * ND];
+        cell_sides<ND>(G, nc, c, sd);
+        float g[ND][ND];   // g[i][j] = d u_i / d x_j
+#pragma unroll
+        for (int i = 0; i < ND; ++i) cell_gradient_at<ND>(G, sd, nc, (int32_t)c, vel + (int64_t)i * ldv, g[i]);
+        if (O.S || model == les_dev::MODEL_SMAGORINSKY) {  // (uniform, as every branch below)
+            const float s = les_dev::shear_rate<ND>(g);
+            if (O.S) O.S[c] = s;
+            if (model == les_dev::MODEL_SMAGORINSKY) O.nusgs[c] = les_dev::smagorinsky(Delta[c], s, Cmodel);
+        }
+        if constexpr (ND == 3) {
+            if (model == les_dev::MODEL_WALE) O.nusgs[c] = les_dev::wale(g, Delta[c], Cmodel);
+        }
+        if (O.ducros) O.ducros[c] = les_dev::ducros<ND>(g);
+        if (O.shock) O.shock[c] = les_dev::shock<ND>(g);
+        if (O.G) store_gradients<ND>(g, O.G, O.ldg, c);
+    }
+}
+// the right-hand sides of the standard k-epsilon model (ibh_k_epsilon_rhs): standard_kϵ with the expressions of
+// k_keps above, then both transport sums in one walk over the cell's faces (tr_dev::cell_sum: the walk and the flux
+// of k_scalar_transport).  The diffusivity nu + nut / sigma of the cell across a face is made from that cell's own k and eps
+// -- the bits the composition reads back from nuk / nue.
+template <int ND>
+__global__ void k_k_epsilon_rhs_cells(int32_t nc, GradDims G, const float* __restrict__ vel, int64_t ldv,
+                                      const float* __restrict__ kf, const float* __restrict__ ef, float nu, tr_dev::KEps P,
+                                      float* __restrict__ rk, float* __restrict__ reps, float* __restrict__ nut,
+                                      float* __restrict__ Sout, float* __restrict__ Gout, int64_t ldg) {
+    for (int64_t c = IBH_WG_X() * (int64_t)blockDim.x + threadIdx.x; c < nc; c += (int64_t)gridDim.x * blockDim.x) {
+        int32_t sd[2 * ND];
+        cell_sides<ND>(G, nc, c, sd);
+        float g[ND][ND];   // g[i][j] = d u_i / d x_j
+#pragma unroll
+        for (int i = 0; i < ND; ++i) cell_gradient_at<ND>(G, sd, nc, (int32_t)c, vel + (int64_t)i * ldv, g[i]);
+        const float S = les_dev::shear_rate<ND>(g);
+        if (Sout) Sout[c] = S;   // (uniform, as every branch on an output pointer)
+        if (Gout) store_gradients<ND>(g, Gout, ldg, c);
+        const float kk = kf[c], ee = ef[c];
+        const float nt = tr_dev::keps_nut(P, kk, ee);
+        const float Pk = nt * (S * S);
+        if (nut) nut[c] = nt;
+        float rt[2] = {tr_dev::keps_Sk(Pk, ee), tr_dev::keps_Se(P, Pk, kk, ee)};
+        tr_dev::cell_sum<ND, 2>(G.d, G.h, sd, (int32_t)c, [&](int d, int32_t o, int32_t n, float (&f)[2]) {
+            const float ho = G.h[d][o], hn = G.h[d][n];
+            const float ko = kf[o], kn = kf[n], eo = ef[o], en = ef[n];
+            const float vo = vel[(int64_t)d * ldv + o], vn = vel[(int64_t)d * ldv + n];
+            const float nto = tr_dev::keps_nut(P, ko, eo), ntn = tr_dev::keps_nut(P, kn, en);
+            f[0] = tr_dev::flux(ko, kn, nu + nto / P.sk, nu + ntn / P.sk, vo * ko, vn * kn, ho, hn);
+            f[1] = tr_dev::flux(eo, en, nu + nto / P.se, nu + ntn / P.se, vo * eo, vn * en, ho, hn);
+        }, rt);
+        rk[c] = rt[0];
+        reps[c] = rt[1];
+    }
+}
+// Wray_Agarwal of the gradients of (R, S) (ibh_wray_agarwal_of)
+template <int ND>
+__global__ void k_wray_agarwal_of_cells(int32_t nc, GradDims G, const float* __restrict__ R, const float* __restrict__ S,
+                                        float sigmaR, float C1, float kappa, float* __restrict__ nut,
+                                        float* __restrict__ nuR, float* __restrict__ Sout) {
+    const float C2 = sigmaR + C1 / (kappa * kappa);
+    for (int64_t c = IBH_WG_X() * (int64_t)blockDim.x + threadIdx.x; c < nc; c += (int64_t)gridDim.x * blockDim.x) {
+        int32_t sd[2 * ND];
+        cell_sides<ND>(G, nc, c, sd);
+        float gR[ND], gS[ND];
+        cell_gradient_at<ND>(G, sd, nc, (int32_t)c, R, gR);
+        cell_gradient_at<ND>(G, sd, nc, (int32_t)c, S, gS);
+        float dot = gR[0] * gS[0];
+#pragma unroll
+        for (int d = 1; d < ND; ++d) dot = dot + gR[d] * gS[d];
+        const les_dev::WrayAgarwal w = les_dev::wray_agarwal(R[c], S[c], dot, sigmaR, C1, C2);
+        nut[c] = w.nut;
+        nuR[c] = w.nuR;
+        Sout[c] = w.S;
     }
 }
 
@@ -544,15 +652,17 @@ void launch_blocks3(void (*k)(const BlockDesc3*, const int32_t*, const int32_t*,
     const int32_t nwg = (p->nblk + 3) / 4;
     hipLaunchKernelGGL(k, dim3(nwg), dim3(256), 0, ibh_stream, p->blocks3, p->htab3, p->ftab3, p->nblk, nwg, args...);
 }
-// the dispatch of a fused closure: nothing on an empty partition, cells() on one without block structure (the face-list
-// kernels of ibh_ops.hip; the tuple cell_gradient is the face-list kernel there), blocks() on one made of complete 3-D
-// blocks, the caller's message anywhere else
+// the dispatch of a fused closure: nothing on an empty partition, cells() on one without block structure (the *_cells
+// kernels above through launch_nd; the tuple cell_gradient is the face-list kernel there), blocks() on one made of complete
+// 3-D blocks, the caller's message anywhere else
 template <class Cells, class Blocks>
 int fused_closure(const ibh_part* p, const char* needs, Cells cells, Blocks blocks) {
     if (p->nc == 0) return 0;
-    if (!fused::has_blocks(p)) return cells();
-    IBH_REQUIRE(fused::all_blocks3(p), needs);
-    blocks();
+    if (!fused::has_blocks(p)) cells();
+    else {
+        IBH_REQUIRE(fused::all_blocks3(p), needs);
+        blocks();
+    }
     IBH_LAUNCH_CHECK();
     return 0;
 }
@@ -680,7 +790,10 @@ int ibh_shear_rate_of_velocity_grad(ibh_part* p, const float* vel, int64_t ldv, 
     return fused_closure(
         p, "ibh_shear_rate_of_velocity: needs a 3-D partition made of complete blocks or one without "
            "block structure (compose cell_gradient and shear_rate otherwise)",
-        [&] { return ibh_shear_rate_of_velocity_cells(p, vel, ldv, S, G, ldg); },
+        [&] {
+            launch_nd(p->nd, p->nc, k_shear_of_velocity_cells<2>, k_shear_of_velocity_cells<3>, p->nc, grad_dims(p), vel, ldv, S,
+                      G, ldg);
+        },
         [&] { launch_blocks3(k_shear_of_velocity3, p, FieldPtrs<3>{{vel, vel + ldv, vel + 2 * ldv}}, S, G, (uint32_t)ldg); });
 }
 int ibh_shear_rate_of_velocity(ibh_part* p, const float* vel, int64_t ldv, float* S) {
@@ -692,7 +805,10 @@ int ibh_wray_agarwal_of(ibh_part* p, const float* R, const float* S, float sigma
     return fused_closure(
         p, "ibh_wray_agarwal_of: needs a 3-D partition made of complete blocks or one without block "
            "structure (compose cell_gradient and Wray_Agarwal otherwise)",
-        [&] { return ibh_wray_agarwal_of_cells(p, R, S, sigmaR, C1, kappa, nut, nuR, Sout); },
+        [&] {
+            launch_nd(p->nd, p->nc, k_wray_agarwal_of_cells<2>, k_wray_agarwal_of_cells<3>, p->nc, grad_dims(p), R, S, sigmaR, C1,
+                      kappa, nut, nuR, Sout);
+        },
         [&] { launch_blocks3(k_wray_agarwal_of3, p, FieldPtrs<2>{{R, S}}, sigmaR, C1, kappa, nut, nuR, Sout); });
 }
 
@@ -711,7 +827,10 @@ int ibh_les_of(ibh_part* p, const float* vel, int64_t ldv, const float* Delta, i
     return fused_closure(
         p, "ibh_les_of: needs a 3-D partition made of complete blocks or one without block "
            "structure (compose cell_gradient and the pointwise closures otherwise)",
-        [&] { return ibh_les_of_cells(p, vel, ldv, Delta, model, Cmodel, nusgs, ducros, shock, S, G, ldg); },
+        [&] {
+            launch_nd(p->nd, p->nc, k_les_of_cells<2>, k_les_of_cells<3>, p->nc, grad_dims(p), vel, ldv, Delta, model, Cmodel,
+                      les_dev::Outputs{nusgs, ducros, shock, S, G, ldg});
+        },
         [&] {
             launch_blocks3(model == 0 ? k_les_of3<0> : model == 1 ? k_les_of3<1> : k_les_of3<2>, p,
                            FieldPtrs<3>{{vel, vel + ldv, vel + 2 * ldv}}, Delta, Cmodel,
@@ -729,7 +848,10 @@ int ibh_k_epsilon_rhs(ibh_part* p, const float* vel, int64_t ldv, const float* k
     return fused_closure(
         p, "ibh_k_epsilon_rhs: needs a 3-D partition made of complete blocks or one without block "
            "structure (compose shear_rate_of_velocity, standard_k_epsilon and scalar_transport otherwise)",
-        [&] { return ibh_k_epsilon_rhs_cells(p, vel, ldv, k, eps, nu, params5, rk, reps, nut, S, G, ldg); },
+        [&] {
+            launch_nd(p->nd, p->nc, k_k_epsilon_rhs_cells<2>, k_k_epsilon_rhs_cells<3>, p->nc, grad_dims(p), vel, ldv, k, eps, nu,
+                      tr_dev::keps_params(params5), rk, reps, nut, S, G, ldg);
+        },
         [&] {
             launch_blocks3(k_k_epsilon_rhs3, p, (uint32_t)p->nc, p->spacing, vel, (uint32_t)ldv, k, eps, nu,
                            tr_dev::keps_params(params5), rk, reps, nut, S, G, (uint32_t)ldg);

@@ -9,8 +9,9 @@ The compositions: the restriction is ``primitive2state``, the broadcast ``R .+ S
 
 Meshes: ``adv_mesh_coarse`` as one partition (3904 cells, refinement, immersed walls) with the two coarser levels of
 ``multigrid`` (8 -> 4 -> 2 cells per block side: 976 and 244 cells), and the 3-D ``corner`` mesh with one coarser level.  Every
-row of their operators starts on a 16-byte boundary, so a synthetic operator with rows of 0 .. 5 entries -- rows off the
-boundary, empty rows -- and more rows than one pass of either grid covers stands beside them.
+row of their operators starts on a 16-byte boundary, so synthetic operators -- rows of 0 .. 12 entries on and off the
+boundary (``percell_steps.synthetic_csr``), and one with more rows than one pass of either grid covers -- stand beside them.
+The restricted defect ``D_c`` is also held bit for bit against ``euler_mg_model.apply``, numpy's statement of the row walk.
 """
 import ctypes as C
 
@@ -21,6 +22,7 @@ import torch
 import euler_forms as ef
 import euler_mg_model as mg
 import ibamd
+import percell_steps as ps
 import regimes as rg
 from conftest import ADV_FAMILIES, RAE_FAMILIES
 from euler_forms import FLUID, NAN, SCALE, padded, same_bits
@@ -82,12 +84,17 @@ TRANSFERS = [("adv", 0), ("adv", 1), ("corner", 0)]        # (mesh, the finer of
 
 
 def ragged(n_out, n_in, seed=3):
-    """A synthetic operator: row ``r`` has ``r % 6`` entries (rows off the 16-byte boundary, empty rows, tails after a group
-    of four), random donors and weights."""
+    """A synthetic operator with random donors and positive weights (the restricted density stays positive).  Its rows are
+    those of ``percell_steps.synthetic_csr``: every length of ``ROW_LENGTHS`` -- empty rows, tails after one and after two
+    groups of four -- starting at every residue of the 16-byte boundary (asserted).  The grid-stride shape, too long for that
+    row-by-row construction, keeps ``r % 6`` entries in row ``r``."""
     rng = np.random.default_rng(seed)
-    lengths = np.arange(n_out) % 6
-    off = np.concatenate([[0], np.cumsum(lengths)])
-    idx = rng.integers(0, n_in, int(off[-1]))
+    if n_out < 10 ** 5:
+        off, idx, _ = ps.synthetic_csr(n_out, n_in, seed=seed)
+        ps.assert_paths_covered(off)
+    else:
+        off = np.concatenate([[0], np.cumsum(np.arange(n_out) % 6)])
+        idx = rng.integers(0, n_in, int(off[-1]))
     w = rng.uniform(0.05, 0.5, int(off[-1])).astype(f32)
     return Accumulator(csr=(off, idx, w), n_input=n_in)
 
@@ -133,6 +140,11 @@ def check_restrict(acc, P, R, S, what):
         assert got[0] is oP and got[1] is oD
         same_bits(oP, ref_P, tag + " P_c")
         same_bits(oD, ref_D, tag + " D_c")
+        # D_c against a witness that shares no code with the device's row walk (multiplications and additions only: the
+        # model's bits; P_c passes through divisions and stays proved against the composition)
+        Rh = ibamd.to_host(R)
+        model_D = mg.apply(acc, Rh + ibamd.to_host(S) if with_S else Rh)
+        same_bits(oD, torch.from_numpy(model_D), tag + " D_c against the numpy model")
         aP, aD = ibamd.restrict_euler(acc, P, R, Sx, FLUID)
         same_bits(aP, ref_P, tag + " P_c allocated")
         same_bits(aD, ref_D, tag + " D_c allocated")
@@ -200,8 +212,9 @@ def test_prolong_bit_for_bit(hier, mesh, l):
 @pytest.mark.parametrize("nd,n_out,n_in", [(2, 1000, 333), (3, 777, 2100), (3, 4096 * 256 + 77, 2048 * 256 + 55)],
                          ids=["2d", "3d", "3d_grid_stride"])
 def test_transfers_on_ragged_rows(nd, n_out, n_in):
-    """Rows of 0 .. 5 entries that start on and off 16-byte boundaries; the last case has more output rows than one pass of
-    the row kernels' grids (4096 x 256) and more input rows than one pass of the pack kernel's (2048 x 256)."""
+    """Rows of 0 .. 12 entries (0 .. 5 in the last case) that start on and off 16-byte boundaries; the last case has more
+    output rows than one pass of the row kernels' grids (4096 x 256) and more input rows than one pass of the pack kernel's
+    (2048 x 256)."""
     acc = ragged(n_out, n_in)
     P, R = rows(n_in, nd, 5)
     _, S = rows(n_in, nd, 6)

@@ -141,6 +141,34 @@ def test_diff_add(n_out, n_in, nvs):
         _record("diff_add packed" if packed and 2 <= nv <= 8 else "diff_add rows", e)
 
 
+@pytest.mark.parametrize("n_out,n_in", [(255, 300), (1020, 255)], ids=["rows", "packed"])
+def test_row_walk_bits_against_the_model(n_out, n_in):
+    """The order of the row walk (ibh_stencil_dev.h), which the float64 bound above cannot see: ``ibh_accumulate`` and
+    ``ibh_accumulate_diff_add`` bit for bit against ``euler_mg_model.apply`` -- numpy Float32, product per entry, the first
+    assigned, entry order; multiplications and additions only, so IEEE arithmetic without contraction leaves no room
+    (tests/test_percell_steps.py::test_row_walk_model_is_sound).  (255, 300): ``diff_add`` through ``k_accumulate_rows<8,
+    true>``; (1020, 255): ``n_out >= 4 n_in``, through ``k_pack_diff8`` + ``k_accumulate_packed_add<6>``."""
+    import euler_mg_model as mg
+    from euler_forms import same_bits
+    host = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=f32))      # (same_bits takes tensors)
+    for weighted in (True, False):
+        off, idx, w = ps.synthetic_csr(n_out, n_in, seed=n_out, weighted=weighted)
+        ps.assert_paths_covered(off)
+        acc = Accumulator(csr=(off, idx, w), n_input=n_in)
+        dacc = B.DeviceAccumulator(acc)
+        for nv in (1, 3, 6):
+            v = ps.seeded((n_in, nv), 10 + nv)
+            model = mg.apply(acc, v)
+            assert np.isfinite(model).all()
+            same_bits(host(_apply(dacc, v, n_in + 5, n_out + 3)), host(model), f"accumulate n_out={n_out} w={weighted} nv={nv}")
+        nv = 6                                             # (without weights both shapes take k_accumulate_rows<8, true>)
+        a, b, o0 = ps.seeded((n_in, nv), nv), ps.seeded((n_in, nv), nv + 20), ps.seeded((n_out, nv), nv + 40)
+        ld, ldo = n_in + 3, n_out + 1
+        ab, bb, ob = to_field(a, ld), to_field(b, ld), to_field(o0, ldo)
+        call("ibh_accumulate_diff_add", dacc.handle, B._ptr(ab), B._ptr(bb), nv, ld, B._ptr(ob), ldo)
+        same_bits(host(from_field(ob, n_out)), host(o0 + mg.apply(acc, a - b)), f"diff_add n_out={n_out} n_in={n_in} w={weighted}")
+
+
 def _octree_domain():
     from ibamd.mesher import Ball, Mesh
     msh = Mesh(f32([-2, -2, -2]), f32([4, 4, 4]), block_size=8,

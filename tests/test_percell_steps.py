@@ -40,6 +40,32 @@ def test_calibration_accumulator():
     print("Float32 oracle against float64, accumulator:", {k: f"{v:.2e}" for k, v in worst.items()})
 
 
+def test_row_walk_model_is_sound():
+    """``euler_mg_model.apply`` -- numpy Float32, product per entry, the first one assigned, the others added in entry order:
+    the witness tests/test_gpu_percell_steps.py and tests/test_gpu_euler_mg.py hold the device's row walk against bit for bit,
+    and which shares no code with it -- on the synthetic rows, weighted and unweighted: within ``BOUND_ACC`` of the float64
+    reference and the bits of the Float32 oracle, with and without ``diff`` and ``add``."""
+    import euler_mg_model as mg
+    from ibamd.accumulator import Accumulator
+    worst = 0.0
+    for n_out, n_in in ((255, 300), (1020, 255), (257, 64)):
+        for weighted in (True, False):
+            off, idx, w = ps.synthetic_csr(n_out, n_in, seed=n_out, weighted=weighted)
+            ps.assert_paths_covered(off)
+            acc = Accumulator(csr=(off, idx, w), n_input=n_in)
+            for nv in (1, 3, 6):
+                v, v2, o0 = ps.seeded((n_in, nv), 1), ps.seeded((n_in, nv), 2), ps.seeded((n_out, nv), 3)
+                for name, got, kw in (("apply", mg.apply(acc, v), {}),
+                                      ("diff_add", o0 + mg.apply(acc, v - v2), dict(v2=v2, out0=o0))):
+                    what = f"{name} n_out={n_out} w={weighted} nv={nv}"
+                    assert got.dtype == f32 and np.isfinite(got).all(), what
+                    ref, sc = ps.acc_ref(off, idx, w, v, **kw)
+                    worst = max(worst, ps.check(got, ref, sc, ps.BOUND_ACC, what))
+                    oracle = np.asarray(ps.acc_oracle32(off, idx, w, v, **kw), f32)
+                    assert np.array_equal(got.view(np.uint32), oracle.view(np.uint32)), what
+    print(f"Float32 model of the row walk against float64: {worst:.2e}")
+
+
 def _oracle_set(a, bs):
     dom = ps.oracle_boundaries(bs)
     return ps.oracle_impose(a, dom, [(f"b{k}", b["mode"], b["value"]) for k, b in enumerate(bs)])
