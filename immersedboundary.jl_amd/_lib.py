@@ -41,6 +41,7 @@ _SIGS = {
     "ibh_h2d": [c_vp, c_vp, C.c_size_t],
     "ibh_d2h": [c_vp, c_vp, C.c_size_t],
     "ibh_memset": [c_vp, c_int, C.c_size_t],
+    "ibh_owned_device_memory": [C.POINTER(c_i64), C.POINTER(c_i64)],
     "ibh_partition_create": [C.POINTER(c_vp), c_int, C.c_int32, c_vp, c_vp, c_vp,
                              C.POINTER(c_vp), C.POINTER(c_vp), C.POINTER(c_vp), C.POINTER(c_vp),
                              C.POINTER(c_vp), C.POINTER(c_vp), C.c_int32, c_vp, c_vp, c_int, c_int],

@@ -187,8 +187,24 @@ def _like(t, n):
 # ---------------------------------------------------------------------------
 # structs on the device
 # ---------------------------------------------------------------------------
-class DevicePartition:
+class _Handle:
+    """A library handle and the name of the entry that destroys it: ``handle`` is set by the subclass once its create call
+    has succeeded, and goes to ``_destroy`` once, when the object goes."""
+    _destroy = None
+    handle = None
+
+    def __del__(self):
+        try:
+            if self.handle:
+                h, self.handle = self.handle, None
+                getattr(_lib.load(), self._destroy)(h)
+        except Exception:  # noqa: BLE001
+            pass
+
+
+class DevicePartition(_Handle):
     """Device-resident Partition: ``to_backend(part, hip)`` (uploads once, caches the handle)."""
+    _destroy = "ibh_partition_destroy"
 
     def __init__(self, part: Partition):
         dev = _dev()
@@ -245,17 +261,10 @@ class DevicePartition:
     def ndims(self):
         return self.nd
 
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                _lib.load().ibh_partition_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
 
-
-class DeviceAccumulator:
+class DeviceAccumulator(_Handle):
     """Device-resident Accumulator; callable like the reference's (accumulator.jl:78-130)."""
+    _destroy = "ibh_acc_destroy"
 
     def __init__(self, acc: Accumulator):
         _dev()
@@ -289,17 +298,10 @@ class DeviceAccumulator:
         call("ibh_accumulate_diff_add", self.handle, _ptr(a), _ptr(b), nv, ld, _ptr(o), ldo)
         return out
 
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                _lib.load().ibh_acc_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
 
-
-class DeviceBoundary:
+class DeviceBoundary(_Handle):
     """Device-resident Boundary (ImmersedBoundary.jl:406-414)."""
+    _destroy = "ibh_bc_destroy"
 
     def __init__(self, b: Boundary):
         self.host = b
@@ -319,14 +321,6 @@ class DeviceBoundary:
         self.normals = hip(b.normals)
         self.image_distances = hip(b.image_distances)
         self.ghost_distances = hip(b.ghost_distances)
-
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                _lib.load().ibh_bc_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
 
 
 class DeviceSurface:
@@ -627,12 +621,13 @@ def residual_advection_repeat(part, u, C_, out, n, flags=0):
 # ---------------------------------------------------------------------------
 # an explicit solver step, device resident (test/advection.jl:30-89)
 # ---------------------------------------------------------------------------
-class BCSet:
+class BCSet(_Handle):
     """An ordered list of ``impose_bc!`` calls (ImmersedBoundary.jl:1197-1247) whose closures the library knows --
     ``(name, value)``: ``do bdry, u; value end``; ``(name, "copy")``: ``do bdry, u; copy(u) end`` (the three calls of
     test/advection.jl:30-46) -- on the one partition ``ipart`` of ``dom`` whose local cell order is the global one.
     ``apply(u)`` has the semantics of the sequential calls; boundaries that do not read each other's ghost cells share
     their two launches (``n_levels`` pairs in all)."""
+    _destroy = "ibh_bcset_destroy"
 
     def __init__(self, dom, specs, ipart=1):
         part = dom.partitions[ipart]
@@ -658,7 +653,8 @@ class BCSet:
         self.n_direct_levels = int(nl.value) >> 16      # levels blended straight into the field (one launch each)
 
     def healthy(self):
-        """False if a barrier of the one-launch form ever gave up (its bound is far beyond anything a healthy launch needs)."""
+        """True while the set reports a ghost count that is not negative, which is always: the library has no form of the
+        set left that can fail after it was created (``ibh_bcset_info`` is host code and reads nothing back)."""
         ng, nl = C.c_int32(0), C.c_int32(0)
         call("ibh_bcset_info", self.handle, C.byref(ng), C.byref(nl))
         return ng.value >= 0
@@ -676,12 +672,14 @@ class BCSet:
         call("ibh_bcset_apply", self.handle, _ptr(f))
         return u
 
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                _lib.load().ibh_bcset_destroy(self.handle)
-        except Exception:  # noqa: BLE001
-            pass
+
+def owned_device_memory():
+    """``(bytes, buffers)`` of device memory that the live library handles own -- partitions, accumulators, boundaries,
+    BC sets and domain plans with the workspaces they allocate on first use (``ibh_owned_device_memory``).  Exact: a failed
+    create leaves it unchanged, a destroy takes the handle's share off."""
+    nb, nbuf = C.c_int64(0), C.c_int64(0)
+    call("ibh_owned_device_memory", C.byref(nb), C.byref(nbuf))
+    return int(nb.value), int(nbuf.value)
 
 
 def timestep_advection(part, C_, scale=1.0, out=None):
@@ -1211,9 +1209,10 @@ def _on_device(a):
     return isinstance(a, HipArray) or (isinstance(a, torch.Tensor) and a.is_cuda)
 
 
-class DomainPlan:
+class DomainPlan(_Handle):
     """Device tables of the domain call of one Domain (``ibh_domain_plan_create``; ``domain_plan_tables`` is the same
     construction in numpy) plus the partitions' ``to_backend`` handles, in call order.  Cached on the Domain."""
+    _destroy = "ibh_domain_plan_destroy"
 
     def __init__(self, dom):
         from .domain import domain_plan_tables
@@ -1246,14 +1245,6 @@ class DomainPlan:
         k = len(a)
         call(name, self.handle, k, (c_vp * k)(*a), _hptr(np.asarray(nvs, dtype=np.int32)),
              _hptr(np.asarray(lds, dtype=np.int64)), (c_vp * k)(*b))
-
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                _lib.load().ibh_domain_plan_destroy(self.handle)
-                self.handle = None
-        except Exception:  # noqa: BLE001
-            pass
 
 
 def domain_plan(dom):

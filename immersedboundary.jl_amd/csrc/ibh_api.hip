@@ -1,6 +1,8 @@
 // libibhip: runtime, memory and handle management (host side of the C ABI).
 #include <string.h>
 
+#include <memory>
+
 #include "ibh_common.h"
 
 thread_local std::string ibh_err;
@@ -10,19 +12,6 @@ int ibh_fail(int code, const char* what, const char* file, int line) {
     ibh_err = std::string(what) + " (" + file + ":" + std::to_string(line) + ")";
     return code ? code : -1;
 }
-
-template <class T>
-int ibh_upload(T** dptr, const T* host, size_t n) {
-    *dptr = nullptr;
-    if (n == 0) return 0;
-    IBH_HIP(hipMalloc((void**)dptr, n * sizeof(T)));
-    IBH_HIP(hipMemcpy(*dptr, host, n * sizeof(T), hipMemcpyHostToDevice));
-    return 0;
-}
-template int ibh_upload<int32_t>(int32_t**, const int32_t*, size_t);
-template int ibh_upload<float>(float**, const float*, size_t);
-template int ibh_upload<BlockDesc2>(BlockDesc2**, const BlockDesc2*, size_t);
-template int ibh_upload<BlockDesc3>(BlockDesc3**, const BlockDesc3*, size_t);
 
 static std::vector<int32_t> rebased(const int32_t* p, size_t n, int base) {
     std::vector<int32_t> v(n);
@@ -176,6 +165,11 @@ int ibh_free(void* p) {
     if (p) IBH_HIP(hipFree(p));
     return 0;
 }
+int ibh_owned_device_memory(int64_t* bytes, int64_t* buffers) {
+    if (bytes) *bytes = ibh_owned_bytes;
+    if (buffers) *buffers = ibh_owned_buffers;
+    return 0;
+}
 int ibh_h2d(void* dst, const void* src, size_t bytes) {
     IBH_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ibh_stream));
     IBH_HIP(hipStreamSynchronize(ibh_stream));
@@ -199,26 +193,26 @@ int ibh_partition_create(ibh_part** out, int nd, int32_t nc, const float* spacin
                          const int32_t* image_in_domain, const int32_t* domain, int block_size, int index_base) {
     IBH_REQUIRE(out && spacing && nf && owners && neighbors && left_off && left_idx && right_off && right_idx,
                 "ibh_partition_create: null argument");
+    *out = nullptr;
     IBH_REQUIRE(nd == 2 || nd == 3, "ibh_partition_create: nd must be 2 or 3");
     IBH_REQUIRE(nc >= 0 && (index_base == 0 || index_base == 1), "ibh_partition_create: bad nc/index_base");
     HostPartView v;
-    int rc = make_view(v, nd, nc, spacing, nf, owners, neighbors, left_off, left_idx, right_off, right_idx, domain,
-                       block_size, index_base);
-    if (rc) return rc;
-    ibh_part* p = new ibh_part();
+    IBH_TRY(make_view(v, nd, nc, spacing, nf, owners, neighbors, left_off, left_idx, right_off, right_idx, domain,
+                      block_size, index_base));
+    std::unique_ptr<ibh_part> p(new ibh_part());   // freed with all its buffers by any return before the release
     p->nd = nd;
     p->nc = nc;
-    if ((rc = ibh_upload(&p->spacing, spacing, (size_t)nc * nd))) return rc;
-    if (centers && (rc = ibh_upload(&p->centers, centers, (size_t)nc * nd))) return rc;
+    IBH_TRY(p->own.upload(&p->spacing, spacing, (size_t)nc * nd));
+    if (centers) IBH_TRY(p->own.upload(&p->centers, centers, (size_t)nc * nd));
     for (int d = 0; d < nd; ++d) {
         DimData& D = p->dim[d];
         D.nf = nf[d];
-        if ((rc = ibh_upload(&D.owners, v.owners[d].data(), v.owners[d].size()))) return rc;
-        if ((rc = ibh_upload(&D.neighbors, v.neighbors[d].data(), v.neighbors[d].size()))) return rc;
-        if ((rc = ibh_upload(&D.loff, v.loff[d].data(), v.loff[d].size()))) return rc;
-        if ((rc = ibh_upload(&D.lidx, v.lidx[d].data(), v.lidx[d].size()))) return rc;
-        if ((rc = ibh_upload(&D.roff, v.roff[d].data(), v.roff[d].size()))) return rc;
-        if ((rc = ibh_upload(&D.ridx, v.ridx[d].data(), v.ridx[d].size()))) return rc;
+        IBH_TRY(p->own.upload(&D.owners, v.owners[d]));
+        IBH_TRY(p->own.upload(&D.neighbors, v.neighbors[d]));
+        IBH_TRY(p->own.upload(&D.loff, v.loff[d]));
+        IBH_TRY(p->own.upload(&D.lidx, v.lidx[d]));
+        IBH_TRY(p->own.upload(&D.roff, v.roff[d]));
+        IBH_TRY(p->own.upload(&D.ridx, v.ridx[d]));
     }
     {
         std::vector<int32_t> side((size_t)2 * nd * nc);
@@ -241,23 +235,23 @@ int ibh_partition_create(ibh_part** out, int nd, int32_t nc, const float* spacin
                     direct += t >= 0;
                 }
             }
-        if ((rc = ibh_upload(&p->side, side.data(), side.size()))) return rc;
+        IBH_TRY(p->own.upload(&p->side, side));
         p->info[17] = direct;
     }
     p->n_image = n_image;
     if (n_image > 0 && image_in_domain) {
         std::vector<int32_t> iid = rebased(image_in_domain, n_image, index_base);
         for (int32_t x : iid) IBH_REQUIRE(x >= 0 && x < nc, "ibh_partition_create: image_in_domain out of range");
-        if ((rc = ibh_upload(&p->image_in_domain, iid.data(), iid.size()))) return rc;
+        IBH_TRY(p->own.upload(&p->image_in_domain, iid));
     }
     p->bs = 0;
     if (domain && block_size > 0 && nd == 2 && block_size == 8) {
         Host2D H;
         analyze2_host(v, n_image, image_in_domain, index_base, H);
         for (int i = 0; i < 12; ++i) p->info[i] = H.info[i];
-        if ((rc = ibh_upload(&p->htab, H.htab.data(), H.htab.size()))) return rc;
-        if ((rc = ibh_upload(&p->etab, H.etab.data(), H.etab.size()))) return rc;
-        if ((rc = ibh_upload(&p->dtab, H.dtab.data(), H.dtab.size()))) return rc;
+        IBH_TRY(p->own.upload(&p->htab, H.htab));
+        IBH_TRY(p->own.upload(&p->etab, H.etab));
+        IBH_TRY(p->own.upload(&p->dtab, H.dtab));
         p->n_dt = (int32_t)(H.dtab.size() / 64);
         p->fuse_all = H.fuse_all;
         p->rows_ok = H.rows_ok;
@@ -265,7 +259,7 @@ int ibh_partition_create(ibh_part** out, int nd, int32_t nc, const float* spacin
         p->n_img = (int32_t)H.img.size();
         p->n_img_int = H.n_img_int;
         p->img_all_fz = H.img_all_fz;
-        if (p->img_all_fz && (rc = ibh_upload(&p->img_list, H.img.data(), H.img.size()))) return rc;
+        if (p->img_all_fz) IBH_TRY(p->own.upload(&p->img_list, H.img));
         if (!p->fuse_all && H.info[8] > 0) {
             p->n_fz = (int32_t)H.fz.size();
             p->n_ng = (int32_t)H.ng.size();
@@ -273,9 +267,9 @@ int ibh_partition_create(ibh_part** out, int nd, int32_t nc, const float* spacin
             p->n_fz_int = H.n_fz_int;
             p->n_ng_int = H.n_ng_int;
             p->n_nf_int = H.n_nf_int;
-            if ((rc = ibh_upload(&p->fz_list, H.fz.data(), H.fz.size()))) return rc;
-            if ((rc = ibh_upload(&p->ng_list, H.ng.data(), H.ng.size()))) return rc;
-            if ((rc = ibh_upload(&p->nf_list, H.nf.data(), H.nf.size()))) return rc;
+            IBH_TRY(p->own.upload(&p->fz_list, H.fz));
+            IBH_TRY(p->own.upload(&p->ng_list, H.ng));
+            IBH_TRY(p->own.upload(&p->nf_list, H.nf));
         }
         for (int k = 0; k < 2; ++k) {
             const QuadSet2& Q = H.quads[k];
@@ -294,16 +288,16 @@ int ibh_partition_create(ibh_part** out, int nd, int32_t nc, const float* spacin
                 p->npair = (int32_t)Q.pd.size();
                 p->nqs2 = (int32_t)Q.singles2.size();
                 p->info[18] = p->npair;
-                if ((rc = ibh_upload(&p->qd[k], qd.data(), qd.size()))) return rc;
-                if ((rc = ibh_upload(&p->qtab[k], qt.data(), qt.size()))) return rc;
-                if ((rc = ibh_upload(&p->qsingles2, Q.singles2.data(), Q.singles2.size()))) return rc;
+                IBH_TRY(p->own.upload(&p->qd[k], qd));
+                IBH_TRY(p->own.upload(&p->qtab[k], qt));
+                IBH_TRY(p->own.upload(&p->qsingles2, Q.singles2));
                 std::vector<int32_t> qa(Q.qaux);
                 qa.insert(qa.end(), Q.paux.begin(), Q.paux.end());
-                if ((rc = ibh_upload(&p->qaux[k], qa.data(), qa.size()))) return rc;
+                IBH_TRY(p->own.upload(&p->qaux[k], qa));
             } else {
-                if ((rc = ibh_upload(&p->qd[k], Q.qd.data(), Q.qd.size()))) return rc;
-                if ((rc = ibh_upload(&p->qtab[k], Q.qtab.data(), Q.qtab.size()))) return rc;
-                if ((rc = ibh_upload(&p->qaux[k], Q.qaux.data(), Q.qaux.size()))) return rc;
+                IBH_TRY(p->own.upload(&p->qd[k], Q.qd));
+                IBH_TRY(p->own.upload(&p->qtab[k], Q.qtab));
+                IBH_TRY(p->own.upload(&p->qaux[k], Q.qaux));
             }
             {
                 int64_t arith = 0;
@@ -311,7 +305,7 @@ int ibh_partition_create(ibh_part** out, int nd, int32_t nc, const float* spacin
                     for (int l = 0; l < 8; ++l) arith += Q.qaux[i + 32 + l] >= 0;
                 if (k == 0) p->info[19] = arith;     // half-sides of the quads whose halo ids are arithmetic
             }
-            if ((rc = ibh_upload(&p->qsingles[k], Q.singles.data(), Q.singles.size()))) return rc;
+            IBH_TRY(p->own.upload(&p->qsingles[k], Q.singles));
         }
         p->nA1 = H.nph[0];
         p->nB1 = H.nph[1];
@@ -324,8 +318,8 @@ int ibh_partition_create(ibh_part** out, int nd, int32_t nc, const float* spacin
             for (size_t b = 0; tiled && b < H.blocks.size(); ++b) tiled = H.blocks[b].base == (int32_t)(64 * b);
             p->info[20] = tiled ? 1 : 0;
         }
-        if ((rc = ibh_upload(&p->blocks2, H.blocks.data(), H.blocks.size()))) return rc;
-        if ((rc = ibh_upload(&p->irr_cells, H.irr.data(), H.irr.size()))) return rc;
+        IBH_TRY(p->own.upload(&p->blocks2, H.blocks));
+        IBH_TRY(p->own.upload(&p->irr_cells, H.irr));
     } else if (domain && block_size == 8 && nd == 3) {
         std::vector<BlockDesc3> blocks;
         std::vector<int32_t> irr, htab, ftab;
@@ -340,9 +334,9 @@ int ibh_partition_create(ibh_part** out, int nd, int32_t nc, const float* spacin
         p->info[9] = sw.all ? 0 : (int64_t)blocks.size();   // blocks whose gradients go through the workspace
         p->info[12] = (int64_t)(sw.r4tab.size() / 4);         // rim neighbours made of four finer cells
         if (sw.r4tab.empty()) sw.r4tab.assign(4, 0);
-        if ((rc = ibh_upload(&p->rtab3, sw.rtab.data(), sw.rtab.size()))) return rc;
-        if ((rc = ibh_upload(&p->r4tab3, sw.r4tab.data(), sw.r4tab.size()))) return rc;
-        if ((rc = ibh_upload(&p->ftab3, ftab.data(), ftab.size()))) return rc;
+        IBH_TRY(p->own.upload(&p->rtab3, sw.rtab));
+        IBH_TRY(p->own.upload(&p->r4tab3, sw.r4tab));
+        IBH_TRY(p->own.upload(&p->ftab3, ftab));
         p->nA1 = nph[0];
         p->nB1 = nph[1];
         p->bs = block_size;
@@ -353,27 +347,27 @@ int ibh_partition_create(ibh_part** out, int nd, int32_t nc, const float* spacin
             for (size_t b = 0; tiled && b < blocks.size(); ++b) tiled = blocks[b].base == (int32_t)(512 * b);
             p->info[20] = tiled ? 1 : 0;
         }
-        if ((rc = ibh_upload(&p->blocks3, blocks.data(), blocks.size()))) return rc;
-        if ((rc = ibh_upload(&p->htab3, htab.data(), htab.size()))) return rc;
+        IBH_TRY(p->own.upload(&p->blocks3, blocks));
+        IBH_TRY(p->own.upload(&p->htab3, htab));
         if (have_img && !sw.all) {   // a partition with skirt fragments: the image blocks for the image-only sweeps
             Image3Host im;
             ibh_analyze_image3(v, image_in_domain, n_image, im);
             if (im.all) {
                 if (im.r4tab.empty()) im.r4tab.assign(4, 0);
                 if (im.ftab.empty()) im.ftab.assign(4, 0);
-                if ((rc = ibh_upload(&p->iblocks3, im.blocks.data(), im.blocks.size()))) return rc;
-                if ((rc = ibh_upload(&p->ihtab3, im.htab.data(), im.htab.size()))) return rc;
-                if ((rc = ibh_upload(&p->iftab3, im.ftab.data(), im.ftab.size()))) return rc;
-                if ((rc = ibh_upload(&p->irtab3, im.rtab.data(), im.rtab.size()))) return rc;
-                if ((rc = ibh_upload(&p->ir4tab3, im.r4tab.data(), im.r4tab.size()))) return rc;
-                if ((rc = ibh_upload(&p->idtab3, im.dtab.data(), im.dtab.size()))) return rc;
+                IBH_TRY(p->own.upload(&p->iblocks3, im.blocks));
+                IBH_TRY(p->own.upload(&p->ihtab3, im.htab));
+                IBH_TRY(p->own.upload(&p->iftab3, im.ftab));
+                IBH_TRY(p->own.upload(&p->irtab3, im.rtab));
+                IBH_TRY(p->own.upload(&p->ir4tab3, im.r4tab));
+                IBH_TRY(p->own.upload(&p->idtab3, im.dtab));
                 p->n_img3 = (int32_t)im.blocks.size();
                 p->img_all3 = 1;
             }
         }
         p->info[10] = p->img_all3 || sw.all;       // image blocks all eligible for the single-kernel sweeps
         p->info[11] = p->img_all3 ? p->n_img3 : (sw.all ? (int64_t)blocks.size() : 0);
-        if ((rc = ibh_upload(&p->irr_cells, irr.data(), irr.size()))) return rc;
+        IBH_TRY(p->own.upload(&p->irr_cells, irr));
     } else {
         p->info[0] = 0;
         p->info[1] = nc;
@@ -404,9 +398,9 @@ int ibh_partition_create(ibh_part** out, int nd, int32_t nc, const float* spacin
                     }
                 }
         }
-        if (ok && (rc = ibh_upload(&p->irr_rec, rec.data(), rec.size()))) return rc;
+        if (ok) IBH_TRY(p->own.upload(&p->irr_rec, rec));
     }
-    *out = p;
+    *out = p.release();
     return 0;
 }
 
@@ -418,9 +412,8 @@ int ibh_analyze2_host(ibh_host2d** out, int32_t nc, const float* spacing, const 
     IBH_REQUIRE(out && spacing && nf && owners && neighbors && left_off && left_idx && right_off && right_idx && domain,
                 "ibh_analyze2_host: null argument");
     HostPartView v;
-    int rc = make_view(v, 2, nc, spacing, nf, owners, neighbors, left_off, left_idx, right_off, right_idx, domain, 8,
-                       index_base);
-    if (rc) return rc;
+    IBH_TRY(make_view(v, 2, nc, spacing, nf, owners, neighbors, left_off, left_idx, right_off, right_idx, domain, 8,
+                      index_base));
     ibh_host2d* h = new ibh_host2d();
     analyze2_host(v, n_image, image_in_domain, index_base, h->H);
     *out = h;
@@ -466,42 +459,6 @@ int ibh_host2d_destroy(ibh_host2d* h) {
 }
 
 int ibh_partition_destroy(ibh_part* p) {
-    if (!p) return 0;
-    hipFree(p->spacing);
-    hipFree(p->centers);
-    for (int d = 0; d < p->nd; ++d) {
-        DimData& D = p->dim[d];
-        hipFree(D.owners); hipFree(D.neighbors);
-        hipFree(D.loff); hipFree(D.lidx); hipFree(D.roff); hipFree(D.ridx);
-    }
-    hipFree(p->image_in_domain);
-    hipFree(p->side);
-    hipFree(p->blocks2);
-    hipFree(p->htab);
-    hipFree(p->etab);
-    hipFree(p->dtab);
-    hipFree(p->img_list);
-    hipFree(p->march_tmp);
-    for (int k = 0; k < 2; ++k) {
-        hipFree(p->qd[k]);
-        hipFree(p->qtab[k]);
-        hipFree(p->qaux[k]);
-        hipFree(p->qsingles[k]);
-        if (k == 0) hipFree(p->qsingles2);
-    }
-    hipFree(p->fz_list);
-    hipFree(p->ng_list);
-    hipFree(p->nf_list);
-    hipFree(p->blocks3);
-    hipFree(p->htab3);
-    hipFree(p->iblocks3); hipFree(p->ihtab3); hipFree(p->iftab3); hipFree(p->irtab3); hipFree(p->ir4tab3);
-    hipFree(p->idtab3);
-    hipFree(p->ftab3);
-    hipFree(p->rtab3);
-    hipFree(p->r4tab3);
-    hipFree(p->irr_cells);
-    hipFree(p->irr_rec);
-    hipFree(p->G);
     delete p;
     return 0;
 }
@@ -524,27 +481,23 @@ static int acc_fill(ibh_acc* a, int32_t n_output, int32_t n_input, const int32_t
     for (int32_t x : ix) IBH_REQUIRE(x >= 0 && x < n_input, "ibh_acc_create: donor index out of range");
     a->n_out = n_output;
     a->n_in = n_input;
-    int rc;
-    if ((rc = ibh_upload(&a->off, o.data(), o.size()))) return rc;
-    if ((rc = ibh_upload(&a->idx, ix.data(), ix.size()))) return rc;
-    a->w = nullptr;
-    if (w && (rc = ibh_upload(&a->w, w, nnz))) return rc;
+    IBH_TRY(a->own.upload(&a->off, o));
+    IBH_TRY(a->own.upload(&a->idx, ix));
+    if (w) IBH_TRY(a->own.upload(&a->w, w, nnz));
     return 0;
 }
 
 int ibh_acc_create(ibh_acc** out, int32_t n_output, int32_t n_input, const int32_t* off, const int32_t* idx,
                    const float* w, int index_base) {
     IBH_REQUIRE(out, "ibh_acc_create: null out");
-    ibh_acc* a = new ibh_acc();
-    int rc = acc_fill(a, n_output, n_input, off, idx, w, index_base);
-    if (rc) { delete a; return rc; }
-    *out = a;
+    *out = nullptr;
+    std::unique_ptr<ibh_acc> a(new ibh_acc());
+    IBH_TRY(acc_fill(a.get(), n_output, n_input, off, idx, w, index_base));
+    *out = a.release();
     return 0;
 }
 
 int ibh_acc_destroy(ibh_acc* a) {
-    if (!a) return 0;
-    hipFree(a->off); hipFree(a->idx); hipFree(a->w); hipFree(a->packed);
     delete a;
     return 0;
 }
@@ -554,18 +507,18 @@ int ibh_bc_create(ibh_bc** out, int32_t ng, const int32_t* ghost_indices, const 
                   const int32_t* interp_off, const int32_t* interp_idx, const float* interp_w, int index_base) {
     IBH_REQUIRE(out && ghost_indices && ghost_distances && image_distances && image_domain,
                 "ibh_bc_create: null argument");
-    ibh_bc* b = new ibh_bc();
+    *out = nullptr;
+    std::unique_ptr<ibh_bc> b(new ibh_bc());
     b->ng = ng;
     b->nid = nid;
     std::vector<int32_t> g = rebased(ghost_indices, ng, index_base);
     std::vector<int32_t> idm = rebased(image_domain, nid, index_base);
     std::vector<float> eta(ng);
     for (int32_t i = 0; i < ng; ++i) eta[i] = ghost_distances[i] / image_distances[i];  // :1220
-    int rc;
-    if ((rc = ibh_upload(&b->ghost, g.data(), g.size()))) return rc;
-    if ((rc = ibh_upload(&b->image_domain, idm.data(), idm.size()))) return rc;
-    if ((rc = ibh_upload(&b->eta, eta.data(), eta.size()))) return rc;
-    if ((rc = acc_fill(&b->interp, ng, nid, interp_off, interp_idx, interp_w, index_base))) return rc;
+    IBH_TRY(b->own.upload(&b->ghost, g));
+    IBH_TRY(b->own.upload(&b->image_domain, idm));
+    IBH_TRY(b->own.upload(&b->eta, eta));
+    IBH_TRY(acc_fill(&b->interp, ng, nid, interp_off, interp_idx, interp_w, index_base));
     // host copies (ibh_bcset_create)
     b->h_ghost = g;
     b->h_eta = eta;
@@ -583,14 +536,11 @@ int ibh_bc_create(ibh_bc** out, int32_t ng, const int32_t* ghost_indices, const 
             b->h_w[k] = interp_w ? interp_w[k] : 1.0f;
         }
     }
-    *out = b;
+    *out = b.release();
     return 0;
 }
 
 int ibh_bc_destroy(ibh_bc* b) {
-    if (!b) return 0;
-    hipFree(b->ghost); hipFree(b->image_domain); hipFree(b->eta);
-    hipFree(b->interp.off); hipFree(b->interp.idx); hipFree(b->interp.w);
     delete b;
     return 0;
 }

@@ -3,9 +3,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/ibhip.h"
+#include "ibh_owner.h"
 
 #define IBH_MAXD 3
 
@@ -92,6 +94,7 @@ struct DimData {
     int32_t *loff = nullptr, *lidx = nullptr;         // CSR of left faces  (cell is the neighbour)
     int32_t *roff = nullptr, *ridx = nullptr;         // CSR of right faces (cell is the owner)
 };
+static_assert(std::is_trivially_copyable<DimData>::value, "DimData is passed to kernels by value");
 
 struct ibh_part {
     int nd = 0;
@@ -156,6 +159,7 @@ struct ibh_part {
     float* march_tmp = nullptr;  // workgroup maxima of ibh_timestep_advection's reduction
     size_t march_tmp_n = 0;
     size_t G_bytes = 0;
+    ibh_owner own;  // every device buffer above, G and march_tmp included (last: callers' stand-ins set nd and nc by position)
 };
 
 struct ibh_acc {
@@ -163,6 +167,7 @@ struct ibh_acc {
     int32_t *off = nullptr, *idx = nullptr;
     float* w = nullptr;
     float* packed = nullptr;  // [n_in][8] scratch of ibh_accumulate_diff_add: the fields of a donor side by side
+    ibh_owner own;
 };
 
 struct ibh_bc {
@@ -177,6 +182,7 @@ struct ibh_bc {
     // ibh_bc_flow: 1 = no ghost cell is a donor of the boundary's stencils (written in the launch that interpolates), 0 = some
     // are (staged and scattered), -1 = not looked at yet
     mutable int flow_direct = -1;
+    ibh_owner own;  // ghost, image_domain, eta (interp owns its own)
 };
 
 // An ordered list of ghost-cell boundary conditions with closures the library knows (mode 0: a constant value, mode 1:
@@ -187,10 +193,10 @@ struct ibh_bcset {
     int32_t ng = 0;                 // ghost cells of all boundaries, ordered by level
     int32_t seg[IBH_MAX_BC + 1] = {0};  // ghost ranges of the levels
     bool direct[IBH_MAX_BC] = {false};  // no ghost cell of the level is a donor of the level: blended straight into the field
-    unsigned int* sync = nullptr;       // [4] one-launch form: barrier counter, finished workgroups, status, spare
     int32_t *ghost = nullptr, *off = nullptr, *donor = nullptr, *bidx = nullptr;
     float *eta = nullptr, *w = nullptr, *gval = nullptr, *value = nullptr;
     int32_t* mode = nullptr;
+    ibh_owner own;
 };
 
 // internal: the boundary-condition set with the next step's time step beside it (ibh_timestep.hip), called from ibh_fused.hip
@@ -224,9 +230,10 @@ int ibh_fail(int code, const char* what, const char* file, int line);
         if (!(cond)) return ibh_fail(-1, msg, __FILE__, __LINE__);           \
     } while (0)
 #define IBH_LAUNCH_CHECK() IBH_HIP(hipGetLastError())
-
-template <class T>
-int ibh_upload(T** dptr, const T* host, size_t n);
+#define IBH_TRY(call)                                                        \
+    do {                                                                     \
+        if (const int rc__ = (call)) return rc__;                            \
+    } while (0)
 
 // host-side block analysis (ibh_analyze.cpp)
 struct HostPartView {

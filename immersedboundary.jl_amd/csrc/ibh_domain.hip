@@ -16,6 +16,7 @@
 #include "ibh_common.h"
 
 #include <algorithm>
+#include <memory>
 #include <vector>
 
 #define DOM_BLOCK 256
@@ -41,6 +42,7 @@ struct ibh_domain_plan {
     int2* wg_gather = nullptr;      // workgroup -> (partition, first domain row)
     int2* wg_scatter = nullptr;     // workgroup -> (partition, first image row)
     int32_t n_wg_gather = 0, n_wg_scatter = 0;
+    ibh_owner own;
 };
 
 namespace {
@@ -52,6 +54,7 @@ struct DomFields {
     int32_t nv[IBH_DOM_MAXF];
     int32_t nf;
 };
+static_assert(std::is_trivially_copyable<DomFields>::value, "DomFields is passed to kernels by value");
 
 __global__ __launch_bounds__(DOM_BLOCK) void k_domain_gather(const int2* __restrict__ wg, const Part* __restrict__ parts,
                                                              const int32_t* __restrict__ rows, DomFields F) {
@@ -83,25 +86,6 @@ __global__ __launch_bounds__(DOM_BLOCK) void k_domain_scatter(const int2* __rest
 }
 
 int64_t pad64(int64_t n) { return (n + 63) & ~(int64_t)63; }
-
-void plan_free(ibh_domain_plan* p) {
-    if (!p) return;
-    hipFree(p->rows);
-    hipFree(p->img);
-    hipFree(p->parts);
-    hipFree(p->wg_gather);
-    hipFree(p->wg_scatter);
-    delete p;
-}
-
-template <class T>
-int upload(T** d, const std::vector<T>& h) {
-    *d = nullptr;
-    if (h.empty()) return 0;
-    IBH_HIP(hipMalloc((void**)d, h.size() * sizeof(T)));
-    IBH_HIP(hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-    return 0;
-}
 
 // fields [k0, k0 + nf) of the call; `gather` selects the direction
 int launch(const ibh_domain_plan* p, bool gather, int k0, int nf, const float* const* src, const int* nv,
@@ -194,25 +178,24 @@ int ibh_domain_plan_create(ibh_domain_plan** out, int n_parts, const int32_t* co
     }
     IBH_REQUIRE(wg_g.size() <= (size_t)INT32_MAX && wg_s.size() <= (size_t)INT32_MAX,
                 "ibh_domain_plan_create: too many workgroups");
-    ibh_domain_plan* p = new ibh_domain_plan;
+    std::unique_ptr<ibh_domain_plan> p(new ibh_domain_plan);
     p->n_parts = n_parts;
     p->n_global = n_global;
     p->ws_rows = ws_off[n_parts];
     p->ws_off = ws_off;
     p->n_wg_gather = (int32_t)wg_g.size();
     p->n_wg_scatter = (int32_t)wg_s.size();
-    int rc;
-    if ((rc = upload(&p->rows, rows)) || (rc = upload(&p->img, img)) || (rc = upload(&p->parts, parts)) ||
-        (rc = upload(&p->wg_gather, wg_g)) || (rc = upload(&p->wg_scatter, wg_s))) {
-        plan_free(p);
-        return rc;
-    }
-    *out = p;
+    IBH_TRY(p->own.upload(&p->rows, rows));
+    IBH_TRY(p->own.upload(&p->img, img));
+    IBH_TRY(p->own.upload(&p->parts, parts));
+    IBH_TRY(p->own.upload(&p->wg_gather, wg_g));
+    IBH_TRY(p->own.upload(&p->wg_scatter, wg_s));
+    *out = p.release();
     return 0;
 }
 
 int ibh_domain_plan_destroy(ibh_domain_plan* p) {
-    plan_free(p);
+    delete p;
     return 0;
 }
 

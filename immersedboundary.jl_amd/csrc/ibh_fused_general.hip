@@ -156,7 +156,7 @@ int ensure_G(ibh_part* p) {
         return ibh_fail(-1, "the gradient workspace is allocated on the first two-kernel sweep of a partition: run one "
                             "sweep before capturing it into a HIP graph", __FILE__, __LINE__);
     const size_t bytes = (size_t)(p->nd * (p->nd + 2) + 1) * (size_t)p->nc * sizeof(float);
-    IBH_HIP(hipMalloc((void**)&p->G, bytes));
+    IBH_TRY(p->own.alloc(&p->G, bytes / sizeof(float)));
     p->G_bytes = bytes;
     return 0;
 }

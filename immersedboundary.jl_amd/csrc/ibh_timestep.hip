@@ -85,11 +85,11 @@ K dt_kernel(K const (&k)[2][2], const ibh_part* p) {
 
 // the workgroup maxima of the time step live with the partition, not in the per-thread scratch: a march step launches them
 // in one call and reduces them in the next (partials_done below)
-hipError_t ensure_march_tmp(ibh_part* p) {
-    if (p->march_tmp) return hipSuccess;
-    const hipError_t e = hipMalloc((void**)&p->march_tmp, 8192 * sizeof(float));
-    if (e == hipSuccess) p->march_tmp_n = 8192;
-    return e;
+int ensure_march_tmp(ibh_part* p) {
+    if (p->march_tmp) return 0;
+    IBH_TRY(p->own.alloc(&p->march_tmp, 8192));
+    p->march_tmp_n = 8192;
+    return 0;
 }
 
 }  // namespace
@@ -98,7 +98,7 @@ extern "C" {
 
 int ibh_timestep_advection(ibh_part* p, const float* C, int64_t ldc, float scale, float* dt_dev) {
     IBH_REQUIRE(p && C && dt_dev && (p->nd == 2 || p->nd == 3) && p->nc > 0, "ibh_timestep_advection: bad argument");
-    IBH_HIP(ensure_march_tmp(p));
+    IBH_TRY(ensure_march_tmp(p));
     const GradDims G = grad_dims(p);
     // one cell per thread up to 2 M cells (every load of a cell in flight at once: the kernel is two dependent round trips,
     // not bandwidth; with 1 024 workgroups and 3-4 cells per thread it took 18.6 us at 0.87 M cells)
@@ -121,7 +121,7 @@ int ibh_timestep_euler(ibh_part* p, const ibh_fluid* f, const float* P, int64_t 
     IBH_REQUIRE(p->nd == 2 || p->nd == 3, "ibh_timestep_euler: nd must be 2 or 3");
     IBH_REQUIRE(p->nc > 0, "ibh_timestep_euler: empty partition");
     IBH_REQUIRE(ldp >= p->nc, "ibh_timestep_euler: ldp is smaller than the number of cells");
-    IBH_HIP(ensure_march_tmp(p));
+    IBH_TRY(ensure_march_tmp(p));
     const GradDims G = grad_dims(p);
     const int nwg = ibh_grid_cap(p->nc, OPS_BLOCK, 8192);
     static constexpr decltype(&k_timestep_euler<2, false, false>) k[2][2][2] = {
@@ -142,7 +142,7 @@ int ibh_timestep_euler(ibh_part* p, const ibh_fluid* f, const float* P, int64_t 
 int ibh_bcset_apply_with_dt(const ibh_bcset* s, float* a, ibh_part* p, const float* C, int64_t ldc, float scale,
                             float* dt_next, int partials_done) {
     IBH_REQUIRE(s && a && p && C && dt_next && (p->nd == 2 || p->nd == 3) && p->nc > 0, "ibh_bcset_apply_with_dt: bad argument");
-    IBH_HIP(ensure_march_tmp(p));
+    IBH_TRY(ensure_march_tmp(p));
     const GradDims G = grad_dims(p);
     const int nwg_dt = ibh_grid_cap(p->nc, OPS_BLOCK, 8192);
     static constexpr decltype(&k_bcinterp_dt<2, false>) k_interp_dt[2][2] = DT_KERNELS(k_bcinterp_dt);

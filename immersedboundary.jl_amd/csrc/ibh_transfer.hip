@@ -207,7 +207,7 @@ int ibh_accumulate_diff_add(const ibh_acc* a, const float* v, const float* v2, i
     if (a->w && nv >= 2 && nv <= 8 && (int64_t)a->n_out >= 4 * (int64_t)a->n_in) {
         // many rows per donor (a prolongation): pack the donors' differences once, gather them 16 bytes at a time
         ibh_acc* am = const_cast<ibh_acc*>(a);
-        if (!am->packed) IBH_HIP(hipMalloc((void**)&am->packed, sizeof(float) * 8 * (size_t)a->n_in));
+        if (!am->packed) IBH_TRY(am->own.alloc(&am->packed, 8 * (size_t)a->n_in));
         hipLaunchKernelGGL(k_pack_diff8, grid2((int64_t)a->n_in * 8, 1), dim3(OPS_BLOCK), 0, ibh_stream, a->n_in, nv, v, v2,
                            ldv, am->packed);
         const float4* d4 = reinterpret_cast<const float4*>(am->packed);

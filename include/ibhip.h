@@ -65,6 +65,12 @@ int ibh_free(void* dptr);
 int ibh_h2d(void* dst, const void* src, size_t bytes);
 int ibh_d2h(void* dst, const void* src, size_t bytes);
 int ibh_memset(void* dst, int value, size_t bytes);
+/* Device memory that the live handles of this process own (partitions, accumulators, boundaries, BC sets, domain plans --
+ * the workspaces they allocate on first use included): bytes requested and number of buffers.  Every create adds to it,
+ * a failed create leaves it as it was, every destroy takes its handle's share off again.  Exact, unlike hipMemGetInfo.
+ * Not counted: ibh_malloc / ibh_free, the IPC and halo buffers, the per-thread reduction scratch.  Either pointer may be
+ * NULL. */
+int ibh_owned_device_memory(int64_t* bytes, int64_t* buffers);
 
 /* ---- Partition: replaces `to_backend(part, conv)` (ImmersedBoundary.jl:848, :788) ----
  * Uploads once.  `spacing`/`centers` are `(nc, nd)` column-major (part.spacing,
@@ -403,7 +409,8 @@ int ibh_step_advection_xgmi(ibh_part*, float* u, const float* C, int64_t ldc, fl
 typedef struct ibh_bcset ibh_bcset;
 int ibh_bcset_create(ibh_bcset** out, int n_bc, const ibh_bc* const* bcs, const int32_t* modes, const float* values);
 int ibh_bcset_destroy(ibh_bcset*);
-/* n_levels: low 16 bits = levels, high 16 bits = levels none of whose ghost cells is a donor of the level (one launch) */
+/* n_ghost: ghost cells of all boundaries (never negative); n_levels: low 16 bits = levels, high 16 bits = levels none of
+ * whose ghost cells is a donor of the level (one launch).  Host code only: no device call, no synchronisation. */
 int ibh_bcset_info(const ibh_bcset*, int32_t* n_ghost, int32_t* n_levels);
 int ibh_bcset_apply(const ibh_bcset*, float* a);
 int ibh_timestep_advection(ibh_part*, const float* C, int64_t ldc, float scale, float* dt_device);

@@ -1,6 +1,8 @@
 """Edge cases through the C ABI: empty and ragged inputs, strided / non-column-major fields, wide fields,
-error reporting instead of crashes, partitions without block information, index_base = 1 (Julia callers)."""
+error reporting instead of crashes, partitions without block information, index_base = 1 (Julia callers), and the device
+memory of the handles: a create that fails leaks nothing, create and destroy balance (``owned_device_memory``)."""
 import ctypes as C
+import gc
 
 import numpy as np
 import pytest
@@ -82,8 +84,11 @@ def test_wide_field(adv_domains):
     assert rel_inf(ibamd.to_host(ibamd.at_faces(dpart, ibamd.hip(u), 2)), od.at_faces(opart, u, 2)) <= 1e-6
 
 
-def _raw_create(part, block_size, index_base, with_domain=True):
-    nd, nc = 2, part.spacing.shape[0]
+def _raw_create(part, block_size, index_base, with_domain=True, iid=None, check=True):
+    """``ibh_partition_create`` on the arrays of ``part`` (``iid``: another ``image_in_domain``, 0-based).  The handle, or
+    with ``check=False`` (return code, handle)."""
+    nd, nc = part.ndims, part.spacing.shape[0]
+    dims = range(1, nd + 1)
     keep = []
 
     def parr(arrs):
@@ -91,18 +96,20 @@ def _raw_create(part, block_size, index_base, with_domain=True):
         keep.append(arrs)
         return (B.c_vp * nd)(*[a.ctypes.data for a in arrs])
     fon, fa = part.face_owners_neighbors, part.face_accumulators
-    owners, neigh = parr([fon[d][0] for d in (1, 2)]), parr([fon[d][1] for d in (1, 2)])
-    loff, lidx = parr([fa[(d, False)].off for d in (1, 2)]), parr([fa[(d, False)].idx for d in (1, 2)])
-    roff, ridx = parr([fa[(d, True)].off for d in (1, 2)]), parr([fa[(d, True)].idx for d in (1, 2)])
-    nf = np.array([fon[1][0].size, fon[2][0].size], dtype=np.int32)
-    sp = np.asfortranarray(part.spacing)
-    iid = np.ascontiguousarray(part.image_in_domain + index_base, dtype=np.int32)
+    owners, neigh = parr([fon[d][0] for d in dims]), parr([fon[d][1] for d in dims])
+    loff, lidx = parr([fa[(d, False)].off for d in dims]), parr([fa[(d, False)].idx for d in dims])
+    roff, ridx = parr([fa[(d, True)].off for d in dims]), parr([fa[(d, True)].idx for d in dims])
+    nf = np.array([fon[d][0].size for d in dims], dtype=np.int32)
+    sp = np.asfortranarray(part.spacing, dtype=np.float32)
+    iid = np.ascontiguousarray((part.image_in_domain if iid is None else iid) + index_base, dtype=np.int32)
     dom = np.ascontiguousarray(part.domain + index_base, dtype=np.int32)
     h = B.c_vp()
     B._dev()
-    B.call("ibh_partition_create", C.byref(h), nd, nc, sp.ctypes.data_as(B.c_vp), B.c_vp(None), nf.ctypes.data_as(B.c_vp),
-           owners, neigh, loff, lidx, roff, ridx, int(iid.size), B._hptr(iid),
-           B._hptr(dom) if with_domain else B.c_vp(None), block_size, index_base)
+    args = (C.byref(h), nd, nc, sp.ctypes.data_as(B.c_vp), B.c_vp(None), nf.ctypes.data_as(B.c_vp), owners, neigh, loff, lidx,
+            roff, ridx, int(iid.size), B._hptr(iid), B._hptr(dom) if with_domain else B.c_vp(None), block_size, index_base)
+    if not check:
+        return _lib.load().ibh_partition_create(*args), h
+    B.call("ibh_partition_create", *args)
     return h
 
 
@@ -136,6 +143,106 @@ def test_bad_indices_are_rejected(adv_domains):
         ibamd.to_backend(bad)
     lib = _lib.load()
     assert lib.ibh_accumulate(None, None, 1, 1, None, 1) != 0 and b"null" in lib.ibh_last_error()
+
+
+def test_failed_creates_leak_nothing(adv_domains):
+    """A create that refuses its input after it has uploaded some of it -- ``image_in_domain`` past the last cell (2-D and
+    3-D partitions), a stencil index past the last image cell -- returns an error, leaves the handle null and frees what it
+    had uploaded: the bytes and the buffer count of ``owned_device_memory`` stay what they were."""
+    import les_model
+    dp, _ = adv_domains
+    lib = _lib.load()
+    part2 = dp.partitions[1]                                         # 64 complete blocks and face-list cells
+    part3 = les_model.one_partition(les_model.single_block_mesh())   # one 8^3 block
+    gc.collect()                                     # handles of earlier tests that wait in reference cycles go now
+    base = B.owned_device_memory()
+    for part in (part2, part3):
+        nc = part.spacing.shape[0]
+        assert part.ndims == (2 if part is part2 else 3)
+        iid = np.array(part.image_in_domain, dtype=np.int32)
+        iid[iid.size // 2] = nc
+        rc, h = _raw_create(part, 8, 0, iid=iid, check=False)
+        assert rc != 0 and b"image_in_domain out of range" in lib.ibh_last_error()
+        assert not h.value
+        assert B.owned_device_memory() == base
+    b = dp.boundaries["upper"][1]
+    acc = b.image_interpolator
+    ng, nid = int(b.ghost_indices.shape[0]), int(b.image_domain.size)
+    gi, idm = np.ascontiguousarray(b.ghost_indices, np.int32), np.ascontiguousarray(b.image_domain, np.int32)
+    gd, idist = np.ascontiguousarray(b.ghost_distances, f32), np.ascontiguousarray(b.image_distances, f32)
+    off, w = np.ascontiguousarray(acc.off, np.int32), np.ascontiguousarray(acc.w, f32)
+    idx = np.array(acc.idx, dtype=np.int32)
+    assert ng > 0 and idx.size > 0 and idx.max() < nid
+    idx[idx.size // 2] = nid
+    h = B.c_vp()
+    rc = lib.ibh_bc_create(C.byref(h), ng, B._hptr(gi), B._hptr(gd), B._hptr(idist), nid, B._hptr(idm), B._hptr(off),
+                           B._hptr(idx), B._hptr(w), 0)
+    assert rc != 0 and b"out of range" in lib.ibh_last_error()
+    assert not h.value
+    assert B.owned_device_memory() == base
+
+
+class _RawSet(B._Handle):
+    """``ibh_bcset_create`` on boundaries of any partition (``BCSet`` takes one-partition domains)."""
+    _destroy = "ibh_bcset_destroy"
+
+    def __init__(self, bcs, modes, values):
+        self._bcs = bcs
+        arr = (B.c_vp * len(bcs))(*[b.handle for b in bcs])
+        h = B.c_vp()
+        B.call("ibh_bcset_create", C.byref(h), len(bcs), arr, B._hptr(np.asarray(modes, np.int32)),
+               B._hptr(np.asarray(values, f32)))
+        self.handle = h
+
+
+def test_create_and_destroy_balance(adv_domains):
+    """Every handle type, with the buffers allocated on first use (the gradient workspace, the time step's partial maxima,
+    the packed donors of ``diff_add``): what the handles own grows with every step that allocates and is back at the
+    starting figure, to the byte and the buffer, once the objects are gone."""
+    dp, _ = adv_domains
+    for p in dp.partitions.values():
+        ibamd.to_backend(p, ibamd.hip)               # cached on the host partitions (DomainPlan asks for them): not ours
+    part, bdry = dp.partitions[1], dp.boundaries["upper"][1]
+    nc = part.spacing.shape[0]
+    gc.collect()                                     # handles of earlier tests that wait in reference cycles go now
+    base = B.owned_device_memory()
+    seen = [base]
+
+    def grew(what):
+        now = B.owned_device_memory()
+        assert now[0] > seen[-1][0] and now[1] > seen[-1][1], (what, seen[-1], now)
+        seen.append(now)
+
+    dpart = B.DevicePartition(part)
+    grew("partition")
+    u, Cd = ibamd.hip(seeded_field(part.centers)), ibamd.hip(np.ones((nc, 2), dtype=f32))
+    ibamd.residual_advection(dpart, u, Cd, flags=B.IBH_NO_FUSE)
+    grew("gradient workspace")
+    ibamd.timestep_advection(dpart, Cd)
+    grew("time step partials")
+    n_in, n_out = 5, 24                              # four rows per donor and more: the packed form of diff_add
+    rng = np.random.default_rng(7)
+    acc = B.DeviceAccumulator(ibamd.Accumulator([rng.integers(0, n_in, 3).tolist() for _ in range(n_out)],
+                                                [[0.5, 0.25, 0.25]] * n_out, n_input=n_in))
+    grew("accumulator")
+    acc.diff_add(ibamd.hip(np.zeros((n_out, 3), f32)), ibamd.hip(np.ones((n_in, 3), f32)), ibamd.hip(np.zeros((n_in, 3), f32)))
+    grew("packed donors")
+    n = len(dp)                                      # a boundary names cells of the whole domain
+    assert bdry.ghost_indices.size > 0 and bdry.ghost_indices.max() < n and bdry.image_domain.max() < n
+    db = B.DeviceBoundary(bdry)
+    grew("boundary")
+    bcs = _RawSet([db], [0], [1.0])
+    grew("boundary-condition set")
+    a = ibamd.hip(np.zeros(n, dtype=f32))
+    B._stream()
+    B.call("ibh_bcset_apply", bcs.handle, B._ptr(a))
+    assert np.any(ibamd.to_host(a)[bdry.ghost_indices] != 0)
+    plan = B.DomainPlan(dp)
+    grew("domain plan")
+    torch.cuda.synchronize()
+    del dpart, acc, bcs, db, plan
+    gc.collect()
+    assert B.owned_device_memory() == base
 
 
 def test_image_only_flag(adv_domains):

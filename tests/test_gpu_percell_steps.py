@@ -7,8 +7,7 @@ arg-max of every probe) is asserted from the data.
 
 The boundary conditions run as ``ibh_bc_apply`` (both closures), ``BCSet.apply`` and inside ``step_advection(...,
 next_dt=...)`` (the BC + time-step launches), on real boundaries and on synthetic sets that each force one branch of the
-level construction of ``ibh_bcset_create`` (level and direct-level counts asserted from ``ibh_bcset_info``).  The opt-in
-one-launch form of the set (read at library load, measured slower) is not run.
+level construction of ``ibh_bcset_create`` (level and direct-level counts asserted from ``ibh_bcset_info``).
 """
 import ctypes as C
 import math
