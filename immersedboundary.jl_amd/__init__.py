@@ -10,7 +10,8 @@ that computes needs libibhip.so and a gfx950 device and fails loudly otherwise.
 from .mesher import (Ball, Box, DistanceField, Line, Mesh, Stereolitography, cat, centers_and_normals,
                      feature_regions, get_cells, merge_points, refine_to_length)
 from .accumulator import Accumulator
-from .domain import Boundary, Domain, Partition, Surface, multigrid
+from .domain import (ROLE_FLUID, ROLE_GHOST, ROLE_SOLID, Boundary, Domain, Partition, Surface, cell_roles,
+                     multigrid)
 
 
 def __getattr__(name):

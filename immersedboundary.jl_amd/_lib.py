@@ -114,6 +114,10 @@ _SIGS = {
                              C.c_float, C.c_float, c_vp, c_i64, c_int],
     "ibh_restrict_euler": [c_vp, C.POINTER(ibh_fluid), c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64],
     "ibh_prolong_euler": [c_vp, C.POINTER(ibh_fluid), c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64],
+    "ibh_restrict_euler_roles": [c_vp, C.POINTER(ibh_fluid), c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64,
+                                 c_vp, c_i64],
+    "ibh_forcing_roles": [c_i64, c_int, c_vp, c_i64, c_vp, c_i64, c_vp],
+    "ibh_sumsq_roles": [c_i64, c_int, c_vp, c_i64, c_vp, c_vp],
     "ibh_smooth_residual": [c_vp, c_vp, c_int, c_i64, C.c_float, c_int, c_vp, c_i64, c_vp, c_i64],
     "ibh_update_euler_smoothed": [c_vp, C.POINTER(ibh_fluid), c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64,
                                   C.c_float, c_vp, c_int, C.c_float, C.c_float, C.c_float, c_vp, c_i64],

@@ -1046,13 +1046,68 @@ def _coarse_out(what, name, t, n, nv):
     return t, [_ptr(o), ld]
 
 
+class Roles:
+    """The cell roles of one partition on the device (``domain.cell_roles``: fluid, ghost, solid) and what blanks its solid
+    rows: ``roles``, the ``uint8`` array ``(nc,)``; ``solid``, the ``int32`` list of the solid rows; ``solid_rows``, a
+    compact ``(n_solid, nd+2)`` array whose every row is ``solid_state`` -- ``blank(P)`` scatters it into the solid rows of
+    ``P`` (``ibh_scatter_rows``: one launch, none without solid rows).
+
+    ``part``: the partition, host or device; ``roles``: ``cell_roles(dom)[part.domain]``, ``nc`` values of ``ROLE_*``;
+    ``solid_state``: the ``nd + 2`` primitives the solid rows are held at, e.g. the free stream.  A wrong length of either
+    raises ``ValueError`` before anything is asked of the device."""
+
+    def __init__(self, part, roles, solid_state):
+        nd = int(part.ndims)
+        nc = int(part.nc) if hasattr(part, "nc") else int(part.spacing.shape[0])
+        r = np.asarray(roles)
+        if r.ndim != 1 or r.shape[0] != nc:
+            raise ValueError(f"Roles: roles must be one value per cell of the partition, ({nc},); got {tuple(r.shape)}")
+        if r.size and not np.isin(r, (0, 1, 2)).all():
+            raise ValueError("Roles: roles are ROLE_FLUID (0), ROLE_GHOST (1) or ROLE_SOLID (2)")
+        st = np.asarray(solid_state, dtype=np.float32)
+        if st.ndim != 1 or st.shape[0] != nd + 2:
+            raise ValueError(f"Roles: solid_state must be the nd + 2 = {nd + 2} primitives of a row; got shape {tuple(st.shape)}")
+        r = np.ascontiguousarray(r, dtype=np.uint8)
+        solid = np.nonzero(r == 2)[0].astype(np.int32)
+        dev = _dev()
+        self.nc, self.nd, self.n_solid = nc, nd, int(solid.size)
+        self.counts = tuple(int(x) for x in np.bincount(r, minlength=3))     # (fluid, ghost, solid)
+        self.roles = torch.from_numpy(r).to(dev)
+        self.solid = torch.from_numpy(solid).to(dev)
+        self.solid_rows = hip(np.tile(st, (max(self.n_solid, 1), 1)))[:self.n_solid]
+
+    def blank(self, P):
+        """``solid_state`` into the solid rows of ``P`` (column-major ``(nc, nd+2)``), in place; returns ``P``."""
+        if self.n_solid:
+            f, nv, ld = _field_inplace(P, self.nc, "P")
+            if nv != self.nd + 2:
+                raise ValueError(f"Roles.blank: P must be ({self.nc}, {self.nd + 2})")
+            _stream()
+            call("ibh_scatter_rows", _ptr(self.solid), self.n_solid, _ptr(self.solid_rows), nv, self.n_solid, _ptr(f), ld)
+        return P
+
+
+def _roles(what, roles, n):
+    """The device ``uint8`` array of ``n`` role bytes from a ``Roles`` or such a tensor."""
+    r = roles.roles if isinstance(roles, Roles) else roles
+    if not isinstance(r, torch.Tensor) or not r.is_cuda or r.dtype != torch.uint8 or r.ndim != 1 or not r.is_contiguous():
+        raise TypeError(f"{what}: roles must be a Roles or a contiguous uint8 device tensor")
+    if r.shape[0] != n:
+        raise ValueError(f"{what}: roles has {r.shape[0]} entries, expected {n}")
+    return r
+
+
 @_hipaware
-def restrict_euler(coarsener, P, R, S=None, fluid=None, out=None, out_D=None):
+def restrict_euler(coarsener, P, R, S=None, fluid=None, out=None, out_D=None, roles=None):
     """The restriction of a multigrid cycle of the Euler march in conserved variables, one launch:
     ``P_c = state2primitive(fluid, coarsener(primitive2state(fluid, P)))`` and ``D_c = coarsener(R .+ S)`` (``S=None``:
     ``coarsener(R)``), bit for bit those launches.  ``P``: the fine primitives ``(n_input, nd+2)``; ``R``, ``S``: the fine
     residual and forcing in conserved variables.  Returns ``(P_c, D_c)`` -- ``out`` and ``out_D`` where given, ``(n_output,
-    nd+2)``, which alias neither each other nor an input.  The coarse forcing of the cycle is ``D_c .- R_c(P_c)``."""
+    nd+2)``, which alias neither each other nor an input.  The coarse forcing of the cycle is ``D_c .- R_c(P_c)``.
+
+    ``roles`` (a ``Roles`` of the fine partition or its ``uint8`` device array): ``D_c = coarsener(t)`` with ``t = R .+ S`` in
+    fluid rows and ``+0`` in every other one (``ibh_restrict_euler_roles``, a select: a NaN in a masked row never reaches
+    ``D_c``); ``P_c`` is unchanged."""
     acc = _transfer("restrict_euler", coarsener)
     P, nv, ldp = _primitives(P, acc.n_input)
     R, nvr, ldr = _field(R, acc.n_input)
@@ -1066,12 +1121,60 @@ def restrict_euler(coarsener, P, R, S=None, fluid=None, out=None, out_D=None):
         Sc = [_ptr(S), lds]
     out, O = _coarse_out("restrict_euler", "out", out, acc.n_output, nv)
     out_D, D = _coarse_out("restrict_euler", "out_D", out_D, acc.n_output, nv)
+    if roles is not None:
+        roles = _roles("restrict_euler", roles, acc.n_input)
     if acc.n_output == 0:     # (no rows: nothing to launch, and an empty array has no address to pass)
         return out, out_D
     f = _cfluid(fluid)
     _stream()
-    call("ibh_restrict_euler", acc.handle, C.byref(f), nv - 2, _ptr(P), ldp, _ptr(R), ldr, *Sc, *O, *D)
+    if roles is not None:
+        call("ibh_restrict_euler_roles", acc.handle, C.byref(f), nv - 2, _ptr(P), ldp, _ptr(R), ldr, *Sc, _ptr(roles), *O, *D)
+    else:
+        call("ibh_restrict_euler", acc.handle, C.byref(f), nv - 2, _ptr(P), ldp, _ptr(R), ldr, *Sc, *O, *D)
     return out, out_D
+
+
+@_hipaware
+def forcing_roles(D, R, roles):
+    """The coarse forcing of a multigrid cycle with cell roles, in place and in one launch: ``D = D .- R`` in fluid rows and
+    ``+0`` in every other one (``ibh_forcing_roles``), bit for bit the broadcast and the select.  ``D`` (column-major, written)
+    and ``R``: ``(n, nv)``, ``nv <= 8``; ``roles``: a ``Roles`` or its ``uint8`` device array.  Returns ``D``."""
+    Df, nv, ldd = _field_inplace(D, None, "D")
+    n = Df.shape[0]
+    Rf, nvr, ldr = _field(R, n)
+    if nvr != nv:
+        raise ValueError(f"forcing_roles: R must be ({n}, {nv})")
+    if nv > 8:
+        raise ValueError("forcing_roles: D has more than 8 columns")
+    roles = _roles("forcing_roles", roles, n)
+    if n == 0:
+        return D
+    _stream()
+    call("ibh_forcing_roles", n, nv, _ptr(Df), ldd, _ptr(Rf), ldr, _ptr(roles))
+    return D
+
+
+@_hipaware
+def sumsq_roles(x, roles, out=None):
+    """Per column of ``x`` (``(n,)`` or ``(n, nv)``, ``nv <= 8``) the sum of squares over the fluid rows, accumulated in double
+    on the device (``ibh_sumsq_roles``: one launch for all columns and the one-launch final stage).  Returns ``out``: ``nv``
+    device doubles, assigned (None: a new tensor).  No read-back."""
+    xf, nv, ldx = _field(x)
+    n = xf.shape[0]
+    if nv > 8:
+        raise ValueError("sumsq_roles: x has more than 8 columns")
+    roles = _roles("sumsq_roles", roles, n)
+    if out is None:
+        out = torch.zeros(nv, dtype=torch.float64, device=xf.device)
+    elif not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float64 or out.ndim != 1 \
+            or out.shape[0] != nv or not out.is_contiguous():
+        raise ValueError(f"sumsq_roles: out must be a contiguous Float64 device tensor of {nv} elements")
+    if n == 0:
+        out.zero_()
+        return out
+    _stream()
+    call("ibh_sumsq_roles", n, nv, _ptr(xf), ldx, _ptr(roles), _ptr(out))
+    return out
 
 
 @_hipaware

@@ -132,6 +132,8 @@ smooth_residual = B.smooth_residual                # (ibh_smooth_residual / ibh_
 update_euler_smoothed = B.update_euler_smoothed
 restrict_euler = B.restrict_euler                  # (ibh_restrict_euler / ibh_prolong_euler: the transfers of a multigrid cycle)
 prolong_euler = B.prolong_euler
+forcing_roles = B.forcing_roles                    # (ibh_forcing_roles / ibh_sumsq_roles: the cycle and its norm on fluid rows)
+sumsq_roles = B.sumsq_roles
 
 
 def inviscid_fluxes(fluid, PL, PR, *args):

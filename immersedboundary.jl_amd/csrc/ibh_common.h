@@ -290,10 +290,14 @@ static inline int ibh_grid_cap(int64_t n, int block, int cap) {
 // The two-stage reductions (ibh_reduce.hip, device side ibh_reduce_dev.h): the per-host-thread scratch for the workgroup
 // partials, one region of IBH_RED_BYTES per entry point (2 048 doubles: the largest grid of a reduction), and the
 // one-workgroup final stage of the sums in double.  ibh_red_scratch returns null if the allocation failed.
-enum ibh_red_region { IBH_RED_FAS, IBH_RED_SUMSQ, IBH_RED_DOT, IBH_RED_MAXABS, IBH_RED_EW, IBH_RED_REGIONS };
+enum ibh_red_region {
+    IBH_RED_FAS, IBH_RED_SUMSQ, IBH_RED_DOT, IBH_RED_MAXABS, IBH_RED_EW, IBH_RED_SUMSQ_ROLES, IBH_RED_REGIONS
+};
 #define IBH_RED_BYTES (2048 * sizeof(double))
+#define IBH_SUMSQ_ROLES_MAX_NV 8   // the columns of ibh_sumsq_roles share one region: 256 partials each
 void* ibh_red_scratch(ibh_red_region region);
-void ibh_launch_sum_partials(int n, const double* part, double* out);
+// `ncols` sums in one launch: n partials from part[c * n] into out[c]
+void ibh_launch_sum_partials(int n, const double* part, double* out, int ncols = 1);
 
 // XCD-aware placement of workgroup `wg` of `nwg` (cdna_hip_programming.md T1): workgroups are dealt round-robin over the 8
 // XCDs, each with its own L2; this gives every XCD one CONTIGUOUS run of the work list (cells and blocks are in depth-first

@@ -748,3 +748,52 @@ def multigrid(dom, max_levels=0, factor=2):
         coarse_doms.append(cdom)
         tree_old, Xold = tree, X
     return coarse_doms, prolongators, coarseners
+
+
+ROLE_FLUID, ROLE_GHOST, ROLE_SOLID = 0, 1, 2   # IBH_ROLE_* of include/ibhip.h
+
+
+def cell_roles(dom, fluid_seed=None):
+    """What every cell of ``dom`` IS, ``np.uint8[len(dom)]`` in global cell order (not in the reference, which blanks
+    nothing: its solid cells march a flow of their own behind the ghost layer):
+
+    * ``ROLE_GHOST``: a ghost cell of any boundary (``ghost_indices``);
+    * ``ROLE_FLUID``: the cells of one connected component of the face graph with the ghost cells removed -- the one that
+      holds the cell ``fluid_seed``, by default the largest.  The graph is that of every partition's
+      ``face_owners_neighbors`` (a mirror face is a self-loop and connects nothing);
+    * ``ROLE_SOLID``: every other cell: a ghost layer is closed, so what it cuts off from the fluid lies inside a body.
+
+    The local form of a partition is ``roles[part.domain]``.  A coarse level of ``multigrid(dom)`` is classified on its own
+    graph: ``cell_roles(coarse_dom)``."""
+    n = len(dom)
+    roles = np.full(n, ROLE_SOLID, dtype=np.uint8)
+    for parts in dom.boundaries.values():
+        for b in parts.values():
+            roles[np.asarray(b.ghost_indices, dtype=np.int64)] = ROLE_GHOST
+    open_ = roles != ROLE_GHOST
+    edges = []
+    for part in dom.partitions.values():
+        g = np.asarray(part.domain, dtype=np.int64)
+        for o, nb in part.face_owners_neighbors.values():
+            a, b = g[o], g[nb]
+            keep = (a != b) & open_[a] & open_[b]
+            edges.append(np.stack([a[keep], b[keep]]))
+    a, b = np.concatenate(edges, axis=1) if edges else np.zeros((2, 0), np.int64)
+    from scipy.sparse import coo_matrix
+    from scipy.sparse.csgraph import connected_components
+    graph = coo_matrix((np.ones(a.size, dtype=np.int8), (a, b)), shape=(n, n))
+    _, label = connected_components(graph, directed=False)
+    if fluid_seed is None:
+        if not open_.any():
+            return roles
+        sizes = np.bincount(label[open_], minlength=n)
+        fluid = int(np.argmax(sizes))                       # (ties: the component found first, in cell order)
+    else:
+        seed = int(fluid_seed)
+        if not 0 <= seed < n:
+            raise ValueError(f"cell_roles: fluid_seed must be a cell index in 0 .. {n - 1}")
+        if not open_[seed]:
+            raise ValueError(f"cell_roles: fluid_seed {seed} is a ghost cell")
+        fluid = int(label[seed])
+    roles[open_ & (label == fluid)] = ROLE_FLUID
+    return roles

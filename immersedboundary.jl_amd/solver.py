@@ -218,12 +218,26 @@ class EulerMarch:
     ``n_iter + 1`` launches.  A forward-Euler step is the stage form on the step's input with ``c = 1``.  The smoothing
     arrays (none for ``n_iter = 1``, one for 2, two from 3) are allocated here.  The march is no longer time accurate:
     ``smoothing`` with ``average`` raises, and so do the image-only, phase and single-pass ``flags`` -- the smoothing
-    would gather rows the sweep never wrote."""
+    would gather rows the sweep never wrote.
+
+    ``roles``: a ``backend.Roles`` of the partition (``cell_roles``: what every row IS -- fluid, ghost or solid).  After
+    every stage, after the stage's ``bcs``, the solid rows are set to the ``Roles``' ``solid_state`` (``Roles.blank``: one
+    ``ibh_scatter_rows`` launch more per stage, none without solid rows; it can be captured in a graph), so the cells
+    inside a body no longer march a flow of their own; every other row has the bits of the march without roles as long
+    as no sweep reads a solid row for it.  ``residual_norms(P)`` is then the norm of the residual over the fluid rows.
+    Without ``roles`` the march makes the calls it always made."""
 
     def __init__(self, part, fluid=None, scheme="hll", scale=0.75, bcs=None, average=None, local_dt=False, dt_every=1,
-                 residual=None, flags=0, stages=1, smoothing=None):
+                 residual=None, flags=0, stages=1, smoothing=None, roles=None):
         from . import cfd
+        if roles is not None and not isinstance(roles, B.Roles):
+            raise ValueError("roles must be a backend.Roles of the partition (Roles(part, cell_roles(dom)[part.domain], "
+                             "solid_state)) or None")
         self.part = B._part(part)
+        if roles is not None and (roles.nc, roles.nd) != (self.part.nc, self.part.nd):
+            raise ValueError(f"roles are those of a partition of {roles.nc} cells in {roles.nd} dimensions; this one has "
+                             f"{self.part.nc} in {self.part.nd}")
+        self.roles = roles
         self.fluid = fluid if fluid is not None else cfd.Fluid()
         if scheme not in B._EULER_SCHEMES:
             raise ValueError('scheme must be "hll" or "sensor"')
@@ -267,6 +281,7 @@ class EulerMarch:
                 raise ValueError("smoothing: IBH_IMAGE_ONLY, the overlap phases and the single-pass flags are not taken: "
                                  "the smoothing gathers the residual of every cell")
             self._smooth = tuple(B.colmajor_empty(nc, nv) for _ in range(min(self.smoothing[1] - 1, 2)))
+        self._norms = torch.zeros(nv, dtype=torch.float64, device=self.work.device) if roles is not None else None
         self.nsteps = 0
 
     def step(self, P):
@@ -295,8 +310,28 @@ class EulerMarch:
             self._stage(record, src, P, out)
             if self.bcs is not None:
                 self.bcs(out)
+            if self.roles is not None:
+                self.roles.blank(out)
             src = out
         return src
+
+    def sweep(self, P):
+        """``R(P)`` into ``work`` (the ``residual`` callable, or the sweep of the march's scheme); returns ``work``."""
+        if self.residual is not None:
+            self.residual(self.part, P, self.work)
+            return self.work
+        fn = B.residual_euler_hll if self.scheme == "hll" else B.residual_euler_sensor
+        return fn(self.part, P, out=self.work, flags=self.flags, fluid=self.fluid)
+
+    def residual_norms(self, P):
+        """The sums of squares of the ``nd + 2`` columns of ``R(P)`` over the FLUID rows, as ``nd + 2`` device doubles: the
+        sweep into ``work``, then ``sumsq_roles``.  No read-back and no allocation; the tensor returned is the march's own
+        and the next call overwrites it.  Needs ``roles``."""
+        if self.roles is None:
+            raise ValueError("residual_norms: the march has no roles (EulerMarch(..., roles=Roles(...)))")
+        if not isinstance(P, torch.Tensor):
+            P = P.t
+        return B.sumsq_roles(self.sweep(P), self.roles, out=self._norms)
 
     def _stage(self, record, src, P0, out):
         """One stage of a step from ``P0`` (the time step is in ``self.dt``): the sweep of the previous stage ``src`` and the
@@ -378,8 +413,8 @@ class _Level(EulerMarch):
     level's partition, and beside the records of the steady stages those of the forced ones, ``stage_euler_dual`` with the
     level's forcing ``S`` and ``g`` -- picked per call of ``smooth``; the stage loop is ``EulerMarch._stages`` either way."""
 
-    def __init__(self, part, fluid, scheme, scale, bcs, local_dt, dt_every, flags, stages):
-        super().__init__(part, fluid, scheme, scale, bcs, None, local_dt, dt_every, None, flags, stages)
+    def __init__(self, part, fluid, scheme, scale, bcs, local_dt, dt_every, flags, stages, roles=None):
+        super().__init__(part, fluid, scheme, scale, bcs, None, local_dt, dt_every, None, flags, stages, roles=roles)
         self._plain = self._records
         self._forced = [("dual", "P0", (alpha,)) + _dual_calls(alpha) for alpha in self.stages]
         self.S, self.g = None, 0.0
@@ -393,11 +428,6 @@ class _Level(EulerMarch):
             P = self._stages(P, self.nsteps)
             self.nsteps += 1
         return P
-
-    def sweep(self, P):
-        """``R(P)`` into ``work``."""
-        fn = B.residual_euler_hll if self.scheme == "hll" else B.residual_euler_sensor
-        return fn(self.part, P, out=self.work, flags=self.flags, fluid=self.fluid)
 
 
 class MultigridMarch:
@@ -438,13 +468,29 @@ class MultigridMarch:
     cycle first: the library's workspaces come with their first use).  The returned array is one of level 0's ping-pong
     arrays: valid during the next cycle's first step, overwritten later.
 
+    ``roles``: None, or one ``backend.Roles`` per level, each from ``cell_roles`` of that level's own domain.  The cycle
+    then knows what every row is: every level's steps blank the solid rows as ``EulerMarch`` does, and so do the two other
+    places a state is made -- ``P_{l+1}^0`` after its ``bcs`` and the prolonged array after its ``bcs``; the restriction is
+    ``restrict_euler(..., roles=...)``, whose defect takes fluid rows only; the coarse forcing is ``forcing_roles`` with the
+    coarse roles, zero outside the fluid rows; and entry ``k`` of the history becomes the ``nd + 2`` sums of squares of
+    ``sumsq_roles`` over the fluid rows of level 0's ``work``: ``residual_history()`` is ``(history, nd + 2)``.  Without
+    ``roles`` every call and the history's shape are as above.
+
     Not taken, each with a message: ``smoothing`` (``update_euler_smoothed`` has no source row), Shu-Osher triples (as in
     ``DualTimeMarch``), a ``residual`` callable, the image-only, phase and single-pass ``flags``, a ``TimeAverage``."""
 
     def __init__(self, parts, coarseners=(), prolongators=(), fluid=None, scheme="hll", scale=0.75, bcs=None, local_dt=True,
                  dt_every=1, stages=1, pre=1, post=1, n_coarsest=2, flags=0, history=0, smoothing=None, residual=None,
-                 average=None):
+                 average=None, roles=None):
         from . import cfd
+        parts = list(parts)
+        if roles is not None:
+            roles = list(roles)
+            if len(roles) != len(parts):
+                raise ValueError(f"MultigridMarch: roles is None or one Roles per level: {len(parts)} levels, {len(roles)} "
+                                 "roles")
+            if not all(isinstance(r, B.Roles) for r in roles):
+                raise ValueError("MultigridMarch: every entry of roles must be a backend.Roles of its level")
         if smoothing is not None:
             raise ValueError("MultigridMarch: residual smoothing is not taken: update_euler_smoothed has no source row for the "
                              "coarse forcing")
@@ -474,7 +520,10 @@ class MultigridMarch:
                 raise ValueError(f"MultigridMarch: {name} must be an integer >= 0")
         self.pre, self.post, self.n_coarsest = int(pre), int(post), int(n_coarsest)
         self.fluid = fluid if fluid is not None else cfd.Fluid()
-        self.levels = [_Level(p, self.fluid, scheme, scale, b, local_dt, dt_every, flags, stages) for p, b in zip(parts, bcs)]
+        if roles is None:
+            roles = [None] * len(parts)
+        self.levels = [_Level(p, self.fluid, scheme, scale, b, local_dt, dt_every, flags, stages, r)
+                       for p, b, r in zip(parts, bcs, roles)]
         for l, m in enumerate(self.levels):
             host = getattr(m.part, "host", None)
             if host is not None and (len(host.image) != m.part.nc or len(host.domain) != m.part.nc):
@@ -494,7 +543,8 @@ class MultigridMarch:
             m.pack = torch.empty(8 * max(nc, 1), dtype=torch.float32, device=m.work.device)
         self._hist = None
         if int(history):
-            self._hist = torch.full((int(history),), float("nan"), dtype=torch.float64, device=self.levels[0].work.device)
+            shape = (int(history),) if roles[0] is None else (int(history), self.levels[0].part.nd + 2)
+            self._hist = torch.full(shape, float("nan"), dtype=torch.float64, device=self.levels[0].work.device)
         self.ncycles = 0
 
     def cycle(self, P, S=None, g=0.0):
@@ -517,27 +567,38 @@ class MultigridMarch:
             return m.smooth(P, self.n_coarsest, S, g)
         P = m.smooth(P, self.pre, S, g)
         m.sweep(P)
-        if l == 0 and self._hist is not None and self.ncycles < self._hist.numel():
-            B._stream()
-            B.call("ibh_sumsq", m.part.nc, B._ptr(m.work), B._ptr(self._hist[self.ncycles:]))
+        if l == 0 and self._hist is not None and self.ncycles < self._hist.shape[0]:
+            if m.roles is not None:
+                B.sumsq_roles(m.work, m.roles, out=self._hist[self.ncycles])
+            else:
+                B._stream()
+                B.call("ibh_sumsq", m.part.nc, B._ptr(m.work), B._ptr(self._hist[self.ncycles:]))
         c = self.levels[l + 1]
-        B.restrict_euler(self.coarseners[l], P, m.work, S, self.fluid, out=c.P0, out_D=c.D)
+        B.restrict_euler(self.coarseners[l], P, m.work, S, self.fluid, out=c.P0, out_D=c.D, roles=m.roles)
         if c.bcs is not None:
             c.bcs(c.P0)
+        if c.roles is not None:
+            c.roles.blank(c.P0)
         c.sweep(c.P0)
-        _sub_into(c.D, c.work)
+        if c.roles is not None:
+            B.forcing_roles(c.D, c.work, c.roles)
+        else:
+            _sub_into(c.D, c.work)
         Pc = self._level(l + 1, c.P0, c.D, g)
         out = next(b for b in m._buf if b.data_ptr() != P.data_ptr())
         B.prolong_euler(self.prolongators[l], P, Pc, c.P0, self.fluid, out=out, pack=c.pack)
         if m.bcs is not None:
             m.bcs(out)
+        if m.roles is not None:
+            m.roles.blank(out)
         return m.smooth(out, self.post, S, g)
 
     def residual_history(self):
         """The history as a host array of ``history`` doubles: entry ``k`` is the sum of squares of the density residual that
-        cycle ``k`` restricted, NaN where no cycle has written.  The one read-back of the class."""
+        cycle ``k`` restricted, NaN where no cycle has written; with ``roles`` ``(history, nd + 2)``: the sums over the fluid
+        rows of every column of that residual.  The one read-back of the class."""
         if self._hist is None:
-            return np.zeros(0, dtype=np.float64)
+            return np.zeros(0 if self.levels[0].roles is None else (0, self.levels[0].part.nd + 2), dtype=np.float64)
         return self._hist.cpu().numpy()
 
 
@@ -571,10 +632,10 @@ class DualTimeMarch(EulerMarch):
     the march did not return (the caller's, on the first step) is copied into the history once and never written.  No host
     read-back in ``step``: it can be captured in ``torch.cuda.graph`` and replayed (the replay reads the history arrays the
     capture saw: it continues the march once; to repeat it, restore them).  ``n_inner`` is fixed: a stopping criterion would
-    need a read-back."""
+    need a read-back.  ``roles``: as in ``EulerMarch`` -- the solid rows are blanked after every stage's ``bcs``."""
 
     def __init__(self, part, dt_real, n_inner, order=2, fluid=None, scheme="hll", scale=0.75, bcs=None, average=None,
-                 local_dt=True, dt_every=1, residual=None, flags=0, stages=1, smoothing=None):
+                 local_dt=True, dt_every=1, residual=None, flags=0, stages=1, smoothing=None, roles=None):
         later = bdf_coefficients(order, dt_real)
         self._bdf = {int(order): later, 1: bdf_coefficients(1, dt_real)}        # (the first step is BDF1)
         if isinstance(n_inner, bool) or int(n_inner) != n_inner or int(n_inner) < 1:
@@ -584,7 +645,7 @@ class DualTimeMarch(EulerMarch):
                              "the inner iterations to smooth(R) + S = g Q, which is not the backward-difference equation")
         if isinstance(stages, (tuple, list)) and any(isinstance(a, (tuple, list)) for a in stages):
             raise ValueError("DualTimeMarch: stages are rk_stages(m) or plain coefficients; Shu-Osher triples are not taken")
-        super().__init__(part, fluid, scheme, scale, bcs, None, local_dt, dt_every, residual, flags, stages)
+        super().__init__(part, fluid, scheme, scale, bcs, None, local_dt, dt_every, residual, flags, stages, roles=roles)
         self.average, self.dt_real, self.n_inner, self.order = average, dt_real, int(n_inner), int(order)
         self._records = [("dual", "P0", (alpha,)) + _dual_calls(alpha) for alpha in self.stages]
         nc, nv = self.part.nc, self.part.nd + 2

@@ -578,6 +578,26 @@ int ibh_restrict_euler(const ibh_acc* coarsener, const ibh_fluid*, int nd, const
 int ibh_prolong_euler(const ibh_acc* prolongator, const ibh_fluid*, int nd, const float* Pc_new, const float* Pc_old,
                       int64_t ldc, float* pack /* n_input x 8 floats, 32-byte aligned */, const float* P_f, int64_t ldpf,
                       float* P_out, int64_t ldo);
+/* ---- cell roles of an immersed-boundary march (not in the reference, which blanks nothing): one byte per row says what the
+ *   row IS -- fluid, a ghost row of a boundary, or a solid row behind the ghost layer (cell_roles(dom) on the host).  Only
+ *   fluid rows carry a defect, a forcing or a norm; every test below is a SELECT, so a NaN in a masked row stops there.
+ * ibh_restrict_euler_roles: ibh_restrict_euler with D_c = coarsener(t), t_i = R_f[i] .+ S_f[i] (rounded; S_f NULL: R_f[i])
+ *   where roles_f[i] == IBH_ROLE_FLUID and +0 elsewhere -- bit for bit ibh_restrict_euler on that t with S_f NULL.  P_c is
+ *   ibh_restrict_euler's: the state of a masked row is restricted like any other.  One launch, one byte more per fine row.
+ * ibh_forcing_roles: the coarse forcing in place, D[i] = D[i] - R[i] where roles[i] == IBH_ROLE_FLUID and +0 elsewhere, for
+ *   the nv <= 8 columns of (n, nv) arrays, one launch: the broadcast D .- R and the select.  D overlaps neither R nor roles.
+ * ibh_sumsq_roles: out[v] (device, double) = the sum of x[i, v]^2 over the rows with roles[i] == IBH_ROLE_FLUID, for the
+ *   nv <= 8 columns in one launch and the one-launch final stage of ibh_sumsq; out is assigned, never added to.
+ * Every misuse (null pointer, nd / nv out of range, a leading dimension below the row count, an output that overlaps an
+ * input) is an error before any launch; zero rows are no error and no launch (ibh_sumsq_roles then leaves out as it was). */
+#define IBH_ROLE_FLUID 0
+#define IBH_ROLE_GHOST 1
+#define IBH_ROLE_SOLID 2
+int ibh_restrict_euler_roles(const ibh_acc* coarsener, const ibh_fluid*, int nd, const float* P_f, int64_t ldpf,
+                             const float* R_f, int64_t ldrf, const float* S_f /* may be NULL */, int64_t ldsf,
+                             const uint8_t* roles_f, float* P_c, int64_t ldpc, float* D_c, int64_t lddc);
+int ibh_forcing_roles(int64_t n, int nv, float* D, int64_t ldd, const float* R, int64_t ldr, const uint8_t* roles);
+int ibh_sumsq_roles(int64_t n, int nv, const float* x, int64_t ldx, const uint8_t* roles, double* out /* nv */);
 int ibh_axpy_clamped(int64_t n, float omega, const float* r, float* q);
 /* y = a*x + y */
 int ibh_axpy(int64_t n, float a, const float* x, float* y);

@@ -969,6 +969,42 @@ function restrict_euler!(P_c::HipArray{Float32}, D_c::HipArray{Float32}, coarsen
     P_c, D_c
 end
 
+"Cell roles of an immersed-boundary march, one `UInt8` per row (`cell_roles` of the Python package builds them on the host)."
+const ROLE_FLUID, ROLE_GHOST, ROLE_SOLID = 0x00, 0x01, 0x02
+
+"`restrict_euler!` with cell roles: `D_c = coarsener(t)` with `t = R .+ S` (or `R`) in the rows whose role is `ROLE_FLUID` and `+0`
+in every other one -- a select, so a NaN in a masked row never reaches `D_c`; `P_c` is `restrict_euler!`'s.  One launch."
+function restrict_euler_roles!(P_c::HipArray{Float32}, D_c::HipArray{Float32}, coarsener::HipAccumulator, fluid,
+                               P::HipArray{Float32}, R::HipArray{Float32}, S::Union{HipArray{Float32}, Nothing},
+                               roles::HipArray{UInt8})
+    length(roles) == size(P, 1) || error("restrict_euler_roles!: one role per fine row")
+    f = Ref(IbhFluid(fluid))
+    check(ccall((:ibh_restrict_euler_roles, lib), Cint,
+        (Ptr{Cvoid}, Ptr{IbhFluid}, Cint, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Int64,
+         Ptr{Cvoid}, Int64),
+        coarsener.handle, f, size(P, 2) - 2, P.ptr, ld(P), R.ptr, ld(R), isnothing(S) ? C_NULL : S.ptr, isnothing(S) ? 0 : ld(S),
+        roles.ptr, P_c.ptr, ld(P_c), D_c.ptr, ld(D_c)))
+    P_c, D_c
+end
+
+"The coarse forcing of a cycle with cell roles, in place and in one launch: `D .= D .- R` in the rows whose role is `ROLE_FLUID`,
+`+0` in every other one.  At most 8 columns; `D` aliases neither `R` nor `roles`."
+function forcing_roles!(D::HipArray{Float32}, R::HipArray{Float32}, roles::HipArray{UInt8})
+    size(D) == size(R) && length(roles) == size(D, 1) || error("forcing_roles!: D and R of one shape, one role per row")
+    check(ccall((:ibh_forcing_roles, lib), Cint, (Int64, Cint, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}),
+        size(D, 1), size(D, 2), D.ptr, ld(D), R.ptr, ld(R), roles.ptr))
+    D
+end
+
+"Per column of `x` (at most 8) the sum of squares over the rows whose role is `ROLE_FLUID`, in `Float64` on the device: `out`
+holds `size(x, 2)` values and is assigned.  One launch for all columns and the one-launch final stage of the sums."
+function sumsq_roles!(out::HipArray{Float64}, x::HipArray{Float32}, roles::HipArray{UInt8})
+    length(out) == size(x, 2) && length(roles) == size(x, 1) || error("sumsq_roles!: one output per column, one role per row")
+    check(ccall((:ibh_sumsq_roles, lib), Cint, (Int64, Cint, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}),
+        size(x, 1), size(x, 2), x.ptr, ld(x), roles.ptr, out.ptr))
+    out
+end
+
 "The prolongation of a multigrid cycle of the Euler march: `P_out = state2primitive(fluid, primitive2state(fluid, P) .+
 prolongator(primitive2state(fluid, Pc_new) .- primitive2state(fluid, Pc_old)))` in two launches, bit for bit `primitive2state`
 three times, `accumulate_diff_add!` and `state2primitive`.  `pack`: `8 * n_input` Float32 of scratch on the device, 32-byte
