@@ -308,20 +308,22 @@ def _build_partition(ipart, image, ncells, fd, fo, fn, centers, widths, skirt_de
 # ghosts / boundaries (ImmersedBoundary.jl:194-326, :422-476)
 # ---------------------------------------------------------------------------
 def _project_2d(dfield, X, R):
-    """Vectorised ``projection(dfield, x, R)`` for segment surfaces (mesher.jl:778-801, :549-567)."""
+    """Vectorised ``projection(dfield, x, R)`` for segment surfaces (mesher.jl:778-801, :549-567), in Float64 on the
+    Float32 data like ``DistanceField.projection`` (see there), the chosen foot rounded once."""
     n = X.shape[1]
     idx, d = dfield.nn(X)
     P = dfield.centers[:, idx].copy()
-    dcur = d.copy()
+    X = X.astype(np.float64)
+    dcur = _dist_cols(X, dfield.centers[:, idx].astype(np.float64))
     cand = dfield.tree.query_ball_point(np.ascontiguousarray(X.T, dtype=np.float64), r=R.astype(np.float64))
     lens = np.array([len(c) for c in cand])
-    use = R > d
+    use = R > dcur
     lens = np.where(use, lens, 0)
     if lens.sum() == 0:
         return P
     rows = np.repeat(np.arange(n), lens)
     sidx = np.concatenate([np.sort(np.asarray(c, dtype=np.int64)) for c, u_ in zip(cand, use) if u_ and len(c)])
-    pts = dfield.stl.points
+    pts = dfield.stl.points.astype(np.float64)
     simp = dfield.stl.simplices - 1
     p0 = pts[:, simp[0, sidx]]
     p1 = pts[:, simp[1, sidx]]
@@ -338,14 +340,12 @@ def _project_2d(dfield, X, R):
     proj = np.where(xi > 1.0 + eps_, p1, proj)
     dd = proj - x
     dist = np.sqrt(dd[0] * dd[0] + dd[1] * dd[1])
-    # sequential "first strict improvement" per row == first minimum below the nn distance
+    # sequential "first strict improvement" per row == first minimum; the nearest centre is no bar (its own simplex is a
+    # candidate and the stored centre a rounding of a point of it, see ``DistanceField.projection``)
     starts = np.concatenate([[0], np.cumsum(lens)])
     for r in np.nonzero(lens)[0]:
         s, e = starts[r], starts[r + 1]
-        seg = dist[s:e]
-        k = int(np.argmin(seg))
-        if seg[k] < dcur[r]:
-            P[:, r] = proj[:, s + k]
+        P[:, r] = proj[:, s + int(np.argmin(dist[s:e]))]
     return P
 
 
@@ -376,15 +376,15 @@ def _dist_cols(a, b):
 
 def _tri_cache(dfield):
     """Per triangle of a surface: the vertices, the 3 x 2 edge matrix, its pseudo-inverse (one SVD per triangle) and
-    the largest vertex distance from the centre (with a safety margin, Float64)."""
-    pts = dfield.stl.points
+    the largest vertex distance from the centre (with a safety margin), all in Float64 on the Float32 vertices."""
+    pts = dfield.stl.points.astype(np.float64)
     simp = dfield.stl.simplices - 1
     T0, T1, T2 = pts[:, simp[0]], pts[:, simp[1]], pts[:, simp[2]]
     cache = getattr(dfield, "_tri_cache", None)
     if cache is None:
         M = np.stack([T1 - T0, T2 - T0], axis=2).transpose(1, 0, 2)          # (nt, 3, 2)
         pinvM = np.linalg.pinv(M)                                            # (nt, 2, 3)
-        ctr = dfield.centers
+        ctr = dfield.centers.astype(np.float64)
         rmax = np.maximum(np.maximum(_dist_cols(T0, ctr), _dist_cols(T1, ctr)), _dist_cols(T2, ctr))
         cache = dfield._tri_cache = (M, pinvM, rmax.astype(np.float64) * 1.0001 + 1e-12)
     return T0, T1, T2, cache
@@ -395,15 +395,20 @@ def _project_3d(dfield, X, R, chunk=20_000):
     :544-596): the (ghost, candidate triangle) pairs of a chunk of ghosts at once -- ``pinv`` of the 3 x 2 edge
     matrix once per triangle, the three edge projections where the foot point falls outside the triangle (first
     strict minimum, faces in the order of ``simplex_faces``), then per ghost the first candidate, in ascending simplex
-    order, that strictly improves on the nearest-centre distance.  A candidate is dropped beforehand when it cannot
-    win: |x - centre| - (largest vertex distance from the centre) >= nearest-centre distance -- the reference replaces
-    the nearest centre only by a strictly closer point, so the result is the same.  Agrees with the per-ghost loop to
-    the last bit or two of the ``pinv`` product (tests/test_3d.py checks the ghost sets and the projections)."""
+    order, at the least distance.  A candidate is dropped beforehand when it cannot win: |x - centre| - (largest vertex
+    distance from the centre) >= nearest-centre distance, which the nearest centre's own triangle is within.  In Float64 on the Float32 data like
+    ``DistanceField.projection`` (see there), the chosen foot rounded once; agrees with the per-ghost loop to that
+    rounding (tests/test_3d.py checks the ghost sets and the projections)."""
     n = X.shape[1]
-    idx, d = dfield.nn(X)
+    idx, _ = dfield.nn(X)
     P = dfield.centers[:, idx].copy()
     if n == 0:
         return P
+    X = X.astype(np.float64)
+    # upper bound of the distance to the surface: to the nearest stored centre, plus the Float32 rounding of that centre
+    # (the stored centre itself is no bar for the candidates, see ``DistanceField.projection``)
+    d = (_dist_cols(X, dfield.centers[:, idx].astype(np.float64))
+         + 4 * float(np.finfo(f32).eps) * float(np.abs(dfield.centers).max()))
     eps_ = f32(1e-14)
     T0, T1, T2, cache = _tri_cache(dfield)
     M, pinvM, rmax = cache
@@ -440,7 +445,7 @@ def _project_3d(dfield, X, R, chunk=20_000):
         if outside.any():
             o = np.nonzero(outside)[0]
             xo = x[:, o]
-            best = np.empty((3, o.size), dtype=X.dtype)
+            best = np.empty((3, o.size), dtype=np.float64)
             bd = np.full(o.size, np.inf, dtype=np.float64)
             # simplex_faces: the simplex without vertex i, i = 1, 2, 3
             for (a, b) in ((p1, p2), (p0, p2), (p0, p1)):
@@ -455,8 +460,7 @@ def _project_3d(dfield, X, R, chunk=20_000):
         order = np.lexsort((tri, dist, rows))
         rs = rows[order]
         first = order[np.concatenate([[True], rs[1:] != rs[:-1]])]
-        better = dist[first] < d[rows[first]]
-        P[:, rows[first][better]] = pr[:, first[better]]
+        P[:, rows[first]] = pr[:, first]
     return P
 
 
@@ -581,7 +585,8 @@ def boundary_partitions(cT, wT, tree, ghosts, projs, max_partition_size, ghost_r
 class Surface:
     """Post-processing surface of an immersed boundary (ImmersedBoundary.jl:328-343, built at :744-766): control
     points = simplex centres of the (refined) STL, ``offsets`` = 1.01 x diameter of the nearest cell, unit ``normals``,
-    ``areas`` = norm of the area-weighted normals, ``interpolator`` (stencil searched at points + normals*offset,
+    ``areas`` = norm of the area-weighted normals (+ eps) in 2-D and the triangle areas in 3-D (``make_surface``),
+    ``interpolator`` (stencil searched at points + normals*offset,
     evaluated AT the points) and ``offset_interpolator`` (at points + normals*offset*ghost_layer_ratio)."""
 
     def __init__(self, points, offsets, normals, areas, interpolator, offset_interpolator, stl):
@@ -600,6 +605,15 @@ def make_surface(dfield, cT, tree, diams, ghost_layer_ratio):
     A = (np.sqrt(_rowsum(fnT * fnT)) + eps_).astype(f32)
     fnT = (fnT / A[:, None]).astype(f32)
     fcT = np.ascontiguousarray(fcenters.T).astype(f32)
+    if fcT.shape[1] == 3:
+        # NOT the reference, which hands the norm above to ``areas`` in 3-D as well: the cross product of two edges has
+        # twice the triangle's area, so its surface integrals over a 3-D body come out doubled; and the eps of the division
+        # guard is 3.5e-5 of the cross product of a triangle of a 7 200-triangle unit sphere: the areas come out long
+        # and the normals short by that.  Here: the triangle's area, and a unit normal (a degenerate triangle keeps a zero
+        # normal).  tests/test_ib_geometry.py holds both to the polyhedron.  (2-D stays the reference's, bit for bit.)
+        nrm = np.sqrt(_rowsum(fnormals.T * fnormals.T)).astype(f32)
+        A = (nrm / f32(2)).astype(f32)
+        fnT = (np.ascontiguousarray(fnormals.T) / np.where(nrm > 0, nrm, f32(1))[:, None]).astype(f32)
     bias = (fnT * h[:, None]).astype(f32)
     return Surface(fcT, h, fnT, A, interpolator(cT, fcT, tree, bias=bias),
                    interpolator(cT, (fcT + bias * f32(ghost_layer_ratio)).astype(f32), tree), dfield.stl)

@@ -375,15 +375,23 @@ class DistanceField:
         return idx, np.sqrt(s)
 
     def projection(self, x, R=0.0):
-        """Projection on the surface, candidates within ``R`` (mesher.jl:778-801)."""
+        """Projection on the surface, candidates within ``R`` (mesher.jl:778-801).  The foot points and the distances
+        that choose among them are evaluated in Float64 on the Float32 data and the chosen foot is rounded once (the
+        reference does this arithmetic in Float32): two facets that meet at a flat angle are as far from a cell as
+        Float32 can tell, the foot on the farther one lies up to 5e-4 cell diameters from the closest point, and the
+        wall normal of the cell turns with it (tests/test_ib_geometry.py)."""
         x = np.asarray(x)
         _, idx = self.tree.query(x.astype(np.float64))
-        d = self._dist(x, idx)
         p = self.centers[:, idx].copy()
+        x = x.astype(np.float64)
+        d = _norm(x - self.centers[:, idx].astype(np.float64))
         if R > d:
-            cand = self.tree.query_ball_point(x.astype(np.float64), float(R))
+            # the nearest centre's own simplex is a candidate, and the stored centre is a Float32 rounding of a point of it:
+            # the rounded centre may be closer to x than the simplex by that rounding, so it is no bar for the candidates
+            d = np.inf
+            cand = self.tree.query_ball_point(x, float(R))
             for i in sorted(cand):
-                simp = self.stl.points[:, self.stl.simplices[:, i] - 1]
+                simp = self.stl.points[:, self.stl.simplices[:, i] - 1].astype(np.float64)
                 _p = proj2simplex(simp, x)
                 _d = _norm(_p - x)
                 if _d < d:

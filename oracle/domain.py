@@ -76,7 +76,9 @@ class Boundary:
 
 
 class Surface:
-    """ImmersedBoundary.jl:328-376 (struct, surface_integral, call, at_offset), built at :744-766."""
+    """ImmersedBoundary.jl:328-376 (struct, surface_integral, call, at_offset), built at :744-766.  Literal also where the
+    reference is off: in 3-D its ``areas`` are the norms of the edges' cross products, twice the triangle areas; the product's
+    ``make_surface`` departs from it there (tests/test_ib_geometry.py holds the product's areas to the polyhedron)."""
 
     def __init__(self, points, offsets, normals, areas, interpolator, offset_interpolator, stl):
         self.points, self.offsets, self.normals, self.areas = points, offsets, normals, areas
@@ -84,7 +86,7 @@ class Surface:
 
     @staticmethod
     def build(dfield, cT, tree, diams, ghost_layer_ratio):
-        from ibamd.mesher import centers_and_normals
+        from .mesher import centers_and_normals   # (the oracle's own, simplex by simplex)
         eps_ = np.finfo(f32).eps
         fcenters, fnormals = centers_and_normals(dfield.stl)
         _, idx = tree.query(np.ascontiguousarray(fcenters.T, dtype=np.float64))
@@ -327,7 +329,9 @@ def hcube_faces(hc_origin, hc_widths, origins, widths):
 # ghosts (ImmersedBoundary.jl:194-326)
 # ---------------------------------------------------------------------------
 def ghosts_and_projections(dfield, centers, widths, ghost_layer_ratio=f32(1.5)):
-    """ImmersedBoundary.jl:194-230 (distance-field surfaces)."""
+    """ImmersedBoundary.jl:194-230 (distance-field surfaces).  ``dfield`` is the mesh's own distance field (its nearest-centre
+    query and its per-ghost ``projection``), so this restates the loop around them and not the geometry: which cells are
+    ghosts and where they project is pinned against an exact closest-point search in tests/test_ib_geometry.py."""
     ratio = f32(ghost_layer_ratio)
     diams = np.sqrt(_colsum(widths * widths))
     _, dists = dfield.nn(centers)

@@ -72,6 +72,35 @@ def get_cells(block_origins, block_widths, block_size):
     return np.concatenate(cols_c, axis=1).astype(f32), np.concatenate(cols_w, axis=1).astype(f32)
 
 
+def _simplex_center(simplex):
+    """mesher.jl:630-632: ``sum(simplex; dims = 2) ./ size(simplex, 2)``, the vertices added in order."""
+    s = simplex[:, 0].copy()
+    for k in range(1, simplex.shape[1]):
+        s = s + simplex[:, k]
+    return s / simplex.shape[1]
+
+
+def _simplex_normal(simplex):
+    """mesher.jl:601-628 with ``normalize = false``: the edge turned by a quarter turn in 2-D, the cross product of the two
+    edges from the first vertex in 3-D (its norm is that of the parallelogram they span)."""
+    if simplex.shape[0] == 2:
+        v = simplex[:, 1] - simplex[:, 0]
+        return np.array([v[1], -v[0]], dtype=simplex.dtype)
+    p0 = simplex[:, 0]
+    a, b = simplex[:, 1] - p0, simplex[:, 2] - p0
+    return np.array([a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]], dtype=simplex.dtype)
+
+
+def centers_and_normals(stl):
+    """mesher.jl:639-660, simplex by simplex: centres and area-weighted normals, ``(ndims, nsimplices)`` each.  The oracle's
+    own: the product's vectorised ``centers_and_normals`` is compared with it bit for bit through the ``Surface`` arrays
+    (tests/test_oracle_known_answers.py)."""
+    simplices = [stl.points[:, stl.simplices[:, k] - 1] for k in range(stl.simplices.shape[1])]
+    centers = np.stack([_simplex_center(s) for s in simplices], axis=1)
+    normals = np.stack([_simplex_normal(s) for s in simplices], axis=1)
+    return centers, normals
+
+
 class BlockTree:
     """The mesh container the oracle's ``Domain`` and ``multigrid`` need -- origin / widths of the box, the block tree
     (``block_origins``, ``block_widths``: (ndims, nblocks), depth-first order), ``block_size`` and the distance fields of the
