@@ -20,6 +20,29 @@ class IbhError(RuntimeError):
     pass
 
 
+# The named slots of ibh_partition_info in slot order: the IBH_INFO_* enum of include/ibhip.h in lower case (slot 12 is
+# ``quads`` on a 2-D partition and ``rim4_rows`` on a 3-D one); INFO_COUNT entries are reported, the rest are zero.
+INFO_SLOTS = ("full_blocks", "irregular_cells", "sides_same", "sides_mirror", "sides_coarse", "sides_fine", "sides_general",
+              "interior_blocks", "fusable_blocks", "workspace_blocks", "image_all_eligible", "image_blocks", "quads",
+              "quad_singles", "image_quads", "image_quad_singles", "row_sweep", "direct_sides", "quad_pairs",
+              "quad_arith_half_sides", "tiled")
+INFO_COUNT = 24
+INFO_BOOLS = ("image_all_eligible", "row_sweep", "tiled")
+INFO_2D_ONLY = ("quads", "quad_pairs", "quad_arith_half_sides")
+INFO_KEYS = {"image_all_eligible": "image_blocks_all_eligible"}   # keys of DevicePartition.info that are not the slot's name
+
+
+def info_dict(nd, values):
+    """``DevicePartition.info``: the named slots of ``values`` (what ibh_partition_info reports) for a partition of ``nd``
+    dimensions -- flags as bool, the 2-D slots zero in 3-D, and slot 12 under its 3-D name ``rim4_rows`` (zero in 2-D)."""
+    out = {}
+    for name, x in zip(INFO_SLOTS, values):
+        x = bool(x) if name in INFO_BOOLS else int(x)
+        out[INFO_KEYS.get(name, name)] = 0 if (nd != 2 and name in INFO_2D_ONLY) else x
+    out["rim4_rows"] = int(values[INFO_SLOTS.index("quads")]) if nd == 3 else 0
+    return out
+
+
 class ibh_fluid(C.Structure):
     _fields_ = [("R", C.c_float), ("gamma", C.c_float), ("mu_ref", C.c_float), ("Tref", C.c_float),
                 ("S", C.c_float), ("nk", C.c_int32), ("k", C.c_float * 4)]

@@ -27,6 +27,7 @@ from . import _lib
 from ._lib import call, c_vp
 from .accumulator import Accumulator
 from .domain import Boundary, Partition, Surface
+from .hostview import partition_args
 
 IBH_FORCE_GENERAL = 1
 IBH_IMAGE_ONLY = 2
@@ -212,50 +213,22 @@ class DevicePartition(_Handle):
         self.id = part.id
         self.nd = part.ndims
         self.nc = part.spacing.shape[0]
-        nd, nc = self.nd, self.nc
-        spacing = np.asfortranarray(part.spacing, dtype=np.float32)
         centers = np.asfortranarray(part.centers, dtype=np.float32)
-        self.nf = [int(part.face_owners_neighbors[d + 1][0].shape[0]) for d in range(nd)]
-        nf = np.array(self.nf, dtype=np.int32)
-        keep = []
-
-        def parr(arrs):
-            arrs = [np.ascontiguousarray(a, dtype=np.int32) for a in arrs]
-            keep.append(arrs)
-            return (c_vp * nd)(*[a.ctypes.data for a in arrs])
-
-        owners = parr([part.face_owners_neighbors[d + 1][0] for d in range(nd)])
-        neighbors = parr([part.face_owners_neighbors[d + 1][1] for d in range(nd)])
-        loff = parr([part.face_accumulators[(d + 1, False)].off for d in range(nd)])
-        lidx = parr([part.face_accumulators[(d + 1, False)].idx for d in range(nd)])
-        roff = parr([part.face_accumulators[(d + 1, True)].off for d in range(nd)])
-        ridx = parr([part.face_accumulators[(d + 1, True)].idx for d in range(nd)])
-        iid = np.ascontiguousarray(part.image_in_domain, dtype=np.int32)
-        dom = np.ascontiguousarray(part.domain, dtype=np.int32)
+        args, keep = partition_args(part)
+        self.nf = [int(n) for n in keep["nf"]]
         h = c_vp()
-        call("ibh_partition_create", C.byref(h), nd, nc, spacing.ctypes.data_as(c_vp), centers.ctypes.data_as(c_vp),
-             nf.ctypes.data_as(c_vp), owners, neighbors, loff, lidx, roff, ridx, int(iid.size), _hptr(iid),
-             _hptr(dom), int(getattr(part, "block_size", 0)), 0)
+        call("ibh_partition_create", C.byref(h), self.nd, self.nc, _hptr(keep["spacing"]), _hptr(centers), *args[:-1],
+             int(getattr(part, "block_size", 0)), args[-1])
         self.handle = h
         # device copies of what user closures read (part.spacing[:, dim], part.centers)
         self.spacing = hip(part.spacing)
         self.centers = hip(part.centers)
-        self.domain = torch.from_numpy(dom).to(dev)
+        self.domain = torch.from_numpy(keep["domain"]).to(dev)
         self.image = torch.from_numpy(np.ascontiguousarray(part.image, dtype=np.int32)).to(dev)
-        self.image_in_domain = torch.from_numpy(iid).to(dev)
-        info = (C.c_int64 * 24)()
-        call("ibh_partition_info", h, info, 24)
-        self.info = dict(full_blocks=info[0], irregular_cells=info[1], sides_same=info[2], sides_mirror=info[3],
-                         sides_coarse=info[4], sides_fine=info[5], sides_general=info[6], interior_blocks=info[7],
-                         fusable_blocks=info[8], workspace_blocks=info[9],
-                         image_blocks_all_eligible=bool(info[10]), image_blocks=info[11],
-                         quads=info[12] if self.nd == 2 else 0, quad_singles=info[13], image_quads=info[14],
-                         image_quad_singles=info[15], row_sweep=bool(info[16]), direct_sides=info[17],
-                         quad_pairs=info[18] if self.nd == 2 else 0,   # pair tiles among the blocks outside quads
-                         quad_arith_half_sides=info[19] if self.nd == 2 else 0,   # of 8 per quad: halo ids computed, not read
-                         tiled=bool(info[20]),   # complete blocks in order: the time step takes in-block neighbours by index
-                         # 3-D single-kernel sweeps: rim neighbours of halo cells that are four finer cells
-                         rim4_rows=info[12] if self.nd == 3 else 0)
+        self.image_in_domain = torch.from_numpy(keep["image_in_domain"]).to(dev)
+        info = (C.c_int64 * _lib.INFO_COUNT)()
+        call("ibh_partition_info", h, info, _lib.INFO_COUNT)
+        self.info = _lib.info_dict(self.nd, info)   # the slots by name: include/ibhip.h says what each one counts
 
     @property
     def ndims(self):

@@ -23,10 +23,10 @@ inline bool on_opp_edge(int s, int pos) {
 
 }  // namespace
 
-void ibh_analyze_blocks2(const HostPartView& v, std::vector<BlockDesc2>& blocks, std::vector<int32_t>& irr,
-                         int64_t* info, const int32_t* image_in_domain, int32_t n_image, int32_t* n_phase1,
-                         std::vector<int32_t>& htab, std::vector<int32_t>& etab, std::vector<char>& fus,
-                         std::vector<char>& needg, std::vector<int32_t>& dtab) {
+static void ibh_analyze_blocks2(const HostPartView& v, const int32_t* image_in_domain, int32_t n_image, Host2D& H) {
+    std::vector<BlockDesc2>& blocks = H.blocks;
+    std::vector<int32_t>&irr = H.irr, &htab = H.htab, &etab = H.etab, &dtab = H.dtab;
+    std::vector<char>&fus = H.fus, &needg = H.needg;
     const int32_t nc = v.nc;
     const int NPB = 64;
     const float* hx = v.spacing;
@@ -60,8 +60,6 @@ void ibh_analyze_blocks2(const HostPartView& v, std::vector<BlockDesc2>& blocks,
     std::vector<char> cell_irr(nc, 0);
     std::vector<std::array<int32_t, 64>> halos;  // halo cell ids per block, in the order blocks are found
     for (int32_t c = 0; c < nc; ++c) cell_irr[c] = !in_full[c];
-    int64_t counts[5] = {0, 0, 0, 0, 0};
-
     for (int32_t base : bases) {
         // 2. interior faces must be the implicit ones
         bool good = true;
@@ -184,7 +182,7 @@ void ibh_analyze_blocks2(const HostPartView& v, std::vector<BlockDesc2>& blocks,
             b.sub[s] = sub < 0 ? 0 : sub;
             b.q[s] = type == SIDE_COARSE ? (1.0f / 3.0f) : type == SIDE_FINE ? (2.0f / 3.0f) : 0.5f;
             b.rt[s] = type == SIDE_COARSE ? 2.0f : type == SIDE_FINE ? 0.5f : 1.0f;
-            counts[type]++;
+            H.sum.sides[type]++;
             if (type == SIDE_GENERAL)
                 for (int t = 0; t < 8; ++t) cell_irr[base + pos_own(s, t)] = 1;
         }
@@ -198,7 +196,7 @@ void ibh_analyze_blocks2(const HostPartView& v, std::vector<BlockDesc2>& blocks,
     //    neighbour is a skirt cell (not in `image`).  A1 = blocks without such a cell (pass A can run before
     //    the halo exchange lands); B1 = A1 blocks whose side neighbours are all A1 (pass B as well).
     //    Block table order: [B1 | A1 only | rest].
-    n_phase1[0] = n_phase1[1] = 0;
+    H.nph[0] = H.nph[1] = 0;
     {
         std::vector<char> is_image(nc, 0), dep(nc, 0);
         for (int32_t k = 0; k < n_image; ++k) is_image[image_in_domain[k] - v.index_base] = 1;
@@ -237,9 +235,9 @@ void ibh_analyze_blocks2(const HostPartView& v, std::vector<BlockDesc2>& blocks,
         hordered.reserve(blocks.size());
         auto take = [&](size_t b) { ordered.push_back(blocks[b]); hordered.push_back(halos[b]); };
         for (size_t b = 0; b < blocks.size(); ++b) if (b1[b]) take(b);
-        n_phase1[1] = (int32_t)ordered.size();
+        H.nph[1] = (int32_t)ordered.size();
         for (size_t b = 0; b < blocks.size(); ++b) if (a1[b] && !b1[b]) take(b);
-        n_phase1[0] = (int32_t)ordered.size();
+        H.nph[0] = (int32_t)ordered.size();
         for (size_t b = 0; b < blocks.size(); ++b) if (!a1[b]) take(b);
         blocks.swap(ordered);
         halos.swap(hordered);
@@ -276,7 +274,7 @@ void ibh_analyze_blocks2(const HostPartView& v, std::vector<BlockDesc2>& blocks,
             }
             return n;
         };
-        int64_t nfus = 0;
+        H.nfus = 0;
         for (size_t bi = 0; bi < blocks.size(); ++bi) {
             BlockDesc2& b = blocks[bi];
             b.dt = -1;
@@ -335,9 +333,8 @@ void ibh_analyze_blocks2(const HostPartView& v, std::vector<BlockDesc2>& blocks,
                 dtab.insert(dtab.end(), deep, deep + 64);
             }
             fus[bi] = ok;
-            nfus += ok;
+            H.nfus += ok;
         }
-        info[8] = nfus;
     }
     // 7. mixed launches (partitions with skirt blocks): eligible blocks take the single kernel, the others the
     //    two-kernel form.  The gradient workspace is then needed only where somebody reads it: in the blocks
@@ -361,10 +358,6 @@ void ibh_analyze_blocks2(const HostPartView& v, std::vector<BlockDesc2>& blocks,
             needg[bi] = need;
         }
     }
-    info[7] = n_phase1[1];
-    info[0] = (int64_t)blocks.size();
-    info[1] = (int64_t)irr.size();
-    for (int k = 0; k < 5; ++k) info[2 + k] = counts[k];
 }
 
 // ------------------------------------------------------------------------------------------
@@ -411,6 +404,20 @@ void ibh_build_quads2(const std::vector<BlockDesc2>& blocks, const std::vector<i
     auto same_to = [&](const BlockDesc2& a, int s, int32_t base) {
         return a.type[s] == SIDE_SAME && a.nb[s][0] == base;
     };
+    // an outer side a quad / pair can have.  Paired gathers of the quad sweep (quad_load_halo_paired): on bottom / top sides the
+    // 8-byte load at a halo cell must stay inside the arrays, and the two sub-face cells of a FINE side must be x neighbours
+    auto side_ok = [&](int32_t bi, int s) {
+        const BlockDesc2& b = blocks[bi];
+        const int ty = b.type[s];
+        bool ok = ty == SIDE_SAME || ty == SIDE_COARSE || ty == SIDE_FINE;
+        if (ok && s >= 2)
+            for (int t = 0; t < 8 && ok; ++t) {
+                const int32_t h0 = htab[(size_t)bi * 64 + (s * 8 + t) * 2], h1 = htab[(size_t)bi * 64 + (s * 8 + t) * 2 + 1];
+                const int32_t dl = s == 2 ? -8 : 8;
+                ok = h0 + 1 < nc && h0 + dl >= 0 && h0 + dl + 1 < nc && (ty != SIDE_FINE || h1 == h0 + 1);
+            }
+        return ok;
+    };
     // outer sides of the block at position k (0 LL, 1 LR, 2 UL, 3 UR)
     static const int outer[4][2] = {{0, 2}, {1, 2}, {0, 3}, {1, 3}};
     for (int32_t o : order) {
@@ -430,19 +437,7 @@ void ibh_build_quads2(const std::vector<BlockDesc2>& blocks, const std::vector<i
         for (int k = 0; k < 4 && ok; ++k) {
             const BlockDesc2& b = blocks[idx[k]];
             ok = b.dt < 0 && b.h[0] == b0.h[0] && b.h[1] == b0.h[1];
-            for (int e = 0; e < 2 && ok; ++e) {
-                const int s = outer[k][e];
-                const int ty = b.type[s];
-                ok = ty == SIDE_SAME || ty == SIDE_COARSE || ty == SIDE_FINE;
-                // paired gathers of the quad sweep (quad_load_halo_paired): on bottom / top sides the 8-byte load at a
-                // halo cell must stay inside the arrays, and the two sub-face cells of a FINE side must be x neighbours
-                if (ok && s >= 2)
-                    for (int t = 0; t < 8 && ok; ++t) {
-                        const int32_t h0 = htab[(size_t)idx[k] * 64 + (s * 8 + t) * 2], h1 = htab[(size_t)idx[k] * 64 + (s * 8 + t) * 2 + 1];
-                        const int32_t dl = s == 2 ? -8 : 8;
-                        ok = h0 + 1 < nc && h0 + dl >= 0 && h0 + dl + 1 < nc && (ty != SIDE_FINE || h1 == h0 + 1);
-                    }
-            }
+            ok = ok && side_ok(idx[k], outer[k][0]) && side_ok(idx[k], outer[k][1]);
         }
         if (!ok) continue;
         Q q;
@@ -454,31 +449,31 @@ void ibh_build_quads2(const std::vector<BlockDesc2>& blocks, const std::vector<i
         }
         quads.push_back(q);
     }
-    // side of lane row g, and the block holding half-side (g, half)
+    // appends descriptor, row and companion row of a quad / pair based at block b0 whose half-side (g, half) -- lane row g =
+    // 0..3 = sides left, bottom, top, right -- is held by block bi[g][half]
     static const int side_of_g[4] = {0, 2, 3, 1};
-    static const int blk_of[4][2] = {{0, 2}, {0, 1}, {2, 3}, {1, 3}};
+    auto add_tile = [&](const BlockDesc2& b0, const int32_t (&bi)[4][2], std::vector<QuadDesc2>& qd, std::vector<int32_t>& tab,
+                        std::vector<int32_t>& aux) {
+        QuadDesc2 d = {b0.base, 0, {b0.rh[0], b0.rh[1]}};
+        const size_t row = tab.size();
+        tab.resize(row + IBH_QROW);
+        for (int g = 0; g < 4; ++g)
+            for (int half = 0; half < 2; ++half) {
+                const int s = side_of_g[g], l = 2 * g + half;
+                const size_t b = (size_t)bi[g][half];
+                d.cls |= (uint32_t)blocks[b].type[s] << (4 * l);
+                for (int t = 0; t < 8; ++t)
+                    for (int k = 0; k < 2; ++k) tab[row + 2 * (16 * g + 8 * half + t) + k] = htab[b * 64 + (s * 8 + t) * 2 + k];
+                for (int e = 0; e < 4; ++e) tab[row + 128 + 4 * l + e] = etab[b * 16 + s * 4 + e];
+            }
+        qd.push_back(d);
+        quad_aux_row(tab.data() + row, d.cls, aux);
+    };
     for (int pass = 0; pass < 2; ++pass)
         for (const Q& q : quads) {
             if (q.interior != (pass == 0)) continue;
-            QuadDesc2 d;
-            d.base = blocks[q.b[0]].base;
-            d.rh[0] = blocks[q.b[0]].rh[0];
-            d.rh[1] = blocks[q.b[0]].rh[1];
-            d.cls = 0;
-            const size_t row = out.qtab.size();
-            out.qtab.resize(row + IBH_QROW);
-            for (int g = 0; g < 4; ++g)
-                for (int half = 0; half < 2; ++half) {
-                    const int s = side_of_g[g], l = 2 * g + half;
-                    const int32_t bi = q.b[blk_of[g][half]];
-                    d.cls |= (uint32_t)blocks[bi].type[s] << (4 * l);
-                    for (int t = 0; t < 8; ++t)
-                        for (int k = 0; k < 2; ++k)
-                            out.qtab[row + 2 * (16 * g + 8 * half + t) + k] = htab[(size_t)bi * 64 + (s * 8 + t) * 2 + k];
-                    for (int e = 0; e < 4; ++e) out.qtab[row + 128 + 4 * l + e] = etab[(size_t)bi * 16 + s * 4 + e];
-                }
-            out.qd.push_back(d);
-            quad_aux_row(out.qtab.data() + row, d.cls, out.qaux);
+            const int32_t bi[4][2] = {{q.b[0], q.b[2]}, {q.b[0], q.b[1]}, {q.b[2], q.b[3]}, {q.b[1], q.b[3]}};
+            add_tile(blocks[q.b[0]], bi, out.qd, out.qtab, out.qaux);
             if (pass == 0) out.nq_int++;
         }
     for (int pass = 0; pass < 2; ++pass)
@@ -493,18 +488,6 @@ void ibh_build_quads2(const std::vector<BlockDesc2>& blocks, const std::vector<i
         return;
     }
     std::vector<char> paired(nb, 0);
-    auto side_ok = [&](int32_t bi, int s) {
-        const BlockDesc2& b = blocks[bi];
-        const int ty = b.type[s];
-        bool ok = ty == SIDE_SAME || ty == SIDE_COARSE || ty == SIDE_FINE;
-        if (ok && s >= 2)
-            for (int t = 0; t < 8 && ok; ++t) {
-                const int32_t h0 = htab[(size_t)bi * 64 + (s * 8 + t) * 2], h1 = htab[(size_t)bi * 64 + (s * 8 + t) * 2 + 1];
-                const int32_t dl = s == 2 ? -8 : 8;
-                ok = h0 + 1 < nc && h0 + dl >= 0 && h0 + dl + 1 < nc && (ty != SIDE_FINE || h1 == h0 + 1);
-            }
-        return ok;
-    };
     for (int32_t o : order) {
         if (used[o] || paired[o] || !cand[o]) continue;
         const BlockDesc2& b0 = blocks[o];
@@ -518,29 +501,137 @@ void ibh_build_quads2(const std::vector<BlockDesc2>& blocks, const std::vector<i
         ok = ok && side_ok(o, 0) && side_ok(o, 2) && side_ok(o, 3) && side_ok(i1, 1) && side_ok(i1, 2) && side_ok(i1, 3);
         if (!ok) continue;
         paired[o] = paired[i1] = 1;
-        // lane rows g = 0..3 = sides left, bottom, top, right; half-sides (g, half): the block that holds them, or the
-        // half-side they repeat where a pair has none (left / right upper halves)
-        const int32_t blk_of_pair[4][2] = {{o, o}, {o, i1}, {o, i1}, {i1, i1}};
-        QuadDesc2 d;
-        d.base = b0.base;
-        d.rh[0] = b0.rh[0];
-        d.rh[1] = b0.rh[1];
-        d.cls = 0;
-        const size_t row = out.ptab.size();
-        out.ptab.resize(row + IBH_QROW);
-        for (int g = 0; g < 4; ++g)
-            for (int half = 0; half < 2; ++half) {
-                const int s = side_of_g[g], l = 2 * g + half;
-                const int32_t bi = blk_of_pair[g][half];
-                d.cls |= (uint32_t)blocks[bi].type[s] << (4 * l);
-                for (int t = 0; t < 8; ++t)
-                    for (int k = 0; k < 2; ++k)
-                        out.ptab[row + 2 * (16 * g + 8 * half + t) + k] = htab[(size_t)bi * 64 + (s * 8 + t) * 2 + k];
-                for (int e = 0; e < 4; ++e) out.ptab[row + 128 + 4 * l + e] = etab[(size_t)bi * 16 + s * 4 + e];
-            }
-        out.pd.push_back(d);
-        quad_aux_row(out.ptab.data() + row, d.cls, out.paux);
+        // the half-sides a pair has none of (left / right upper halves) repeat the lower one
+        const int32_t bi[4][2] = {{o, o}, {o, i1}, {o, i1}, {i1, i1}};
+        add_tile(b0, bi, out.pd, out.ptab, out.paux);
     }
     for (int32_t b : out.singles)
         if (!paired[b]) out.singles2.push_back(b);
+}
+
+// Row sweep (ibh_rows2d.h): its halo cell ids are arithmetic on the neighbour block bases.  Taken only where that
+// arithmetic -- restated here -- reproduces the halo table (which was read off the registered faces) for every slot
+// of every block, every neighbour block is complete, and no block takes its deeper cells from a table.
+static bool rows_reproduce_htab(const Host2D& H) {
+    if (!H.fuse_all || !H.dtab.empty()) return false;
+    for (size_t b = 0; b < H.blocks.size(); ++b) {
+        const BlockDesc2& B = H.blocks[b];
+        for (int s = 0; s < 4; ++s) {
+            const int d = s >> 1, sd = d == 0 ? 1 : 8, st = d == 0 ? 8 : 1;
+            const bool low = (s & 1) == 0;
+            const int opp = low ? 7 * sd : 0, own = low ? 0 : 7 * sd;
+            const int ty = B.type[s];
+            if (ty == SIDE_GENERAL) return false;
+            if (ty != SIDE_MIRROR && (B.nb[s][0] < 0 || (ty == SIDE_FINE && B.nb[s][1] < 0))) return false;
+            for (int t = 0; t < 8; ++t)
+                for (int k = 0; k < 2; ++k) {
+                    const int tt = ty == SIDE_COARSE ? (t >> 1) + 4 * B.sub[s] : ty == SIDE_FINE ? 2 * (t & 3) + k : t;
+                    const int32_t nbb = (ty == SIDE_FINE && (t >> 2)) ? B.nb[s][1] : B.nb[s][0];
+                    const int32_t id = ty == SIDE_MIRROR ? B.base + own + t * st : nbb + opp + tt * st;
+                    if (id != H.htab[b * 64 + (s * 8 + t) * 2 + k]) return false;
+                }
+        }
+    }
+    return true;
+}
+
+void ibh_analyze2(const HostPartView& v, const int32_t* image_in_domain, int32_t n_image, Host2D& H) {
+    const int32_t nc = v.nc;
+    const bool have_img = n_image > 0 && image_in_domain;
+    ibh_analyze_blocks2(v, image_in_domain, have_img ? n_image : 0, H);
+    const int32_t nb = (int32_t)H.blocks.size();
+    H.fuse_all = nb > 0 && H.irr.empty() && H.nfus == nb;
+    std::vector<char> is_imgblk(nb, 0);
+    if (have_img) {  // image blocks: eligible, all of them?
+        std::vector<char> is_img(nc, 0);
+        for (int32_t k = 0; k < n_image; ++k) is_img[image_in_domain[k] - v.index_base] = 1;
+        bool all = true;
+        for (int32_t b = 0; b < nb; ++b)
+            if (is_img[H.blocks[b].base]) {
+                H.img.push_back(b);
+                is_imgblk[b] = 1;
+                H.n_img_int += b < H.nph[1];
+                all = all && H.fus[b];
+            }
+        H.img_all_fz = all && (int64_t)H.img.size() * 64 == (int64_t)n_image;
+    }
+    if (!H.fuse_all && H.nfus > 0)  // the lists of the mixed launches
+        for (int32_t b = 0; b < nb; ++b) {
+            if (H.fus[b]) { H.fz.push_back(b); H.n_fz_int += b < H.nph[1]; }
+            else { H.nf.push_back(b); H.n_nf_int += b < H.nph[1]; }
+            if (H.needg[b]) { H.ng.push_back(b); H.n_ng_int += b < H.nph[0]; }
+        }
+    if (H.fuse_all) ibh_build_quads2(H.blocks, H.htab, H.etab, H.fus, H.nph[1], H.quads[0], nc);
+    H.rows_ok = rows_reproduce_htab(H);
+    if (H.img_all_fz && !H.fuse_all) ibh_build_quads2(H.blocks, H.htab, H.etab, is_imgblk, H.nph[1], H.quads[1], nc);
+
+    PartSummary& S = H.sum;  // (sides: ibh_analyze_blocks2)
+    S.full_blocks = nb;
+    S.irregular_cells = (int64_t)H.irr.size();
+    S.interior_blocks = H.nph[1];
+    S.fusable_blocks = H.nfus;
+    S.workspace_blocks = H.fuse_all ? 0 : (int64_t)H.ng.size();
+    S.image_all_eligible = H.img_all_fz;
+    S.image_blocks = (int64_t)H.img.size();
+    S.quads_or_rim4_rows = (int64_t)H.quads[0].qd.size();
+    S.quad_singles = (int64_t)H.quads[0].singles.size();
+    S.image_quads = (int64_t)H.quads[1].qd.size();
+    S.image_quad_singles = (int64_t)H.quads[1].singles.size();
+    S.row_sweep = H.rows_ok;
+    S.quad_pairs = (int64_t)H.quads[0].pd.size();
+    const std::vector<int32_t>& qaux = H.quads[0].qaux;  // half-sides of the quads whose halo ids are arithmetic
+    for (size_t i = 0; i < qaux.size(); i += IBH_QAUX)
+        for (int l = 0; l < 8; ++l) S.quad_arith_half_sides += qaux[i + 32 + l] >= 0;
+    S.tiled = ibh_tiled(H.blocks, 64, H.irr.size(), nc);
+}
+
+// ---- shared between the dimensions: functions of the view alone
+std::vector<int32_t> ibh_side_table(const HostPartView& v, int64_t* direct) {
+    const int32_t nc = v.nc;
+    std::vector<int32_t> side((size_t)2 * v.nd * nc);
+    *direct = 0;
+    for (int d = 0; d < v.nd; ++d)
+        for (int s = 0; s < 2; ++s) {
+            const std::vector<int32_t>& off = s ? v.roff[d] : v.loff[d];
+            const std::vector<int32_t>& idx = s ? v.ridx[d] : v.lidx[d];
+            int32_t* T = side.data() + (size_t)(2 * d + s) * nc;
+            for (int32_t c = 0; c < nc; ++c) {
+                const int32_t b = off[c], e = off[c + 1];
+                int32_t t = -1;
+                if (e == b) t = -2;
+                else if (e == b + 1) {
+                    const int32_t f = idx[b];
+                    const int32_t o = v.owners[d][f], n = v.neighbors[d][f];
+                    if (s ? (o == c) : (n == c)) t = s ? n : o;      // right faces: c owns; left faces: c is the neighbour
+                }
+                T[c] = t;
+                *direct += t >= 0;
+            }
+        }
+    return side;
+}
+
+std::vector<int32_t> ibh_irr_records(const HostPartView& v, const std::vector<int32_t>& irr) {
+    const size_t n = irr.size();
+    std::vector<int32_t> rec((size_t)v.nd * 2 * 5 * n, 0);
+    for (size_t t = 0; t < n; ++t) {
+        const int32_t cc = irr[t];
+        for (int d = 0; d < v.nd; ++d)
+            for (int side = 0; side < 2; ++side) {
+                const std::vector<int32_t>& off = side ? v.roff[d] : v.loff[d];
+                const std::vector<int32_t>& idx = side ? v.ridx[d] : v.lidx[d];
+                const int cnt = off[cc + 1] - off[cc];
+                if (cnt > 4) return {};
+                const size_t q = (size_t)(2 * d + side);
+                rec[(q * 5) * n + t] = cnt;
+                for (int k = 0; k < cnt; ++k) {
+                    const int32_t f = idx[off[cc] + k];
+                    const int32_t o = v.owners[d][f], nn = v.neighbors[d][f];
+                    // left face: this cell is the neighbour, the other cell is the owner (and vice versa)
+                    if ((side ? o : nn) != cc) return {};
+                    rec[(q * 5 + 1 + k) * n + t] = side ? nn : o;
+                }
+            }
+    }
+    return rec;
 }

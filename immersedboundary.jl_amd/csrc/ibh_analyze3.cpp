@@ -5,28 +5,11 @@
 
 #include "ibh_common.h"
 
-namespace {
+using namespace blk3pos;
 
-constexpr int NPB = 512;
-const int STR[3] = {1, 8, 64};
-
-// tangential dims of dim d, increasing
-inline void tang(int d, int& a, int& b) {
-    a = d == 0 ? 1 : 0;
-    b = d == 2 ? 1 : 2;
-}
-inline int pos3(int d, int n, int t1, int t2) {
-    int a, b;
-    tang(d, a, b);
-    return n * STR[d] + t1 * STR[a] + t2 * STR[b];
-}
-inline int coord(int pos, int d) { return (pos / STR[d]) % 8; }
-
-}  // namespace
-
-void ibh_analyze_blocks3(const HostPartView& v, std::vector<BlockDesc3>& blocks, std::vector<int32_t>& irr,
-                         int64_t* info, const int32_t* image_in_domain, int32_t n_image, int32_t* n_phase1,
-                         std::vector<int32_t>& htab, std::vector<int32_t>& ftab, Sweep3Host* sw) {
+static void ibh_analyze_blocks3(const HostPartView& v, const int32_t* image_in_domain, int32_t n_image, Host3D& H) {
+    std::vector<BlockDesc3>& blocks = H.blocks;
+    std::vector<int32_t>&irr = H.irr, &htab = H.htab, &ftab = H.ftab;
     const int32_t nc = v.nc;
     const float* hh[3] = {v.spacing, v.spacing + nc, v.spacing + 2 * (size_t)nc};
     auto gid = [&](int32_t c) { return (int64_t)v.domain[c] - v.index_base; };
@@ -55,7 +38,6 @@ void ibh_analyze_blocks3(const HostPartView& v, std::vector<BlockDesc3>& blocks,
     };
     std::vector<char> cell_irr(nc, 0);
     for (int32_t c = 0; c < nc; ++c) cell_irr[c] = !in_full[c];
-    int64_t counts[5] = {0, 0, 0, 0, 0};
     std::vector<int32_t> fine0;        // sub-face-0 cells of FINE sides, 64 per entry of fine0_key
     std::vector<int64_t> fine0_key;    // (block base << 3) | side
     std::unordered_map<int64_t, std::vector<int32_t>> fine_nb;  // same key -> bases of the 4 fine neighbour blocks
@@ -173,7 +155,7 @@ void ibh_analyze_blocks3(const HostPartView& v, std::vector<BlockDesc3>& blocks,
                 for (int t = 0; t < 64; t += 4)  // one boundary cell of every 4x4 quadrant (t1 = 0 or 4, t2 = 0 or 4)
                     if ((t % 8) % 4 == 0 && (t / 8) % 4 == 0) nbs.push_back(blockbase[gid(fcell[s][t][0]) / NPB]);
             }
-            counts[type]++;
+            H.sum.sides[type]++;
             if (type == SIDE_GENERAL)
                 for (int t = 0; t < 64; ++t) cell_irr[base + pos3(d, low ? 0 : 7, t % 8, t / 8)] = 1;
         }
@@ -183,7 +165,7 @@ void ibh_analyze_blocks3(const HostPartView& v, std::vector<BlockDesc3>& blocks,
         if (cell_irr[c]) irr.push_back(c);
 
     // overlap phases, as in 2-D
-    n_phase1[0] = n_phase1[1] = 0;
+    H.nph[0] = H.nph[1] = 0;
     {
         std::vector<char> is_image(nc, 0), dep(nc, 0);
         for (int32_t k = 0; k < n_image; ++k) is_image[image_in_domain[k] - v.index_base] = 1;
@@ -223,9 +205,9 @@ void ibh_analyze_blocks3(const HostPartView& v, std::vector<BlockDesc3>& blocks,
         std::vector<BlockDesc3> ordered;
         ordered.reserve(blocks.size());
         for (size_t b = 0; b < blocks.size(); ++b) if (b1[b]) ordered.push_back(blocks[b]);
-        n_phase1[1] = (int32_t)ordered.size();
+        H.nph[1] = (int32_t)ordered.size();
         for (size_t b = 0; b < blocks.size(); ++b) if (a1[b] && !b1[b]) ordered.push_back(blocks[b]);
-        n_phase1[0] = (int32_t)ordered.size();
+        H.nph[0] = (int32_t)ordered.size();
         for (size_t b = 0; b < blocks.size(); ++b) if (!a1[b]) ordered.push_back(blocks[b]);
         blocks.swap(ordered);
     }
@@ -258,14 +240,14 @@ void ibh_analyze_blocks3(const HostPartView& v, std::vector<BlockDesc3>& blocks,
     // 16 (FINE: the rims of the 16 x 16 patch of fine halo cells); >= 0: a cell (the halo cell itself at the domain
     // boundary), < 0: -(k + 1) = row k of r4tab, the four finer cells beyond.  The sweep is used when EVERY block
     // qualifies (sides SAME / COARSE / FINE / MIRROR towards verified full blocks, rim neighbours 1 or 4 cells).
-    if (sw) {
+    {
         std::unordered_map<int32_t, int32_t> base2bi;
         for (size_t bi = 0; bi < blocks.size(); ++bi) base2bi[blocks[bi].base] = (int32_t)bi;
         bool all = irr.empty() && !blocks.empty();
-        sw->rtab.assign(blocks.size() * 384, 0);
+        H.sw.rtab.assign(blocks.size() * 384, 0);
         for (size_t bi = 0; bi < blocks.size() && all; ++bi) {
             const BlockDesc3& b = blocks[bi];
-            int32_t* row = sw->rtab.data() + bi * 384;
+            int32_t* row = H.sw.rtab.data() + bi * 384;
             for (int s = 0; s < 6 && all; ++s) {
                 const int ty = b.type[s];
                 const int d = s / 2;
@@ -308,21 +290,39 @@ void ibh_analyze_blocks3(const HostPartView& v, std::vector<BlockDesc3>& blocks,
                         if (cnt == 1) {
                             row[s * 64 + r * n + i] = o4[0];  // o == h: domain boundary, the difference is zero
                         } else {
-                            row[s * 64 + r * n + i] = -(int32_t)(sw->r4tab.size() / 4 + 1);
-                            sw->r4tab.insert(sw->r4tab.end(), o4, o4 + 4);
+                            row[s * 64 + r * n + i] = -(int32_t)(H.sw.r4tab.size() / 4 + 1);
+                            H.sw.r4tab.insert(H.sw.r4tab.end(), o4, o4 + 4);
                         }
                     }
                 }
             }
         }
-        sw->all = all;
+        H.sw.all = all;
         if (!all) {
-            sw->rtab.clear();
-            sw->r4tab.clear();
+            H.sw.rtab.clear();
+            H.sw.r4tab.clear();
         }
     }
-    info[0] = (int64_t)blocks.size();
-    info[1] = (int64_t)irr.size();
-    for (int k = 0; k < 5; ++k) info[2 + k] = counts[k];
-    info[7] = n_phase1[1];
+}
+
+void ibh_analyze3(const HostPartView& v, const int32_t* image_in_domain, int32_t n_image, Host3D& H) {
+    const bool have_img = n_image > 0 && image_in_domain;
+    ibh_analyze_blocks3(v, image_in_domain, have_img ? n_image : 0, H);
+    // a partition with skirt fragments: the image blocks for the image-only sweeps
+    if (have_img && !H.sw.all) ibh_analyze_image3(v, image_in_domain, n_image, H.im);
+    const int64_t nb = (int64_t)H.blocks.size();
+    PartSummary& S = H.sum;  // (sides: ibh_analyze_blocks3)
+    S.full_blocks = nb;
+    S.irregular_cells = (int64_t)H.irr.size();
+    S.interior_blocks = H.nph[1];
+    S.fusable_blocks = H.sw.all ? nb : 0;    // blocks of the single-kernel sweep
+    S.workspace_blocks = H.sw.all ? 0 : nb;  // blocks whose gradients go through the workspace
+    S.image_all_eligible = H.im.all || H.sw.all;
+    S.image_blocks = H.im.all ? (int64_t)H.im.blocks.size() : (H.sw.all ? nb : 0);
+    S.quads_or_rim4_rows = (int64_t)(H.sw.r4tab.size() / 4);
+    S.tiled = ibh_tiled(H.blocks, 512, H.irr.size(), v.nc);
+    // an empty r4tab / ftab goes up as one placeholder row of four ints, so that its device pointer is never null
+    if (H.sw.r4tab.empty()) H.sw.r4tab.assign(4, 0);
+    if (H.im.all && H.im.r4tab.empty()) H.im.r4tab.assign(4, 0);
+    if (H.im.all && H.im.ftab.empty()) H.im.ftab.assign(4, 0);
 }

@@ -13,22 +13,7 @@
 
 #include "ibh_common.h"
 
-namespace {
-
-constexpr int NPB = 512;
-const int STR[3] = {1, 8, 64};
-inline void tang(int d, int& a, int& b) {
-    a = d == 0 ? 1 : 0;
-    b = d == 2 ? 1 : 2;
-}
-inline int pos3(int d, int n, int t1, int t2) {
-    int a, b;
-    tang(d, a, b);
-    return n * STR[d] + t1 * STR[a] + t2 * STR[b];
-}
-inline int coord(int pos, int d) { return (pos / STR[d]) % 8; }
-
-}  // namespace
+using namespace blk3pos;
 
 void ibh_analyze_image3(const HostPartView& v, const int32_t* image_in_domain, int32_t n_image, Image3Host& out) {
     out = Image3Host();

@@ -19,81 +19,7 @@ static std::vector<int32_t> rebased(const int32_t* p, size_t n, int base) {
     return v;
 }
 
-// Host-only part of ibh_partition_create for 2-D partitions: block analysis, launch lists, quads.  No HIP call in
-// here, so the CPU tests can run it through ibh_analyze2_host().
-struct Host2D {
-    std::vector<BlockDesc2> blocks;
-    std::vector<int32_t> irr, htab, etab, dtab, img, fz, ng, nf;
-    std::vector<char> fus, needg;
-    int32_t nph[2] = {0, 0};
-    int32_t n_img_int = 0, img_all_fz = 0, fuse_all = 0, rows_ok = 0, n_fz_int = 0, n_ng_int = 0, n_nf_int = 0;
-    int64_t info[12] = {0};
-    QuadSet2 quads[2];  // 0: all blocks (fuse_all partitions), 1: image blocks (img_all_fz partitions)
-};
-struct ibh_host2d {
-    Host2D H;
-};
-
-static void analyze2_host(const HostPartView& v, int32_t n_image, const int32_t* image_in_domain, int index_base,
-                          Host2D& H) {
-    const int32_t nc = v.nc;
-    const bool have_img = n_image > 0 && image_in_domain;
-    std::vector<int32_t> none;
-    ibh_analyze_blocks2(v, H.blocks, H.irr, H.info, have_img ? image_in_domain : none.data(), have_img ? n_image : 0,
-                        H.nph, H.htab, H.etab, H.fus, H.needg, H.dtab);
-    const int32_t nb = (int32_t)H.blocks.size();
-    H.fuse_all = nb > 0 && H.irr.empty() && H.info[8] == (int64_t)nb;
-    std::vector<char> is_imgblk(nb, 0);
-    if (have_img) {  // image blocks: eligible, all of them?
-        std::vector<char> is_img(nc, 0);
-        for (int32_t k = 0; k < n_image; ++k) is_img[image_in_domain[k] - index_base] = 1;
-        bool all = true;
-        for (int32_t b = 0; b < nb; ++b)
-            if (is_img[H.blocks[b].base]) {
-                H.img.push_back(b);
-                is_imgblk[b] = 1;
-                H.n_img_int += b < H.nph[1];
-                all = all && H.fus[b];
-            }
-        H.img_all_fz = all && (int64_t)H.img.size() * 64 == (int64_t)n_image;
-        H.info[10] = H.img_all_fz;
-        H.info[11] = (int64_t)H.img.size();
-    }
-    if (!H.fuse_all && H.info[8] > 0)
-        for (int32_t b = 0; b < nb; ++b) {
-            if (H.fus[b]) { H.fz.push_back(b); H.n_fz_int += b < H.nph[1]; }
-            else { H.nf.push_back(b); H.n_nf_int += b < H.nph[1]; }
-            if (H.needg[b]) { H.ng.push_back(b); H.n_ng_int += b < H.nph[0]; }
-        }
-    H.info[9] = H.fuse_all ? 0 : (int64_t)H.ng.size();
-    if (H.fuse_all) ibh_build_quads2(H.blocks, H.htab, H.etab, H.fus, H.nph[1], H.quads[0], nc);
-    // Row sweep (ibh_rows2d.h): its halo cell ids are arithmetic on the neighbour block bases.  Taken only where that
-    // arithmetic -- restated here -- reproduces the halo table (which was read off the registered faces) for every slot
-    // of every block, every neighbour block is complete, and no block takes its deeper cells from a table.
-    if (H.fuse_all && H.dtab.empty()) {
-        bool ok = true;
-        for (int32_t b = 0; b < nb && ok; ++b) {
-            const BlockDesc2& B = H.blocks[b];
-            for (int s = 0; s < 4 && ok; ++s) {
-                const int d = s >> 1, sd = d == 0 ? 1 : 8, st = d == 0 ? 8 : 1;
-                const bool low = (s & 1) == 0;
-                const int opp = low ? 7 * sd : 0, own = low ? 0 : 7 * sd;
-                const int ty = B.type[s];
-                if (ty == SIDE_GENERAL) { ok = false; break; }
-                if (ty != SIDE_MIRROR && (B.nb[s][0] < 0 || (ty == SIDE_FINE && B.nb[s][1] < 0))) { ok = false; break; }
-                for (int t = 0; t < 8 && ok; ++t)
-                    for (int k = 0; k < 2; ++k) {
-                        const int tt = ty == SIDE_COARSE ? (t >> 1) + 4 * B.sub[s] : ty == SIDE_FINE ? 2 * (t & 3) + k : t;
-                        const int32_t nbb = (ty == SIDE_FINE && (t >> 2)) ? B.nb[s][1] : B.nb[s][0];
-                        const int32_t id = ty == SIDE_MIRROR ? B.base + own + t * st : nbb + opp + tt * st;
-                        if (id != H.htab[(size_t)b * 64 + (s * 8 + t) * 2 + k]) { ok = false; break; }
-                    }
-            }
-        }
-        H.rows_ok = ok;
-    }
-    if (H.img_all_fz && !H.fuse_all) ibh_build_quads2(H.blocks, H.htab, H.etab, is_imgblk, H.nph[1], H.quads[1], nc);
-}
+struct ibh_host2d : Host2D {};
 
 static int make_view(HostPartView& v, int nd, int32_t nc, const float* spacing, const int32_t* nf,
                      const int32_t* const* owners, const int32_t* const* neighbors, const int32_t* const* left_off,
@@ -128,6 +54,119 @@ static int make_view(HostPartView& v, int nd, int32_t nc, const float* spacing, 
         for (int32_t x : v.lidx[d]) IBH_REQUIRE(x >= 0 && x < nf[d], "ibh_partition_create: left face id out of range");
         for (int32_t x : v.ridx[d]) IBH_REQUIRE(x >= 0 && x < nf[d], "ibh_partition_create: right face id out of range");
     }
+    return 0;
+}
+
+// ---- the uploads of ibh_partition_create, in its order
+static int upload_faces(ibh_part* p, const HostPartView& v, const float* spacing, const float* centers) {
+    IBH_TRY(p->own.upload(&p->spacing, spacing, (size_t)v.nc * v.nd));
+    if (centers) IBH_TRY(p->own.upload(&p->centers, centers, (size_t)v.nc * v.nd));
+    for (int d = 0; d < v.nd; ++d) {
+        DimData& D = p->dim[d];
+        D.nf = v.nf[d];
+        IBH_TRY(p->own.upload(&D.owners, v.owners[d]));
+        IBH_TRY(p->own.upload(&D.neighbors, v.neighbors[d]));
+        IBH_TRY(p->own.upload(&D.loff, v.loff[d]));
+        IBH_TRY(p->own.upload(&D.lidx, v.lidx[d]));
+        IBH_TRY(p->own.upload(&D.roff, v.roff[d]));
+        IBH_TRY(p->own.upload(&D.ridx, v.ridx[d]));
+    }
+    return 0;
+}
+
+static int upload_image_ids(ibh_part* p, int32_t n_image, const int32_t* image_in_domain, int index_base) {
+    p->n_image = n_image;
+    if (n_image > 0 && image_in_domain) {
+        std::vector<int32_t> iid = rebased(image_in_domain, n_image, index_base);
+        for (int32_t x : iid) IBH_REQUIRE(x >= 0 && x < p->nc, "ibh_partition_create: image_in_domain out of range");
+        IBH_TRY(p->own.upload(&p->image_in_domain, iid));
+    }
+    return 0;
+}
+
+template <class T>
+static std::vector<T> joined(std::vector<T> a, const std::vector<T>& b) {
+    a.insert(a.end(), b.begin(), b.end());
+    return a;
+}
+// quad set k; the pair tiles of set 0 go behind the quads, in the same arrays (the kernel tells them apart by index)
+static int upload_quads2(ibh_part* p, int k, const QuadSet2& Q) {
+    p->nq[k] = (int32_t)Q.qd.size();
+    p->nq_int[k] = Q.nq_int;
+    p->nqs[k] = (int32_t)Q.singles.size();
+    p->nqs_int[k] = Q.ns_int;
+    if (k == 0 && !Q.pd.empty()) {
+        p->npair = (int32_t)Q.pd.size();
+        p->nqs2 = (int32_t)Q.singles2.size();
+        IBH_TRY(p->own.upload(&p->qd[k], joined(Q.qd, Q.pd)));
+        IBH_TRY(p->own.upload(&p->qtab[k], joined(Q.qtab, Q.ptab)));
+        IBH_TRY(p->own.upload(&p->qsingles2, Q.singles2));
+        IBH_TRY(p->own.upload(&p->qaux[k], joined(Q.qaux, Q.paux)));
+    } else {
+        IBH_TRY(p->own.upload(&p->qd[k], Q.qd));
+        IBH_TRY(p->own.upload(&p->qtab[k], Q.qtab));
+        IBH_TRY(p->own.upload(&p->qaux[k], Q.qaux));
+    }
+    return p->own.upload(&p->qsingles[k], Q.singles);
+}
+
+static int upload2(ibh_part* p, const Host2D& H) {
+    IBH_TRY(p->own.upload(&p->htab, H.htab));
+    IBH_TRY(p->own.upload(&p->etab, H.etab));
+    IBH_TRY(p->own.upload(&p->dtab, H.dtab));
+    p->n_dt = (int32_t)(H.dtab.size() / 64);
+    p->fuse_all = H.fuse_all;
+    p->rows_ok = H.rows_ok;
+    p->n_img = (int32_t)H.img.size();
+    p->n_img_int = H.n_img_int;
+    p->img_all_fz = H.img_all_fz;
+    if (p->img_all_fz) IBH_TRY(p->own.upload(&p->img_list, H.img));
+    if (!H.fuse_all && H.nfus > 0) {
+        p->n_fz = (int32_t)H.fz.size();
+        p->n_ng = (int32_t)H.ng.size();
+        p->n_nf = (int32_t)H.nf.size();
+        p->n_fz_int = H.n_fz_int;
+        p->n_ng_int = H.n_ng_int;
+        p->n_nf_int = H.n_nf_int;
+        IBH_TRY(p->own.upload(&p->fz_list, H.fz));
+        IBH_TRY(p->own.upload(&p->ng_list, H.ng));
+        IBH_TRY(p->own.upload(&p->nf_list, H.nf));
+    }
+    for (int k = 0; k < 2; ++k) IBH_TRY(upload_quads2(p, k, H.quads[k]));
+    return p->own.upload(&p->blocks2, H.blocks);
+}
+
+static int upload3(ibh_part* p, const Host3D& H) {
+    p->sweep3 = H.sw.all ? 1 : 0;
+    IBH_TRY(p->own.upload(&p->rtab3, H.sw.rtab));
+    IBH_TRY(p->own.upload(&p->r4tab3, H.sw.r4tab));
+    IBH_TRY(p->own.upload(&p->ftab3, H.ftab));
+    IBH_TRY(p->own.upload(&p->blocks3, H.blocks));
+    IBH_TRY(p->own.upload(&p->htab3, H.htab));
+    if (H.im.all) {
+        IBH_TRY(p->own.upload(&p->iblocks3, H.im.blocks));
+        IBH_TRY(p->own.upload(&p->ihtab3, H.im.htab));
+        IBH_TRY(p->own.upload(&p->iftab3, H.im.ftab));
+        IBH_TRY(p->own.upload(&p->irtab3, H.im.rtab));
+        IBH_TRY(p->own.upload(&p->ir4tab3, H.im.r4tab));
+        IBH_TRY(p->own.upload(&p->idtab3, H.im.dtab));
+        p->n_img3 = (int32_t)H.im.blocks.size();
+        p->img_all3 = 1;
+    }
+    return 0;
+}
+
+// what Host = Host2D and Host3D share: the block counts, the face-list cells with their stencil records, the summary
+template <class Host>
+static int upload_common(ibh_part* p, const HostPartView& v, const Host& H) {
+    p->nA1 = H.nph[0];
+    p->nB1 = H.nph[1];
+    p->bs = v.bs;
+    p->nblk = (int32_t)H.blocks.size();
+    p->n_irr = (int32_t)H.irr.size();
+    IBH_TRY(p->own.upload(&p->irr_cells, H.irr));
+    IBH_TRY(p->own.upload(&p->irr_rec, ibh_irr_records(v, H.irr)));
+    p->sum = H.sum;
     return 0;
 }
 
@@ -185,7 +224,6 @@ int ibh_memset(void* dst, int value, size_t bytes) {
     return 0;
 }
 
-
 int ibh_partition_create(ibh_part** out, int nd, int32_t nc, const float* spacing, const float* centers,
                          const int32_t* nf, const int32_t* const* owners, const int32_t* const* neighbors,
                          const int32_t* const* left_off, const int32_t* const* left_idx,
@@ -202,204 +240,25 @@ int ibh_partition_create(ibh_part** out, int nd, int32_t nc, const float* spacin
     std::unique_ptr<ibh_part> p(new ibh_part());   // freed with all its buffers by any return before the release
     p->nd = nd;
     p->nc = nc;
-    IBH_TRY(p->own.upload(&p->spacing, spacing, (size_t)nc * nd));
-    if (centers) IBH_TRY(p->own.upload(&p->centers, centers, (size_t)nc * nd));
-    for (int d = 0; d < nd; ++d) {
-        DimData& D = p->dim[d];
-        D.nf = nf[d];
-        IBH_TRY(p->own.upload(&D.owners, v.owners[d]));
-        IBH_TRY(p->own.upload(&D.neighbors, v.neighbors[d]));
-        IBH_TRY(p->own.upload(&D.loff, v.loff[d]));
-        IBH_TRY(p->own.upload(&D.lidx, v.lidx[d]));
-        IBH_TRY(p->own.upload(&D.roff, v.roff[d]));
-        IBH_TRY(p->own.upload(&D.ridx, v.ridx[d]));
-    }
-    {
-        std::vector<int32_t> side((size_t)2 * nd * nc);
-        int64_t direct = 0;
-        for (int d = 0; d < nd; ++d)
-            for (int s = 0; s < 2; ++s) {
-                const std::vector<int32_t>& off = s ? v.roff[d] : v.loff[d];
-                const std::vector<int32_t>& idx = s ? v.ridx[d] : v.lidx[d];
-                int32_t* T = side.data() + (size_t)(2 * d + s) * nc;
-                for (int32_t c = 0; c < nc; ++c) {
-                    const int32_t b = off[c], e = off[c + 1];
-                    int32_t t = -1;
-                    if (e == b) t = -2;
-                    else if (e == b + 1) {
-                        const int32_t f = idx[b];
-                        const int32_t o = v.owners[d][f], n = v.neighbors[d][f];
-                        if (s ? (o == c) : (n == c)) t = s ? n : o;      // right faces: c owns; left faces: c is the neighbour
-                    }
-                    T[c] = t;
-                    direct += t >= 0;
-                }
-            }
-        IBH_TRY(p->own.upload(&p->side, side));
-        p->info[17] = direct;
-    }
-    p->n_image = n_image;
-    if (n_image > 0 && image_in_domain) {
-        std::vector<int32_t> iid = rebased(image_in_domain, n_image, index_base);
-        for (int32_t x : iid) IBH_REQUIRE(x >= 0 && x < nc, "ibh_partition_create: image_in_domain out of range");
-        IBH_TRY(p->own.upload(&p->image_in_domain, iid));
-    }
-    p->bs = 0;
-    if (domain && block_size > 0 && nd == 2 && block_size == 8) {
+    IBH_TRY(upload_faces(p.get(), v, spacing, centers));
+    int64_t direct = 0;
+    IBH_TRY(p->own.upload(&p->side, ibh_side_table(v, &direct)));
+    IBH_TRY(upload_image_ids(p.get(), n_image, image_in_domain, index_base));
+    // analysis record -> upload -> summary; without block information every cell is a face-list cell
+    if (domain && block_size == 8 && nd == 2) {
         Host2D H;
-        analyze2_host(v, n_image, image_in_domain, index_base, H);
-        for (int i = 0; i < 12; ++i) p->info[i] = H.info[i];
-        IBH_TRY(p->own.upload(&p->htab, H.htab));
-        IBH_TRY(p->own.upload(&p->etab, H.etab));
-        IBH_TRY(p->own.upload(&p->dtab, H.dtab));
-        p->n_dt = (int32_t)(H.dtab.size() / 64);
-        p->fuse_all = H.fuse_all;
-        p->rows_ok = H.rows_ok;
-        p->info[16] = H.rows_ok;
-        p->n_img = (int32_t)H.img.size();
-        p->n_img_int = H.n_img_int;
-        p->img_all_fz = H.img_all_fz;
-        if (p->img_all_fz) IBH_TRY(p->own.upload(&p->img_list, H.img));
-        if (!p->fuse_all && H.info[8] > 0) {
-            p->n_fz = (int32_t)H.fz.size();
-            p->n_ng = (int32_t)H.ng.size();
-            p->n_nf = (int32_t)H.nf.size();
-            p->n_fz_int = H.n_fz_int;
-            p->n_ng_int = H.n_ng_int;
-            p->n_nf_int = H.n_nf_int;
-            IBH_TRY(p->own.upload(&p->fz_list, H.fz));
-            IBH_TRY(p->own.upload(&p->ng_list, H.ng));
-            IBH_TRY(p->own.upload(&p->nf_list, H.nf));
-        }
-        for (int k = 0; k < 2; ++k) {
-            const QuadSet2& Q = H.quads[k];
-            p->nq[k] = (int32_t)Q.qd.size();
-            p->nq_int[k] = Q.nq_int;
-            p->nqs[k] = (int32_t)Q.singles.size();
-            p->nqs_int[k] = Q.ns_int;
-            p->info[12 + 2 * k] = p->nq[k];
-            p->info[13 + 2 * k] = p->nqs[k];
-            if (k == 0 && !Q.pd.empty()) {
-                // pair tiles behind the quads, in the same arrays (the kernel tells them apart by index)
-                std::vector<QuadDesc2> qd(Q.qd);
-                qd.insert(qd.end(), Q.pd.begin(), Q.pd.end());
-                std::vector<int32_t> qt(Q.qtab);
-                qt.insert(qt.end(), Q.ptab.begin(), Q.ptab.end());
-                p->npair = (int32_t)Q.pd.size();
-                p->nqs2 = (int32_t)Q.singles2.size();
-                p->info[18] = p->npair;
-                IBH_TRY(p->own.upload(&p->qd[k], qd));
-                IBH_TRY(p->own.upload(&p->qtab[k], qt));
-                IBH_TRY(p->own.upload(&p->qsingles2, Q.singles2));
-                std::vector<int32_t> qa(Q.qaux);
-                qa.insert(qa.end(), Q.paux.begin(), Q.paux.end());
-                IBH_TRY(p->own.upload(&p->qaux[k], qa));
-            } else {
-                IBH_TRY(p->own.upload(&p->qd[k], Q.qd));
-                IBH_TRY(p->own.upload(&p->qtab[k], Q.qtab));
-                IBH_TRY(p->own.upload(&p->qaux[k], Q.qaux));
-            }
-            {
-                int64_t arith = 0;
-                for (size_t i = 0; i < Q.qaux.size(); i += IBH_QAUX)
-                    for (int l = 0; l < 8; ++l) arith += Q.qaux[i + 32 + l] >= 0;
-                if (k == 0) p->info[19] = arith;     // half-sides of the quads whose halo ids are arithmetic
-            }
-            IBH_TRY(p->own.upload(&p->qsingles[k], Q.singles));
-        }
-        p->nA1 = H.nph[0];
-        p->nB1 = H.nph[1];
-        p->bs = block_size;
-        p->nblk = (int32_t)H.blocks.size();
-        p->n_irr = (int32_t)H.irr.size();
-        {   // complete blocks in order: cell c lies in block c / 64 at position c % 64 (face-list kernels take in-block
-            // neighbours by index arithmetic then: k_timestep_advection<TILED>)
-            bool tiled = !H.blocks.empty() && H.irr.empty() && (int64_t)H.blocks.size() * 64 == (int64_t)nc;
-            for (size_t b = 0; tiled && b < H.blocks.size(); ++b) tiled = H.blocks[b].base == (int32_t)(64 * b);
-            p->info[20] = tiled ? 1 : 0;
-        }
-        IBH_TRY(p->own.upload(&p->blocks2, H.blocks));
-        IBH_TRY(p->own.upload(&p->irr_cells, H.irr));
-    } else if (domain && block_size == 8 && nd == 3) {
-        std::vector<BlockDesc3> blocks;
-        std::vector<int32_t> irr, htab, ftab;
-        int32_t nph[2] = {0, 0};
-        std::vector<int32_t> none;
-        const bool have_img = n_image > 0 && image_in_domain;
-        Sweep3Host sw;
-        ibh_analyze_blocks3(v, blocks, irr, p->info, have_img ? image_in_domain : none.data(), have_img ? n_image : 0,
-                            nph, htab, ftab, &sw);
-        p->sweep3 = sw.all ? 1 : 0;
-        p->info[8] = sw.all ? (int64_t)blocks.size() : 0;   // blocks of the single-kernel sweep
-        p->info[9] = sw.all ? 0 : (int64_t)blocks.size();   // blocks whose gradients go through the workspace
-        p->info[12] = (int64_t)(sw.r4tab.size() / 4);         // rim neighbours made of four finer cells
-        if (sw.r4tab.empty()) sw.r4tab.assign(4, 0);
-        IBH_TRY(p->own.upload(&p->rtab3, sw.rtab));
-        IBH_TRY(p->own.upload(&p->r4tab3, sw.r4tab));
-        IBH_TRY(p->own.upload(&p->ftab3, ftab));
-        p->nA1 = nph[0];
-        p->nB1 = nph[1];
-        p->bs = block_size;
-        p->nblk = (int32_t)blocks.size();
-        p->n_irr = (int32_t)irr.size();
-        {
-            bool tiled = !blocks.empty() && irr.empty() && (int64_t)blocks.size() * 512 == (int64_t)nc;
-            for (size_t b = 0; tiled && b < blocks.size(); ++b) tiled = blocks[b].base == (int32_t)(512 * b);
-            p->info[20] = tiled ? 1 : 0;
-        }
-        IBH_TRY(p->own.upload(&p->blocks3, blocks));
-        IBH_TRY(p->own.upload(&p->htab3, htab));
-        if (have_img && !sw.all) {   // a partition with skirt fragments: the image blocks for the image-only sweeps
-            Image3Host im;
-            ibh_analyze_image3(v, image_in_domain, n_image, im);
-            if (im.all) {
-                if (im.r4tab.empty()) im.r4tab.assign(4, 0);
-                if (im.ftab.empty()) im.ftab.assign(4, 0);
-                IBH_TRY(p->own.upload(&p->iblocks3, im.blocks));
-                IBH_TRY(p->own.upload(&p->ihtab3, im.htab));
-                IBH_TRY(p->own.upload(&p->iftab3, im.ftab));
-                IBH_TRY(p->own.upload(&p->irtab3, im.rtab));
-                IBH_TRY(p->own.upload(&p->ir4tab3, im.r4tab));
-                IBH_TRY(p->own.upload(&p->idtab3, im.dtab));
-                p->n_img3 = (int32_t)im.blocks.size();
-                p->img_all3 = 1;
-            }
-        }
-        p->info[10] = p->img_all3 || sw.all;       // image blocks all eligible for the single-kernel sweeps
-        p->info[11] = p->img_all3 ? p->n_img3 : (sw.all ? (int64_t)blocks.size() : 0);
-        IBH_TRY(p->own.upload(&p->irr_cells, irr));
+        ibh_analyze2(v, image_in_domain, n_image, H);
+        IBH_TRY(upload2(p.get(), H));
+        IBH_TRY(upload_common(p.get(), v, H));
+    } else if (domain && block_size == 8) {
+        Host3D H;
+        ibh_analyze3(v, image_in_domain, n_image, H);
+        IBH_TRY(upload3(p.get(), H));
+        IBH_TRY(upload_common(p.get(), v, H));
     } else {
-        p->info[0] = 0;
-        p->info[1] = nc;
+        p->sum.irregular_cells = nc;
     }
-    // flattened stencil records of the face-list cells
-    if (p->n_irr > 0) {
-        std::vector<int32_t> irr(p->n_irr);
-        IBH_HIP(hipMemcpy(irr.data(), p->irr_cells, sizeof(int32_t) * p->n_irr, hipMemcpyDeviceToHost));
-        const size_t n = (size_t)p->n_irr;
-        std::vector<int32_t> rec((size_t)nd * 2 * 5 * n, 0);
-        bool ok = true;
-        for (size_t t = 0; t < n && ok; ++t) {
-            const int32_t cc = irr[t];
-            for (int d = 0; d < nd && ok; ++d)
-                for (int side = 0; side < 2 && ok; ++side) {
-                    const std::vector<int32_t>& off = side ? v.roff[d] : v.loff[d];
-                    const std::vector<int32_t>& idx = side ? v.ridx[d] : v.lidx[d];
-                    const int cnt = off[cc + 1] - off[cc];
-                    if (cnt > 4) { ok = false; break; }
-                    const size_t q = (size_t)(2 * d + side);
-                    rec[(q * 5) * n + t] = cnt;
-                    for (int k = 0; k < cnt; ++k) {
-                        const int32_t f = idx[off[cc] + k];
-                        const int32_t o = v.owners[d][f], nn = v.neighbors[d][f];
-                        // left face: this cell is the neighbour, the other cell is the owner (and vice versa)
-                        if ((side ? o : nn) != cc) { ok = false; break; }
-                        rec[(q * 5 + 1 + k) * n + t] = side ? nn : o;
-                    }
-                }
-        }
-        if (ok) IBH_TRY(p->own.upload(&p->irr_rec, rec));
-    }
+    p->sum.direct_sides = direct;
     *out = p.release();
     return 0;
 }
@@ -415,19 +274,22 @@ int ibh_analyze2_host(ibh_host2d** out, int32_t nc, const float* spacing, const 
     IBH_TRY(make_view(v, 2, nc, spacing, nf, owners, neighbors, left_off, left_idx, right_off, right_idx, domain, 8,
                       index_base));
     ibh_host2d* h = new ibh_host2d();
-    analyze2_host(v, n_image, image_in_domain, index_base, h->H);
+    ibh_analyze2(v, image_in_domain, n_image, *h);
+    ibh_side_table(v, &h->sum.direct_sides);   // the table's count alone: the summary is then create's, slot for slot
     *out = h;
     return 0;
 }
 
 int ibh_host2d_get(const ibh_host2d* h, int what, int set, void* dst, int64_t cap_bytes, int64_t* nbytes) {
     IBH_REQUIRE(h && nbytes && (set == 0 || set == 1), "ibh_host2d_get: bad argument");
-    const Host2D& H = h->H;
+    const Host2D& H = *h;
     const QuadSet2& Q = H.quads[set];
     const void* src = nullptr;
     int64_t n = 0;
     int64_t counts[8] = {(int64_t)H.blocks.size(), (int64_t)Q.qd.size(), Q.nq_int, (int64_t)Q.singles.size(), Q.ns_int,
                          H.fuse_all, H.img_all_fz, H.nph[1]};
+    int64_t slots[IBH_INFO_COUNT];
+    ibh_summary_write(H.sum, slots);
     switch (what) {
         case IBH_H2D_BLOCKS: src = H.blocks.data(); n = (int64_t)(H.blocks.size() * sizeof(BlockDesc2)); break;
         case IBH_H2D_HTAB: src = H.htab.data(); n = (int64_t)(H.htab.size() * 4); break;
@@ -442,7 +304,7 @@ int ibh_host2d_get(const ibh_host2d* h, int what, int set, void* dst, int64_t ca
         case IBH_H2D_QUAD_AUX: src = Q.qaux.data(); n = (int64_t)(Q.qaux.size() * 4); break;
         case IBH_H2D_PAIR_AUX: src = Q.paux.data(); n = (int64_t)(Q.paux.size() * 4); break;
         case IBH_H2D_COUNTS: src = counts; n = (int64_t)sizeof(counts); break;
-        case IBH_H2D_INFO: src = H.info; n = (int64_t)sizeof(H.info); break;
+        case IBH_H2D_INFO: src = slots; n = (int64_t)sizeof(slots); break;
         default: return ibh_fail(-1, "ibh_host2d_get: unknown item", __FILE__, __LINE__);
     }
     *nbytes = n;
@@ -465,7 +327,9 @@ int ibh_partition_destroy(ibh_part* p) {
 
 int ibh_partition_info(const ibh_part* p, int64_t* info, int n) {
     IBH_REQUIRE(p && info, "ibh_partition_info: null argument");
-    for (int i = 0; i < n && i < 24; ++i) info[i] = p->info[i];
+    int64_t slots[IBH_INFO_COUNT];
+    ibh_summary_write(p->sum, slots);
+    if (n > 0) memcpy(info, slots, sizeof(int64_t) * (size_t)(n < IBH_INFO_COUNT ? n : IBH_INFO_COUNT));
     return 0;
 }
 

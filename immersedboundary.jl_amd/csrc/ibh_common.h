@@ -1,6 +1,7 @@
 // Internal declarations shared by the libibhip translation units (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <string>
 #include <type_traits>
@@ -96,8 +97,37 @@ struct DimData {
 };
 static_assert(std::is_trivially_copyable<DimData>::value, "DimData is passed to kernels by value");
 
+// What the analysis found, by name: ibh_partition_info and IBH_H2D_INFO report it (the meanings are in include/ibhip.h),
+// the host dispatch reads `tiled` and sides[SIDE_GENERAL].
+struct PartSummary {
+    int64_t full_blocks = 0, irregular_cells = 0;
+    int64_t sides[5] = {0, 0, 0, 0, 0};  // by SIDE_* class
+    int64_t interior_blocks = 0, fusable_blocks = 0, workspace_blocks = 0;
+    int64_t image_all_eligible = 0, image_blocks = 0;
+    int64_t quads_or_rim4_rows = 0;  // one slot: 2-D the quads, 3-D the rim neighbours made of four finer cells
+    int64_t quad_singles = 0, image_quads = 0, image_quad_singles = 0;  // 2-D
+    int64_t row_sweep = 0, direct_sides = 0, quad_pairs = 0, quad_arith_half_sides = 0;
+    int64_t tiled = 0;  // complete blocks in order: the face-list kernels take in-block neighbours by index arithmetic
+};
+// The one place that knows the slot numbering of ibh_partition_info.
+inline void ibh_summary_write(const PartSummary& s, int64_t* info) {
+    const int64_t slots[][2] = {
+        {IBH_INFO_FULL_BLOCKS, s.full_blocks}, {IBH_INFO_IRREGULAR_CELLS, s.irregular_cells},
+        {IBH_INFO_INTERIOR_BLOCKS, s.interior_blocks}, {IBH_INFO_FUSABLE_BLOCKS, s.fusable_blocks},
+        {IBH_INFO_WORKSPACE_BLOCKS, s.workspace_blocks}, {IBH_INFO_IMAGE_ALL_ELIGIBLE, s.image_all_eligible},
+        {IBH_INFO_IMAGE_BLOCKS, s.image_blocks}, {IBH_INFO_QUADS, s.quads_or_rim4_rows},
+        {IBH_INFO_QUAD_SINGLES, s.quad_singles}, {IBH_INFO_IMAGE_QUADS, s.image_quads},
+        {IBH_INFO_IMAGE_QUAD_SINGLES, s.image_quad_singles}, {IBH_INFO_ROW_SWEEP, s.row_sweep},
+        {IBH_INFO_DIRECT_SIDES, s.direct_sides}, {IBH_INFO_QUAD_PAIRS, s.quad_pairs},
+        {IBH_INFO_QUAD_ARITH_HALF_SIDES, s.quad_arith_half_sides}, {IBH_INFO_TILED, s.tiled}};
+    for (int i = 0; i < IBH_INFO_COUNT; ++i) info[i] = 0;
+    for (const auto& kv : slots) info[kv[0]] = kv[1];
+    for (int k = 0; k < 5; ++k) info[IBH_INFO_SIDES_SAME + k] = s.sides[k];
+}
+static_assert(IBH_INFO_SIDES_GENERAL - IBH_INFO_SIDES_SAME == SIDE_GENERAL - SIDE_SAME, "side slots in SIDE_* order");
+
 struct ibh_part {
-    int nd = 0;
+    int nd = 0;                // nd and nc first: callers' stand-ins (below) set them by position
     int32_t nc = 0;
     float* spacing = nullptr;  // (nc, nd) column-major
     float* centers = nullptr;  // (nc, nd) or null
@@ -153,14 +183,17 @@ struct ibh_part {
     // rec[(q*5 + 1 + k)*n_irr + t] = the cell across its k-th face (accumulator order).  One coalesced read
     // replaces the offsets -> face ids -> owner/neighbour chain of the CSR walk.
     int32_t* irr_rec = nullptr;
-    int64_t info[24] = {0};
+    PartSummary sum;
     // workspace for per-cell gradients + sensor (pass A output)
     float* G = nullptr;
     float* march_tmp = nullptr;  // workgroup maxima of ibh_timestep_advection's reduction
     size_t march_tmp_n = 0;
     size_t G_bytes = 0;
-    ibh_owner own;  // every device buffer above, G and march_tmp included (last: callers' stand-ins set nd and nc by position)
+    ibh_owner own;  // every device buffer above, G and march_tmp included
 };
+// The stand-in contract: a zero-filled buffer of 8192 bytes with nd and nc set is a partition without blocks.
+static_assert(offsetof(ibh_part, nd) == 0 && offsetof(ibh_part, nc) == sizeof(int), "stand-ins set nd and nc by position");
+static_assert(sizeof(ibh_part) <= 8192, "a zero-filled 8192-byte buffer stands in for a partition");
 
 struct ibh_acc {
     int32_t n_out = 0, n_in = 0;
@@ -246,16 +279,54 @@ struct HostPartView {
     int index_base;
     int bs;
 };
-void ibh_analyze_blocks2(const HostPartView& v, std::vector<BlockDesc2>& blocks,
-                         std::vector<int32_t>& irr_cells, int64_t* info, const int32_t* image_in_domain,
-                         int32_t n_image, int32_t* n_phase1, std::vector<int32_t>& htab,
-                         std::vector<int32_t>& etab, std::vector<char>& fusable, std::vector<char>& needg,
-                         std::vector<int32_t>& dtab);
+// The analysis record of a 2-D partition: everything ibh_partition_create uploads and reports, made without a HIP call
+// (ibh_analyze2_host shows it to the CPU tests).  ibh_analyze_blocks2 fills the tables, `nfus` and sum.sides from the view
+// and the image ids (base v.index_base; none: n_image = 0); ibh_analyze2 calls it and completes the record.
+struct Host2D {
+    std::vector<BlockDesc2> blocks;
+    std::vector<int32_t> irr, htab, etab, dtab, img, fz, ng, nf;
+    std::vector<char> fus, needg;
+    int32_t nph[2] = {0, 0};
+    int32_t nfus = 0;  // blocks eligible for the single-kernel sweep
+    int32_t n_img_int = 0, img_all_fz = 0, fuse_all = 0, rows_ok = 0, n_fz_int = 0, n_ng_int = 0, n_nf_int = 0;
+    QuadSet2 quads[2];  // 0: all blocks (fuse_all partitions), 1: image blocks (img_all_fz partitions)
+    PartSummary sum;    // all but direct_sides (ibh_side_table)
+};
+void ibh_analyze2(const HostPartView& v, const int32_t* image_in_domain, int32_t n_image, Host2D& H);
 
 // quads among the candidate blocks (cand[b] != 0); blocks < nB1 are interior-phase blocks
 void ibh_build_quads2(const std::vector<BlockDesc2>& blocks, const std::vector<int32_t>& htab,
                       const std::vector<int32_t>& etab, const std::vector<char>& cand, int32_t nB1, QuadSet2& out,
                       int32_t nc);
+
+// Shared between the dimensions (ibh_analyze.cpp).  The side table of ibh_part::side and the number of its entries >= 0:
+std::vector<int32_t> ibh_side_table(const HostPartView& v, int64_t* direct);
+// the flattened stencil records of the face-list cells `irr`, or empty where they cannot be built (ibh_part::irr_rec)
+std::vector<int32_t> ibh_irr_records(const HostPartView& v, const std::vector<int32_t>& irr);
+// complete blocks in order: cell c lies in block c / npb at position c % npb
+template <class Block>
+bool ibh_tiled(const std::vector<Block>& blocks, int32_t npb, size_t n_irr, int32_t nc) {
+    bool tiled = !blocks.empty() && n_irr == 0 && (int64_t)blocks.size() * npb == (int64_t)nc;
+    for (size_t b = 0; tiled && b < blocks.size(); ++b) tiled = blocks[b].base == (int32_t)(npb * b);
+    return tiled;
+}
+
+// positions inside an 8x8x8 block, local = i + 8*j + 64*k (ibh_analyze3.cpp, ibh_analyze3_image.cpp)
+namespace blk3pos {
+constexpr int NPB = 512;
+constexpr int STR[3] = {1, 8, 64};
+// tangential dims of dim d, increasing
+inline void tang(int d, int& a, int& b) {
+    a = d == 0 ? 1 : 0;
+    b = d == 2 ? 1 : 2;
+}
+inline int pos3(int d, int n, int t1, int t2) {
+    int a, b;
+    tang(d, a, b);
+    return n * STR[d] + t1 * STR[a] + t2 * STR[b];
+}
+inline int coord(int pos, int d) { return (pos / STR[d]) % 8; }
+}  // namespace blk3pos
 
 // tables of the 3-D single-kernel sweep (blk3::sweep_adv), see ibh_analyze3.cpp
 struct Sweep3Host {
@@ -271,9 +342,17 @@ struct Image3Host {
     std::vector<int32_t> dtab;   // [nblk][6][64][4] the cell one step deeper behind halo cell k of slot t
 };
 void ibh_analyze_image3(const HostPartView& v, const int32_t* image_in_domain, int32_t n_image, Image3Host& out);
-void ibh_analyze_blocks3(const HostPartView& v, std::vector<BlockDesc3>& blocks, std::vector<int32_t>& irr_cells,
-                         int64_t* info, const int32_t* image_in_domain, int32_t n_image, int32_t* n_phase1,
-                         std::vector<int32_t>& htab, std::vector<int32_t>& ftab, Sweep3Host* sw);
+// The analysis record of a 3-D partition, as Host2D.  ibh_analyze_blocks3 fills the tables, `sw` and sum.sides;
+// ibh_analyze3 calls it, analyses the image blocks where they are wanted (`im`, used where im.all) and completes the record.
+struct Host3D {
+    std::vector<BlockDesc3> blocks;
+    std::vector<int32_t> irr, htab, ftab;
+    int32_t nph[2] = {0, 0};
+    Sweep3Host sw;
+    Image3Host im;
+    PartSummary sum;  // all but direct_sides (ibh_side_table)
+};
+void ibh_analyze3(const HostPartView& v, const int32_t* image_in_domain, int32_t n_image, Host3D& H);
 
 static inline int ibh_grid(int64_t n, int block) {
     int64_t g = (n + block - 1) / block;

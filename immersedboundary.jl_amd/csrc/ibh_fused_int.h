@@ -60,7 +60,8 @@ inline bool image3(const ibh_part* p, int flags) { return whole3(p, flags) && (f
 inline bool single3(const ibh_part* p, int flags) { return whole3(p, flags) && !(flags & IBH_IMAGE_ONLY) && p->sweep3; }
 // every cell of the partition in a complete 8^3 block without a GENERAL side (what the fused closures need)
 inline bool all_blocks3(const ibh_part* p) {
-    return p->nd == 3 && has_blocks(p) && p->n_irr == 0 && (int64_t)p->nblk * 512 == p->nc && p->info[6] == 0;
+    return p->nd == 3 && has_blocks(p) && p->n_irr == 0 && (int64_t)p->nblk * 512 == p->nc &&
+           p->sum.sides[SIDE_GENERAL] == 0;
 }
 // quad set `k` (0: all blocks, 1: image blocks) carries quads and the call may use them
 inline bool quads_usable(const ibh_part* p, int k, int flags) { return T.quad && !(flags & IBH_NO_QUAD) && p->nq[k] > 0; }

@@ -75,12 +75,12 @@ __global__ __launch_bounds__(OPS_BLOCK) void k_bcinterp_dtfinal(int nwg_bc, BcLa
 }
 
 // the four instantiations of a kernel K<ND, TILED> (K<ND, TILED, CELLS> for the second form) as k[nd - 2][tiled]; the kernel
-// of partition p is dt_kernel(k, p) (tiled: complete blocks in order, ibh_api.hip)
+// of partition p is dt_kernel(k, p) (tiled: complete blocks in order, ibh_tiled)
 #define DT_KERNELS(K) {{K<2, false>, K<2, true>}, {K<3, false>, K<3, true>}}
 #define DT_KERNELS_CELLS(K, CELLS) {{K<2, false, CELLS>, K<2, true, CELLS>}, {K<3, false, CELLS>, K<3, true, CELLS>}}
 template <class K>
 K dt_kernel(K const (&k)[2][2], const ibh_part* p) {
-    return k[p->nd - 2][p->info[20] != 0];
+    return k[p->nd - 2][p->sum.tiled != 0];
 }
 
 // the workgroup maxima of the time step live with the partition, not in the per-thread scratch: a march step launches them

@@ -19,30 +19,37 @@ QUAD_DTYPE = np.dtype([("base", "<i4"), ("cls", "<u4"), ("rh", "<f4", (2,))])
 SIDE_SAME, SIDE_MIRROR, SIDE_COARSE, SIDE_FINE, SIDE_GENERAL = range(5)
 
 
+def partition_args(part, index_base=0, image_in_domain=None):
+    """The arguments ``ibh_partition_create`` and ``ibh_analyze2_host`` share, in their order -- ``nf``, the owners and
+    neighbours and the four CSR arrays per dimension, ``n_image``, ``image_in_domain``, ``domain`` -- followed by
+    ``index_base``, and the arrays behind the pointers, which must outlive the call: ``(args, keep)``, ``keep`` a dict that also
+    holds ``spacing`` (column-major Float32).  Every index is written with ``index_base`` (the partition's are 0-based);
+    ``image_in_domain``: other 0-based image ids than the partition's."""
+    dims = range(1, part.ndims + 1)
+    fon, fa = part.face_owners_neighbors, part.face_accumulators
+
+    def i32(a):
+        return np.ascontiguousarray(a if index_base == 0 else np.asarray(a) + index_base, dtype=np.int32)
+
+    faces = [[i32(a) for a in arrs] for arrs in
+             ([fon[d][0] for d in dims], [fon[d][1] for d in dims],
+              [fa[(d, False)].off for d in dims], [fa[(d, False)].idx for d in dims],
+              [fa[(d, True)].off for d in dims], [fa[(d, True)].idx for d in dims])]
+    keep = dict(spacing=np.asfortranarray(part.spacing, dtype=np.float32),
+                nf=np.array([fon[d][0].shape[0] for d in dims], dtype=np.int32),
+                image_in_domain=i32(part.image_in_domain if image_in_domain is None else image_in_domain),
+                domain=i32(part.domain), faces=faces)
+    args = ((keep["nf"].ctypes.data_as(c_vp),) + tuple((c_vp * part.ndims)(*[a.ctypes.data for a in arrs]) for arrs in faces)
+            + (int(keep["image_in_domain"].size), keep["image_in_domain"].ctypes.data_as(c_vp),
+               keep["domain"].ctypes.data_as(c_vp), index_base))
+    return args, keep
+
+
 def analyze2(part):
-    nd = part.ndims
-    assert nd == 2
-    nc = part.spacing.shape[0]
-    spacing = np.asfortranarray(part.spacing, dtype=np.float32)
-    nf = np.array([part.face_owners_neighbors[d + 1][0].shape[0] for d in range(nd)], dtype=np.int32)
-    keep = []
-
-    def parr(arrs):
-        arrs = [np.ascontiguousarray(a, dtype=np.int32) for a in arrs]
-        keep.append(arrs)
-        return (c_vp * nd)(*[a.ctypes.data for a in arrs])
-
-    owners = parr([part.face_owners_neighbors[d + 1][0] for d in range(nd)])
-    neighbors = parr([part.face_owners_neighbors[d + 1][1] for d in range(nd)])
-    loff = parr([part.face_accumulators[(d + 1, False)].off for d in range(nd)])
-    lidx = parr([part.face_accumulators[(d + 1, False)].idx for d in range(nd)])
-    roff = parr([part.face_accumulators[(d + 1, True)].off for d in range(nd)])
-    ridx = parr([part.face_accumulators[(d + 1, True)].idx for d in range(nd)])
-    iid = np.ascontiguousarray(part.image_in_domain, dtype=np.int32)
-    dom = np.ascontiguousarray(part.domain, dtype=np.int32)
+    assert part.ndims == 2
+    args, keep = partition_args(part)
     h = c_vp()
-    call("ibh_analyze2_host", C.byref(h), nc, spacing.ctypes.data_as(c_vp), nf.ctypes.data_as(c_vp), owners, neighbors,
-         loff, lidx, roff, ridx, int(iid.size), iid.ctypes.data_as(c_vp), dom.ctypes.data_as(c_vp), 0)
+    call("ibh_analyze2_host", C.byref(h), part.spacing.shape[0], keep["spacing"].ctypes.data_as(c_vp), *args)
 
     def get(what, dtype, set_=0):
         n = C.c_int64(0)

@@ -92,13 +92,37 @@ int ibh_partition_create(ibh_part** out, int nd, int32_t nc,
                          int32_t n_image, const int32_t* image_in_domain,
                          const int32_t* domain, int block_size, int index_base);
 int ibh_partition_destroy(ibh_part* part);
-/* Introspection of the block analysis: info[0]=full blocks, [1]=irregular cells,
- * [2..6] = number of block sides classified SAME, MIRROR, COARSE, FINE, GENERAL,
- * [7] = blocks whose whole sweep is independent of skirt cells (IBH_PHASE_INTERIOR),
- * [8] = blocks eligible for the single-kernel sweep, [9] = blocks whose gradients go through the workspace
- *       in a mixed launch (0 when every block is eligible), [10] = 1 when every image block is eligible (IBH_IMAGE_ONLY
- *       sweeps are then one launch per phase), [11] = image blocks, [12] / [13] = 2x2 block groups of the quad sweep and
- *       blocks outside them when every block is eligible, [14] / [15] = the same among the image blocks. */
+/* Introspection of the block analysis: ibh_partition_info copies the first min(n, IBH_INFO_COUNT) of these values.
+ *   FULL_BLOCKS            complete 8^nd blocks the block kernels take (0 without block information)
+ *   IRREGULAR_CELLS        cells left to the face-list kernels (all of them without block information)
+ *   SIDES_SAME .. GENERAL  block sides by class: same level, mirror (domain boundary), coarser, finer neighbour, anything else
+ *   INTERIOR_BLOCKS        blocks whose whole sweep is independent of skirt cells (IBH_PHASE_INTERIOR)
+ *   FUSABLE_BLOCKS         blocks eligible for the single-kernel sweep (3-D: all of them or none)
+ *   WORKSPACE_BLOCKS       blocks whose gradients go through the workspace in a mixed launch (0 when every block is eligible)
+ *   IMAGE_ALL_ELIGIBLE     1 when every image block is eligible (IBH_IMAGE_ONLY sweeps are then one launch per phase)
+ *   IMAGE_BLOCKS           image blocks
+ *   QUADS / RIM4_ROWS      one slot, 2-D / 3-D.  2-D: 2x2 block groups of the quad sweep when every block is eligible;
+ *                          3-D: rim neighbours of halo cells that are four finer cells (single-kernel sweeps)
+ *   QUAD_SINGLES           2-D: blocks outside the quads
+ *   IMAGE_QUADS, IMAGE_QUAD_SINGLES  the same two among the image blocks (when they are all eligible and the rest is not)
+ *   ROW_SWEEP              1 when the arithmetic halo ids of the row sweep reproduce the halo table
+ *   DIRECT_SIDES           (dimension, side, cell) triples with exactly one face that names the cell where the CSR says
+ *   QUAD_PAIRS             2-D: pair tiles among the blocks outside quads
+ *   QUAD_ARITH_HALF_SIDES  2-D: outer half-sides of the quads (8 each) whose halo ids are computed, not read
+ *   TILED                  1 when the cells are complete blocks in order: cell c is cell c % 8^nd of block c / 8^nd
+ * The slots up to IBH_INFO_COUNT that have no name are zero. */
+enum {
+    IBH_INFO_FULL_BLOCKS = 0, IBH_INFO_IRREGULAR_CELLS = 1,
+    IBH_INFO_SIDES_SAME = 2, IBH_INFO_SIDES_MIRROR = 3, IBH_INFO_SIDES_COARSE = 4, IBH_INFO_SIDES_FINE = 5,
+    IBH_INFO_SIDES_GENERAL = 6,
+    IBH_INFO_INTERIOR_BLOCKS = 7, IBH_INFO_FUSABLE_BLOCKS = 8, IBH_INFO_WORKSPACE_BLOCKS = 9,
+    IBH_INFO_IMAGE_ALL_ELIGIBLE = 10, IBH_INFO_IMAGE_BLOCKS = 11,
+    IBH_INFO_QUADS = 12, IBH_INFO_RIM4_ROWS = 12,   /* 2-D / 3-D */
+    IBH_INFO_QUAD_SINGLES = 13, IBH_INFO_IMAGE_QUADS = 14, IBH_INFO_IMAGE_QUAD_SINGLES = 15,
+    IBH_INFO_ROW_SWEEP = 16, IBH_INFO_DIRECT_SIDES = 17, IBH_INFO_QUAD_PAIRS = 18, IBH_INFO_QUAD_ARITH_HALF_SIDES = 19,
+    IBH_INFO_TILED = 20,
+    IBH_INFO_COUNT = 24
+};
 int ibh_partition_info(const ibh_part* part, int64_t* info, int n);
 
 /* ---- Elementwise kernels: what `Base.Broadcast` on device arrays lowers to in the reference-side binding
@@ -177,7 +201,7 @@ enum {
     IBH_H2D_QUAD_TAB = 5,  /* int32 [nq][160] */
     IBH_H2D_SINGLES = 6,   /* int32 block indices outside quads */
     IBH_H2D_COUNTS = 7,    /* int64 [8]: blocks, quads, interior quads, singles, interior singles, fuse_all, img_all_fz, nB1 */
-    IBH_H2D_INFO = 8,      /* int64 [12] as ibh_partition_info */
+    IBH_H2D_INFO = 8,      /* int64 [IBH_INFO_COUNT]: every slot of ibh_partition_info, as create would report it */
     IBH_H2D_PAIR_DESC = 9, /* pair tiles (two blocks side by side, base and base + 64) in the quad format; set 0 only */
     IBH_H2D_PAIR_TAB = 10, /* int32 [npair][160] */
     IBH_H2D_SINGLES2 = 11, /* int32 block indices outside quads and pairs */

@@ -99,6 +99,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent-lib")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "handle_ownership", "timings.md"))
+    ap.add_argument("--title", default="Handle ownership", help="what the table's heading names: the change that is measured")
     ap.add_argument("--worker", action="store_true")
     args = ap.parse_args()
     if args.worker:
@@ -107,7 +108,7 @@ def main():
         sys.exit("--parent-lib: the library of the parent commit")
     libs = [("parent", os.path.abspath(args.parent_lib)), ("head", None)]
     good = True
-    lines = ["# Handle ownership: timings against the parent commit", "",
+    lines = [f"# {args.title}: timings against the parent commit", "",
              "Parent and head libraries run on the same MI355X in one session, alternating parent / head (the parent's library",
              "through `IBHIP_LIB`; the scripts and the Python layer are the head's).  Written by",
              "`scripts/bench_handle_ownership.py`.", "",

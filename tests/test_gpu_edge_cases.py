@@ -12,6 +12,7 @@ import ibamd
 from conftest import rel_inf, seeded_field
 from ibamd import _lib
 from ibamd import backend as B
+from ibamd.hostview import partition_args
 from oracle import domain as od
 
 pytestmark = pytest.mark.gpu
@@ -87,26 +88,11 @@ def test_wide_field(adv_domains):
 def _raw_create(part, block_size, index_base, with_domain=True, iid=None, check=True):
     """``ibh_partition_create`` on the arrays of ``part`` (``iid``: another ``image_in_domain``, 0-based).  The handle, or
     with ``check=False`` (return code, handle)."""
-    nd, nc = part.ndims, part.spacing.shape[0]
-    dims = range(1, nd + 1)
-    keep = []
-
-    def parr(arrs):
-        arrs = [np.ascontiguousarray(a + index_base, dtype=np.int32) for a in arrs]
-        keep.append(arrs)
-        return (B.c_vp * nd)(*[a.ctypes.data for a in arrs])
-    fon, fa = part.face_owners_neighbors, part.face_accumulators
-    owners, neigh = parr([fon[d][0] for d in dims]), parr([fon[d][1] for d in dims])
-    loff, lidx = parr([fa[(d, False)].off for d in dims]), parr([fa[(d, False)].idx for d in dims])
-    roff, ridx = parr([fa[(d, True)].off for d in dims]), parr([fa[(d, True)].idx for d in dims])
-    nf = np.array([fon[d][0].size for d in dims], dtype=np.int32)
-    sp = np.asfortranarray(part.spacing, dtype=np.float32)
-    iid = np.ascontiguousarray((part.image_in_domain if iid is None else iid) + index_base, dtype=np.int32)
-    dom = np.ascontiguousarray(part.domain + index_base, dtype=np.int32)
+    shared, keep = partition_args(part, index_base, image_in_domain=iid)
     h = B.c_vp()
     B._dev()
-    args = (C.byref(h), nd, nc, sp.ctypes.data_as(B.c_vp), B.c_vp(None), nf.ctypes.data_as(B.c_vp), owners, neigh, loff, lidx,
-            roff, ridx, int(iid.size), B._hptr(iid), B._hptr(dom) if with_domain else B.c_vp(None), block_size, index_base)
+    args = (C.byref(h), part.ndims, part.spacing.shape[0], B._hptr(keep["spacing"]), B.c_vp(None), *shared[:-2],
+            shared[-2] if with_domain else B.c_vp(None), block_size, index_base)
     if not check:
         return _lib.load().ibh_partition_create(*args), h
     B.call("ibh_partition_create", *args)
@@ -125,7 +111,7 @@ def test_one_based_indices_and_no_block_info(adv_domains):
         h = _raw_create(part, 8, base, with_dom)
         info = (C.c_int64 * 8)()
         B.call("ibh_partition_info", h, info, 8)
-        assert (info[0] > 0) == with_dom
+        assert (info[_lib.INFO_SLOTS.index("full_blocks")] > 0) == with_dom
         out = torch.zeros(u.shape[0], dtype=torch.float32, device="cuda")
         B._stream()
         B.call("ibh_residual_advection", h, B._ptr(ud), B._ptr(Cd), u.shape[0], B._ptr(out), 16 if with_dom else 0)
