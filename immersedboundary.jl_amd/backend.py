@@ -24,22 +24,24 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._header import CONSTANTS as _K
 from ._lib import call, c_vp
 from .accumulator import Accumulator
-from .domain import Boundary, Partition, Surface
+from .domain import ROLE_FLUID, ROLE_GHOST, ROLE_SOLID, Boundary, Partition, Surface
 from .hostview import partition_args
 
-IBH_FORCE_GENERAL = 1
-IBH_IMAGE_ONLY = 2
-IBH_PASS_A_ONLY = 4
-IBH_PASS_B_ONLY = 8
-IBH_EXACT = 16
-IBH_PHASE_INTERIOR = 32
-IBH_PHASE_BOUNDARY = 64
-IBH_NO_FUSE = 128
-IBH_SWEEP_ONLY = 256
-IBH_FORCE_MIXED = 512
-IBH_NO_QUAD = 1024
+# the sweep flags of include/ibhip.h
+IBH_FORCE_GENERAL = _K["IBH_FORCE_GENERAL"]
+IBH_IMAGE_ONLY = _K["IBH_IMAGE_ONLY"]
+IBH_PASS_A_ONLY = _K["IBH_PASS_A_ONLY"]
+IBH_PASS_B_ONLY = _K["IBH_PASS_B_ONLY"]
+IBH_EXACT = _K["IBH_EXACT"]
+IBH_PHASE_INTERIOR = _K["IBH_PHASE_INTERIOR"]
+IBH_PHASE_BOUNDARY = _K["IBH_PHASE_BOUNDARY"]
+IBH_NO_FUSE = _K["IBH_NO_FUSE"]
+IBH_SWEEP_ONLY = _K["IBH_SWEEP_ONLY"]
+IBH_FORCE_MIXED = _K["IBH_FORCE_MIXED"]
+IBH_NO_QUAD = _K["IBH_NO_QUAD"]
 
 _initialised = {}
 
@@ -745,7 +747,7 @@ def residual_euler_sensor(part, P, nu=None, out=None, flags=0, fluid=None):
 # ---------------------------------------------------------------------------
 # an explicit Euler step, device resident (rows of P: [p T u v (w)])
 # ---------------------------------------------------------------------------
-IBH_EULER_HLL, IBH_EULER_SENSOR = 0, 1
+IBH_EULER_HLL, IBH_EULER_SENSOR = _K["IBH_EULER_HLL"], _K["IBH_EULER_SENSOR"]
 _EULER_SCHEMES = {"hll": IBH_EULER_HLL, "sensor": IBH_EULER_SENSOR}
 
 
@@ -1035,13 +1037,13 @@ class Roles:
         r = np.asarray(roles)
         if r.ndim != 1 or r.shape[0] != nc:
             raise ValueError(f"Roles: roles must be one value per cell of the partition, ({nc},); got {tuple(r.shape)}")
-        if r.size and not np.isin(r, (0, 1, 2)).all():
+        if r.size and not np.isin(r, (ROLE_FLUID, ROLE_GHOST, ROLE_SOLID)).all():
             raise ValueError("Roles: roles are ROLE_FLUID (0), ROLE_GHOST (1) or ROLE_SOLID (2)")
         st = np.asarray(solid_state, dtype=np.float32)
         if st.ndim != 1 or st.shape[0] != nd + 2:
             raise ValueError(f"Roles: solid_state must be the nd + 2 = {nd + 2} primitives of a row; got shape {tuple(st.shape)}")
         r = np.ascontiguousarray(r, dtype=np.uint8)
-        solid = np.nonzero(r == 2)[0].astype(np.int32)
+        solid = np.nonzero(r == ROLE_SOLID)[0].astype(np.int32)
         dev = _dev()
         self.nc, self.nd, self.n_solid = nc, nd, int(solid.size)
         self.counts = tuple(int(x) for x in np.bincount(r, minlength=3))     # (fluid, ghost, solid)
@@ -1433,7 +1435,7 @@ def impose_bc(f, dom, bname, *args, conv_to_backend=None, conv_from_backend=None
                 h[...] = conv_from_backend(a)
 
 
-_FLOW_BC_SCALAR_MODES = {"copy": 1, "nut": 2, "k": 3, "omega": 4, "epsilon": 5}   # IBH_BC_SCALAR_* of include/ibhip.h
+_FLOW_BC_SCALAR_MODES = {s: _K["IBH_BC_SCALAR_" + s.upper()] for s in ("copy", "nut", "k", "omega", "epsilon")}
 _WALL_PARAMS = ("kappa", "C_", "A", "beta", "betastar", "D", "Aplus", "omega_fixed_point")
 
 
@@ -1485,7 +1487,7 @@ def impose_flow_bc(dom, bname, bc, P, scalars=(), wall_function=None, transpirat
             modes.append(_FLOW_BC_SCALAR_MODES[spec])
             values.append(0.0)
         else:
-            modes.append(0)
+            modes.append(_K["IBH_BC_SCALAR_CONST"])
             values.append(float(spec))
     if bc.normal_flow:
         if bc.u_inf.size != 1:

@@ -20,6 +20,7 @@ import torch
 
 from . import _lib
 from . import backend as B
+from ._header import constants
 
 
 class Fluid:
@@ -299,8 +300,8 @@ def _kind(x):
 
 class _TA:
     """dt forms and flags of ibh_time_average_push (include/ibhip.h)."""
-    DT_HOST, DT_DEVICE, DT_PER_VAR, DT_ELEMENT = 0, 1, 2, 3
-    F64, FIRST = 1, 2
+    DT_HOST, DT_DEVICE, DT_PER_VAR, DT_ELEMENT = constants("IBH_TA_", "DT_HOST DT_DEVICE DT_PER_VAR DT_ELEMENT")
+    F64, FIRST = constants("IBH_TA_", "F64 FIRST")
 
 
 class TimeAverage:

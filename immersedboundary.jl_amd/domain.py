@@ -17,6 +17,7 @@ from __future__ import annotations
 import numpy as np
 from scipy.spatial import cKDTree
 
+from ._header import constants
 from .accumulator import Accumulator
 from .mesher import Mesh, get_cells, proj2simplex
 
@@ -764,7 +765,7 @@ def multigrid(dom, max_levels=0, factor=2):
     return coarse_doms, prolongators, coarseners
 
 
-ROLE_FLUID, ROLE_GHOST, ROLE_SOLID = 0, 1, 2   # IBH_ROLE_* of include/ibhip.h
+ROLE_FLUID, ROLE_GHOST, ROLE_SOLID = constants("IBH_ROLE_", "FLUID GHOST SOLID")
 
 
 def cell_roles(dom, fluid_seed=None):

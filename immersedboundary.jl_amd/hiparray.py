@@ -14,14 +14,18 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._header import constants
 from ._lib import c_vp, call
 
-ADD, SUB, MUL, DIV, MAX, MIN, SUM = range(7)
-ABS, NEG, SQRT, COPY = 16, 17, 18, 19
-# the rest of Julia's elementwise Float32 math (include/ibhip.h); Bool values are Float32 0 / 1 on the device
-LT, LE, GT, GE, EQ, NE, AND, OR, POW, COPYSIGN, ATAN2, BMUL = range(64, 76)
-EXP, EXP2, LOG, LOG2, LOG10, SIN, COS, TANH, ATAN, SIGN, INV, NOT, POW0, SQR, CUBE, INVSQR = range(80, 96)
-CLAMP, IFELSE = 112, 113
+# the IBH_EW_* opcodes of include/ibhip.h
+ADD, SUB, MUL, DIV, MAX, MIN, SUM = constants("IBH_EW_", "ADD SUB MUL DIV MAX MIN SUM")
+ABS, NEG, SQRT, COPY = constants("IBH_EW_", "ABS NEG SQRT COPY")
+# the rest of Julia's elementwise Float32 math; Bool values are Float32 0 / 1 on the device
+LT, LE, GT, GE, EQ, NE, AND, OR, POW, COPYSIGN, ATAN2, BMUL = constants(
+    "IBH_EW_", "LT LE GT GE EQ NE AND OR POW COPYSIGN ATAN2 BMUL")
+EXP, EXP2, LOG, LOG2, LOG10, SIN, COS, TANH, ATAN, SIGN, INV, NOT, POW0, SQR, CUBE, INVSQR = constants(
+    "IBH_EW_", "EXP EXP2 LOG LOG2 LOG10 SIN COS TANH ATAN SIGN INV NOT POW0 SQR CUBE INVSQR")
+CLAMP, IFELSE = constants("IBH_EW_", "CLAMP IFELSE")
 _PLAIN_BINARY = (ADD, SUB, MUL, DIV, MAX, MIN)
 _PLAIN_UNARY = (ABS, NEG, SQRT, COPY)
 _LITERAL_POW = {0: POW0, 1: COPY, 2: SQR, 3: CUBE, -1: INV, -2: INVSQR}   # Base.literal_pow
@@ -38,7 +42,7 @@ def _B():
     return _backend
 
 
-PUSH_ARRAY, PUSH_SCALAR, PUSH_ROW = 32, 33, 34
+PUSH_ARRAY, PUSH_SCALAR, PUSH_ROW = constants("IBH_EW_", "PUSH_ARRAY PUSH_SCALAR PUSH_ROW")
 _MAX_PROG, _MAX_ARR, _MAX_SCAL, _MAX_DEPTH = 48, 8, 32, 8
 
 

@@ -8,6 +8,7 @@ import ctypes as C
 
 import numpy as np
 
+from ._header import constants
 from ._lib import c_vp, call
 
 BLOCK_DTYPE = np.dtype([("base", "<i4"), ("type", "<i4", (4,)), ("nb", "<i4", (4, 2)), ("sub", "<i4", (4,)),
@@ -15,7 +16,8 @@ BLOCK_DTYPE = np.dtype([("base", "<i4"), ("type", "<i4", (4,)), ("nb", "<i4", (4
                         ("dt", "<i4")])
 QUAD_DTYPE = np.dtype([("base", "<i4"), ("cls", "<u4"), ("rh", "<f4", (2,))])
 (BLOCKS, HTAB, ETAB, FUSABLE, QUAD_DESC, QUAD_TAB, SINGLES, COUNTS, INFO, PAIR_DESC, PAIR_TAB, SINGLES2, QUAD_AUX,
- PAIR_AUX) = range(14)
+ PAIR_AUX) = constants("IBH_H2D_", "BLOCKS HTAB ETAB FUSABLE QUAD_DESC QUAD_TAB SINGLES COUNTS INFO PAIR_DESC PAIR_TAB SINGLES2 "
+                       "QUAD_AUX PAIR_AUX")
 SIDE_SAME, SIDE_MIRROR, SIDE_COARSE, SIDE_FINE, SIDE_GENERAL = range(5)
 
 

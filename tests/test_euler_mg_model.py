@@ -12,6 +12,7 @@ import pytest
 import euler_mg_model as mg
 import euler_step_model as em
 import regimes as rg
+from abi import assert_bound
 from conftest import ADV_FAMILIES, RAE_FAMILIES, oracle_boundaries_view, oracle_view
 from ibamd import _lib
 from ibamd import backend as B
@@ -138,12 +139,9 @@ def test_one_level_cycle_is_the_plain_steps(adv):
 # exports and the checks before any launch
 # ---------------------------------------------------------------------------------------------------------------------
 def test_exported_bound_and_named_by_the_julia_binding():
-    lib = _lib.load()
+    assert_bound(NAMES)
     protos, calls = header_prototypes(), {c[0]: c for c in julia_ccalls()}
     for name in NAMES:
-        assert hasattr(lib, name), f"{name} is not exported"
-        assert name in _lib._SIGS and name in _lib.EXPORTS
-        assert len(_lib._SIGS[name]) == len(protos[name][1])
         assert name in calls and calls[name][1] == protos[name][0] and calls[name][2] == protos[name][1], name
     assert protos["ibh_restrict_euler"][1].count("ptr") == 7 and len(protos["ibh_restrict_euler"][1]) == 13
     assert protos["ibh_prolong_euler"][1].count("ptr") == 7 and len(protos["ibh_prolong_euler"][1]) == 11

@@ -14,6 +14,7 @@ import euler_mg_model as mg
 import euler_roles_model as rm
 import ibamd
 import regimes as rg
+from abi import assert_bound, header_text
 from conftest import ADV_FAMILIES, GOLDEN, RAE_FAMILIES, oracle_boundaries_view, oracle_view
 from ibamd import _lib
 from ibamd import backend as B
@@ -235,24 +236,11 @@ def test_convergence_in_the_model(rae, rae_roles):
 # ---------------------------------------------------------------------------------------------------------------------
 # exports and the checks before any launch
 # ---------------------------------------------------------------------------------------------------------------------
-KIND = {"int": C.c_int, "int64_t": C.c_int64, "float": C.c_float}
-
-
 def test_exported_bound_and_named_by_the_julia_binding():
-    lib = _lib.load()
-    hdr = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "ibhip.h")).read(), flags=re.S)
+    assert_bound(NAMES)
+    hdr = header_text()
     protos, calls = header_prototypes(), {c[0]: c for c in julia_ccalls()}
     for name in NAMES:
-        assert hasattr(lib, name), f"{name} is not exported"
-        assert name in _lib._SIGS and name in _lib.EXPORTS
-        args = [" ".join(a.split()) for a in re.search(r"\bint\s+" + name + r"\s*\(([^;]*?)\)\s*;", hdr).group(1).split(",")]
-        sig = _lib._SIGS[name]
-        assert len(args) == len(sig) == len(protos[name][1]), name
-        for a, t in zip(args, sig):
-            if "*" in a:
-                assert (t is C.POINTER(_lib.ibh_fluid)) if "ibh_fluid" in a else (t is C.c_void_p), (name, a, t)
-            else:
-                assert t is KIND[a.replace("const ", "").split()[0]], (name, a, t)
         assert name in calls, f"julia/IBHip.jl does not ccall {name}"
         assert calls[name][1] == protos[name][0] and calls[name][2] == protos[name][1], name
     assert protos["ibh_restrict_euler_roles"][1] == protos["ibh_restrict_euler"][1][:9] + ["ptr"] + protos["ibh_restrict_euler"][1][9:]

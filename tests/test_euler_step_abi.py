@@ -1,34 +1,20 @@
 """``ibh_timestep_euler`` / ``ibh_update_euler`` / ``ibh_step_euler``: exported, bound by ``_lib`` with the header's argument
 lists, and every misuse reported through ``ibh_last_error`` before anything is launched -- no GPU needed to be told so."""
 import ctypes as C
-import os
 import re
 
 import pytest
 
+from abi import assert_bound, header_text
 from ibamd import _lib
 from ibamd import backend as B
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("ibh_timestep_euler", "ibh_update_euler", "ibh_step_euler")
-KIND = {"int": C.c_int, "int64_t": C.c_int64, "float": C.c_float}
 
 
 def test_exported_and_bound_with_the_headers_prototypes():
-    lib = _lib.load()
-    hdr = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "ibhip.h")).read(), flags=re.S)
-    for name in NAMES:
-        assert hasattr(lib, name), f"{name} is not exported"
-        assert name in _lib._SIGS and name in _lib.EXPORTS
-        args = [" ".join(a.split()) for a in re.search(r"\bint\s+" + name + r"\s*\(([^;]*?)\)\s*;", hdr).group(1).split(",")]
-        sig = _lib._SIGS[name]
-        assert len(args) == len(sig), name
-        for a, t in zip(args, sig):
-            if "*" in a:        # every pointer is passed as an address; the fluid as a pointer to the struct
-                assert t is C.c_void_p or t is C.POINTER(_lib.ibh_fluid), (name, a, t)
-                assert (t is C.POINTER(_lib.ibh_fluid)) == ("ibh_fluid" in a), (name, a, t)
-            else:
-                assert t is KIND[a.replace("const ", "").split()[0]], (name, a, t)
+    assert_bound(NAMES)
+    hdr = header_text()
     for macro, value in (("IBH_EULER_HLL", B.IBH_EULER_HLL), ("IBH_EULER_SENSOR", B.IBH_EULER_SENSOR)):
         assert int(re.search(r"#define\s+" + macro + r"\s+(\d+)", hdr).group(1)) == value
 

@@ -7,20 +7,14 @@ import re
 
 import pytest
 
+from abi import assert_bound
 from ibamd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_exported_and_bound():
-    lib = _lib.load()
-    for name in ("ibh_bc_flow", "ibh_bc_flow_info"):
-        assert hasattr(lib, name), f"{name} is not exported"
-        assert name in _lib._SIGS and name in _lib.EXPORTS
-    hdr = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "ibhip.h")).read(), flags=re.S)
-    for name in ("ibh_bc_flow", "ibh_bc_flow_info"):
-        args = re.search(r"\b" + name + r"\s*\(([^;]*?)\)\s*;", hdr).group(1)
-        assert len(args.split(",")) == len(_lib._SIGS[name]), name
+    assert_bound(("ibh_bc_flow", "ibh_bc_flow_info"))
 
 
 def test_spec_struct_matches_the_header():

@@ -7,6 +7,7 @@ import re
 
 import pytest
 
+from abi import assert_bound
 from ibamd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -14,13 +15,9 @@ ARGS = ("p", "vel", "ldv", "Delta", "model", "Cmodel", "nusgs", "ducros", "shock
 
 
 def test_exported_declared_and_bound():
-    lib = _lib.load()
-    assert hasattr(lib, "ibh_les_of"), "ibh_les_of is not exported"
-    assert "ibh_les_of" in _lib._SIGS and "ibh_les_of" in _lib.EXPORTS
-    hdr = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "ibhip.h")).read(), flags=re.S)
-    args = re.search(r"\bibh_les_of\s*\(([^;]*?)\)\s*;", hdr).group(1)
-    assert len(args.split(",")) == len(_lib._SIGS["ibh_les_of"]) == len(ARGS)
+    assert_bound(("ibh_les_of",))
     sig = _lib._SIGS["ibh_les_of"]
+    assert len(sig) == len(ARGS)
     assert sig[ARGS.index("ldv")] is C.c_int64 and sig[ARGS.index("ldg")] is C.c_int64
     assert sig[ARGS.index("model")] is C.c_int and sig[ARGS.index("Cmodel")] is C.c_float
 
